@@ -13,12 +13,21 @@ at 2 ranks as histogram records of the buckets --, one cou
 pass finishes what arrived; exchange s runs under the local work of steps s - 1 and
 s + 1; value = all ranks' keys / max-over-ranks time.
 
-Rank 0 prints ONE JSON line with the contract fields plus
-  roofline      -- dominant kernel: algorithmic bytes / HIP-event time vs 8 TB/s (N > 1: the whole local sort per GPU,
-                   the exchange's bytes and time beside it)
+Rank 0 prints ONE JSON line with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step).
+A plain run does nothing else: it generates the inputs, warms up, times the --steps steps and prints the line.  When
+more steps are asked for than input arrays fit in HBM, the inputs are generated in groups that fit, each group
+outside the clock, and the timed groups' times are added.
+
+    --dump-outputs DIR  after the timed steps: a fixed, seeded sample (2^20 positions) of what the last timed step
+                        returned, as DIR/<name>.npy in float64 -- keys (u32) or keys_hi32 / keys_lo32 (u64 keys),
+                        rids_hi32 / rids_lo32 (pairs), sample_index; N > 1: per rank, with a _rank<r> suffix
+    --full              also what the headline does not need:
+  verification  -- every timed step's output checked by the library's check kernel AND an independent torch reduction
+  roofline      -- dominant kernel: algorithmic bytes / HIP-event time vs 8 TB/s, from one more profiled sort
+                   (N > 1: the whole local sort per GPU, the exchange's bytes and time measured apart beside it)
   cpu_baseline  -- the reference's own 64-thread sort() (oracle/_ref) on 2^30 (or 2^28) tuples on this host, verified,
                    with its single-thread core on 2^27 keys beside it (rank 0; a reported baseline, not the target)
-  other_configs -- (default single-GPU run) configs c3, c5a, c5b: three verified steps each, after the headline loop
+  other_configs -- (c2 at 2^30 on one GPU) configs c3, c5a, c5b: three verified steps each, after the headline loop
 """
 from __future__ import annotations
 
@@ -36,6 +45,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICRO
 # sequential copy 6.1-6.2 TB/s, random 256-byte block permutation 5.3 TB/s, the direct classify kernel's in-place
 # pattern with no work at all 4.9 TB/s.  Reported beside the spec peak, never instead of it.
 CEILINGS_GBS = {"sequential_copy": 6150.0, "block_permutation_256B": 5300.0, "in_place_pieces_pattern": 4900.0}
+# HBM left free beside the pool of input arrays (one GPU): the library's workspace, torch's temporaries of the --full
+# checks, and one more key array for the --full profiled sort of pairs
+POOL_HEADROOM = 8 << 30
+DUMP_SAMPLE = 1 << 20   # positions per array written by --dump-outputs (8 MB each as float64; N > 1: split over the ranks)
 
 # ---- workloads (BASELINE.json configs; SURVEY.md section 8d gives the ALGORITHMIC bytes: per 8-bit digit pass one
 # histogram read of the key + one permute read + one permute write of key and payload, P = significant key bits / 8)
@@ -93,8 +106,13 @@ def parse():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo: REHEARSAL of the N > 1 path with all ranks on cuda:0 and the collectives staged through "
                          "host memory (RCCL cannot run several ranks on one device); its numbers mean nothing")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="headline only (the default c2 run also times c3, c5a, c5b)")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify every timed step and report roofline, cpu_baseline, other_configs (c2) and, N > 1, the "
+                         "exchange measured apart; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's output as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without c3, c5a, c5b (the full c2 run also times them)")
     ap.add_argument("--scheme", choices=["fine", "coarse"], default=None, help="N > 1: force the sharding scheme (dist.use_fine)")
     ap.add_argument("--whole-keys", action="store_true", help="N > 1, fine scheme: whole keys travel (A/B; dist.FINE_LOW16 = dist.FINE_HIST = False)")
     ap.add_argument("--low-halves", action="store_true", help="N > 1, fine scheme: the keys' low halves travel, never histogram records (A/B; dist.FINE_HIST = False)")
@@ -305,6 +323,33 @@ def whole_sort_block(cfg, n, sec_per_step, real, copy_gbps=None):
             "device_copy_GBps_same_run": None if copy_gbps is None else round(copy_gbps, 1)}
 
 
+def dump_outputs(torch, d, keys, rids, rank, world):
+    """--dump-outputs: the sorted keys (and rids) one step returned, at a fixed, seeded sample of positions that always
+    holds the first and the last, as float64 .npy files (u32 exactly; u64 as two exact 32-bit halves)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = keys.numel()
+    m = DUMP_SAMPLE // world
+    if n <= m:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(0x5EED0D).integers(0, n, m - 2, dtype=np.int64)]))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    it = torch.from_numpy(idx).to(keys.device)
+    arrays = {"sample_index": torch.from_numpy(idx)}
+    for name, t in (("keys", keys), ("rids", rids)):
+        if t is None:
+            continue
+        v = t[it].to(torch.int64)
+        if t.element_size() == 4:
+            arrays[name] = v & 0xFFFFFFFF
+        else:
+            arrays[name + "_hi32"] = (v >> 32) & 0xFFFFFFFF
+            arrays[name + "_lo32"] = v & 0xFFFFFFFF
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + sfx + ".npy"), v.cpu().numpy().astype(np.float64))
+
+
 def make_workload(ctx, torch, config_id, rank, n):
     cfg = CONFIGS[config_id]
     pairs = cfg["val"] > 0
@@ -335,7 +380,7 @@ def run_other_config(config_id, logn, steps=3, warmup=1):
     kernel.  Returns the fields of its line that matter here."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--config", config_id, "--logn", str(logn), "--steps", str(steps), "--warmup", str(warmup),
-           "--no-cpu-baseline", "--no-other-configs"]
+           "--full", "--no-cpu-baseline", "--no-other-configs"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")]
     if p.returncode != 0 or not lines:
@@ -401,15 +446,33 @@ def main():
     W, K = args.warmup, args.steps
     cfg, pairs, tdt, gen, sort = make_workload(ctx, torch, args.config, rank, n)
 
-    # ---- inputs for every step, resident before the clock starts
+    # ---- inputs, resident before the clock starts: step s sorts the array of seed s, held in slot s % P of a pool of
+    # P arrays.  One GPU: P = all W + K steps when they fit in HBM, else as many as fit (the inputs of each group of P
+    # steps are then generated between the groups, outside the clock).  N > 1: every step has its own array.
+    per_step_bytes = n * cfg["key"] * (2 if pairs else 1)
+    if multi:
+        P = W + K
+    else:
+        free_b, _ = torch.cuda.mem_get_info()
+        P = int(max(1, min(W + K, (free_b - POOL_HEADROOM - n * cfg["key"]) // per_step_bytes)))
     bufs, rids = [], []
-    for s in range(W + K):
-        t = torch.empty(n, dtype=tdt, device="cuda")
-        gen(t, s)
-        bufs.append(t)
-        rids.append(t.clone() if pairs else None)   # rid = key, the reference's check(..., same=1) convention (src/msb_64.c:2461)
+    for _ in range(P):
+        bufs.append(torch.empty(n, dtype=tdt, device="cuda"))
+        rids.append(torch.empty(n, dtype=tdt, device="cuda") if pairs else None)   # rid = key, the reference's check(..., same=1) convention (src/msb_64.c:2461)
     ctx.reserve(n + n // 8 if multi else n, cfg["key"], cfg["val"])   # (N > 1: a rank may receive up to n / 8 more than it sent)
-    checks0 = [ctx.check(t) for t in bufs]          # (violations, sum, xor) of every input
+    checks0 = {}                                    # --full: (violations, sum, xor) of every timed step's input
+
+    def fill(lo, hi):
+        for s in range(lo, hi):
+            gen(bufs[s % P], s)
+            if pairs:
+                rids[s % P].copy_(bufs[s % P])
+            if args.full and s >= W:
+                checks0[s] = ctx.check(bufs[s % P])
+
+    def groups(lo, hi):
+        return [(g, min(hi, g + P)) for g in range(lo, hi, P)]
+
     # N > 1: receive buffers with 12.5 % slack (the reference's fudge); the exchange of step s runs (RCCL stream, xGMI)
     # while step s-1 is finished locally -- inplacemsdradixsort_amd.dist.ShardedSorter.
     # Fine scheme (shards of >= 2^27 keys): the shard is ordered by its top 16 bits before the exchange, the counting leaf
@@ -432,87 +495,109 @@ def main():
     def run_steps(lo, hi):
         if not multi:
             for i in range(lo, hi):
-                sort(bufs[i], rids[i])
-            return [(i, bufs[i]) for i in range(lo, hi)]
+                sort(bufs[i % P], rids[i % P])
+            return [(i, bufs[i % P]) for i in range(lo, hi)]
         outs = []
         for i in range(lo, hi):
-            sorter.submit(bufs[i])
+            sorter.submit(bufs[i % P])
             if i > lo:
                 outs.append((i - 1, sorter.collect()))
         if hi > lo:
             outs.append((hi - 1, sorter.collect()))
         return outs
 
-    run_steps(0, W)
+    # ---- --full: verify the timed steps' outputs (outside the clock): the library's check kernel AND an independent torch
+    # reduction.  Returns (all verified, steps verified).
+    def verify(outs):
+        verified, steps_verified = True, 0
+        if not multi:
+            for i, o in outs:
+                v, s_, x_ = ctx.check(o, rids[i % P]) if pairs else ctx.check(o)   # pairs: order and key == rid
+                tv, ts, tm = torch_check(torch, o, rids[i % P] if pairs else None)
+                verified &= (v == 0 and s_ == checks0[i][1] and x_ == checks0[i][2] and tv == 0 and ts == checks0[i][1] and tm == 0)
+                steps_verified += 1
+        else:
+            # Every output still in a buffer (all timed steps when the memory allowed one work buffer each, else the last
+            # nkeep): sorted on its rank (two independent checks), key sum and xor of all ranks' outputs == those of all
+            # ranks' inputs, rank r's keys carry top bits r and follow rank r-1's (what the reference's check() verifies
+            # across its numa arrays, src/msb_64.c:2432-2505).
+            lg = N.bit_length() - 1
+            M64 = (1 << 64) - 1
+            for i, o in outs[-nkeep:]:
+                v, s_, x_ = ctx.check(o)
+                tv, ts, _ = torch_check(torch, o)
+                v += tv + (0 if ts == s_ else 1)
+                cnt = o.numel()
+                lo_k = (int(o[0].item()) & 0xFFFFFFFF) if cnt else -1
+                hi_k = (int(o[-1].item()) & 0xFFFFFFFF) if cnt else -1
+                # sums travel as two 32-bit halves in int64 (exact), xors and boundaries as they are
+                row = torch.tensor([v, cnt, s_ & 0xFFFFFFFF, s_ >> 32, x_ & 0xFFFFFFFF, x_ >> 32,
+                                    checks0[i][1] & 0xFFFFFFFF, checks0[i][1] >> 32, checks0[i][2] & 0xFFFFFFFF, checks0[i][2] >> 32,
+                                    lo_k, hi_k], dtype=torch.int64, device="cuda")
+                rows = [torch.empty_like(row) for _ in range(N)]
+                dist.all_gather(rows, row)
+                R = [r_.tolist() for r_ in rows]
+                ok = all(r_[0] == 0 for r_ in R) and sum(r_[1] for r_ in R) == N * n
+                s_out = sum(r_[2] + (r_[3] << 32) for r_ in R) & M64
+                s_in = sum(r_[6] + (r_[7] << 32) for r_ in R) & M64
+                x_out = x_in = 0
+                for r_ in R:
+                    x_out ^= r_[4] | (r_[5] << 32)
+                    x_in ^= r_[8] | (r_[9] << 32)
+                ok &= s_out == s_in and x_out == x_in
+                prev = -1
+                for g, r_ in enumerate(R):
+                    if r_[1]:
+                        ok &= (r_[10] >> (32 - lg)) == g and (r_[11] >> (32 - lg)) == g and r_[10] > prev
+                        prev = r_[11]
+                verified &= bool(ok)
+                if not ok:   # say what failed (rank 0's view), for the record
+                    fail_detail.append({"step": i, "violations_per_rank": [r_[0] for r_ in R], "keys_out": sum(r_[1] for r_ in R), "keys_in": N * n,
+                                        "sum_ok": s_out == s_in, "xor_ok": x_out == x_in, "first_last_per_rank": [(r_[10], r_[11]) for r_ in R]})
+                steps_verified += 1
+            flag = torch.tensor([1 if verified else 0], dtype=torch.int32, device="cuda")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            verified = bool(flag.item())
+        return verified, steps_verified
+
+    verified, steps_verified, fail_detail = True, 0, []
+    pooled = W + K > P
+    if not pooled:
+        fill(0, W + K)
+    for lo, hi in groups(0, W):
+        if pooled:
+            fill(lo, hi)
+        run_steps(lo, hi)
     torch.cuda.synchronize()
-    if multi:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    outs = run_steps(W, W + K)
-    torch.cuda.synchronize()
-    if multi:
-        dist.barrier()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt = 0.0
+    for lo, hi in groups(W, W + K):
+        if pooled:
+            fill(lo, hi)
+        torch.cuda.synchronize()
+        if multi:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = run_steps(lo, hi)
+        torch.cuda.synchronize()
+        if multi:
+            dist.barrier()
+        torch.cuda.synchronize()
+        dt += time.perf_counter() - t0
+        if args.full:   # before the next group overwrites the pool
+            v_, n_ = verify(outs)
+            verified &= v_
+            steps_verified += n_
     if multi:
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-
-    # ---- verify the timed steps' outputs (outside the clock): the library's check kernel AND an independent torch reduction
-    verified, steps_verified, fail_detail = True, 0, []
-    if not multi:
-        for i, o in outs:
-            v, s_, x_ = ctx.check(o, rids[i]) if pairs else ctx.check(o)   # pairs: order and key == rid
-            tv, ts, tm = torch_check(torch, o, rids[i] if pairs else None)
-            verified &= (v == 0 and s_ == checks0[i][1] and x_ == checks0[i][2] and tv == 0 and ts == checks0[i][1] and tm == 0)
-            steps_verified += 1
-    else:
-        # Every output still in a buffer (all timed steps when the memory allowed one work buffer each, else the last
-        # nkeep): sorted on its rank (two independent checks), key sum and xor of all ranks' outputs == those of all
-        # ranks' inputs, rank r's keys carry top bits r and follow rank r-1's (what the reference's check() verifies
-        # across its numa arrays, src/msb_64.c:2432-2505).
-        lg = N.bit_length() - 1
-        M64 = (1 << 64) - 1
-        for i, o in outs[-nkeep:]:
-            v, s_, x_ = ctx.check(o)
-            tv, ts, _ = torch_check(torch, o)
-            v += tv + (0 if ts == s_ else 1)
-            cnt = o.numel()
-            lo_k = (int(o[0].item()) & 0xFFFFFFFF) if cnt else -1
-            hi_k = (int(o[-1].item()) & 0xFFFFFFFF) if cnt else -1
-            # sums travel as two 32-bit halves in int64 (exact), xors and boundaries as they are
-            row = torch.tensor([v, cnt, s_ & 0xFFFFFFFF, s_ >> 32, x_ & 0xFFFFFFFF, x_ >> 32,
-                                checks0[i][1] & 0xFFFFFFFF, checks0[i][1] >> 32, checks0[i][2] & 0xFFFFFFFF, checks0[i][2] >> 32,
-                                lo_k, hi_k], dtype=torch.int64, device="cuda")
-            rows = [torch.empty_like(row) for _ in range(N)]
-            dist.all_gather(rows, row)
-            R = [r_.tolist() for r_ in rows]
-            ok = all(r_[0] == 0 for r_ in R) and sum(r_[1] for r_ in R) == N * n
-            s_out = sum(r_[2] + (r_[3] << 32) for r_ in R) & M64
-            s_in = sum(r_[6] + (r_[7] << 32) for r_ in R) & M64
-            x_out = x_in = 0
-            for r_ in R:
-                x_out ^= r_[4] | (r_[5] << 32)
-                x_in ^= r_[8] | (r_[9] << 32)
-            ok &= s_out == s_in and x_out == x_in
-            prev = -1
-            for g, r_ in enumerate(R):
-                if r_[1]:
-                    ok &= (r_[10] >> (32 - lg)) == g and (r_[11] >> (32 - lg)) == g and r_[10] > prev
-                    prev = r_[11]
-            verified &= bool(ok)
-            if not ok:   # say what failed (rank 0's view), for the record
-                fail_detail.append({"step": i, "violations_per_rank": [r_[0] for r_ in R], "keys_out": sum(r_[1] for r_ in R), "keys_in": N * n,
-                                    "sum_ok": s_out == s_in, "xor_ok": x_out == x_in, "first_last_per_rank": [(r_[10], r_[11]) for r_ in R]})
-            steps_verified += 1
-        flag = torch.tensor([1 if verified else 0], dtype=torch.int32, device="cuda")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        verified = bool(flag.item())
+    if args.dump_outputs:
+        i, o = outs[-1]
+        dump_outputs(torch, args.dump_outputs, o, rids[i % P] if pairs and not multi else None, rank, N)
 
     roofline, real, copy_gbps, mg = None, None, None, None
-    if not multi:
+    if args.full and not multi:
         r = bufs[0].clone() if pairs else None
         roofline, real = profile_one_sort(ctx, torch, cfg, args.config, n, gen, sort, bufs[0], r)
         del r
@@ -527,47 +612,48 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         copy_gbps = 5 * 2 * a.numel() * a.element_size() / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    else:
-        # ---- N > 1: what a step consists of, measured apart after the clock has stopped (3 repetitions, max over ranks):
-        # the local work alone (before + after the exchange, nothing in flight) and the exchange alone.  The timed loop
-        # overlaps them (ms_per_step); their sum is what it would cost without the overlap.
-        def max_over_ranks(ms):
-            x = torch.tensor([ms], dtype=torch.float64, device="cuda")
-            dist.all_reduce(x, op=dist.ReduceOp.MAX)
-            return float(x.item())
+    elif multi:
+        if args.full:
+            # ---- N > 1: what a step consists of, measured apart after the clock has stopped (3 repetitions, max over ranks):
+            # the local work alone (before + after the exchange, nothing in flight) and the exchange alone.  The timed loop
+            # overlaps them (ms_per_step); their sum is what it would cost without the overlap.
+            def max_over_ranks(ms):
+                x = torch.tensor([ms], dtype=torch.float64, device="cuda")
+                dist.all_reduce(x, op=dist.ReduceOp.MAX)
+                return float(x.item())
 
-        pre_ms, post_ms, xch_ms, xch_bytes = [], [], [], 0
-        for rep in range(3):
-            gen(bufs[0], 300 + rep)
-            torch.cuda.synchronize()
-            dist.barrier()
-            t1 = time.perf_counter()
-            sorter.submit(bufs[0])                      # pre-exchange pass + count exchange (blocks: the counts come to the host) + the all-to-all is STARTED
-            t2 = time.perf_counter()                    # (no device synchronisation here: it would wait for the exchange as well)
-            out_view, handles, _ = sorter._pending[0]
-            for h in handles or []:
-                h.wait()
-            torch.cuda.synchronize()
-            dist.barrier()
-            t3 = time.perf_counter()
-            sorter.collect()
-            torch.cuda.synchronize()
-            t4 = time.perf_counter()
-            pre_ms.append((t2 - t1) * 1e3)
-            xch_ms.append((t3 - t2) * 1e3)
-            post_ms.append((t4 - t3) * 1e3)
-            xch_bytes = out_view.numel() * out_view.element_size()   # (fine scheme: the keys' low halves, 2 bytes each)
+            pre_ms, post_ms, xch_ms, xch_bytes = [], [], [], 0
+            for rep in range(3):
+                gen(bufs[0], 300 + rep)
+                torch.cuda.synchronize()
+                dist.barrier()
+                t1 = time.perf_counter()
+                sorter.submit(bufs[0])                      # pre-exchange pass + count exchange (blocks: the counts come to the host) + the all-to-all is STARTED
+                t2 = time.perf_counter()                    # (no device synchronisation here: it would wait for the exchange as well)
+                out_view, handles, _ = sorter._pending[0]
+                for h in handles or []:
+                    h.wait()
+                torch.cuda.synchronize()
+                dist.barrier()
+                t3 = time.perf_counter()
+                sorter.collect()
+                torch.cuda.synchronize()
+                t4 = time.perf_counter()
+                pre_ms.append((t2 - t1) * 1e3)
+                xch_ms.append((t3 - t2) * 1e3)
+                post_ms.append((t4 - t3) * 1e3)
+                xch_bytes = out_view.numel() * out_view.element_size()   # (fine scheme: the keys' low halves, 2 bytes each)
+            mg = {"scheme": (f"fine (top 16 bits before the exchange, {sorter.last_format} travel, counting leaf over what arrived)"
+                             if fine else "coarse (top digit before the exchange)"),
+                     "local_before_exchange_ms": round(max_over_ranks(min(pre_ms)), 3),
+                     "local_after_exchange_ms": round(max_over_ranks(min(post_ms)), 3),
+                     "exchange_alone_ms": round(max_over_ranks(min(xch_ms)), 3),
+                     "note_before": "includes the count exchange (one all-gather + one small device-to-host copy) and the launch of the all-to-all; "
+                                    "the all-to-all then runs alone (not overlapped) and is what exchange_alone_ms times",
+                     "exchange_bytes_received_per_gpu": int(xch_bytes),
+                     "exchange_GBps_per_gpu_alone": round(xch_bytes / (max(min(xch_ms), 1e-6) * 1e-3) / 1e9, 1)}
         k_algo = algo_bytes_per_elem(cfg)
         sec = dt / K
-        mg = {"scheme": (f"fine (top 16 bits before the exchange, {sorter.last_format} travel, counting leaf over what arrived)"
-                         if fine else "coarse (top digit before the exchange)"),
-                 "local_before_exchange_ms": round(max_over_ranks(min(pre_ms)), 3),
-                 "local_after_exchange_ms": round(max_over_ranks(min(post_ms)), 3),
-                 "exchange_alone_ms": round(max_over_ranks(min(xch_ms)), 3),
-                 "note_before": "includes the count exchange (one all-gather + one small device-to-host copy) and the launch of the all-to-all; "
-                                "the all-to-all then runs alone (not overlapped) and is what exchange_alone_ms times",
-                 "exchange_bytes_received_per_gpu": int(xch_bytes),
-                 "exchange_GBps_per_gpu_alone": round(xch_bytes / (max(min(xch_ms), 1e-6) * 1e-3) / 1e9, 1)}
         # the `roofline` object of an N > 1 line: the whole per-GPU step against the HBM peak (algorithmic bytes as for one
         # GPU: the rank sorts 2^logn keys per step whatever their origin); the exchange is reported beside it
         roofline = {"bound": "hbm", "kernel": "whole per-GPU step (pre-exchange pass + counting leaf; exchange overlapped)",
@@ -594,14 +680,15 @@ def main():
                                                        " (REHEARSAL: gloo via host memory, all ranks on one GPU)" if rehearsal else ""),
         "config": {"workload": f"2^{args.logn} {cfg['title']} per GPU, in-place MSD radix sort, 8-bit digits" + how,
                    "config_id": args.config, "elements_per_gpu": n, "passes": cfg["passes_note"],
-                   "verified": bool(verified), "steps_verified": steps_verified, **({"verify_failures": fail_detail[:4]} if fail_detail else {}),
-                   "verified_by": "msd_check_* (device) and an independent chunked torch reduction (order, sum" + (", key == rid)" if pairs else ")"),
+                   "verified": bool(verified) if args.full else None, "steps_verified": steps_verified, **({"verify_failures": fail_detail[:4]} if fail_detail else {}),
+                   "verified_by": ("msd_check_* (device) and an independent chunked torch reduction (order, sum" + (", key == rid)" if pairs else ")")
+                                   if args.full else "not checked in a plain run (bench.py --full verifies every timed step)"),
                    "workspace_bytes": ctx.workspace_bytes},
         "whole_sort": whole_sort_block(cfg, n, dt / K, real, copy_gbps),
         "roofline": roofline,
     }
-    # ---- the other single-GPU configs in the same record (default run only): headline buffers are freed first
-    if not multi and args.config == "c2" and not args.no_other_configs and args.logn == 30:
+    # ---- the other single-GPU configs in the same record (full c2 run only): headline buffers are freed first
+    if args.full and not multi and args.config == "c2" and not args.no_other_configs and args.logn == 30:
         a = b = None
         del bufs, rids, outs, a, b
         torch.cuda.empty_cache()
@@ -613,7 +700,7 @@ def main():
                 others[cid] = {"error": f"{type(e).__name__}: {e}"}
         out["other_configs"] = others
     if rank == 0:
-        out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(args.cpu_logn, args.cpu_logn_1t)
+        out["cpu_baseline"] = None if args.no_cpu_baseline or not args.full else cpu_baseline(args.cpu_logn, args.cpu_logn_1t)
         print(json.dumps(out), flush=True)
     if multi:
         dist.barrier()            # the other ranks wait for rank 0's CPU baseline

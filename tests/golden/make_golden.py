@@ -11,6 +11,10 @@ section 8c), so these are outputs of the reference's own functions on seeded inp
 * golden_hist.npz        histogram(keys, shift, radix_bits)     src/msb_64.c:701
 * golden_partition.npz   histogram + partition_ip / partition_ip_buf  :740 / :785
 * golden_c1_digest.json  sha256 of the sorted 2^20 uniform u32 keys of config C1
+* golden_ref_outputs.json  what the reference returns on the inputs of the tests that compare
+                         the oracle with it (tests/test_oracle.py, the duplicate rule in
+                         tests/test_dist_gloo.py): sha256 of single-thread core, histogram,
+                         partition and rand.c outputs, extract_delimiters as they are
 """
 import hashlib
 import json
@@ -62,8 +66,39 @@ def main():
     json.dump({"n": 1 << 20, "seed": 0x5EED0001, "sha256_sorted": hashlib.sha256(out.tobytes()).hexdigest(),
                "sum": int(out.astype(np.uint64).sum()), "first": out[:4].tolist(), "last": out[-4:].tolist()},
               open(os.path.join(HERE, "golden_c1_digest.json"), "w"))
+    ref_outputs()
     print("golden vectors written")
 
 
+def ref_outputs():
+    """golden_ref_outputs.json, from the inputs the tests themselves build."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle as T
+    import test_dist_gloo as D
+    rec = {"restatement": {}, "histogram": {}, "partition": {}, "splitters": {}, "mt19937_64": {}}
+    for n in T.RESTATEMENT_N:
+        for bits, kind in T.RESTATEMENT_KINDS:
+            k, r = T.restatement_input(n, bits, kind)
+            rk, rr = O.ref_sort_pairs_u64(k, r, bits)
+            rec["restatement"][f"{n},{bits},{kind}"] = {"keys_in": T.digest(k), "keys": T.digest(rk), "rids": T.digest(rr)}
+    k, r = T.hist_partition_input()
+    for shift, rb in T.HIST_CASES:
+        rec["histogram"][f"{shift},{rb}"] = T.digest(O.ref_histogram(k, shift, rb))
+    for shift, rb, buf in T.PARTITION_CASES:
+        rec["partition"][f"{shift},{rb},{int(buf)}"] = [T.digest(x) for x in O.ref_partition(k, r, shift, rb, buf)]
+    for kind, parts in T.SPLITTER_CASES:
+        _, smp = T.splitter_sample(kind)
+        rec["splitters"][f"{kind},{parts}"] = O.ref_extract_delimiters(smp, parts).tolist()
+    for seed in T.MT_SEEDS:
+        rec["mt19937_64"][str(seed)] = T.digest(O.ref_mt19937_64(1000, seed))
+    smp, parts = D.duplicate_rule_sample()
+    rec["duplicate_rule"] = O.ref_extract_delimiters(smp, parts).tolist()
+    json.dump(rec, open(os.path.join(HERE, "golden_ref_outputs.json"), "w"), indent=0)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref_outputs"]:
+        assert O.have_ref(), "reference library not built"
+        ref_outputs()
+    else:
+        main()

@@ -1,6 +1,7 @@
 """world_size-2 and -4 gloo tests (CPU) of the multi-GPU exchange logic: the same
 ``sort_sharded_u32`` the GPU bench calls, with a numpy stand-in engine (test
 infrastructure) in place of the HIP context."""
+import json
 import os
 import socket
 import sys
@@ -473,20 +474,29 @@ def test_receive_overflow_is_raised_on_every_rank():
         assert len(res[r]) == 3 and all("receive buffer too small on rank(s) 0:" in m for m in res[r]), res[r]
 
 
+def duplicate_rule_sample():
+    from oracle import oracle as O
+    return np.sort(O.gen_zipf_u32(4000, seed=3).astype(np.uint64)), 8
+
+
 def test_splitters_follow_the_reference_duplicate_rule():
+    """splitters_equi_depth == the reference's extract_delimiters on the same sorted sample: the delimiters it returned
+    are recorded in tests/golden/golden_ref_outputs.json (tests/golden/make_golden.py), and the live reference is asked
+    as well when oracle/_ref is built."""
     from inplacemsdradixsort_amd.dist import splitters_equi_depth
     from oracle import oracle as O
-    if not O.have_ref():
-        pytest.skip("needs oracle/_ref")
-    import ctypes as C
-    s = np.sort(O.gen_zipf_u32(4000, seed=3).astype(np.uint64))
-    parts = 8
-    delim = np.zeros(parts, np.uint64)
-    delim[parts - 1] = np.uint64(2**64 - 1)  # terminator the reference scans for (src/msb_64.c:1307)
-    L = O.ref().lib
-    L.extract_delimiters.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]
-    L.extract_delimiters(s.ctypes.data_as(C.POINTER(C.c_uint64)), s.size, delim.ctypes.data_as(C.POINTER(C.c_uint64)))
-    assert splitters_equi_depth(s, parts) == delim[:parts - 1].tolist()
+    s, parts = duplicate_rule_sample()
+    got = splitters_equi_depth(s, parts)
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "golden_ref_outputs.json")))
+    assert got == rec["duplicate_rule"]
+    if O.have_ref():
+        import ctypes as C
+        delim = np.zeros(parts, np.uint64)
+        delim[parts - 1] = np.uint64(2**64 - 1)  # terminator the reference scans for (src/msb_64.c:1307)
+        L = O.ref().lib
+        L.extract_delimiters.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]
+        L.extract_delimiters(s.ctypes.data_as(C.POINTER(C.c_uint64)), s.size, delim.ctypes.data_as(C.POINTER(C.c_uint64)))
+        assert got == delim[:parts - 1].tolist()
 
 
 def _wide_worker(rank, world, port, n, pairs, q):

@@ -111,13 +111,22 @@ def test_generators_are_the_survey_ones():
     assert 0.70 < (z < (1 << 24)).mean() < 0.80  # ~75 % of keys have a zero top byte
 
 
-needs_ref = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
+# Outputs of the reference's own functions on the inputs below, recorded by tests/golden/make_golden.py (sha256 of the
+# little-endian u64 arrays, delimiters as they are): every test compares with the record, and with the live reference
+# as well when oracle/_ref is built.
+def ref_record(part):
+    return json.load(open(os.path.join(G, "golden_ref_outputs.json")))[part]
 
 
-@needs_ref
-@pytest.mark.parametrize("n", [1, 21, 4096, 6501, 1 << 16, (1 << 18) + 7])
-@pytest.mark.parametrize("bits,kind", [(32, "u32"), (64, "u64"), (58, "u58"), (32, "dup"), (32, "skew")])
-def test_restatement_equals_reference(n, bits, kind):
+def digest(a) -> str:
+    return hashlib.sha256(np.ascontiguousarray(a, dtype="<u8").tobytes()).hexdigest()
+
+
+RESTATEMENT_N = [1, 21, 4096, 6501, 1 << 16, (1 << 18) + 7]
+RESTATEMENT_KINDS = [(32, "u32"), (64, "u64"), (58, "u58"), (32, "dup"), (32, "skew")]
+
+
+def restatement_input(n, bits, kind):
     rng = np.random.default_rng(n * 7 + bits)
     if kind == "u32":
         k = rng.integers(0, 2**32, n, dtype=np.uint64)
@@ -129,32 +138,52 @@ def test_restatement_equals_reference(n, bits, kind):
         k = rng.integers(0, 256, n, dtype=np.uint64) * np.uint64(0x01010101)
     else:
         k = (rng.random(n) ** 8 * 2**32).astype(np.uint64)
-    r = np.arange(n, dtype=np.uint64)
+    return k, np.arange(n, dtype=np.uint64)
+
+
+@pytest.mark.parametrize("n", RESTATEMENT_N)
+@pytest.mark.parametrize("bits,kind", RESTATEMENT_KINDS)
+def test_restatement_equals_reference(n, bits, kind):
+    k, r = restatement_input(n, bits, kind)
     ok, orr = O.sort_pairs_u64(k, r, bits)
-    rk, rr = O.ref_sort_pairs_u64(k, r, bits)
-    assert (ok == rk).all() and (ok == np.sort(k)).all()
-    assert (orr == rr).all()
+    assert (ok == np.sort(k)).all()
+    rec = ref_record("restatement")[f"{n},{bits},{kind}"]
+    assert digest(k) == rec["keys_in"]                    # the recorded input, not a different one
+    assert digest(ok) == rec["keys"] and digest(orr) == rec["rids"]
+    if O.have_ref():
+        rk, rr = O.ref_sort_pairs_u64(k, r, bits)
+        assert (ok == rk).all()
+        assert (orr == rr).all()
 
 
-@needs_ref
-def test_histogram_and_partition_equal_reference():
+HIST_CASES = ((56, 8), (0, 8), (30, 9), (61, 3))
+PARTITION_CASES = ((56, 8, True), (55, 9, True), (59, 5, False), (61, 3, False))
+
+
+def hist_partition_input():
     k = O.gen_uniform_u64(50000, seed=5)
-    r = np.arange(k.size, dtype=np.uint64)
-    for shift, rb in ((56, 8), (0, 8), (30, 9), (61, 3)):
-        assert (O.histogram(k, shift, rb) == O.ref_histogram(k, shift, rb)).all()
-    for shift, rb, buf in ((56, 8, True), (55, 9, True), (59, 5, False), (61, 3, False)):
+    return k, np.arange(k.size, dtype=np.uint64)
+
+
+def test_histogram_and_partition_equal_reference():
+    k, r = hist_partition_input()
+    for shift, rb in HIST_CASES:
+        h = O.histogram(k, shift, rb)
+        assert digest(h) == ref_record("histogram")[f"{shift},{rb}"]
+        if O.have_ref():
+            assert (h == O.ref_histogram(k, shift, rb)).all()
+    for shift, rb, buf in PARTITION_CASES:
         a = O.partition(k, r, shift, rb, buf)
-        b = O.ref_partition(k, r, shift, rb, buf)
-        assert all((x == y).all() for x, y in zip(a, b))
+        assert [digest(x) for x in a] == ref_record("partition")[f"{shift},{rb},{int(buf)}"]
+        if O.have_ref():
+            b = O.ref_partition(k, r, shift, rb, buf)
+            assert all((x == y).all() for x, y in zip(a, b))
 
 
-@pytest.mark.parametrize("kind,parts", [("zipf", 2), ("zipf", 8), ("zipf", 64), ("uniform", 8), ("dup", 8), ("const", 4)])
-def test_splitter_front_end_equals_reference(kind, parts):
-    """extract_delimiters (src/msb_64.c:1304-1322) restated in the oracle == the reference's own, on sorted samples
-    drawn the way the build draws them (mulhi(rand64, n) indices, :1511-1521); the range function (:188-204) agrees
-    with numpy's lower bound."""
-    if not O.have_ref():
-        pytest.skip("needs oracle/_ref")
+SPLITTER_CASES = [("zipf", 2), ("zipf", 8), ("zipf", 64), ("uniform", 8), ("dup", 8), ("const", 4)]
+
+
+def splitter_sample(kind):
     n, m = 200000, 5000
     if kind == "zipf":
         k = O.gen_zipf_u32(n, seed=11)
@@ -164,18 +193,33 @@ def test_splitter_front_end_equals_reference(kind, parts):
         k = (O.gen_uniform_u32(n, seed=13) % 5).astype(np.uint32) * 1000
     else:
         k = np.full(n, 77, np.uint32)
-    s = np.sort(O.sample_u32(k, m, seed=99)).astype(np.uint64)
+    return k, np.sort(O.sample_u32(k, m, seed=99)).astype(np.uint64)
+
+
+@pytest.mark.parametrize("kind,parts", SPLITTER_CASES)
+def test_splitter_front_end_equals_reference(kind, parts):
+    """extract_delimiters (src/msb_64.c:1304-1322) restated in the oracle == the reference's own, on sorted samples
+    drawn the way the build draws them (mulhi(rand64, n) indices, :1511-1521); the range function (:188-204) agrees
+    with numpy's lower bound."""
+    k, s = splitter_sample(kind)
+    n = k.size
     d = O.extract_delimiters(s, parts)
-    assert (d == O.ref_extract_delimiters(s, parts)).all()
+    assert d.tolist() == ref_record("splitters")[f"{kind},{parts}"]
+    if O.have_ref():
+        assert (d == O.ref_extract_delimiters(s, parts)).all()
     cnt = O.range_histogram_u32(k, d)
     assert int(cnt.sum()) == n and (cnt == np.bincount(O.range_of_u32(k, d), minlength=parts)).all()
 
 
+MT_SEEDS = (0, 1, 0x5EED0001, 2**64 - 1)
+
+
 def test_mt19937_64_restatement_equals_reference_rand_c():
     """src/rand.c:47-86 restated in the oracle == the reference's rand64_init / rand64_next (across a block boundary)."""
-    if not O.have_ref():
-        pytest.skip("needs oracle/_ref")
-    for seed in (0, 1, 0x5EED0001, 2**64 - 1):
-        assert (O.mt19937_64(1000, seed) == O.ref_mt19937_64(1000, seed)).all()
+    for seed in MT_SEEDS:
+        m = O.mt19937_64(1000, seed)
+        assert digest(m) == ref_record("mt19937_64")[str(seed)]
+        if O.have_ref():
+            assert (m == O.ref_mt19937_64(1000, seed)).all()
     # known-answer: std::mt19937_64's 10000th output for the default seed 5489 (the C++ standard pins it)
     assert int(O.mt19937_64(10000, 5489)[-1]) == 9981545732273789042
