@@ -269,15 +269,11 @@ int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, 
  *   Rounds after the first follow (from exact per-parent digit counts) if the first round did.
  * "direct_min": smallest round (elements) direct placement is tried on (default 2^22).
  * "direct_min_parent": rounds after the first: smallest parent segment (default 2^17).
- * "direct_kernel": accepted and ignored (round 1's first version of the direct kernel is gone;
- *   profiles/r02_sq_counters.json and r02_stamps_classify_direct_before.json keep its measurements).
  * "count16": u32 keys with 16 open bits: 1 (default) = count_place16_kernel for segments of about 2^14
  *   keys, 2 = always, 0 = never (count_place_kernel).
  * "leaf17": u64 keys and tuples: 1 (default) = segments of <= 17408 elements are finished in one pass by leaf17_kernel (read
  *   once, sorted in registers and LDS, written once), 0 = tuples: register partition + the small leaves, u64 keys:
  *   leaf_count_sort_kernel (round 2).
- * "stream_kernel": the streaming classify of rounds that do not place directly: 2 (default) = classify_stream2_kernel
- *   (one fetch-add per key, no per-key second pass), 1 = round 2's classify_kernel.
  * "mid_leaf": u32 keys: 1 (default) = counting-leaf segments the register-resident kernels do not take (17 Ki .. 128 Ki
  *   keys, crowded ones) are finished by the 16-bit-counter leaf (merge_count_kernel) instead of count_walk_kernel; 0 = never.
  * "merge_leaf": msd_merge_buckets_u32: 0 (default) = by bucket size, 1 = the register-resident leaf, 2 = the 16-bit-counter leaf.

@@ -6,11 +6,11 @@
 // cycle-leader swap with fetch-add claims, :1220-1302 combine/inject) rather
 // than its single sequential cycle (partition_ip_buf, :785-978):
 //
-//   A  classify_kernel   each workgroup streams its stripe through LDS, appends
-//                        keys to 256 per-bucket LDS buffers (rank = LDS fetch-add)
-//                        and flushes every full buffer as one aligned 256-byte
-//                        block BEHIND its own read cursor; the digit histogram
-//                        falls out of this pass (no separate counting read).
+//   A  classify_stream2_kernel (msd_stream2.hpp)  each workgroup streams its
+//                        stripe through registers into 256 per-bucket LDS buffers
+//                        (rank = LDS fetch-add) and flushes every full buffer as one
+//                        aligned 256-byte block BEHIND its own read cursor; the digit
+//                        histogram falls out of this pass (no separate counting read).
 //   B  chains_kernel     block-granular permutation: a lane owns a hole, claims
 //                        the next misplaced block of the hole's bucket with a
 //                        fetch-add on that bucket's list cursor, moves it into
@@ -135,7 +135,7 @@ static_assert(sizeof(Counters) % 8 == 0, "the words behind the counters are used
 // -DMSD_STAMPS (tools/stamps_build.sh, never the shipped library): wave 0 (a "bucket wave") and the last wave of
 // every classify_direct workgroup add the shader cycles they spend in each section of the tile loop to
 // g_stamps[which wave][section]; read back with msd_debug_stamps().
-#ifdef MSD_STAMPS // = 1: classify_direct kernels, 2: count_place kernels, 3: leaf_count_sort_kernel, 4/5: bigcount write/hist, 6: classify_kernel
+#ifdef MSD_STAMPS // = 1: classify_direct kernels, 2: count_place kernels, 3: leaf_count_sort_kernel, 4/5: bigcount write/hist, 6: classify_stream2_kernel
 __device__ unsigned long long g_stamps[2][16];
 #define MSD_STAMP_DECL(id)                          \
 	constexpr bool kStampThis = MSD_STAMPS == (id); \
@@ -270,373 +270,6 @@ __device__ __forceinline__ uint64_t block_excl_scan256_64(uint64_t v, uint64_t *
 template <typename K> struct Vec16;
 template <> struct Vec16<uint32_t> { static constexpr int N = 4; };
 template <> struct Vec16<uint64_t> { static constexpr int N = 2; };
-
-// ------------------------------------------------------------ A: classify
-
-template <typename K, typename V> struct ClassifyLds {
-	using C = Cfg<K, V>;
-	static constexpr bool HV = has_val<V>::value;
-	static constexpr size_t kbuf = (size_t)(kP * C::B) * sizeof(K); // per-bucket partial buffers
-	static constexpr size_t vbuf = HV ? (size_t)(kP * C::B) * sizeof(uint64_t) : 0;
-	static constexpr size_t head = (size_t)C::B * sizeof(K) + (HV ? (size_t)C::B * sizeof(uint64_t) : 0);
-	static constexpr int JOBS = kP + 8;
-	// meta, cnt, hc, loff : 4*kP u32 ; jobs ; tmp 16
-	static constexpr size_t small = (size_t)(4 * kP + JOBS + 16 + 64 + 64) * sizeof(uint32_t);
-	static constexpr size_t bytes = kbuf + vbuf + head + small;
-};
-
-// RANGE: the bucket of a key is not a digit but its range among `splitters` (2^width - 1 ascending delimiters,
-// padded with the largest key): bucket p = number of delimiters < key, i.e. range p holds the keys in
-// (delim[p-1], delim[p]] -- the reference's lower-bound range function (binary_search_64, src/msb_64.c:188-204;
-// SIMD form :239-351).  Everything behind the classification (blocks, maps, permutation) is the same.
-template <typename K, typename V, bool RANGE = false>
-__global__ __launch_bounds__((Cfg<K, V>::TH), (Cfg<K, V>::TH >= 1024 ? (has_val<V>::value ? 4 : 8) : 1)) void classify_kernel(
-	K *__restrict__ keys, uint64_t *__restrict__ vals, const Stripe *__restrict__ stripes,
-	const Parent *__restrict__ parents, uint8_t *__restrict__ block_map,
-	uint32_t *__restrict__ fb, uint32_t *__restrict__ lo_cnt, uint32_t *__restrict__ lo_off,
-	K *__restrict__ lo_keys, uint64_t *__restrict__ lo_vals, uint32_t *__restrict__ nfull,
-	const K *__restrict__ splitters = nullptr,
-	// launched behind a direct-placement attempt: runs only if that declined (Counters::direct_uneven != 0) -- the
-	// decision stays on the device, the host does not wait for it
-	const uint32_t *__restrict__ run_if_nonzero = nullptr)
-{
-	if (run_if_nonzero && *run_if_nonzero == 0) return;
-	using C = Cfg<K, V>;
-	constexpr bool HV = has_val<V>::value;
-	constexpr int B = C::B, T = C::T, TH = C::TH;
-	constexpr int VEC = Vec16<K>::N;
-	constexpr int KPT = T / TH;    // keys per thread per tile
-	constexpr int NV = KPT / VEC;  // 16-byte vectors per thread per tile
-	constexpr int LPB = B / VEC;   // lanes that move one block
-	constexpr int PB = kP * B;
-	static_assert(KPT % VEC == 0 && NV >= 1, "tile geometry");
-	using L = ClassifyLds<K, V>;
-
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	K *kbuf = reinterpret_cast<K *>(smem); // [0,PB) partial buffers
-	uint64_t *vbuf = reinterpret_cast<uint64_t *>(smem + L::kbuf);
-	K *headk = reinterpret_cast<K *>(smem + L::kbuf + L::vbuf);
-	uint64_t *headv = reinterpret_cast<uint64_t *>(smem + L::kbuf + L::vbuf + (size_t)B * sizeof(K));
-	uint32_t *meta = reinterpret_cast<uint32_t *>(smem + L::kbuf + L::vbuf + L::head);
-	uint32_t *cnt = meta + kP;   // tile count per bucket
-	uint32_t *hc = cnt + kP;     // head keys per bucket
-	uint32_t *loff = hc + kP;    // leftover offsets
-	uint32_t *jobs = loff + kP;  // flush job table: bucket whose buffer goes to slot wslot+g
-	uint32_t *tmp = jobs + L::JOBS; // [0..1] slots | jobs << 16 claimed per tile (ping-pong), [4..7] scan scratch, [8..9] skew
-	uint32_t *multi = tmp + 16;     // buckets that completed more than one block in this tile: bucket | blocks << 8 | first slot << 16
-	uint32_t *spare = multi + 64;   // a word per lane that only ever receives zeros
-	K *spl = reinterpret_cast<K *>(smem + L::bytes); // RANGE only: the delimiters (the launch adds kP keys of LDS)
-
-	const uint32_t tid = threadIdx.x;
-	const Stripe st = stripes[blockIdx.x];
-	const Parent pa = parents[st.parent];
-	const uint32_t shift = pa.shift, mask = (1u << pa.width) - 1u;
-	if constexpr (RANGE) {
-		if (tid < kP) spl[tid] = tid < pa.pad ? splitters[tid] : ~(K)0; // pa.pad: number of delimiters
-	}
-	// bucket of a key: digit, or number of delimiters below it (branch-free binary search in LDS)
-	auto digit_of = [&](K key, uint32_t sh, uint32_t mk) -> uint32_t {
-		if constexpr (RANGE) {
-			uint32_t p = 0;
-			for (uint32_t step = (mk + 1u) >> 1; step; step >>= 1)
-				if (spl[p + step - 1u] < key) p += step;
-			return p;
-		} else
-			return msd::digit_of(key, sh, mk);
-	};
-
-	if (tid < kP) {
-		meta[tid] = 0;
-		cnt[tid] = 0;
-		hc[tid] = 0;
-	}
-	if (tid < 16) tmp[tid] = 0;
-	if (tid < 64) spare[tid] = 0;
-	const uint64_t a0 = (uint64_t)st.slot_lo * B; // first aligned position >= begin
-	// ---- head keys (only a parent's first stripe has them): parked in LDS until the end
-	const uint32_t h = (uint32_t)((a0 < st.end ? a0 : st.end) - st.begin);
-	if (tid < h) {
-		headk[tid] = keys[st.begin + tid];
-		if (HV) headv[tid] = vals[st.begin + tid];
-	}
-	__syncthreads();
-	if (tid < h) atomicAdd(&hc[digit_of(headk[tid], shift, mask)], 1u);
-
-	uint32_t wslot = st.slot_lo; // next output slot (uniform)
-	uint32_t fill_r = 0;         // thread d<kP: fill of bucket d (register copy)
-	uint32_t fb_r = 0;
-
-	K kreg[KPT];
-	uint64_t vreg[HV ? KPT : 1];
-	// remainders of buckets flushed in the previous tile: written during this tile's scatter
-	K dkey[KPT];
-	uint64_t dval[HV ? KPT : 1];
-	uint32_t dat[KPT];
-#pragma unroll
-	for (int i = 0; i < KPT; ++i) dat[i] = 0xFFFFFFFFu;
-
-	// (uniform 64-bit base + 32-bit per-thread offset: a per-thread 64-bit index would be kept in two
-	// registers across the tile loop, spilled, and its reload would wait for the prefetch in flight)
-	auto load_tile = [&](uint64_t pos, K *kr, uint64_t *vr) {
-		const K *kp = keys + pos;
-		const uint64_t *vp = vals + pos;
-		const uint32_t rem = pos < st.end ? (uint32_t)(st.end - pos < (uint64_t)T ? st.end - pos : (uint64_t)T) : 0u;
-#pragma unroll
-		for (int v = 0; v < NV; ++v) {
-			const uint32_t off = (uint32_t)(v * TH + tid) * VEC;
-			if (off + VEC <= rem) {
-				if constexpr (sizeof(K) == 4) {
-					const uint4 q = *reinterpret_cast<const uint4 *>(kp + off);
-					kr[v * VEC + 0] = q.x; kr[v * VEC + 1] = q.y; kr[v * VEC + 2] = q.z; kr[v * VEC + 3] = q.w;
-				} else {
-					const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(kp + off);
-					kr[v * VEC + 0] = q.x; kr[v * VEC + 1] = q.y;
-				}
-				if constexpr (HV) {
-					const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(vp + off);
-					vr[v * VEC + 0] = q.x; vr[v * VEC + 1] = q.y;
-				}
-			} else {
-#pragma unroll
-				for (int e = 0; e < VEC; ++e) {
-					if (off + e < rem) {
-						kr[v * VEC + e] = kp[off + e];
-						if constexpr (HV) vr[v * VEC + e] = vp[off + e];
-					}
-				}
-			}
-		}
-	};
-
-	uint64_t pos = a0;
-	K kregB[KPT];
-	uint64_t vregB[HV ? KPT : 1];
-	if (pos < st.end) load_tile(pos, kreg, vreg);
-	if (pos + T < st.end) load_tile(pos + T, kregB, vregB);
-	uint32_t par = 0; // tile parity: which pair of claim counters is live
-	MSD_STAMP_DECL(6);
-	MSD_STAMP_START();
-
-	// One tile: [ranks] B1 [per-bucket bookkeeping] B2 [scatter] B3 [prefetch tile t+2 into the
-	// registers this tile just vacated] [flush].  Two register sets alternate (no copies), so a load
-	// is issued two tiles before its first use and, like the flush stores, a whole tile before the
-	// explicit vmcnt(0) (vmcnt counts loads and stores together).  The flush of tile t overlaps the
-	// rank phase of tile t+1; nothing it reads is written before B2 of tile t+1.
-	auto tile = [&](K (&kc)[KPT], uint64_t (&vc)[HV ? KPT : 1]) {
-		const uint64_t npos = pos + T;
-		const bool full = npos <= st.end;                  // uniform: every key of the tile exists
-		MSD_STAMP(9);
-		MSD_STAMP_TICK(11);
-
-		// ---- rank every key inside its bucket for this tile (LDS fetch-add)
-		uint32_t dr[KPT]; // digit | rank<<8
-		const uint32_t hflag = tmp[8 + (par ^ 1)];
-		if (full && hflag && sizeof(K) == 4) {
-			// the previous tile was skewed -- bucket hflag - 1 took more than a sixteenth of it: the lanes of a wave that
-			// hold a key of that bucket take ONE fetch-add together (a same-address LDS atomic serialises per lane), their
-			// first lane for all of them.  Branch-free, all fetch-adds of the tile before the first result is looked at:
-			// a lane whose key is counted by another one adds zero to its own spare word.
-			const uint32_t h = hflag - 1u;
-			uint32_t old[KPT];
-			uint64_t hm[KPT];
-#pragma unroll
-			for (int i = 0; i < KPT; ++i) {
-				const uint32_t d = digit_of(kc[i], shift, mask);
-				hm[i] = __ballot(d == h);
-				const bool rides = d == h && popc_below_lane(hm[i]) != 0;
-				uint32_t *at = rides ? spare + lane_id() : cnt + d;
-				old[i] = atomicAdd(at, rides ? 0u : (d == h ? (uint32_t)__popcll(hm[i]) : 1u));
-				dr[i] = d;
-			}
-			__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-			for (int i = 0; i < KPT; ++i) {
-				const int lead = hm[i] ? __ffsll((long long)hm[i]) - 1 : 0;
-				const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)old[i], lead);
-				dr[i] |= (dr[i] == h ? base + popc_below_lane(hm[i]) : old[i]) << 8;
-			}
-		} else if (full && hflag) {
-			// (8-byte keys: the batched form above spills at this kernel's register budget) lanes that share lane 0's
-			// digit take one fetch-add together
-#pragma unroll
-			for (int i = 0; i < KPT; ++i) {
-				const uint32_t d = digit_of(kc[i], shift, mask);
-				const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
-				const uint64_t same = __ballot(d == d0);
-				uint32_t r;
-				if (__popcll(same) >= 8) {
-					uint32_t base = 0;
-					if (lane_id() == 0) base = atomicAdd(&cnt[d0], (uint32_t)__popcll(same));
-					base = __builtin_amdgcn_readfirstlane(base);
-					r = d == d0 ? base + popc_below_lane(same) : atomicAdd(&cnt[d], 1u);
-				} else
-					r = atomicAdd(&cnt[d], 1u);
-				dr[i] = d | (r << 8);
-			}
-		} else if (full) {
-#pragma unroll
-			for (int i = 0; i < KPT; ++i) {
-				const uint32_t d = digit_of(kc[i], shift, mask);
-				dr[i] = d | (atomicAdd(&cnt[d], 1u) << 8);
-			}
-		} else {
-			const uint32_t rem = (uint32_t)(st.end - pos); // < T here (partial last tile)
-#pragma unroll
-			for (int i = 0; i < KPT; ++i) {
-				const uint32_t off = (uint32_t)((i / VEC) * TH + tid) * VEC + (i % VEC);
-				dr[i] = 0xFFFFFFFFu;
-				if (off < rem) {
-					const uint32_t d = digit_of(kc[i], shift, mask);
-					dr[i] = d | (atomicAdd(&cnt[d], 1u) << 8);
-				}
-			}
-		}
-		MSD_STAMP(0); // ranks (incl. the wait for the keys)
-		__syncthreads(); // B1
-		MSD_STAMP(1);
-
-		// ---- per bucket: blocks completed by this tile claim consecutive output slots
-		if (tid < kP) {
-			const uint32_t ct = cnt[tid];
-			if (ct > (uint32_t)T / 16) tmp[8 + par] = 1u + tid; // skewed tile: the next one counts this bucket's keys per wave
-			const uint32_t L_r = fill_r + ct;
-			cnt[tid] = 0;
-			const uint32_t nb_r = L_r / B;
-			uint32_t bbase = 0;
-			if (nb_r) {
-				// ONE fetch-add claims the slots wslot+bbase .. +nb_r-1 (low half) and a place in the job table (high half);
-				// the bucket's LDS buffer becomes the first block, further ones (skewed tiles only) are written straight
-				// from registers; the flush writes the map entries of all of them
-				const uint32_t claim = atomicAdd(&tmp[par], nb_r | 0x10000u);
-				bbase = claim & 0xFFFFu;
-				jobs[claim >> 16] = tid | (bbase << 8);
-				if (nb_r > 1) multi[atomicAdd(&tmp[10 + par], 1u)] = tid | (nb_r << 8) | (bbase << 16);
-			}
-			meta[tid] = fill_r | (nb_r << 8) | (bbase << 20);
-			fill_r = L_r - nb_r * B;
-			fb_r += nb_r;
-		}
-		if (tid == 0) { // the other parity's counters were last read before B1
-			tmp[par ^ 1] = 0;
-			tmp[8 + (par ^ 1)] = 0;
-			tmp[10 + (par ^ 1)] = 0;
-		}
-		MSD_STAMP(2); // bookkeeping
-		__syncthreads(); // B2
-		MSD_STAMP(3);
-		const uint32_t nbtot = tmp[par] & 0xFFFFu, njobs = tmp[par] >> 16, nmulti = tmp[10 + par];
-
-		// ---- scatter: first the remainders deferred from the previous tile, then this tile's keys
-#pragma unroll
-		for (int i = 0; i < KPT; ++i) {
-			if (dat[i] != 0xFFFFFFFFu) {
-				kbuf[dat[i]] = dkey[i];
-				if constexpr (HV) vbuf[dat[i]] = dval[i];
-				dat[i] = 0xFFFFFFFFu;
-			}
-		}
-		uint32_t mt[KPT]; // (all look-ups before the first use: one LDS round trip, not one per key)
-		if constexpr (sizeof(K) == 4) { // (8-byte keys: spills at this kernel's register budget)
-#pragma unroll
-			for (int i = 0; i < KPT; ++i) mt[i] = meta[dr[i] & 0xFFu];
-		}
-#pragma unroll
-		for (int i = 0; i < KPT; ++i) {
-			if (dr[i] != 0xFFFFFFFFu) {
-				const uint32_t d = dr[i] & 0xFFu, r = dr[i] >> 8;
-				const uint32_t m = sizeof(K) == 4 ? mt[i] : meta[d];
-				const uint32_t vp = (m & 0xFFu) + r, nb = (m >> 8) & 0xFFFu;
-				if (nb == 0 || vp < (uint32_t)B) { // tops up the bucket's buffer
-					kbuf[d * B + vp] = kc[i];
-					if constexpr (HV) vbuf[d * B + vp] = vc[i];
-				} else if (vp < nb * B) { // skewed tile: a further whole block of this bucket, straight to its slot
-					const uint64_t at = (uint64_t)(wslot + (m >> 20)) * B + vp;
-					keys[at] = kc[i];
-					if constexpr (HV) vals[at] = vc[i];
-				} else { // remainder of a flushed bucket: its buffer is still being flushed, park it
-					dat[i] = d * B + vp - nb * B;
-					dkey[i] = kc[i];
-					if constexpr (HV) dval[i] = vc[i];
-				}
-			}
-		}
-		MSD_STAMP(4); // scatter
-		__syncthreads(); // B3
-		MSD_STAMP(5);
-
-		// ---- everything outstanding is a tile old: drain it, then refill the vacated registers
-		__builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
-		MSD_STAMP(6); // drain
-		if (npos + T < st.end) load_tile(npos + T, kc, vc);
-		MSD_STAMP(7); // refill issue
-
-		// ---- flush the completed buffers to their slots behind the read cursor
-		for (uint32_t g = tid / LPB; g < njobs; g += TH / LPB) {
-			const uint32_t j = jobs[g], slot = j >> 8;
-			const uint32_t src = (j & 0xFFu) * B + (tid % LPB) * VEC;
-			const uint64_t dst = (uint64_t)(wslot + slot) * B + (tid % LPB) * VEC;
-			*reinterpret_cast<uint4 *>(keys + dst) = *reinterpret_cast<const uint4 *>(kbuf + src);
-			if constexpr (HV)
-				*reinterpret_cast<uint4 *>(vals + dst) = *reinterpret_cast<const uint4 *>(vbuf + src);
-			if ((tid % LPB) == 0) block_map[wslot + slot] = (uint8_t)(j & 0xFFu);
-		}
-		for (uint32_t e = 0; e < nmulti; ++e) { // (skewed tiles only) the map entries of a bucket's further blocks
-			const uint32_t m = multi[e], nb = (m >> 8) & 0xFFu;
-			for (uint32_t q = tid; q + 1u < nb; q += TH) block_map[wslot + (m >> 16) + 1u + q] = (uint8_t)(m & 0xFFu);
-		}
-		wslot += nbtot;
-		pos = npos;
-		par ^= 1;
-		MSD_STAMP(8); // flush
-	};
-	while (pos < st.end) {
-		tile(kreg, vreg);
-		if (pos >= st.end) break;
-		tile(kregB, vregB);
-	}
-	MSD_STAMP_FLUSH(TH / 64);
-	__syncthreads();
-	// remainders deferred by the last tile
-#pragma unroll
-	for (int i = 0; i < KPT; ++i) {
-		if (dat[i] != 0xFFFFFFFFu) {
-			kbuf[dat[i]] = dkey[i];
-			if constexpr (HV) vbuf[dat[i]] = dval[i];
-		}
-	}
-	if (tid < kP) meta[tid] = fill_r;
-	__syncthreads();
-
-	// ---- stripe epilogue: leftovers (partial buffers + head keys) to the side area
-	uint32_t lc = 0;
-	if (tid < kP) lc = fill_r + hc[tid];
-	uint32_t ltot;
-	const uint32_t lex = block_excl_scan256(lc, tmp + 4, ltot);
-	const size_t so = (size_t)blockIdx.x * kP + tid;
-	if (tid < kP) {
-		loff[tid] = lex;
-		lo_cnt[so] = lc;
-		lo_off[so] = lex;
-		fb[so] = fb_r;
-		hc[tid] = 0; // reused as head cursor
-	}
-	if (tid == 0) nfull[blockIdx.x] = wslot - st.slot_lo;
-	__syncthreads();
-	for (uint32_t idx = tid; idx < (uint32_t)PB; idx += TH) {
-		const uint32_t d = idx / B, j = idx % B;
-		if (j < (meta[d] & 0xFFu)) {
-			lo_keys[st.lo_base + loff[d] + j] = kbuf[idx];
-			if constexpr (HV) lo_vals[st.lo_base + loff[d] + j] = vbuf[idx];
-		}
-	}
-	if (tid < h) {
-		const uint32_t d = digit_of(headk[tid], shift, mask);
-		const uint32_t r = atomicAdd(&hc[d], 1u);
-		const uint64_t at = st.lo_base + loff[d] + (meta[d] & 0xFFu) + r;
-		lo_keys[at] = headk[tid];
-		if constexpr (HV) lo_vals[at] = headv[tid];
-	}
-}
 
 // ------------------------------------ A': classify with direct block placement
 

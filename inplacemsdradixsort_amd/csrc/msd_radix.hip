@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -17,10 +18,6 @@
 using namespace msd;
 
 #define MSD_VERSION "inplacemsdradixsort_amd 0.2 (gfx950)"
-
-// range partitioning (classify_kernel<.., true>) is built for every element type: the multi-GPU path shards u32 keys,
-// u64 keys and the reference's own (u64 key, u64 rid) tuples by sampled splitters when the keys are skewed
-template <typename K, typename V> constexpr bool kHasRange = true;
 
 struct PhaseRec {
 	const char *name;
@@ -56,7 +53,6 @@ struct msd_ctx {
 	int regpart = 1;       // u64 keys / tuples: rounds of small parents as one register-resident pass (0: A/B comparisons)
 	int count16 = 1;       // u32 keys: count_place16_kernel in front of count_place_kernel (0: A/B comparisons)
 	int leaf17 = 1;        // u64 keys and tuples: segments of <= 17408 elements are finished by leaf17_kernel (0: tuples: register partition + small leaves, keys: leaf_count_sort_kernel; A/B comparisons)
-	int stream_kernel = 2; // streaming classify: 2 = classify_stream2_kernel (lean tile loop), 1 = classify_kernel (round 2; A/B comparisons)
 	int mid_leaf = 1;      // u32 keys: merge_count_kernel (list mode) in front of count_walk_kernel (0: A/B comparisons)
 	const uint32_t *order_keys = nullptr; // msd_order_low16_counts_u32 has run on these keys and its tables are still in the slab
 	uint64_t order_n = 0;
@@ -173,6 +169,76 @@ static int pinned_reserve(msd_ctx *c, size_t bytes)
 	bytes = align_up(bytes * 2, 4096);
 	HIPCHK(c, hipHostMalloc(&c->pinned, bytes, hipHostMallocDefault));
 	c->pinned_bytes = bytes;
+	return MSD_OK;
+}
+
+// The slab in two passes: `carve` (a function of a Bump) sizes it, the slab grows to that (at least to `min_bytes`), and
+// `carve` lays it out
+template <typename F> static int slab_carve(msd_ctx *c, F &&carve, size_t min_bytes = 0, bool exact = false)
+{
+	Bump sz(nullptr);
+	carve(sz);
+	if (int rc = slab_reserve(c, std::max(sz.off + 4096, min_bytes), exact)) return rc;
+	Bump real(c->slab);
+	carve(real);
+	return MSD_OK;
+}
+
+// ------------------------------------------------------------ host <-> device through the pinned staging buffer
+
+struct ToDevice { void *dst; const void *src; size_t bytes; };
+// Host arrays to the device: one wait until the staging buffer's last contents have left (the caller has reserved it big
+// enough), then one hipMemcpyAsync per non-empty piece, the pieces one behind the other in the buffer
+static int upload(msd_ctx *c, std::initializer_list<ToDevice> pieces)
+{
+	HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
+	char *at = (char *)c->pinned;
+	for (const ToDevice &p : pieces) {
+		if (!p.bytes) continue;
+		memcpy(at, p.src, p.bytes);
+		HIPCHK(c, hipMemcpyAsync(p.dst, at, p.bytes, hipMemcpyHostToDevice, c->stream));
+		at += p.bytes;
+	}
+	return MSD_OK;
+}
+
+struct ToHost { size_t at; const void *src; size_t bytes; }; // (at: offset in the staging buffer)
+// The counters, and with them the non-empty `extra` device ranges (to their places in the staging buffer): one synchronisation
+static int read_counters(msd_ctx *c, const Counters *ctr, Counters &hc, std::initializer_list<ToHost> extra = {})
+{
+	HIPCHK(c, hipMemcpyAsync(c->pinned, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+	for (const ToHost &p : extra)
+		if (p.bytes) HIPCHK(c, hipMemcpyAsync((char *)c->pinned + p.at, p.src, p.bytes, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	memcpy(&hc, c->pinned, sizeof hc);
+	return MSD_OK;
+}
+
+// `count` elements of a device array appended to `out` (the staging buffer grows to fit; one copy, one synchronisation)
+template <typename T> static int fetch(msd_ctx *c, const T *src, size_t count, std::vector<T> &out)
+{
+	if (int rc = pinned_reserve(c, count * sizeof(T))) return rc;
+	HIPCHK(c, hipMemcpyAsync(c->pinned, src, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	out.insert(out.end(), (const T *)c->pinned, (const T *)c->pinned + count);
+	return MSD_OK;
+}
+
+static void sort_by_start(std::vector<Segment> &v)
+{
+	std::sort(v.begin(), v.end(), [](const Segment &a, const Segment &b) { return a.start < b.start; });
+}
+
+// A device Segment list appended to `out`, then `out` in the order of `start` (atomic appends arrive in any order; the plan
+// must be deterministic).  A list of up to `ahead` entries came back with the counters, to `pre`: no copy then.
+static int fetch_segments(msd_ctx *c, const Segment *src, uint32_t count, std::vector<Segment> &out, const void *pre = nullptr,
+			  size_t ahead = 0)
+{
+	if (count <= ahead)
+		out.insert(out.end(), (const Segment *)pre, (const Segment *)pre + count);
+	else if (int rc = fetch(c, src, count, out))
+		return rc;
+	sort_by_start(out);
 	return MSD_OK;
 }
 
@@ -386,21 +452,6 @@ static void carve_round(Bump &b, const RoundPlan &rp, uint64_t small_max, RoundB
 	rb.plans = b.take<DirectPlan>(np <= kDirectMaxParents ? np : 1);
 }
 
-// scan helper on the context stream
-static int run_scan(msd_ctx *c, const uint64_t *in, uint64_t *out, uint64_t n,
-		    unsigned long long *state, uint32_t *ctr, uint32_t *err, bool cleared = false)
-{
-	if (n == 0) return MSD_OK;
-	const size_t ntiles = (n + kScanTile - 1) / kScanTile;
-	if (!cleared) { // (the sort's rounds clear the state in round_init_kernel)
-		HIPCHK(c, hipMemsetAsync(state, 0, ntiles * sizeof(unsigned long long), c->stream));
-		HIPCHK(c, hipMemsetAsync(ctr, 0, 16, c->stream));
-	}
-	hipLaunchKernelGGL(scan_lookback_kernel, dim3((unsigned)ntiles), dim3(kScanTh), 0, c->stream, in, out, n, state, ctr, err);
-	HIPCHK(c, hipGetLastError());
-	return MSD_OK;
-}
-
 // ------------------------------------------------------------------ the sort
 
 // Leaf-list entries msd_reserve() provides up front: what evenly spread keys need (two 8-bit rounds over 2^30 u32 keys
@@ -412,14 +463,31 @@ template <typename K, typename V> static uint64_t leaf_list_guess(uint64_t n)
 	return std::min<uint64_t>(n / 8192 + 4096, n / 2 + 16);
 }
 
+namespace { // (the sort's own types: not exported)
+
+// Device buffers that live for a whole sort call of n elements (the context's `keep` area)
+struct KeepBufs {
+	uint8_t *block_map, *slot_full; // bucket of every block slot; slots a direct round filled
+	Counters *ctr;       // counters + scratch for the varying-bit reduction
+	uint32_t big_cap;
+	Segment *big;        // big counting-sort segments
+	Segment *dev_list;   // (u64 keys) parents of a device-planned round
+	template <typename K, typename V> void carve_keep(Bump &b, uint64_t n)
+	{
+		constexpr uint64_t B = Cfg<K, V>::B, small_max = (uint64_t)Cfg<K, V>::SORT_TH * Cfg<K, V>::SORT_KPT;
+		block_map = b.take<uint8_t>(n / B + 2);
+		slot_full = b.take<uint8_t>(n / B + 2);
+		ctr = b.take<Counters>(2);
+		big_cap = (uint32_t)std::min<uint64_t>(n / small_max + 16, 0x7FFFFFFFu);
+		big = b.take<Segment>(big_cap);
+		dev_list = sizeof(K) == 8 ? b.take<Segment>(n / (small_max + 1) + 2) : nullptr;
+	}
+};
+
 template <typename K, typename V> static size_t keep_bytes_for(uint64_t n)
 {
 	Bump b(nullptr);
-	b.take<uint8_t>(n / Cfg<K, V>::B + 2);
-	b.take<uint8_t>(n / Cfg<K, V>::B + 2); // slot_full (direct placement)
-	b.take<Counters>(2); // counters + scratch for the varying-bit reduction
-	b.take<Segment>(n / ((uint64_t)Cfg<K, V>::SORT_TH * Cfg<K, V>::SORT_KPT) + 16); // big counting-sort segments
-	if (sizeof(K) == 8) b.take<Segment>(n / ((uint64_t)Cfg<K, V>::SORT_TH * Cfg<K, V>::SORT_KPT + 1) + 2); // parents of a device-planned round
+	KeepBufs().carve_keep<K, V>(b, n);
 	return b.off + 4096;
 }
 
@@ -449,85 +517,121 @@ static size_t round_bytes_estimate(uint64_t n, int sm_count)
 	return worst + 4096;
 }
 
-template <typename K, typename V>
-static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bit,
-		     // single-pass mode (msd_partition_*): one round, caller-chosen digit
-		     bool single_pass, unsigned sp_shift, unsigned sp_width, uint64_t *sp_count,
-		     // ... or, instead of a digit, the key's range among nsplit ascending delimiters (msd_partition_by_splitters_*)
-		     const K *splitters = nullptr, uint32_t nsplit = 0,
-		     // ... or a sort of nseg independent segments [seg_off[i], seg_off[i + 1]) on their low end_bit bits (msd_sort_*_segments)
-		     const uint64_t *seg_off = nullptr, uint32_t nseg = 0,
-		     // ... or of an explicit list of disjoint segments, each with its own number of open bits (internal: what the merge leaf rejected)
-		     const std::vector<Segment> *seg_list = nullptr,
-		     // stop early: the keys are only to be ordered by key >> stop_bits (msd_sort_*_top)
-		     uint32_t stop_bits = 0)
-{
-	using C = Cfg<K, V>;
-	constexpr bool HV = has_val<V>::value;
-	constexpr int B = C::B;
-	const uint64_t small_max = (uint64_t)C::SORT_TH * C::SORT_KPT;
-	if (n == 0) return MSD_OK;
-	if (!keys || (HV && !vals)) return fail(c, MSD_EINVAL, "null data pointer");
-	if (((uintptr_t)keys & 15) || (HV && ((uintptr_t)vals & 15)))
-		return fail(c, MSD_EINVAL, "keys/rids must be 16-byte aligned (the reference asserts the same, src/msb_64.c:2273)");
-	if (end_bit < 0 || end_bit > (int)sizeof(K) * 8) return fail(c, MSD_EINVAL, "end_bit out of range");
-	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large for 32-bit block slots");
-	HIPCHK(c, hipSetDevice(c->device));
-	c->stats.clear();
-	phase_begin(c);
+// What one call of sort_impl does.  Every entry point builds one; sort_impl checks the arguments that go with it.
+template <typename K> struct SortJob {
+	enum Kind {
+		kWhole,   // sort every key (on its low end_bit bits) ...
+		kDigit,   // ... or one round on a caller-chosen digit (msd_partition_*)
+		kRanges,  // ... or one round whose buckets are the key's range among nsplit ascending delimiters (msd_partition_by_splitters_*)
+		kOffsets, // ... or a sort of nseg independent segments [seg_off[i], seg_off[i + 1]) (msd_sort_*_segments)
+		kList,    // ... or of explicit disjoint segments, each with its own number of open bits (internal: what the merge leaf rejected)
+	} kind = kWhole;
+	uint32_t stop_bits = 0;            // kWhole: stop early, the keys are only to be ordered by key >> stop_bits (msd_sort_*_top)
+	unsigned shift = 0, width = 0;     // kDigit: the digit; kRanges: its width
+	uint64_t *counts = nullptr;        // kDigit, kRanges: bucket sizes (optional)
+	const K *splitters = nullptr;      // kRanges (nsplit of them)
+	const uint64_t *seg_off = nullptr; // kOffsets (nseg + 1 of them)
+	uint32_t nsplit = 0, nseg = 0;
+	const std::vector<Segment> *segs = nullptr; // kList
 
-	std::vector<Segment> cur;
-	if (single_pass) {
-		if (sp_width < 1 || sp_width > 8 || sp_shift + sp_width > sizeof(K) * 8)
-			return fail(c, MSD_EINVAL, "partition: radix_bits must be 1..8 and shift+radix_bits within the key");
-		cur.push_back({ 0, n, sp_shift + sp_width, 0 });
-	} else if (nseg) {
-		for (uint32_t i = 0; i < nseg; ++i) {
-			if (seg_off[i] > seg_off[i + 1] || seg_off[i + 1] > n) return fail(c, MSD_EINVAL, "segments: offsets must ascend and stay within n");
-			if (end_bit > 0 && seg_off[i + 1] - seg_off[i] > 1) cur.push_back({ seg_off[i], seg_off[i + 1] - seg_off[i], (uint32_t)end_bit, 0 });
-		}
-	} else if (seg_list) {
-		for (auto &sg : *seg_list) {
-			if (sg.start + sg.count > n || sg.bits > sizeof(K) * 8) return fail(c, MSD_EINVAL, "segments: a segment lies outside the array");
-			if (sg.bits > 0 && sg.count > 1) cur.push_back(sg);
-		}
-		std::sort(cur.begin(), cur.end(), [](const Segment &a, const Segment &b) { return a.start < b.start; });
-	} else if (end_bit > 0 && n > 1 && (uint32_t)end_bit > stop_bits)
-		cur.push_back({ 0, n, (uint32_t)end_bit, 0 });
-	const bool segmented = nseg != 0 || seg_list != nullptr;
+	static SortJob whole(uint32_t stop_bits = 0) { return { kWhole, stop_bits }; }
+	static SortJob digit(unsigned shift, unsigned width, uint64_t *counts) { return { kDigit, 0, shift, width, counts }; }
+	static SortJob ranges(const K *delims, uint32_t nsplit, unsigned width, uint64_t *counts) { return { kRanges, 0, 0, width, counts, delims, nullptr, nsplit }; }
+	static SortJob offsets(const uint64_t *seg_off, uint32_t nseg) { return { kOffsets, 0, 0, 0, nullptr, nullptr, seg_off, 0, nseg }; }
+	static SortJob list(const std::vector<Segment> &segs) { return { kList, 0, 0, 0, nullptr, nullptr, nullptr, 0, 0, &segs }; }
+	bool single_pass() const { return kind == kDigit || kind == kRanges; }
+	bool segmented() const { return kind == kOffsets || kind == kList; }
+};
+
+// a stage's verdict that the exact check behind a sampled leading-bit skip failed: the sort starts over (not an MSD_ code)
+constexpr int kRestart = 1;
+
+// One sort call: its state between the stages, and the stages
+template <typename K, typename V> struct SortRun : KeepBufs {
+	using C = Cfg<K, V>;
+	static constexpr bool HV = has_val<V>::value;
+	static constexpr int B = C::B;
+	static constexpr uint64_t small_max = (uint64_t)C::SORT_TH * C::SORT_KPT;
+	// keys without payload whose last <= 16 bits are open are finished by the counting sort
+	static constexpr uint32_t count_bits = HV ? (uint32_t)kLeafCountBits : (uint32_t)kCountMaxBits;
+
+	msd_ctx *const c;
+	K *const keys;
+	uint64_t *const vals;
+	const uint64_t n, low_mask;
+	const int end_bit;
+	const SortJob<K> &job;
+
+	std::vector<Segment> cur; // parents of the next round, in the order of `start` ...
+	uint32_t dev_np = 0;      // ... or this many, left on the device (dev_list) by the last round
+	uint32_t nsmall_host = 0, ncount_host = 0, nbig_host = 0; // leaf-list lengths as the host last read them
+	unsigned long long *vres = nullptr;                       // OR / AND words of the varying-bit reduction
+	int round = 0;
+	// the previous round placed its blocks directly (its digit was evenly spread); segments handed in by the caller are
+	// taken to be such a round's children (the shards of a multi-GPU sort after their top-digit pass and exchange)
+	bool prev_direct;
+	bool unverified = false;    // a leading-bit skip stands on the sample alone (skip_leading_bits)
+	uint64_t claimed_const = 0; // bits below end_bit the sample found constant
+	uint64_t exact_vary = 0;    // with kRestart: the bits the exact check found varying
+	bool leaf17_ok = true;      // (tuples) leaf17_kernel has rejected nothing yet in this call
+	uint32_t nfallback_known = 0xFFFFFFFFu; // segments the counting leaves have handed to the general LDS sort, once the host has seen it
+
+	SortRun(msd_ctx *c_, K *keys_, uint64_t *vals_, uint64_t n_, int end_bit_, const SortJob<K> &job_)
+		: c(c_), keys(keys_), vals(vals_), n(n_), low_mask(end_bit_ >= 64 ? ~0ull : ((1ull << end_bit_) - 1ull)), end_bit(end_bit_), job(job_),
+		  prev_direct(job_.kind == SortJob<K>::kOffsets) {}
+
+	// the leaf lists (they move when they grow): LDS leaves (the general LDS sort's fallbacks behind them), counting leaves
+	Segment *small() const { return c->lists; }
+	Segment *small_count() const { return c->lists + 3 * c->lists_cap; }
+
+	// ---- the segments the sort starts on
+	int initial_segments()
+	{
+		if (job.single_pass()) {
+			if (job.width < 1 || job.width > 8 || job.shift + job.width > sizeof(K) * 8)
+				return fail(c, MSD_EINVAL, "partition: radix_bits must be 1..8 and shift+radix_bits within the key");
+			cur.push_back({ 0, n, job.shift + job.width, 0 });
+		} else if (job.kind == SortJob<K>::kOffsets) {
+			const uint64_t *off = job.seg_off;
+			for (uint32_t i = 0; i < job.nseg; ++i) {
+				if (off[i] > off[i + 1] || off[i + 1] > n) return fail(c, MSD_EINVAL, "segments: offsets must ascend and stay within n");
+				if (end_bit > 0 && off[i + 1] - off[i] > 1) cur.push_back({ off[i], off[i + 1] - off[i], (uint32_t)end_bit, 0 });
+			}
+		} else if (job.kind == SortJob<K>::kList) {
+			for (auto &sg : *job.segs) {
+				if (sg.start + sg.count > n || sg.bits > sizeof(K) * 8) return fail(c, MSD_EINVAL, "segments: a segment lies outside the array");
+				if (sg.bits > 0 && sg.count > 1) cur.push_back(sg);
+			}
+			sort_by_start(cur);
+		} else if (end_bit > 0 && n > 1 && (uint32_t)end_bit > job.stop_bits)
+			cur.push_back({ 0, n, (uint32_t)end_bit, 0 });
+		return MSD_OK;
+	}
 
 	// ---- buffers that live for the whole call
+	int reserve_keep()
 	{
 		int rc = keep_reserve(c, keep_bytes_for<K, V>(n), true);
 		if (!rc) rc = pinned_reserve(c, 1 << 16);
 		if (!rc) rc = lists_reserve(c, 4096, 0, 0);
 		if (rc) return rc;
+		Bump kb(c->keep);
+		carve_keep<K, V>(kb, n);
+		vres = reinterpret_cast<unsigned long long *>(ctr + 1);
+		HIPCHK(c, hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+		return MSD_OK;
 	}
-	Bump kb(c->keep);
-	uint8_t *block_map = kb.take<uint8_t>(n / B + 2);
-	uint8_t *slot_full = kb.take<uint8_t>(n / B + 2);
-	Counters *ctr = kb.take<Counters>(2);
-	const uint32_t big_cap = (uint32_t)std::min<uint64_t>(n / small_max + 16, 0x7FFFFFFFu);
-	Segment *big = kb.take<Segment>(big_cap);
-	Segment *dev_list = sizeof(K) == 8 ? kb.take<Segment>(n / (small_max + 1) + 2) : nullptr; // parents of a device-planned round
-	uint32_t dev_np = 0;
-	Segment *small = c->lists, *small_count = c->lists + 3 * c->lists_cap;
-	HIPCHK(c, hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
-	// keys without payload whose last <= 16 bits are open are finished by the counting sort
-	const uint32_t count_bits = HV ? (uint32_t)kLeafCountBits : (uint32_t)kCountMaxBits;
 
-	// ---- leading-bit skipping: a cheap strided sample decides whether an exact OR/AND pass over
-	// all keys can pay off (it does when whole leading digits are constant, e.g. keys whose upper
-	// half is zero); all-equal inputs are finished here.
-	unsigned long long *vres = reinterpret_cast<unsigned long long *>(ctr + 1);
-	auto vres_init = [&]() -> int { // OR accumulator 0, AND accumulator all ones (no host round trip)
+	int vres_init() // OR accumulator 0, AND accumulator all ones (no host round trip)
+	{
 		HIPCHK(c, hipMemsetAsync(vres, 0x00, sizeof(unsigned long long), c->stream));
 		HIPCHK(c, hipMemsetAsync(vres + 1, 0xFF, sizeof(unsigned long long), c->stream));
 		return MSD_OK;
-	};
-	auto run_vary = [&](uint64_t stride, uint64_t *vary_out) -> int {
-		int rc0 = vres_init();
-		if (rc0) return rc0;
+	}
+	// the bits in which the keys at every stride-th position differ
+	int run_vary(uint64_t stride, uint64_t *vary_out)
+	{
+		if (int rc = vres_init()) return rc;
 		const uint64_t cnt = (n + stride - 1) / stride;
 		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (cnt + 255) / 256);
 		hipLaunchKernelGGL((vary_kernel<K>), dim3(grid), dim3(256), 0, c->stream, keys, n, stride, vres);
@@ -537,17 +641,20 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 		const unsigned long long *h = (const unsigned long long *)c->pinned;
 		*vary_out = h[0] ^ h[1];
 		return MSD_OK;
-	};
-	const uint64_t low_mask = end_bit >= 64 ? ~0ull : ((1ull << end_bit) - 1ull);
+	}
+
+	// ---- leading-bit skipping: a cheap strided sample decides whether an exact OR/AND pass over
+	// all keys can pay off (it does when whole leading digits are constant, e.g. keys whose upper
+	// half is zero); all-equal inputs are finished here.
 	// A skip decided from the sample alone is `unverified`: the rounds only permute keys, so the exact check may come
 	// later -- on the exact histogram pass of the second round if that reads every key (it costs that pass nothing:
 	// 1.4 ms less for 2^30 tuples with 32 constant key bits), else in a pass of its own before the leaves, which
 	// re-generate keys from a common prefix and must not run on a wrong one.  If the check fails (some key differs
 	// in a bit the sample found constant) the sort starts over on all bits the exact pass found varying: the data is
 	// still the same multiset.
-	bool unverified = false;
-	uint64_t claimed_const = 0; // bits below end_bit the sample found constant
-	if (!single_pass && !segmented && !cur.empty() && n >= 4096) {
+	int skip_leading_bits()
+	{
+		if (job.single_pass() || job.segmented() || cur.empty() || n < 4096) return MSD_OK;
 		uint64_t vary = 0;
 		int rc = run_vary(std::max<uint64_t>(1, n / 8192), &vary);
 		if (rc) return rc;
@@ -572,292 +679,236 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 			}
 		}
 		phase_mark(c, "bit skip");
-		if (!cur.empty() && cur[0].bits <= stop_bits) cur.clear(); // (a sort that stops above every varying bit)
+		if (!cur.empty() && cur[0].bits <= job.stop_bits) cur.clear(); // (a sort that stops above every varying bit)
+		return MSD_OK;
 	}
 
-	uint32_t nsmall_host = 0, ncount_host = 0, nbig_host = 0;
-	if (segmented && !cur.empty()) {
-		// segments that need no partition round go to the leaf lists at once, by collect_kernel's rules
-		std::vector<Segment> l_small, l_count, l_big, parents;
-		for (auto &sg : cur) {
-			const bool countable = !HV && sg.bits <= count_bits;
-			if (countable && sg.count >= 64 && sg.count <= std::max<uint64_t>(small_max, kCountMedMax))
-				l_count.push_back(sg);
-			else if (sg.count > small_max) {
-				if (countable && sg.count < 0xFFFF0000ull && l_big.size() < big_cap) l_big.push_back(sg); else parents.push_back(sg);
-			} else
-				l_small.push_back(sg);
+	// ---- segments that need no partition round go to the leaf lists at once
+	int route_to_leaves()
+	{
+		if (job.segmented() && !cur.empty()) { // by collect_kernel's rules
+			std::vector<Segment> l_small, l_count, l_big, parents;
+			for (auto &sg : cur) {
+				const bool countable = !HV && sg.bits <= count_bits;
+				if (countable && sg.count >= 64 && sg.count <= std::max<uint64_t>(small_max, kCountMedMax))
+					l_count.push_back(sg);
+				else if (sg.count > small_max) {
+					if (countable && sg.count < 0xFFFF0000ull && l_big.size() < big_cap) l_big.push_back(sg); else parents.push_back(sg);
+				} else
+					l_small.push_back(sg);
+			}
+			int rc = lists_reserve(c, std::max(l_small.size(), l_count.size()) + 16, 0, 0);
+			if (!rc) rc = pinned_reserve(c, (l_small.size() + l_count.size() + l_big.size()) * sizeof(Segment) + sizeof(Counters));
+			if (rc) return rc;
+			nsmall_host = (uint32_t)l_small.size();
+			ncount_host = (uint32_t)l_count.size();
+			nbig_host = (uint32_t)l_big.size();
+			Counters hc0 = {}; // the lists' counters continue from here
+			hc0.nsmall = nsmall_host;
+			hc0.ncount = ncount_host;
+			hc0.nbig = nbig_host;
+			rc = upload(c, { { small(), l_small.data(), l_small.size() * sizeof(Segment) },
+					 { small_count(), l_count.data(), l_count.size() * sizeof(Segment) },
+					 { big, l_big.data(), l_big.size() * sizeof(Segment) },
+					 { ctr, &hc0, sizeof hc0 } });
+			if (rc) return rc;
+			cur = parents;
 		}
-		int rc = lists_reserve(c, std::max(l_small.size(), l_count.size()) + 16, 0, 0);
-		if (!rc) rc = pinned_reserve(c, (l_small.size() + l_count.size() + l_big.size()) * sizeof(Segment) + sizeof(Counters));
-		if (rc) return rc;
-		small = c->lists;
-		small_count = c->lists + 3 * c->lists_cap;
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		Segment *ps = (Segment *)c->pinned;
-		auto up = [&](const std::vector<Segment> &v, Segment *dst) -> int {
-			if (v.empty()) return MSD_OK;
-			memcpy(ps, v.data(), v.size() * sizeof(Segment));
-			HIPCHK(c, hipMemcpyAsync(dst, ps, v.size() * sizeof(Segment), hipMemcpyHostToDevice, c->stream));
-			ps += v.size();
-			return MSD_OK;
-		};
-		if ((rc = up(l_small, small)) || (rc = up(l_count, small_count)) || (rc = up(l_big, big))) return rc;
-		nsmall_host = (uint32_t)l_small.size();
-		ncount_host = (uint32_t)l_count.size();
-		nbig_host = (uint32_t)l_big.size();
-		Counters *hc0 = (Counters *)ps; // the lists' counters continue from here
-		memset(hc0, 0, sizeof(Counters));
-		hc0->nsmall = nsmall_host;
-		hc0->ncount = ncount_host;
-		hc0->nbig = nbig_host;
-		HIPCHK(c, hipMemcpyAsync(ctr, hc0, sizeof(Counters), hipMemcpyHostToDevice, c->stream));
-		cur = parents;
-	}
-	if constexpr (!HV) { // <= 16 open bits from the start (small key range): no partition round at all
-		if (!single_pass && !segmented && !cur.empty() && n > small_max && cur[0].bits <= count_bits && n < 0xFFFF0000ull) {
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			memcpy(c->pinned, &cur[0], sizeof(Segment));
-			HIPCHK(c, hipMemcpyAsync(big, c->pinned, sizeof(Segment), hipMemcpyHostToDevice, c->stream));
-			nbig_host = 1;
+		const bool whole = !job.single_pass() && !job.segmented();
+		if constexpr (!HV) { // <= 16 open bits from the start (small key range): no partition round at all
+			if (whole && !cur.empty() && n > small_max && cur[0].bits <= count_bits && n < 0xFFFF0000ull) {
+				if (int rc = upload(c, { { big, &cur[0], sizeof(Segment) } })) return rc;
+				nbig_host = 1;
+				cur.clear();
+			}
+		}
+		if (whole && !cur.empty() && n <= small_max) { // fits LDS: no partition round at all
+			if (int rc = upload(c, { { small(), &cur[0], sizeof(Segment) } })) return rc;
+			nsmall_host = 1;
 			cur.clear();
 		}
-	}
-	if (!single_pass && !segmented && !cur.empty() && n <= small_max) { // fits LDS: no partition round at all
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		memcpy(c->pinned, &cur[0], sizeof(Segment));
-		HIPCHK(c, hipMemcpyAsync(small, c->pinned, sizeof(Segment), hipMemcpyHostToDevice, c->stream));
-		nsmall_host = 1;
-		cur.clear();
+		return MSD_OK;
 	}
 
-	int round = 0;
-	// the previous round placed its blocks directly (its digit was evenly spread); segments handed in by the caller are
-	// taken to be such a round's children (the shards of a multi-GPU sort after their top-digit pass and exchange)
-	bool prev_direct = nseg != 0;
-	// the sort starts over from here if the exact check behind a sampled leading-bit skip fails: on `exact_vary`, the
-	// bits that really vary
-	auto start_over = [&](uint64_t exact_vary) -> int {
-		exact_vary &= low_mask;
-		const int top = exact_vary ? 64 - __builtin_clzll(exact_vary) : 0;
-		set_stat(c, "skipped_bits", (uint64_t)(end_bit - top));
-		add_stat(c, "bit_skip_restarts", 1);
-		cur.clear();
-		if (top > 0 && (uint32_t)top > stop_bits) cur.push_back({ 0, n, (uint32_t)top, 0 });
-		nsmall_host = ncount_host = nbig_host = 0;
-		dev_np = 0;
-		prev_direct = false;
-		unverified = false;
-		HIPCHK(c, hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
-		return MSD_OK;
-	};
-	bool leaf17_ok = true; // (tuples) leaf17_kernel has rejected nothing yet in this call
-	bool again = true;
-	while (again) {
-	again = false;
-	while (!cur.empty() || dev_np) {
-		// ---- segments that fit the registers of one workgroup take ONE register-resident pass (msd_regpart.hpp) instead
-		// of a general round: the last partition round of the tuple sort (65536 parents of about 2^14 tuples at 2^30)
-		if constexpr (sizeof(K) == 8) {
-			if (!single_pass && c->regpart) {
+	// ---- partition rounds until every segment is a leaf (kRestart: a sampled leading-bit skip did not hold)
+	int rounds()
+	{
+		while (!cur.empty() || dev_np) {
+			int rc;
+			if constexpr (sizeof(K) == 8) {
+				// ---- segments that fit the registers of one workgroup take ONE register-resident pass (msd_regpart.hpp) instead
+				// of a general round: the last partition round of the tuple sort (65536 parents of about 2^14 tuples at 2^30)
 				// (dev_np: the previous round left only parents that fit, and their list stayed on the device -- it is
 				// planned there too, regpart_plan_kernel; otherwise the host sorts the fitting parents out of its list)
-				std::vector<Segment> fit, rest;
-				if (!dev_np)
-					for (auto &sg : cur) (sg.count + 1 <= kRpCap && sg.count > small_max ? fit : rest).push_back(sg);
-				if constexpr (HV) {
-					// ---- tuples: such a segment is FINISHED in one pass by leaf17_kernel (msd_leaf17.hpp: read once, sorted in
-					// registers and LDS, written once) instead of a register partition + the small leaves; what it rejects
-					// (a group of > 48 tuples equal on the counted bits) takes that way.  A leaf must not run behind an
-					// unconfirmed leading-bit skip.
-					// (segments with <= 16 open bits -- tuples whose upper key half is constant, config 5b -- too: the leaf counts up to
-					// 16 bits, such a segment has no groups to put in order at all)
-					if (c->leaf17 && leaf17_ok && !unverified && (dev_np || fit.size() >= 64 || (!fit.empty() && rest.empty()))) {
-						const bool on_device = dev_np != 0;
-						const uint32_t np = on_device ? dev_np : (uint32_t)fit.size();
-						dev_np = 0;
-						int rc = slab_reserve(c, 2 * (size_t)np * sizeof(Segment) + 4096);
-						if (!rc) rc = pinned_reserve(c, (size_t)np * sizeof(Segment) + 4096);
+				if (!job.single_pass() && c->regpart) {
+					std::vector<Segment> fit, rest;
+					if (!dev_np)
+						for (auto &sg : cur) (sg.count + 1 <= kRpCap && sg.count > small_max ? fit : rest).push_back(sg);
+					if (dev_np || fit.size() >= 64 || (!fit.empty() && rest.empty())) {
+						// (tuples: such a segment is finished by leaf17_kernel instead, while nothing stands against it)
+						if constexpr (HV)
+							rc = c->leaf17 && leaf17_ok && !unverified ? leaf17_pass(fit, rest) : regpart_round(fit, rest);
+						else
+							rc = regpart_round(fit, rest);
 						if (rc) return rc;
-						Segment *d_segs = reinterpret_cast<Segment *>(c->slab), *d_rej = d_segs + np;
-						if (on_device)
-							HIPCHK(c, hipMemcpyAsync(d_segs, dev_list, (size_t)np * sizeof(Segment), hipMemcpyDeviceToDevice, c->stream));
-						else {
-							HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
-							memcpy(c->pinned, fit.data(), (size_t)np * sizeof(Segment));
-							HIPCHK(c, hipMemcpyAsync(d_segs, c->pinned, (size_t)np * sizeof(Segment), hipMemcpyHostToDevice, c->stream));
-						}
-						HIPCHK(c, hipMemsetAsync(&ctr->nslow2, 0, sizeof(uint32_t), c->stream));
-						HIPCHK(c, hipMemsetAsync(&ctr->l17_slow, 0, sizeof(uint32_t), c->stream));
-						phase_mark(c, "plan+upload");
-						hipLaunchKernelGGL((leaf17_kernel<V>), dim3(std::min<uint32_t>(np, (uint32_t)c->sm_count)), dim3(kL17Th), kL17Lds, c->stream,
-								   (uint64_t *)keys, vals, (const Segment *)d_segs, np, d_rej, &ctr->nslow2, ctr, 0u);
-						HIPCHK(c, hipGetLastError());
-						phase_mark(c, "leaf17");
-						Counters hc;
-						HIPCHK(c, hipMemcpyAsync(c->pinned, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-						HIPCHK(c, hipStreamSynchronize(c->stream));
-						memcpy(&hc, c->pinned, sizeof hc);
-						if (hc.errors) return fail(c, MSD_EINTERNAL, "leaf17: %u internal invariant violations (checks 0x%x)", hc.errors, hc.err_sites);
-						add_stat(c, "leaf17_segments", np - hc.nslow2);
-						add_stat(c, "leaf17_slow_segments", hc.l17_slow);
-						cur = rest;
-						if (hc.nslow2) { // rejected segments: the register partition + the small leaves finish them
-							rc = pinned_reserve(c, (size_t)hc.nslow2 * sizeof(Segment));
-							if (rc) return rc;
-							HIPCHK(c, hipMemcpyAsync(c->pinned, d_rej, (size_t)hc.nslow2 * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-							HIPCHK(c, hipStreamSynchronize(c->stream));
-							cur.insert(cur.end(), (Segment *)c->pinned, (Segment *)c->pinned + hc.nslow2);
-							std::sort(cur.begin(), cur.end(), [](const Segment &a, const Segment &b) { return a.start < b.start; });
-							leaf17_ok = false; // (for the rest of this call)
-							add_stat(c, "leaf17_rejected", hc.nslow2);
-						}
-						phase_mark(c, "readback");
 						continue;
 					}
 				}
-				if (dev_np || fit.size() >= 64 || (!fit.empty() && rest.empty())) {
-					const bool on_device = dev_np != 0;
-					std::vector<Parent> ps(fit.size());
-					uint32_t nc = 0;
-					for (size_t i = 0; i < fit.size(); ++i) {
-						Parent &p = ps[i];
-						p.start = fit[i].start;
-						p.count = fit[i].count;
-						p.width = regpart_width(fit[i].count, fit[i].bits, small_max);
-						p.shift = fit[i].bits - p.width;
-						p.child_base = nc;
-						p.stripe_lo = p.stripe_hi = 0;
-						p.pad = 0;
-						nc += 1u << p.width;
-					}
-					if (on_device) nc = dev_np << regpart_width(kRpCap, 64, small_max); // (an upper bound: the widest digit of the rule)
-					const uint32_t np = on_device ? dev_np : (uint32_t)ps.size();
-					dev_np = 0;
-					const size_t next_cap = (size_t)nc + 2; // (children above the leaf capacity: none on sane input, all at worst)
-					Bump sz(nullptr), *bp = &sz;
-					Parent *d_parents = nullptr;
-					ChildArrays ca = {};
-					Segment *d_next = nullptr;
-					uint32_t *d_scr = nullptr;
-					auto carve = [&]() {
-						d_parents = bp->take<Parent>(np);
-						ca.start = bp->take<uint64_t>(nc);
-						ca.count = bp->take<uint64_t>(nc);
-						d_next = bp->take<Segment>(next_cap);
-						d_scr = bp->take<uint32_t>(64);
-					};
-					carve();
-					int rc = slab_reserve(c, sz.off + 4096);
-					if (!rc) rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + nc + 16, nsmall_host, ncount_host);
-					if (!rc) rc = pinned_reserve(c, std::max<size_t>(on_device ? 0 : np * sizeof(Parent), 256 + 2048 * sizeof(Segment)));
-					if (rc) return rc;
-					small = c->lists;
-					small_count = c->lists + 3 * c->lists_cap;
-					Bump real(c->slab);
-					bp = &real;
-					carve();
-					hipLaunchKernelGGL(round_init_kernel, dim3(1), dim3(256), 0, c->stream, ctr, d_scr + 16, (uint64_t)0,
-							   reinterpret_cast<unsigned long long *>(d_scr + 32), (uint64_t)0, d_scr);
-					if (on_device)
-						hipLaunchKernelGGL(regpart_plan_kernel, dim3((np + 255) / 256), dim3(256), 0, c->stream, (const Segment *)dev_list, np,
-								   small_max, d_parents, ctr);
-					else {
-						HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
-						memcpy(c->pinned, ps.data(), np * sizeof(Parent));
-						HIPCHK(c, hipMemcpyAsync(d_parents, c->pinned, np * sizeof(Parent), hipMemcpyHostToDevice, c->stream));
-					}
-					phase_mark(c, "plan+upload");
-					hipLaunchKernelGGL((regpart_kernel<V>), dim3(std::min<uint32_t>(np, (uint32_t)c->sm_count)), dim3(kRpTh), kRpLds, c->stream,
-							   (uint64_t *)keys, vals, (const Parent *)d_parents, np, ca, ctr);
-					phase_mark(c, "A register partition");
-					const uint32_t wmax_rp = regpart_width(kRpCap, 64, small_max); // (the widest digit of the rule)
-					hipLaunchKernelGGL(collect_kernel, dim3((np + (256u >> wmax_rp) - 1) / (256u >> wmax_rp)), dim3(256), 0, c->stream, (const Parent *)d_parents, np, wmax_rp, ca, small_max, small_max,
-							   (uint32_t)std::min<size_t>(c->lists_cap, 0xFFFFFFFFu), count_bits, d_next, small, small_count,
-							   HV ? (Segment *)nullptr : big, big_cap, ctr, (uint64_t *)nullptr, nc, stop_bits);
-					HIPCHK(c, hipGetLastError());
-					phase_mark(c, "C cleanup");
-					Counters hc;
-					const size_t ahead = std::min<size_t>(next_cap, 2048);
-					HIPCHK(c, hipMemcpyAsync(c->pinned, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-					HIPCHK(c, hipMemcpyAsync((char *)c->pinned + 256, d_next, ahead * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-					HIPCHK(c, hipStreamSynchronize(c->stream));
-					memcpy(&hc, c->pinned, sizeof hc);
-					if (hc.errors) return fail(c, MSD_EINTERNAL, "register partition round: %u internal invariant violations (checks 0x%x)", hc.errors, hc.err_sites);
-					nsmall_host = hc.nsmall;
-					ncount_host = hc.ncount;
-					nbig_host = hc.nbig;
-					add_stat(c, "rounds", 1);
-					add_stat(c, "regpart_rounds", 1);
-					add_stat(c, "parents", np);
-					add_stat(c, "children", nc);
-					cur = rest;
-					if (hc.next_parents) {
-						if (hc.next_parents > ahead) {
-							rc = pinned_reserve(c, (size_t)hc.next_parents * sizeof(Segment));
-							if (rc) return rc;
-							HIPCHK(c, hipMemcpyAsync(c->pinned, d_next, (size_t)hc.next_parents * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-							HIPCHK(c, hipStreamSynchronize(c->stream));
-							cur.insert(cur.end(), (Segment *)c->pinned, (Segment *)c->pinned + hc.next_parents);
-						} else
-							cur.insert(cur.end(), (Segment *)((char *)c->pinned + 256), (Segment *)((char *)c->pinned + 256) + hc.next_parents);
-						std::sort(cur.begin(), cur.end(), [](const Segment &a, const Segment &b) { return a.start < b.start; });
-					}
-					phase_mark(c, "readback");
-					prev_direct = false;
-					++round;
-					continue;
-				}
 			}
+			// ---- the general round: plan + upload, A classify, B block metadata + permutation, C cleanup + collect, summary
+			Round r;
+			if ((rc = plan_upload(r)) || (rc = classify(r)) || (rc = permute_blocks(r)) || (rc = cleanup_collect(r)) || (rc = round_summary(r)))
+				return rc;
 		}
-		RoundPlan rp;
-		plan_round<K, V>(cur, small_max, c->sm_count, rp, count_bits, single_pass ? sp_width : 0u, splitters ? nsplit : 0u);
-		RoundBufs rb;
-		{
-			Bump sz(nullptr);
-			carve_round<K, V>(sz, rp, small_max, rb);
-			size_t need = sz.off + 4096;
-			if (round == 0 && !single_pass) need = std::max(need, round_bytes_estimate<K, V>(n, c->sm_count));
-			int rc = slab_reserve(c, need, round == 0); // between rounds nothing in the slab is live
-			if (rc) return rc;
-			Bump b(c->slab);
-			carve_round<K, V>(b, rp, small_max, rb);
-		}
-		const uint32_t np = (uint32_t)rp.parents.size(), ns = (uint32_t)rp.stripes.size(), nc = rp.nchildren;
-		{ // every child of this round may become a leaf
-			int rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + nc + 16, nsmall_host, ncount_host);
-			if (rc) return rc;
-			small = c->lists;
-			small_count = c->lists + 3 * c->lists_cap;
-		}
-		const uint32_t small_cap = (uint32_t)std::min<size_t>(c->lists_cap, 0xFFFFFFFFu);
-		{ // per-round counters, per-parent plans, scan state: one launch
-			const uint64_t plan_words = (np <= kDirectMaxParents ? np : 1) * sizeof(DirectPlan) / sizeof(uint32_t);
-			const uint64_t ntiles = (nc + kScanTile - 1) / kScanTile + 1;
-			const unsigned grid = (unsigned)std::min<uint64_t>(1024, (std::max(plan_words, ntiles) + 255) / 256 + 1);
-			hipLaunchKernelGGL(round_init_kernel, dim3(grid), dim3(256), 0, c->stream, ctr, reinterpret_cast<uint32_t *>(rb.plans),
-					   plan_words, rb.scan_state, ntiles, rb.scan_ctr);
-		}
-		// ---- upload tables
-		{
-			const size_t bytes = np * sizeof(Parent) + ns * sizeof(Stripe);
-			int rc = pinned_reserve(c, bytes);
-			if (rc) return rc;
-			HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
-			memcpy(c->pinned, rp.parents.data(), np * sizeof(Parent));
-			memcpy((char *)c->pinned + np * sizeof(Parent), rp.stripes.data(), ns * sizeof(Stripe));
-			HIPCHK(c, hipMemcpyAsync(rb.parents, c->pinned, np * sizeof(Parent), hipMemcpyHostToDevice, c->stream));
-			HIPCHK(c, hipMemcpyAsync(rb.stripes, (char *)c->pinned + np * sizeof(Parent), ns * sizeof(Stripe), hipMemcpyHostToDevice, c->stream));
-		}
-		phase_mark(c, "plan+upload");
+		return MSD_OK;
+	}
 
-		// ---- A: classify (histogram falls out of it)
-		bool tried_direct = false, hist_checks = false;
-		// Direct placement (DESIGN.md section 2, A'): the first round from a sample, later rounds -- only
-		// after a direct first round -- from exact counts (a read-only pass).
-		// (the read schedule hands a bucket one slot per tile: with fewer than 256 buckets the tiles
-		// are not filled, so narrower digits keep the streaming kernel unless forced)
-		bool try_direct = c->direct_mode != 0 && rp.round_keys >= c->direct_min && !splitters;
+	// ---- tuples: a segment that fits the registers is FINISHED in one pass by leaf17_kernel (msd_leaf17.hpp: read once, sorted
+	// in registers and LDS, written once) instead of a register partition + the small leaves; what it rejects (a group of > 48
+	// tuples equal on the counted bits) takes that way.  A leaf must not run behind an unconfirmed leading-bit skip.
+	// (segments with <= 16 open bits -- tuples whose upper key half is constant, config 5b -- too: the leaf counts up to
+	// 16 bits, such a segment has no groups to put in order at all)
+	int leaf17_pass(const std::vector<Segment> &fit, const std::vector<Segment> &rest)
+	{
+		const bool on_device = dev_np != 0;
+		const uint32_t np = on_device ? dev_np : (uint32_t)fit.size();
+		dev_np = 0;
+		int rc = slab_reserve(c, 2 * (size_t)np * sizeof(Segment) + 4096);
+		if (!rc) rc = pinned_reserve(c, (size_t)np * sizeof(Segment) + 4096);
+		if (rc) return rc;
+		Segment *d_segs = reinterpret_cast<Segment *>(c->slab), *d_rej = d_segs + np;
+		if (on_device)
+			HIPCHK(c, hipMemcpyAsync(d_segs, dev_list, (size_t)np * sizeof(Segment), hipMemcpyDeviceToDevice, c->stream));
+		else if ((rc = upload(c, { { d_segs, fit.data(), (size_t)np * sizeof(Segment) } })))
+			return rc;
+		HIPCHK(c, hipMemsetAsync(&ctr->nslow2, 0, sizeof(uint32_t), c->stream));
+		HIPCHK(c, hipMemsetAsync(&ctr->l17_slow, 0, sizeof(uint32_t), c->stream));
+		phase_mark(c, "plan+upload");
+		hipLaunchKernelGGL((leaf17_kernel<V>), dim3(std::min<uint32_t>(np, (uint32_t)c->sm_count)), dim3(kL17Th), kL17Lds, c->stream,
+				   (uint64_t *)keys, vals, (const Segment *)d_segs, np, d_rej, &ctr->nslow2, ctr, 0u);
+		HIPCHK(c, hipGetLastError());
+		phase_mark(c, "leaf17");
+		Counters hc;
+		if ((rc = read_counters(c, ctr, hc))) return rc;
+		if (hc.errors) return fail(c, MSD_EINTERNAL, "leaf17: %u internal invariant violations (checks 0x%x)", hc.errors, hc.err_sites);
+		add_stat(c, "leaf17_segments", np - hc.nslow2);
+		add_stat(c, "leaf17_slow_segments", hc.l17_slow);
+		cur = rest;
+		if (hc.nslow2) { // rejected segments: the register partition + the small leaves finish them
+			if ((rc = fetch_segments(c, d_rej, hc.nslow2, cur))) return rc;
+			leaf17_ok = false; // (for the rest of this call)
+			add_stat(c, "leaf17_rejected", hc.nslow2);
+		}
+		phase_mark(c, "readback");
+		return MSD_OK;
+	}
+
+	// ---- the register-resident partition round (msd_regpart.hpp)
+	int regpart_round(const std::vector<Segment> &fit, const std::vector<Segment> &rest)
+	{
+		const bool on_device = dev_np != 0;
+		const uint32_t wmax = regpart_width(kRpCap, 64, small_max); // (the widest digit of the rule)
+		std::vector<Parent> ps;
+		uint32_t nc = 0;
+		for (const Segment &sg : fit) {
+			const uint32_t w = regpart_width(sg.count, sg.bits, small_max);
+			ps.push_back({ sg.start, sg.count, sg.bits - w, w, nc, 0, 0, 0 }); // (shift, width, child_base, no stripes)
+			nc += 1u << w;
+		}
+		if (on_device) nc = dev_np << wmax; // (an upper bound)
+		const uint32_t np = on_device ? dev_np : (uint32_t)ps.size();
+		dev_np = 0;
+		const size_t next_cap = (size_t)nc + 2; // (children above the leaf capacity: none on sane input, all at worst)
+		Parent *d_parents = nullptr;
+		ChildArrays ca = {};
+		Segment *d_next = nullptr;
+		uint32_t *d_scr = nullptr;
+		int rc = slab_carve(c, [&](Bump &b) {
+			d_parents = b.take<Parent>(np);
+			ca.start = b.take<uint64_t>(nc);
+			ca.count = b.take<uint64_t>(nc);
+			d_next = b.take<Segment>(next_cap);
+			d_scr = b.take<uint32_t>(64);
+		});
+		if (!rc) rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + nc + 16, nsmall_host, ncount_host);
+		if (!rc) rc = pinned_reserve(c, std::max<size_t>(on_device ? 0 : np * sizeof(Parent), 256 + 2048 * sizeof(Segment)));
+		if (rc) return rc;
+		hipLaunchKernelGGL(round_init_kernel, dim3(1), dim3(256), 0, c->stream, ctr, d_scr + 16, (uint64_t)0,
+				   reinterpret_cast<unsigned long long *>(d_scr + 32), (uint64_t)0, d_scr);
+		if (on_device)
+			hipLaunchKernelGGL(regpart_plan_kernel, dim3((np + 255) / 256), dim3(256), 0, c->stream, (const Segment *)dev_list, np,
+					   small_max, d_parents, ctr);
+		else if ((rc = upload(c, { { d_parents, ps.data(), np * sizeof(Parent) } })))
+			return rc;
+		phase_mark(c, "plan+upload");
+		hipLaunchKernelGGL((regpart_kernel<V>), dim3(std::min<uint32_t>(np, (uint32_t)c->sm_count)), dim3(kRpTh), kRpLds, c->stream,
+				   (uint64_t *)keys, vals, (const Parent *)d_parents, np, ca, ctr);
+		phase_mark(c, "A register partition");
+		hipLaunchKernelGGL(collect_kernel, dim3((np + (256u >> wmax) - 1) / (256u >> wmax)), dim3(256), 0, c->stream, (const Parent *)d_parents, np, wmax, ca, small_max, small_max,
+				   (uint32_t)std::min<size_t>(c->lists_cap, 0xFFFFFFFFu), count_bits, d_next, small(), small_count(),
+				   HV ? (Segment *)nullptr : big, big_cap, ctr, (uint64_t *)nullptr, nc, job.stop_bits);
+		HIPCHK(c, hipGetLastError());
+		phase_mark(c, "C cleanup");
+		Counters hc;
+		const size_t ahead = std::min<size_t>(next_cap, 2048); // (next parents that travel with the counters)
+		if ((rc = read_counters(c, ctr, hc, { { 256, d_next, ahead * sizeof(Segment) } }))) return rc;
+		if (hc.errors) return fail(c, MSD_EINTERNAL, "register partition round: %u internal invariant violations (checks 0x%x)", hc.errors, hc.err_sites);
+		nsmall_host = hc.nsmall;
+		ncount_host = hc.ncount;
+		nbig_host = hc.nbig;
+		add_stat(c, "rounds", 1);
+		add_stat(c, "regpart_rounds", 1);
+		add_stat(c, "parents", np);
+		add_stat(c, "children", nc);
+		cur = rest;
+		if (hc.next_parents && (rc = fetch_segments(c, d_next, hc.next_parents, cur, (char *)c->pinned + 256, ahead))) return rc;
+		phase_mark(c, "readback");
+		prev_direct = false;
+		++round;
+		return MSD_OK;
+	}
+
+	struct Round { // one general round
+		RoundPlan rp;
+		RoundBufs rb;
+		uint32_t np = 0, ns = 0, nc = 0;
+		bool tried_direct = false; // a direct placement was attempted (its verdict stays on the device until the summary)
+		bool hist_checks = false;  // its exact histogram pass carries the check behind a sampled leading-bit skip
+	};
+	int plan_upload(Round &r)
+	{
+		plan_round<K, V>(cur, small_max, c->sm_count, r.rp, count_bits, job.single_pass() ? job.width : 0u, job.splitters ? job.nsplit : 0u);
+		// (between rounds nothing in the slab is live; the first round reserves the usual shapes' worst case at once)
+		const bool first = round == 0;
+		int rc = slab_carve(c, [&](Bump &b) { carve_round<K, V>(b, r.rp, small_max, r.rb); },
+				    first && !job.single_pass() ? round_bytes_estimate<K, V>(n, c->sm_count) : 0, first);
+		if (rc) return rc;
+		r.np = (uint32_t)r.rp.parents.size(), r.ns = (uint32_t)r.rp.stripes.size(), r.nc = r.rp.nchildren;
+		// every child of this round may become a leaf
+		if ((rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + r.nc + 16, nsmall_host, ncount_host))) return rc;
+		{ // per-round counters, per-parent plans, scan state: one launch
+			const uint64_t plan_words = (r.np <= kDirectMaxParents ? r.np : 1) * sizeof(DirectPlan) / sizeof(uint32_t);
+			const uint64_t ntiles = (r.nc + kScanTile - 1) / kScanTile + 1;
+			const unsigned grid = (unsigned)std::min<uint64_t>(1024, (std::max(plan_words, ntiles) + 255) / 256 + 1);
+			hipLaunchKernelGGL(round_init_kernel, dim3(grid), dim3(256), 0, c->stream, ctr, reinterpret_cast<uint32_t *>(r.rb.plans),
+					   plan_words, r.rb.scan_state, ntiles, r.rb.scan_ctr);
+		}
+		if ((rc = pinned_reserve(c, r.np * sizeof(Parent) + r.ns * sizeof(Stripe))) ||
+		    (rc = upload(c, { { r.rb.parents, r.rp.parents.data(), r.np * sizeof(Parent) }, { r.rb.stripes, r.rp.stripes.data(), r.ns * sizeof(Stripe) } })))
+			return rc;
+		phase_mark(c, "plan+upload");
+		return MSD_OK;
+	}
+
+	// ---- A (direct placement, DESIGN.md section 2, A'): the first round from a sample, later rounds -- only after a direct
+	// first round -- from exact counts (a read-only pass).
+	// (the read schedule hands a bucket one slot per tile: with fewer than 256 buckets the tiles
+	// are not filled, so narrower digits keep the streaming kernel unless forced)
+	int classify_direct(Round &r)
+	{
+		const RoundPlan &rp = r.rp;
+		const uint32_t np = r.np, ns = r.ns;
+		bool try_direct = c->direct_mode != 0 && rp.round_keys >= c->direct_min && !job.splitters;
 		for (size_t i = 0; i < np && try_direct; ++i) try_direct = rp.parents[i].width == 8 || c->direct_mode == 2;
 		if (try_direct && np > 1) {
 			try_direct = prev_direct && np <= kDirectMaxParents;
@@ -871,79 +922,78 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 		uint64_t max_piece = 0; // a piece is at most one stripe's share of its parent's slots; the kernel counts it in 16 bits
 		for (size_t i = 0; i < np && try_direct; ++i)
 			max_piece = std::max<uint64_t>(max_piece, rp.parents[i].count / B / (rp.parents[i].stripe_hi - rp.parents[i].stripe_lo) + 2);
-		if (try_direct && max_piece < 65535) {
-			if (np == 1) {
-				// sample about 2^22 keys or more, as runs of 256 spread evenly over the parent
-				const uint64_t nruns = rp.parents[0].count / 256;
-				const uint32_t every = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, nruns / 16384));
-				const uint32_t sgrid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, nruns / every / 4));
-				hipLaunchKernelGGL((direct_sample_kernel<K>), dim3(sgrid), dim3(256), 0, c->stream, (const K *)keys, rb.parents, rb.plans, every);
-			} else {
-				// (the exact check behind a sampled leading-bit skip rides on this pass if it reads every key)
-				hist_checks = unverified && rp.round_keys == n;
-				if (hist_checks) {
-					int rcv = vres_init();
-					if (rcv) return rcv;
-					add_stat(c, "bit_skip_checked_by_histogram", 1);
-				}
-				hipLaunchKernelGGL((direct_hist_kernel<K>), dim3(ns), dim3(1024), 0, c->stream, (const K *)keys, rb.stripes, rb.parents, rb.plans,
-						   hist_checks ? vres : (unsigned long long *)nullptr);
+		if (!try_direct || max_piece >= 65535) return MSD_OK;
+		const RoundBufs &rb = r.rb;
+		if (np == 1) {
+			// sample about 2^22 keys or more, as runs of 256 spread evenly over the parent
+			const uint64_t nruns = rp.parents[0].count / 256;
+			const uint32_t every = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, nruns / 16384));
+			const uint32_t sgrid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, nruns / every / 4));
+			hipLaunchKernelGGL((direct_sample_kernel<K>), dim3(sgrid), dim3(256), 0, c->stream, (const K *)keys, rb.parents, rb.plans, every);
+		} else {
+			// (the exact check behind a sampled leading-bit skip rides on this pass if it reads every key)
+			r.hist_checks = unverified && rp.round_keys == n;
+			if (r.hist_checks) {
+				if (int rc = vres_init()) return rc;
+				add_stat(c, "bit_skip_checked_by_histogram", 1);
 			}
-			hipLaunchKernelGGL((direct_plan_kernel<B>), dim3(np), dim3(256), 0, c->stream, rb.parents, rb.plans, ctr);
-			phase_mark(c, np == 1 ? "A sample" : "A histogram");
-			// The plan's verdict (Counters::direct_uneven: some parent's children are too unequal, or its keys come in
-			// runs) stays on the device: the direct kernel returns at once if it is non-zero, the streaming kernel
-			// launched behind it if it is zero.  The host learns it with the round's summary.
-			tried_direct = true;
-			const uint32_t force = c->direct_mode == 2 ? 1u : 0u;
-			{
-				constexpr size_t direct_lds = Direct2Lds<K, V>::bytes;
-				hipLaunchKernelGGL((classify_direct2_kernel<K, V>), dim3(ns), dim3(Direct2Cfg<K, V>::TH), direct_lds, c->stream,
-						   keys, vals, rb.stripes, rb.parents, (const DirectPlan *)rb.plans, block_map, slot_full,
-						   rb.fb, rb.lo_cnt, rb.lo_off, (K *)rb.lo_keys, rb.lo_vals, rb.nfull, ctr, force);
-			}
-			HIPCHK(c, hipGetLastError());
-			phase_mark(c, "A classify direct");
+			hipLaunchKernelGGL((direct_hist_kernel<K>), dim3(ns), dim3(1024), 0, c->stream, (const K *)keys, rb.stripes, rb.parents, rb.plans,
+					   r.hist_checks ? vres : (unsigned long long *)nullptr);
 		}
-		if (!tried_direct || c->direct_mode != 2) {
-			const uint32_t *run_if = tried_direct ? (const uint32_t *)&ctr->direct_uneven : (const uint32_t *)nullptr;
-			if (c->stream_kernel == 2) { // the lean tile loop (msd_stream2.hpp)
-				constexpr size_t s2_lds = Stream2Lds<K, V>::bytes;
-				if (splitters)
-					hipLaunchKernelGGL((classify_stream2_kernel<K, V, true>), dim3(ns), dim3(Stream2Cfg<K, V>::TH), s2_lds + kP * sizeof(K), c->stream,
-							   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
-							   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, splitters, run_if);
-				else
-					hipLaunchKernelGGL((classify_stream2_kernel<K, V, false>), dim3(ns), dim3(Stream2Cfg<K, V>::TH), s2_lds, c->stream,
-							   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
-							   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, (const K *)nullptr, run_if);
-			} else { // round 2's kernel (A/B comparisons)
-				constexpr size_t classify_lds = ClassifyLds<K, V>::bytes;
-				if (splitters)
-					hipLaunchKernelGGL((classify_kernel<K, V, true>), dim3(ns), dim3(C::TH), classify_lds + kP * sizeof(K), c->stream,
-							   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
-							   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, splitters, run_if);
-				else
-					hipLaunchKernelGGL((classify_kernel<K, V, false>), dim3(ns), dim3(C::TH), classify_lds, c->stream,
-							   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
-							   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, (const K *)nullptr, run_if);
-			}
-			HIPCHK(c, hipGetLastError());
-		}
-		const uint8_t *full_map = tried_direct ? (const uint8_t *)slot_full : (const uint8_t *)nullptr;
-		const uint32_t force_map = c->direct_mode == 2 ? 1u : 0u;
-		phase_mark(c, "A classify");
+		hipLaunchKernelGGL((direct_plan_kernel<B>), dim3(np), dim3(256), 0, c->stream, rb.parents, rb.plans, ctr);
+		phase_mark(c, np == 1 ? "A sample" : "A histogram");
+		// The plan's verdict (Counters::direct_uneven: some parent's children are too unequal, or its keys come in
+		// runs) stays on the device: the direct kernel returns at once if it is non-zero, the streaming kernel
+		// launched behind it if it is zero.  The host learns it with the round's summary.
+		r.tried_direct = true;
+		const uint32_t force = c->direct_mode == 2 ? 1u : 0u;
+		constexpr size_t direct_lds = Direct2Lds<K, V>::bytes;
+		hipLaunchKernelGGL((classify_direct2_kernel<K, V>), dim3(ns), dim3(Direct2Cfg<K, V>::TH), direct_lds, c->stream,
+				   keys, vals, rb.stripes, rb.parents, (const DirectPlan *)rb.plans, block_map, slot_full,
+				   rb.fb, rb.lo_cnt, rb.lo_off, (K *)rb.lo_keys, rb.lo_vals, rb.nfull, ctr, force);
+		HIPCHK(c, hipGetLastError());
+		phase_mark(c, "A classify direct");
+		return MSD_OK;
+	}
 
-		// ---- block metadata: child geometry, misplaced-block lists, holes
+	// ---- A: classify (the histogram falls out of it): a direct attempt, and the streaming kernel (msd_stream2.hpp) -- behind
+	// a direct attempt it runs only if that declined
+	int classify(Round &r)
+	{
+		if (int rc = classify_direct(r)) return rc;
+		if (!r.tried_direct || c->direct_mode != 2) {
+			const RoundBufs &rb = r.rb;
+			const uint32_t *run_if = r.tried_direct ? (const uint32_t *)&ctr->direct_uneven : (const uint32_t *)nullptr;
+			constexpr size_t s2_lds = Stream2Lds<K, V>::bytes;
+			if (job.splitters)
+				hipLaunchKernelGGL((classify_stream2_kernel<K, V, true>), dim3(r.ns), dim3(Stream2Cfg<K, V>::TH), s2_lds + kP * sizeof(K), c->stream,
+						   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
+						   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, job.splitters, run_if);
+			else
+				hipLaunchKernelGGL((classify_stream2_kernel<K, V, false>), dim3(r.ns), dim3(Stream2Cfg<K, V>::TH), s2_lds, c->stream,
+						   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
+						   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, (const K *)nullptr, run_if);
+			HIPCHK(c, hipGetLastError());
+		}
+		phase_mark(c, "A classify");
+		return MSD_OK;
+	}
+
+	// ---- B: block metadata (child geometry, misplaced-block lists, holes), then the block permutation
+	int permute_blocks(Round &r)
+	{
+		const RoundBufs &rb = r.rb;
+		const uint32_t np = r.np, ns = r.ns, nc = r.nc;
+		const uint8_t *full_map = r.tried_direct ? (const uint8_t *)slot_full : (const uint8_t *)nullptr;
+		const uint32_t force_map = c->direct_mode == 2 ? 1u : 0u;
 		hipLaunchKernelGGL((child_scan_kernel<B>), dim3(np), dim3(1024), 0, c->stream, rb.parents, rb.fb, rb.lo_cnt, rb.lo_dst, rb.ca);
 		hipLaunchKernelGGL((slot_classify_kernel<false>), dim3(ns * kSlotParts), dim3(256), 0, c->stream, rb.stripes, rb.parents,
 				   block_map, rb.nfull, rb.ca, rb.list, rb.holes, ctr, full_map, force_map);
 		hipLaunchKernelGGL(list_prepare_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca, ctr,
-				   (uint32_t)std::min<uint64_t>(rp.nslots, 0xFFFFFFFFu), (uint32_t)(2 * nc + kMinChains));
-		{
-			int rc = run_scan(c, rb.ca.list_len, rb.ca.list_base, nc, rb.scan_state, rb.scan_ctr, &ctr->errors, true);
-			if (rc) return rc;
-		}
+				   (uint32_t)std::min<uint64_t>(r.rp.nslots, 0xFFFFFFFFu), (uint32_t)(2 * nc + kMinChains));
+		hipLaunchKernelGGL(scan_lookback_kernel, dim3((unsigned)((nc + kScanTile - 1) / kScanTile)), dim3(kScanTh), 0, c->stream, // (its state: round_init_kernel)
+				   (const uint64_t *)rb.ca.list_len, rb.ca.list_base, (uint64_t)nc, rb.scan_state, rb.scan_ctr, &ctr->errors);
+		HIPCHK(c, hipGetLastError());
 		hipLaunchKernelGGL((slot_classify_kernel<true>), dim3(ns * kSlotParts), dim3(256), 0, c->stream, rb.stripes, rb.parents,
 				   block_map, rb.nfull, rb.ca, rb.list, rb.holes, ctr, full_map, force_map);
 		// per child: up to 64 waves when there are few children, one thread when there are very many
@@ -954,148 +1004,151 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 		HIPCHK(c, hipGetLastError());
 		phase_mark(c, "B metadata");
 
-		// ---- B: block permutation
-		{
-			// Exactly the workgroups the chip holds at once: a wave's first 64 chain starts are its own by position and the
-			// rest come from the cursor as its chains end, so every hole is in the hands of a running wave from the start.
-			// (Twice as many workgroups: those of the second half whose share held holes started when the first finished
-			// -- 2^30 Zipf keys: 1.3 ms where a wave's own work takes 0.7.)
-			const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * c->chains_per_cu[HV ? 2 : sizeof(K) == 8 ? 1 : 0],
-									 std::max<uint64_t>(1, (rp.nslots + 255) / 256));
-			hipLaunchKernelGGL(list_pack_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca);
-			hipLaunchKernelGGL((chains_kernel<K, V>), dim3(grid), dim3(256), 0, c->stream, rb.ca, rb.list, rb.holes, ctr,
-					   keys, vals, (K *)rb.xkeys, rb.xvals, (uint32_t)(n / B), (uint32_t)(4 * nc + kMinChains));
-			hipLaunchKernelGGL(chains_verify_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca, ctr);
-			HIPCHK(c, hipGetLastError());
-		}
+		// Exactly the workgroups the chip holds at once: a wave's first 64 chain starts are its own by position and the
+		// rest come from the cursor as its chains end, so every hole is in the hands of a running wave from the start.
+		// (Twice as many workgroups: those of the second half whose share held holes started when the first finished
+		// -- 2^30 Zipf keys: 1.3 ms where a wave's own work takes 0.7.)
+		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * c->chains_per_cu[HV ? 2 : sizeof(K) == 8 ? 1 : 0],
+								 std::max<uint64_t>(1, (r.rp.nslots + 255) / 256));
+		hipLaunchKernelGGL(list_pack_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca);
+		hipLaunchKernelGGL((chains_kernel<K, V>), dim3(grid), dim3(256), 0, c->stream, rb.ca, rb.list, rb.holes, ctr,
+				   keys, vals, (K *)rb.xkeys, rb.xvals, (uint32_t)(n / B), (uint32_t)(4 * nc + kMinChains));
+		hipLaunchKernelGGL(chains_verify_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca, ctr);
+		HIPCHK(c, hipGetLastError());
 		phase_mark(c, "B block permute");
+		return MSD_OK;
+	}
 
-		// ---- C: cleanup
-		hipLaunchKernelGGL((cleanup_kernel<K, V>), dim3(ns), dim3(256), 0, c->stream, rb.stripes, rb.parents, rb.lo_cnt,
+	// ---- C: cleanup, then the children to the next round or the leaf lists
+	int cleanup_collect(Round &r)
+	{
+		const RoundBufs &rb = r.rb;
+		const uint32_t np = r.np, nc = r.nc;
+		const bool sp = job.single_pass();
+		hipLaunchKernelGGL((cleanup_kernel<K, V>), dim3(r.ns), dim3(256), 0, c->stream, rb.stripes, rb.parents, rb.lo_cnt,
 				   rb.lo_off, rb.lo_dst, rb.ca, (const K *)rb.lo_keys, rb.lo_vals, keys, vals);
 		hipLaunchKernelGGL((excess_kernel<K, V>), dim3(nc), dim3(64), 0, c->stream, nc, rb.ca, (const K *)rb.xkeys, rb.xvals, keys, vals);
 		uint32_t wmax = 1;
-		for (size_t i = 0; i < np; ++i) wmax = std::max(wmax, rp.parents[i].width);
+		for (size_t i = 0; i < np; ++i) wmax = std::max(wmax, r.rp.parents[i].width);
+		const uint32_t small_cap = (uint32_t)std::min<size_t>(c->lists_cap, 0xFFFFFFFFu);
 		hipLaunchKernelGGL(collect_kernel, dim3((np + (256u >> wmax) - 1) / (256u >> wmax)), dim3(256), 0, c->stream, (const Parent *)rb.parents, np, wmax, rb.ca,
-				   single_pass ? ~0ull : small_max, (HV || single_pass) ? small_max : std::max<uint64_t>(small_max, kCountMedMax),
-				   small_cap, single_pass ? 0u : count_bits,
-				   rb.next_parents, small, small_count, (HV || single_pass) ? (Segment *)nullptr : big, big_cap, ctr,
-				   (single_pass && sp_count) ? sp_count : (uint64_t *)nullptr, splitters ? nsplit + 1u : nc, stop_bits);
+				   sp ? ~0ull : small_max, (HV || sp) ? small_max : std::max<uint64_t>(small_max, kCountMedMax),
+				   small_cap, sp ? 0u : count_bits,
+				   rb.next_parents, small(), small_count(), (HV || sp) ? (Segment *)nullptr : big, big_cap, ctr,
+				   (sp && job.counts) ? job.counts : (uint64_t *)nullptr, job.splitters ? job.nsplit + 1u : nc, job.stop_bits);
 		HIPCHK(c, hipGetLastError());
 		phase_mark(c, "C cleanup");
+		return MSD_OK;
+	}
 
-		// ---- round summary + next parents back to the host (which plans the next round): ONE synchronisation; the
-		// first kReadAhead next parents travel with the counters (more than that only on the odd input: fetched then)
-		constexpr size_t kReadAhead = 2048, kSegOff = 256;
-		const size_t np_cap = rp.round_keys / (small_max + 1) + 2, ahead = single_pass ? 0 : std::min(np_cap, kReadAhead);
-		{
-			int rc = pinned_reserve(c, kSegOff + kReadAhead * sizeof(Segment));
-			if (rc) return rc;
-		}
+	// ---- round summary + next parents back to the host (which plans the next round): ONE synchronisation; the
+	// first kReadAhead next parents travel with the counters (more than that only on the odd input: fetched then)
+	int round_summary(Round &r)
+	{
+		constexpr size_t kReadAhead = 2048, kSegOff = 256, kVresOff = kSegOff - 2 * sizeof(unsigned long long);
+		static_assert(sizeof(Counters) <= kVresOff, "counters and the OR/AND words share the head of the staging buffer");
+		const size_t np_cap = r.rp.round_keys / (small_max + 1) + 2, ahead = job.single_pass() ? 0 : std::min(np_cap, kReadAhead);
 		Counters hc;
-		HIPCHK(c, hipMemcpyAsync(c->pinned, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-		if (ahead)
-			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kSegOff, rb.next_parents, ahead * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-		static_assert(sizeof(Counters) + 2 * sizeof(unsigned long long) <= kSegOff, "counters and the OR/AND words share the head of the staging buffer");
-		if (hist_checks)
-			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kSegOff - 2 * sizeof(unsigned long long), vres, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		memcpy(&hc, c->pinned, sizeof hc);
+		int rc = pinned_reserve(c, kSegOff + kReadAhead * sizeof(Segment));
+		if (rc || (rc = read_counters(c, ctr, hc, { { kSegOff, r.rb.next_parents, ahead * sizeof(Segment) },
+							    { kVresOff, vres, r.hist_checks ? 2 * sizeof(unsigned long long) : 0 } })))
+			return rc;
 		if (hc.errors) return fail(c, MSD_EINTERNAL, "round %d: %u internal invariant violations (checks 0x%x: bit = site of msd_note_error in csrc/; 0 = a scan tile's look-back timed out; "
-									"%u parents, %u stripes, direct placement %s)",
-							     round, hc.errors, hc.err_sites, np, ns, tried_direct ? (hc.direct_uneven ? "declined" : "used") : "not tried");
-		if (hist_checks) {
-			const unsigned long long *h = (const unsigned long long *)((char *)c->pinned + kSegOff - 2 * sizeof(unsigned long long));
-			const uint64_t exact_vary = h[0] ^ h[1];
-			if (exact_vary & claimed_const) { // some key differs in a bit the sample found constant: all over again, on every varying bit
-				int rcs = start_over(exact_vary);
-				if (rcs) return rcs;
-				round = 0;
+						  "%u parents, %u stripes, direct placement %s)",
+					   round, hc.errors, hc.err_sites, r.np, r.ns, r.tried_direct ? (hc.direct_uneven ? "declined" : "used") : "not tried");
+		if (r.hist_checks) {
+			const unsigned long long *h = (const unsigned long long *)((char *)c->pinned + kVresOff);
+			if ((h[0] ^ h[1]) & claimed_const) { // some key differs in a bit the sample found constant
+				exact_vary = h[0] ^ h[1];
 				phase_mark(c, "readback");
-				continue;
+				return kRestart;
 			}
 			unverified = false;
 		}
-		const bool direct = tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
-		if (direct) add_stat(c, "direct_rounds", 1);
-		prev_direct = direct;
+		prev_direct = r.tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
+		if (prev_direct) add_stat(c, "direct_rounds", 1);
 		nsmall_host = hc.nsmall;
 		ncount_host = hc.ncount;
 		nbig_host = hc.nbig;
 		add_stat(c, "rounds", 1);
-		add_stat(c, "parents", np);
-		add_stat(c, "stripes", ns);
-		add_stat(c, "children", nc);
-		add_stat(c, "slots", rp.nslots);
+		add_stat(c, "parents", r.np);
+		add_stat(c, "stripes", r.ns);
+		add_stat(c, "children", r.nc);
+		add_stat(c, "slots", r.rp.nslots);
 		add_stat(c, "holes", hc.nholes);
 		set_stat(c, "chain_steps", hc.chain_steps);
 		cur.clear();
-		if (single_pass) break;
+		if (job.single_pass()) return MSD_OK;
 		bool stays_on_device = false;
 		if constexpr (sizeof(K) == 8) {
 			// every next parent fits a workgroup's registers: the list stays on the device and is planned there
 			if (c->regpart && hc.next_parents >= 64 && (uint64_t)hc.next_max + 1 <= kRpCap) {
-				HIPCHK(c, hipMemcpyAsync(dev_list, rb.next_parents, (size_t)hc.next_parents * sizeof(Segment), hipMemcpyDeviceToDevice, c->stream));
+				HIPCHK(c, hipMemcpyAsync(dev_list, r.rb.next_parents, (size_t)hc.next_parents * sizeof(Segment), hipMemcpyDeviceToDevice, c->stream));
 				dev_np = hc.next_parents;
 				stays_on_device = true;
 			}
 		}
-		if (hc.next_parents && !stays_on_device) {
-			if (hc.next_parents <= ahead)
-				cur.assign((Segment *)((char *)c->pinned + kSegOff), (Segment *)((char *)c->pinned + kSegOff) + hc.next_parents);
-			else {
-				int rc = pinned_reserve(c, (size_t)hc.next_parents * sizeof(Segment));
-				if (rc) return rc;
-				HIPCHK(c, hipMemcpyAsync(c->pinned, rb.next_parents, (size_t)hc.next_parents * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-				HIPCHK(c, hipStreamSynchronize(c->stream));
-				cur.assign((Segment *)c->pinned, (Segment *)c->pinned + hc.next_parents);
-			}
-			// atomic appends arrive in any order; make the plan deterministic
-			std::sort(cur.begin(), cur.end(), [](const Segment &a, const Segment &b) { return a.start < b.start; });
-		}
+		if (hc.next_parents && !stays_on_device &&
+		    (rc = fetch_segments(c, r.rb.next_parents, hc.next_parents, cur, (char *)c->pinned + kSegOff, ahead)))
+			return rc;
 		phase_mark(c, "readback");
 		++round;
+		return MSD_OK;
 	}
-	if (unverified) { // no round's histogram pass carried the check: a pass of its own, before any leaf runs
+
+	// ---- no round's histogram pass carried the exact check behind a sampled skip: a pass of its own, before any leaf runs
+	int verify_skip()
+	{
+		if (!unverified) return MSD_OK;
 		uint64_t vary = 0;
-		int rc = run_vary(1, &vary);
-		if (rc) return rc;
+		if (int rc = run_vary(1, &vary)) return rc;
 		phase_mark(c, "bit skip");
 		if (vary & claimed_const) {
-			if ((rc = start_over(vary))) return rc;
-			again = true;
-		} else
-			unverified = false;
+			exact_vary = vary;
+			return kRestart;
+		}
+		unverified = false;
+		return MSD_OK;
 	}
+
+	// ---- the check behind a sampled skip failed: the sort starts over on the bits that really vary (exact_vary)
+	int start_over()
+	{
+		const uint64_t vary = exact_vary & low_mask;
+		const int top = vary ? 64 - __builtin_clzll(vary) : 0;
+		set_stat(c, "skipped_bits", (uint64_t)(end_bit - top));
+		add_stat(c, "bit_skip_restarts", 1);
+		cur.clear();
+		if (top > 0 && (uint32_t)top > job.stop_bits) cur.push_back({ 0, n, (uint32_t)top, 0 });
+		nsmall_host = ncount_host = nbig_host = dev_np = 0;
+		round = 0;
+		prev_direct = unverified = false;
+		HIPCHK(c, hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
+		return MSD_OK;
 	}
 
 	// ---- leaves, stage 1: one unstable counting pass over all remaining bits (one workgroup per segment)
-	constexpr size_t sort_lds = SortLds<K, V>::bytes;
-	uint32_t nfallback_known = 0xFFFFFFFFu; // segments the counting leaves have handed to the general LDS sort, once the host has seen it
-	if constexpr (!HV) {
-		if (ncount_host && !single_pass) {
+	int count_leaves()
+	{
+		if constexpr (!HV) {
+			if (!ncount_host || job.single_pass()) return MSD_OK;
 			// persistent workgroups (two per CU fit the LDS), segments handed out by ticket; what the fast
 			// kernel cannot place directly is queued (in the round slab, dead by now) for the walking kernel
-			int rcs = slab_reserve(c, 3 * (size_t)ncount_host * sizeof(Segment) + 4096);
-			if (rcs) return rcs;
+			int rc = slab_reserve(c, 3 * (size_t)ncount_host * sizeof(Segment) + 4096);
+			if (rc) return rc;
 			Segment *slow = reinterpret_cast<Segment *>(c->slab), *rej16 = slow + ncount_host, *slow2 = rej16 + ncount_host;
 			const uint32_t count_grid = std::min<uint32_t>(ncount_host, (uint32_t)c->sm_count * 2);
-			if constexpr (sizeof(K) == 4) {
-				// u32 keys with 16 open bits (what the planner aims for): the specialised kernel first, the general one
-				// takes what that leaves (other bit counts, long or crowded segments)
-				// (it pays for segments of about 2^14 keys -- 2^30-key inputs; on shorter ones the per-segment work on the
-				// 2^16 counters dominates and 1024-thread workgroups hide its latency better: 1.15 vs 1.44 ms at 2^28)
-				if (c->count16 == 2 || (c->count16 == 1 && n / ncount_host >= 12000)) {
+			// u32 keys with 16 open bits (what the planner aims for): the specialised kernel first, the general one
+			// takes what that leaves (other bit counts, long or crowded segments)
+			// (it pays for segments of about 2^14 keys -- 2^30-key inputs; on shorter ones the per-segment work on the
+			// 2^16 counters dominates and 1024-thread workgroups hide its latency better: 1.15 vs 1.44 ms at 2^28)
+			const bool c16 = sizeof(K) == 4 && (c->count16 == 2 || (c->count16 == 1 && n / ncount_host >= 12000));
+			if constexpr (sizeof(K) == 4)
+				if (c16)
 					hipLaunchKernelGGL(count_place16_kernel, dim3(count_grid), dim3(kC16Th), kC16Lds, c->stream,
-							   keys, small_count, ncount_host, rej16, ctr, n);
-					hipLaunchKernelGGL((count_place_kernel<K>), dim3(count_grid), dim3(kCountTh), kCountLds, c->stream,
-							   keys, rej16, 0u, (const uint32_t *)&ctr->nslow16, slow, ctr);
-				} else
-					hipLaunchKernelGGL((count_place_kernel<K>), dim3(count_grid), dim3(kCountTh), kCountLds, c->stream,
-							   keys, small_count, ncount_host, (const uint32_t *)nullptr, slow, ctr);
-			} else
-				hipLaunchKernelGGL((count_place_kernel<K>), dim3(count_grid), dim3(kCountTh), kCountLds, c->stream,
-						   keys, small_count, ncount_host, (const uint32_t *)nullptr, slow, ctr);
+							   keys, small_count(), ncount_host, rej16, ctr, n);
+			hipLaunchKernelGGL((count_place_kernel<K>), dim3(count_grid), dim3(kCountTh), kCountLds, c->stream,
+					   keys, c16 ? rej16 : small_count(), c16 ? 0u : ncount_host, c16 ? (const uint32_t *)&ctr->nslow16 : (const uint32_t *)nullptr, slow, ctr);
 			const uint32_t *walk_n = &ctr->nslow;
 			const Segment *walk_list = slow;
 			if constexpr (sizeof(K) == 4) {
@@ -1113,27 +1166,27 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 				}
 			}
 			hipLaunchKernelGGL((count_walk_kernel<K>), dim3(count_grid), dim3(kCountTh), kCountLds, c->stream,
-					   keys, walk_list, walk_n, small, nsmall_host, (uint32_t)small_max, big, big_cap, ctr);
+					   keys, walk_list, walk_n, small(), nsmall_host, (uint32_t)small_max, big, big_cap, ctr);
 			HIPCHK(c, hipGetLastError());
 			phase_mark(c, "count sort");
 			// byte-counter overflows of segments above the LDS-sort capacity joined the big list
-			Counters hc3;
-			HIPCHK(c, hipMemcpyAsync(c->pinned, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			memcpy(&hc3, c->pinned, sizeof hc3);
-			if (hc3.errors) return fail(c, MSD_EINTERNAL, "counting leaf: %u segments could not be queued", hc3.errors);
-			nbig_host = hc3.nbig;
-			nfallback_known = hc3.nfallback;
+			Counters hc;
+			if ((rc = read_counters(c, ctr, hc))) return rc;
+			if (hc.errors) return fail(c, MSD_EINTERNAL, "counting leaf: %u segments could not be queued", hc.errors);
+			nbig_host = hc.nbig;
+			nfallback_known = hc.nfallback;
 		}
+		return MSD_OK;
 	}
+
 	// ---- keys-only segments of any size with <= 16 open bits: multi-workgroup counting sort
-	if constexpr (!HV) {
-		if (nbig_host && !single_pass) {
-			int rc = pinned_reserve(c, (size_t)nbig_host * sizeof(Segment));
+	int big_count_sort()
+	{
+		if constexpr (!HV) {
+			if (!nbig_host || job.single_pass()) return MSD_OK;
+			std::vector<Segment> bs;
+			int rc = fetch(c, big, nbig_host, bs);
 			if (rc) return rc;
-			HIPCHK(c, hipMemcpyAsync(c->pinned, big, (size_t)nbig_host * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			std::vector<Segment> bs((Segment *)c->pinned, (Segment *)c->pinned + nbig_host);
 			const uint32_t batch_max = 4096; // 256 KiB of histogram per segment: 1 GiB per batch
 			for (uint32_t b0 = 0; b0 < nbig_host; b0 += batch_max) {
 				const uint32_t nb = std::min(batch_max, nbig_host - b0);
@@ -1153,23 +1206,15 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 				uint32_t *ghist = nullptr, *d_first = nullptr;
 				K *seg_hi = nullptr;
 				uint16_t *tile_v = nullptr;
-				Bump sz(nullptr), *bp = &sz;
-				auto carve = [&]() {
-					ghist = bp->take<uint32_t>((size_t)nb * 65536);
-					seg_hi = bp->take<K>(nb);
-					d_first = bp->take<uint32_t>(first.size());
-					tile_v = bp->take<uint16_t>(ntiles * kBigGroup + nb + 8);
-				};
-				carve();
-				rc = slab_reserve(c, sz.off + 4096); // the round slab is dead by now
+				rc = slab_carve(c, [&](Bump &b) { // (the round slab is dead by now)
+					ghist = b.take<uint32_t>((size_t)nb * 65536);
+					seg_hi = b.take<K>(nb);
+					d_first = b.take<uint32_t>(first.size());
+					tile_v = b.take<uint16_t>(ntiles * kBigGroup + nb + 8);
+				});
 				if (!rc) rc = pinned_reserve(c, first.size() * sizeof(uint32_t));
+				if (!rc) rc = upload(c, { { d_first, first.data(), first.size() * sizeof(uint32_t) } });
 				if (rc) return rc;
-				Bump bb(c->slab);
-				bp = &bb;
-				carve();
-				HIPCHK(c, hipStreamSynchronize(c->stream));
-				memcpy(c->pinned, first.data(), first.size() * sizeof(uint32_t));
-				HIPCHK(c, hipMemcpyAsync(d_first, c->pinned, first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 				HIPCHK(c, hipMemsetAsync(ghist, 0, (size_t)nb * 65536 * sizeof(uint32_t), c->stream));
 				hipLaunchKernelGGL((bigcount_hist_kernel<K>), dim3((unsigned)std::min<uint64_t>(nchunks, (uint64_t)c->sm_count)), dim3(kBigHistTh), kBigHistLds, c->stream,
 						   (const K *)keys, big + b0, (const uint32_t *)d_first, nb, ghist);
@@ -1181,20 +1226,19 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 				HIPCHK(c, hipGetLastError());
 			}
 			phase_mark(c, "big count sort");
-			Counters hc2;
-			HIPCHK(c, hipMemcpyAsync(c->pinned, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			memcpy(&hc2, c->pinned, sizeof hc2);
-			if (hc2.errors) return fail(c, MSD_EINTERNAL, "counting sort: %u histogram totals disagree with segment sizes", hc2.errors);
+			Counters hc;
+			if ((rc = read_counters(c, ctr, hc))) return rc;
+			if (hc.errors) return fail(c, MSD_EINTERNAL, "counting sort: %u histogram totals disagree with segment sizes", hc.errors);
 		}
+		return MSD_OK;
 	}
-	set_stat(c, "big_count_segments", nbig_host);
 
 	// ---- leaves, stage 2: everything else that fits LDS (payloads, > 16 open bits): counting leaf on the
 	// top varying bits; its rare failures (long groups of equal top bits) and the byte-counter overflows
 	// of stage 1 go to the general LDS sort (their number is only known on the device)
-	if (!single_pass) {
-		const uint32_t nsm = nsmall_host + (HV ? ncount_host : 0u); // tuples: both lists hold leaf_count work
+	int lds_leaves()
+	{
+		if (job.single_pass()) return MSD_OK;
 		// persistent workgroups with prefetch of the next segment: as many per CU as the LDS holds
 		constexpr size_t leaf_lds = LeafCountLds<K, V>::bytes;
 		const uint32_t leaf_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2048 / C::SORT_TH, (160 * 1024) / (leaf_lds + 512)));
@@ -1204,15 +1248,14 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 			// 16 bits where the staging buffer will be, one lane per group of equal counted bits -- finishes a segment in 0.6
 			// of this leaf's time; what it leaves (segments shorter than 4096 keys, a group of more than 48) goes on to it.
 			if (c->leaf17 && nsmall_host && n / nsmall_host >= 8192) {
-				int rc = slab_reserve(c, (size_t)nsmall_host * sizeof(Segment) + 4096);
-				if (rc) return rc;
+				if (int rc = slab_reserve(c, (size_t)nsmall_host * sizeof(Segment) + 4096)) return rc;
 				Segment *d_rej = reinterpret_cast<Segment *>(c->slab);
 				HIPCHK(c, hipMemsetAsync(&ctr->nslow2, 0, sizeof(uint32_t), c->stream));
 				HIPCHK(c, hipMemsetAsync(&ctr->l17_slow, 0, sizeof(uint32_t), c->stream));
 				hipLaunchKernelGGL((leaf17_kernel<NoVal>), dim3(std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count)), dim3(kL17Th), kL17Lds, c->stream,
-						   (uint64_t *)keys, (uint64_t *)nullptr, (const Segment *)small, nsmall_host, d_rej, &ctr->nslow2, ctr, 4096u);
+						   (uint64_t *)keys, (uint64_t *)nullptr, (const Segment *)small(), nsmall_host, d_rej, &ctr->nslow2, ctr, 4096u);
 				hipLaunchKernelGGL((leaf_count_sort_kernel<K, V>), dim3(std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count * leaf_per_cu)), dim3(C::SORT_TH), leaf_lds, c->stream,
-						   keys, vals, (const Segment *)d_rej, nsmall_host, small + nsmall_host, ctr, &ctr->leaf_ticket[0], (const uint32_t *)&ctr->nslow2);
+						   keys, vals, (const Segment *)d_rej, nsmall_host, small() + nsmall_host, ctr, &ctr->leaf_ticket[0], (const uint32_t *)&ctr->nslow2);
 				HIPCHK(c, hipGetLastError());
 				add_stat(c, "leaf17_launches", 1);
 				small_done = true;
@@ -1220,30 +1263,111 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 		}
 		if (nsmall_host && !small_done) {
 			hipLaunchKernelGGL((leaf_count_sort_kernel<K, V>), dim3(std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count * leaf_per_cu)), dim3(C::SORT_TH), leaf_lds, c->stream,
-					   keys, vals, small, nsmall_host, small + nsmall_host, ctr, &ctr->leaf_ticket[0]);
+					   keys, vals, small(), nsmall_host, small() + nsmall_host, ctr, &ctr->leaf_ticket[0]);
 			HIPCHK(c, hipGetLastError());
 		}
 		if (HV && ncount_host) { // (tuples whose last <= 16 bits are open -- 5b after its rounds: same kernel, its own ticket)
 			hipLaunchKernelGGL((leaf_count_sort_kernel<K, V>), dim3(std::min<uint32_t>(ncount_host, (uint32_t)c->sm_count * leaf_per_cu)), dim3(C::SORT_TH), leaf_lds, c->stream,
-					   keys, vals, small_count, ncount_host, small + nsmall_host, ctr, &ctr->leaf_ticket[1]);
+					   keys, vals, small_count(), ncount_host, small() + nsmall_host, ctr, &ctr->leaf_ticket[1]);
 			HIPCHK(c, hipGetLastError());
 		}
-		(void)nsm;
 		// (keys only, no small segments, and the counting leaves are known to have handed nothing on: no launch -- 2^30 uniform
 		// u32 keys: 0.03 ms for workgroups that look at an empty list)
 		const bool may_fall_back = HV || nsmall_host != 0 || nfallback_known != 0;
 		if (may_fall_back && nsmall_host + ncount_host) {
+			constexpr size_t sort_lds = SortLds<K, V>::bytes;
 			hipLaunchKernelGGL((lds_sort_kernel<K, V>), dim3(std::min<uint32_t>(nsmall_host + ncount_host, 2 * c->sm_count)), dim3(C::SORT_TH), sort_lds, c->stream,
-					   keys, vals, small + nsmall_host, 0u, (const uint32_t *)&ctr->nfallback);
+					   keys, vals, small() + nsmall_host, 0u, (const uint32_t *)&ctr->nfallback);
 			HIPCHK(c, hipGetLastError());
 		}
 		phase_mark(c, "LDS sort");
+		return MSD_OK;
 	}
-	set_stat(c, "count_segments", ncount_host);
-	set_stat(c, "small_segments", nsmall_host);
+};
+
+} // namespace
+
+template <typename K, typename V>
+static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bit, const SortJob<K> &job)
+{
+	constexpr bool HV = has_val<V>::value;
+	if (n == 0) return MSD_OK;
+	if (!keys || (HV && !vals)) return fail(c, MSD_EINVAL, "null data pointer");
+	if (((uintptr_t)keys & 15) || (HV && ((uintptr_t)vals & 15)))
+		return fail(c, MSD_EINVAL, "keys/rids must be 16-byte aligned (the reference asserts the same, src/msb_64.c:2273)");
+	if (end_bit < 0 || end_bit > (int)sizeof(K) * 8) return fail(c, MSD_EINVAL, "end_bit out of range");
+	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large for 32-bit block slots");
+	HIPCHK(c, hipSetDevice(c->device));
+	c->stats.clear();
+	phase_begin(c);
+	SortRun<K, V> s(c, keys, vals, n, end_bit, job);
+	int rc = s.initial_segments();
+	if (!rc) rc = s.reserve_keep();
+	if (!rc) rc = s.skip_leading_bits();
+	if (!rc) rc = s.route_to_leaves();
+	// the partition rounds; if the exact check behind a sampled leading-bit skip fails -- on a round's histogram pass or on
+	// a pass of its own behind the rounds -- they start over on the bits that really vary (the data is the same multiset)
+	while (!rc) {
+		rc = s.rounds();
+		if (!rc) rc = s.verify_skip();
+		if (rc != kRestart) break;
+		rc = s.start_over();
+	}
+	if (!rc) rc = s.count_leaves();
+	if (!rc) rc = s.big_count_sort();
+	if (rc) return rc;
+	set_stat(c, "big_count_segments", s.nbig_host);
+	if ((rc = s.lds_leaves())) return rc;
+	set_stat(c, "count_segments", s.ncount_host);
+	set_stat(c, "small_segments", s.nsmall_host);
 	set_stat(c, "workspace_bytes", c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment));
 	phase_end(c);
 	return MSD_OK;
+}
+
+// what msd_reserve() provides for n elements
+template <typename K, typename V> static int reserve_for(msd_ctx *c, uint64_t n)
+{
+	int rc = slab_reserve(c, round_bytes_estimate<K, V>(n, c->sm_count), true);
+	if (!rc) rc = keep_reserve(c, keep_bytes_for<K, V>(n), true);
+	if (!rc) rc = pinned_reserve(c, 1 << 20);
+	if (!rc) rc = lists_reserve(c, leaf_list_guess<K, V>(n), 0, 0, true);
+	return rc;
+}
+
+// ---- the entry points' jobs (the C ABI below: one instance per element type)
+template <typename K, typename V> static int sort_bits(msd_ctx *c, K *k, uint64_t *r, uint64_t n, int end_bit)
+{
+	if (!c) return MSD_EINVAL;
+	return sort_impl<K, V>(c, k, r, n, end_bit, SortJob<K>::whole());
+}
+template <typename K, typename V> static int partition(msd_ctx *c, K *k, uint64_t *r, uint64_t n, unsigned shift, unsigned rb, uint64_t *cnt)
+{
+	if (!c) return MSD_EINVAL;
+	HIPCHK(c, hipSetDevice(c->device));
+	if (cnt && rb <= 8) HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint64_t) << rb, c->stream));
+	return sort_impl<K, V>(c, k, r, n, (int)sizeof(K) * 8, SortJob<K>::digit(shift, rb, cnt));
+}
+// a sort that stops early: afterwards the keys are ordered by key >> begin_bit
+template <typename K, typename V> static int sort_top(msd_ctx *c, K *k, uint64_t *r, uint64_t n, int end_bit, int begin_bit)
+{
+	if (!c) return MSD_EINVAL;
+	if (begin_bit < 0 || begin_bit > end_bit) return fail(c, MSD_EINVAL, "begin_bit must lie in [0, end_bit]");
+	return sort_impl<K, V>(c, k, r, n, end_bit, SortJob<K>::whole((uint32_t)begin_bit));
+}
+template <typename K, typename V>
+static int sort_segments(msd_ctx *c, K *k, uint64_t *r, uint64_t n, const uint64_t *seg_off, uint32_t nseg, int end_bit)
+{
+	if (!c) return MSD_EINVAL;
+	if (nseg == 0) return MSD_OK;
+	if (!seg_off) return fail(c, MSD_EINVAL, "segments: null offsets");
+	return sort_impl<K, V>(c, k, r, n, end_bit, SortJob<K>::offsets(seg_off, nseg));
+}
+
+// the most dynamic LDS `kernel` is launched with
+template <typename F> static hipError_t max_lds(F *kernel, size_t bytes)
+{
+	return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
@@ -1253,60 +1377,33 @@ template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
 		HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, chains_kernel<K, V>, 256, 0));
 		c->chains_per_cu[has_val<V>::value ? 2 : sizeof(K) == 8 ? 1 : 0] = std::max(1, per_cu);
 	}
-	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&classify_kernel<K, V, false>),
-				      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ClassifyLds<K, V>::bytes));
-	if constexpr (kHasRange<K, V>)
-		HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&classify_kernel<K, V, true>),
-					      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ClassifyLds<K, V>::bytes + kP * sizeof(K))));
-	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&classify_stream2_kernel<K, V, false>),
-				      hipFuncAttributeMaxDynamicSharedMemorySize, (int)Stream2Lds<K, V>::bytes));
-	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&classify_stream2_kernel<K, V, true>),
-				      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(Stream2Lds<K, V>::bytes + kP * sizeof(K))));
-	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&lds_sort_kernel<K, V>),
-				      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SortLds<K, V>::bytes));
-	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&classify_direct2_kernel<K, V>),
-				      hipFuncAttributeMaxDynamicSharedMemorySize, (int)Direct2Lds<K, V>::bytes));
+	HIPCHK(c, max_lds(&classify_stream2_kernel<K, V, false>, Stream2Lds<K, V>::bytes));
+	HIPCHK(c, max_lds(&classify_stream2_kernel<K, V, true>, Stream2Lds<K, V>::bytes + kP * sizeof(K)));
+	HIPCHK(c, max_lds(&lds_sort_kernel<K, V>, SortLds<K, V>::bytes));
+	HIPCHK(c, max_lds(&classify_direct2_kernel<K, V>, Direct2Lds<K, V>::bytes));
 	if constexpr (sizeof(K) == 8) {
-		HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&regpart_kernel<V>),
-					      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRpLds));
-		HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&leaf17_kernel<V>),
-					      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kL17Lds));
+		HIPCHK(c, max_lds(&regpart_kernel<V>, kRpLds));
+		HIPCHK(c, max_lds(&leaf17_kernel<V>, kL17Lds));
 	}
-	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&leaf_count_sort_kernel<K, V>),
-				      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LeafCountLds<K, V>::bytes));
+	HIPCHK(c, max_lds(&leaf_count_sort_kernel<K, V>, LeafCountLds<K, V>::bytes));
 	if constexpr (!has_val<V>::value) {
 		if constexpr (sizeof(K) == 4) {
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&count_place16_kernel),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kC16Lds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_place16_kernel<2>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kC16Lds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_place16_kernel<4>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kC16Lds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_place16_kernel<8>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kC16Lds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_count_kernel<false, uint32_t>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMcLds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_count_kernel<false, uint16_t>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMcLds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_count_kernel<false, Hist2>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMcLds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&hist2_pack_kernel<uint32_t>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kH2Lds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&hist2_pack_kernel<uint16_t>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kH2Lds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&scatter_low16_kernel),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kS16Lds));
-			HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&merge_count_kernel<true, uint32_t>),
-						      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMcLds));
+			HIPCHK(c, max_lds(&count_place16_kernel, kC16Lds));
+			HIPCHK(c, max_lds(&merge_place16_kernel<2>, kC16Lds));
+			HIPCHK(c, max_lds(&merge_place16_kernel<4>, kC16Lds));
+			HIPCHK(c, max_lds(&merge_place16_kernel<8>, kC16Lds));
+			HIPCHK(c, max_lds(&merge_count_kernel<false, uint32_t>, kMcLds));
+			HIPCHK(c, max_lds(&merge_count_kernel<false, uint16_t>, kMcLds));
+			HIPCHK(c, max_lds(&merge_count_kernel<false, Hist2>, kMcLds));
+			HIPCHK(c, max_lds(&hist2_pack_kernel<uint32_t>, kH2Lds));
+			HIPCHK(c, max_lds(&hist2_pack_kernel<uint16_t>, kH2Lds));
+			HIPCHK(c, max_lds(&scatter_low16_kernel, kS16Lds));
+			HIPCHK(c, max_lds(&merge_count_kernel<true, uint32_t>, kMcLds));
 		}
-		HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&count_place_kernel<K>),
-					      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCountLds));
-		HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&count_walk_kernel<K>),
-					      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCountLds));
-		HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&bigcount_hist_kernel<K>),
-					      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBigHistLds));
-		HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&bigcount_write_kernel<K>),
-					      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBigWriteLds));
+		HIPCHK(c, max_lds(&count_place_kernel<K>, kCountLds));
+		HIPCHK(c, max_lds(&count_walk_kernel<K>, kCountLds));
+		HIPCHK(c, max_lds(&bigcount_hist_kernel<K>, kBigHistLds));
+		HIPCHK(c, max_lds(&bigcount_write_kernel<K>, kBigWriteLds));
 	}
 	return MSD_OK;
 }
@@ -1426,92 +1523,31 @@ int msd_reserve(msd_ctx *c, uint64_t n, int key_bytes, int val_bytes)
 {
 	if (!c) return MSD_EINVAL;
 	HIPCHK(c, hipSetDevice(c->device));
-	size_t round_b, keep_b, list_n;
-	if (key_bytes == 4 && val_bytes == 0) {
-		round_b = round_bytes_estimate<uint32_t, NoVal>(n, c->sm_count);
-		keep_b = keep_bytes_for<uint32_t, NoVal>(n);
-		list_n = leaf_list_guess<uint32_t, NoVal>(n);
-	} else if (key_bytes == 8 && val_bytes == 0) {
-		round_b = round_bytes_estimate<uint64_t, NoVal>(n, c->sm_count);
-		keep_b = keep_bytes_for<uint64_t, NoVal>(n);
-		list_n = leaf_list_guess<uint64_t, NoVal>(n);
-	} else if (key_bytes == 8 && val_bytes == 8) {
-		round_b = round_bytes_estimate<uint64_t, uint64_t>(n, c->sm_count);
-		keep_b = keep_bytes_for<uint64_t, uint64_t>(n);
-		list_n = leaf_list_guess<uint64_t, uint64_t>(n);
-	} else
-		return fail(c, MSD_EINVAL, "unsupported element layout %d+%d bytes", key_bytes, val_bytes);
-	int rc = slab_reserve(c, round_b, true);
-	if (!rc) rc = keep_reserve(c, keep_b, true);
-	if (!rc) rc = pinned_reserve(c, 1 << 20);
-	if (!rc) rc = lists_reserve(c, list_n, 0, 0, true);
-	return rc;
+	if (key_bytes == 4 && val_bytes == 0) return reserve_for<uint32_t, NoVal>(c, n);
+	if (key_bytes == 8 && val_bytes == 0) return reserve_for<uint64_t, NoVal>(c, n);
+	if (key_bytes == 8 && val_bytes == 8) return reserve_for<uint64_t, uint64_t>(c, n);
+	return fail(c, MSD_EINVAL, "unsupported element layout %d+%d bytes", key_bytes, val_bytes);
 }
 
 uint64_t msd_workspace_bytes(const msd_ctx *c) { return c ? c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment) : 0; }
 const char *msd_last_error(const msd_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-int msd_sort_u32_bits(msd_ctx *c, uint32_t *k, uint64_t n, int end_bit)
-{
-	if (!c) return MSD_EINVAL;
-	return sort_impl<uint32_t, NoVal>(c, k, nullptr, n, end_bit, false, 0, 0, nullptr);
-}
-int msd_sort_u64_bits(msd_ctx *c, uint64_t *k, uint64_t n, int end_bit)
-{
-	if (!c) return MSD_EINVAL;
-	return sort_impl<uint64_t, NoVal>(c, k, nullptr, n, end_bit, false, 0, 0, nullptr);
-}
-int msd_sort_pairs_u64_bits(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, int end_bit)
-{
-	if (!c) return MSD_EINVAL;
-	return sort_impl<uint64_t, uint64_t>(c, k, r, n, end_bit, false, 0, 0, nullptr);
-}
+int msd_sort_u32_bits(msd_ctx *c, uint32_t *k, uint64_t n, int end_bit) { return sort_bits<uint32_t, NoVal>(c, k, nullptr, n, end_bit); }
+int msd_sort_u64_bits(msd_ctx *c, uint64_t *k, uint64_t n, int end_bit) { return sort_bits<uint64_t, NoVal>(c, k, nullptr, n, end_bit); }
+int msd_sort_pairs_u64_bits(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, int end_bit) { return sort_bits<uint64_t, uint64_t>(c, k, r, n, end_bit); }
 int msd_sort_u32(msd_ctx *c, uint32_t *k, uint64_t n) { return msd_sort_u32_bits(c, k, n, 32); }
 int msd_sort_u64(msd_ctx *c, uint64_t *k, uint64_t n) { return msd_sort_u64_bits(c, k, n, 64); }
 int msd_sort_pairs_u64(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n) { return msd_sort_pairs_u64_bits(c, k, r, n, 64); }
 
-int msd_partition_u32(msd_ctx *c, uint32_t *k, uint64_t n, unsigned shift, unsigned rb, uint64_t *cnt)
-{
-	if (!c) return MSD_EINVAL;
-	HIPCHK(c, hipSetDevice(c->device));
-	if (cnt && rb <= 8) HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint64_t) << rb, c->stream));
-	return sort_impl<uint32_t, NoVal>(c, k, nullptr, n, 32, true, shift, rb, cnt);
-}
-int msd_partition_u64(msd_ctx *c, uint64_t *k, uint64_t n, unsigned shift, unsigned rb, uint64_t *cnt)
-{
-	if (!c) return MSD_EINVAL;
-	HIPCHK(c, hipSetDevice(c->device));
-	if (cnt && rb <= 8) HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint64_t) << rb, c->stream));
-	return sort_impl<uint64_t, NoVal>(c, k, nullptr, n, 64, true, shift, rb, cnt);
-}
-int msd_partition_pairs_u64(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, unsigned shift, unsigned rb, uint64_t *cnt)
-{
-	if (!c) return MSD_EINVAL;
-	HIPCHK(c, hipSetDevice(c->device));
-	if (cnt && rb <= 8) HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint64_t) << rb, c->stream));
-	return sort_impl<uint64_t, uint64_t>(c, k, r, n, 64, true, shift, rb, cnt);
-}
+int msd_partition_u32(msd_ctx *c, uint32_t *k, uint64_t n, unsigned shift, unsigned rb, uint64_t *cnt) { return partition<uint32_t, NoVal>(c, k, nullptr, n, shift, rb, cnt); }
+int msd_partition_u64(msd_ctx *c, uint64_t *k, uint64_t n, unsigned shift, unsigned rb, uint64_t *cnt) { return partition<uint64_t, NoVal>(c, k, nullptr, n, shift, rb, cnt); }
+int msd_partition_pairs_u64(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, unsigned shift, unsigned rb, uint64_t *cnt) { return partition<uint64_t, uint64_t>(c, k, r, n, shift, rb, cnt); }
 
 // ---- a sort that stops early: afterwards the keys are ordered by key >> begin_bit (the top-digit passes of a rank of the
 // multi-GPU sort before its exchange; keys that agree above begin_bit may be in any order)
-int msd_sort_u32_top(msd_ctx *c, uint32_t *k, uint64_t n, int end_bit, int begin_bit)
-{
-	if (!c) return MSD_EINVAL;
-	if (begin_bit < 0 || begin_bit > end_bit) return fail(c, MSD_EINVAL, "begin_bit must lie in [0, end_bit]");
-	return sort_impl<uint32_t, NoVal>(c, k, nullptr, n, end_bit, false, 0, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, (uint32_t)begin_bit);
-}
-int msd_sort_u64_top(msd_ctx *c, uint64_t *k, uint64_t n, int end_bit, int begin_bit)
-{
-	if (!c) return MSD_EINVAL;
-	if (begin_bit < 0 || begin_bit > end_bit) return fail(c, MSD_EINVAL, "begin_bit must lie in [0, end_bit]");
-	return sort_impl<uint64_t, NoVal>(c, k, nullptr, n, end_bit, false, 0, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, (uint32_t)begin_bit);
-}
-int msd_sort_pairs_u64_top(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, int end_bit, int begin_bit)
-{
-	if (!c) return MSD_EINVAL;
-	if (begin_bit < 0 || begin_bit > end_bit) return fail(c, MSD_EINVAL, "begin_bit must lie in [0, end_bit]");
-	return sort_impl<uint64_t, uint64_t>(c, k, r, n, end_bit, false, 0, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, (uint32_t)begin_bit);
-}
+int msd_sort_u32_top(msd_ctx *c, uint32_t *k, uint64_t n, int end_bit, int begin_bit) { return sort_top<uint32_t, NoVal>(c, k, nullptr, n, end_bit, begin_bit); }
+int msd_sort_u64_top(msd_ctx *c, uint64_t *k, uint64_t n, int end_bit, int begin_bit) { return sort_top<uint64_t, NoVal>(c, k, nullptr, n, end_bit, begin_bit); }
+int msd_sort_pairs_u64_top(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, int end_bit, int begin_bit) { return sort_top<uint64_t, uint64_t>(c, k, r, n, end_bit, begin_bit); }
 
 } // extern "C"
 
@@ -1551,26 +1587,20 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	c->stats.clear();
 	phase_begin(c);
 	if (n_expected == 0) return MSD_OK;
-	Bump sz(nullptr), *bp = &sz;
 	Counters *ctr = nullptr;
 	uint32_t *status = nullptr, *cnt32 = nullptr;
 	uint64_t *soff = nullptr, *doff = nullptr;
 	Segment *rej = nullptr;
-	auto carve = [&]() {
-		ctr = bp->take<Counters>(1);
-		status = bp->take<uint32_t>(64);
-		cnt32 = bp->take<uint32_t>((size_t)nsrc * nb);
-		soff = bp->take<uint64_t>((size_t)nsrc * nb);
-		doff = bp->take<uint64_t>((size_t)nb + 1);
-		rej = bp->take<Segment>(nb);
-	};
-	carve();
-	int rc = slab_reserve(c, sz.off + 4096);
+	int rc = slab_carve(c, [&](Bump &b) {
+		ctr = b.take<Counters>(1);
+		status = b.take<uint32_t>(64);
+		cnt32 = b.take<uint32_t>((size_t)nsrc * nb);
+		soff = b.take<uint64_t>((size_t)nsrc * nb);
+		doff = b.take<uint64_t>((size_t)nb + 1);
+		rej = b.take<Segment>(nb);
+	});
 	if (!rc) rc = pinned_reserve(c, 4096);
 	if (rc) return rc;
-	Bump real(c->slab);
-	bp = &real;
-	carve();
 	HIPCHK(c, hipMemsetAsync(ctr, 0, (char *)(status + 64) - (char *)ctr, c->stream));
 	MergeBase mb = {};
 	for (uint32_t x = 0; x < nsrc; ++x) mb.b[x] = src_base[x];
@@ -1602,22 +1632,15 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	HIPCHK(c, hipGetLastError());
 	phase_mark(c, "merge leaf");
 	// what the leaf did not take (rare: long or crowded buckets) lies unsorted at its place in dst: the general leaves finish it
-	HIPCHK(c, hipMemcpyAsync(c->pinned, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipMemcpyAsync((char *)c->pinned + 1024, status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
 	Counters hc;
-	memcpy(&hc, c->pinned, sizeof hc);
+	if ((rc = read_counters(c, ctr, hc, { { 1024, status, sizeof(uint32_t) } }))) return rc;
 	if (*(const uint32_t *)((char *)c->pinned + 1024)) return fail(c, MSD_EINVAL, "merge_buckets: the counts do not add up to the expected %llu keys (or a count exceeds 32 bits)", (unsigned long long)n_expected);
 	const uint32_t nrej = hc.nslow16;
 	phase_end(c);
 	if (nrej) {
-		rc = pinned_reserve(c, (size_t)nrej * sizeof(Segment));
-		if (rc) return rc;
-		HIPCHK(c, hipMemcpyAsync(c->pinned, rej, (size_t)nrej * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		std::vector<Segment> segs((Segment *)c->pinned, (Segment *)c->pinned + nrej);
-		rc = sort_impl<uint32_t, NoVal>(c, dst, nullptr, n_expected, 32, false, 0, 0, nullptr, nullptr, 0, nullptr, 0, &segs);
-		if (rc) return rc;
+		std::vector<Segment> segs;
+		if ((rc = fetch(c, rej, nrej, segs))) return rc;
+		if ((rc = sort_impl<uint32_t, NoVal>(c, dst, nullptr, n_expected, 32, SortJob<uint32_t>::list(segs)))) return rc;
 	}
 	set_stat(c, "merge_rejected", nrej);
 	return MSD_OK;
@@ -1689,6 +1712,20 @@ __global__ __launch_bounds__(1024) void bounds16_kernel(const uint64_t *__restri
 	}
 	if (tid == 1023) bounds[65536] = at;
 }
+namespace {
+// the tables msd_order_low16_counts_u32 leaves in the slab for msd_order_low16_scatter_u32
+struct Low16Tables {
+	uint64_t *pb;             // bounds of the 256 top-digit buckets
+	uint32_t *wg;             // per workgroup and bucket: keys counted
+	unsigned long long *base; // per workgroup and bucket: where its share goes
+	void carve(Bump &b)
+	{
+		pb = b.take<uint64_t>(257);
+		wg = b.take<uint32_t>((size_t)65536 * kS16Chunks);
+		base = b.take<unsigned long long>((size_t)65536 * kS16Chunks + 1);
+	}
+};
+} // namespace
 extern "C" {
 int msd_hist2_pack_u32(msd_ctx *c, const uint32_t *d_keys, uint64_t n, const uint64_t *d_bounds, uint32_t nbuckets, void *d_rec, uint64_t rec_bytes,
 		       uint32_t *d_overflow)
@@ -1719,28 +1756,15 @@ int msd_order_low16_counts_u32(msd_ctx *c, uint32_t *d_keys, uint64_t n, uint64_
 	if ((uintptr_t)d_keys & 15) return fail(c, MSD_EINVAL, "order_low16: buffers must be 16-byte aligned");
 	if (n >= (1ull << 40)) return fail(c, MSD_EINVAL, "order_low16: too many keys");
 	// one in-place round on the top 8 bits (the direct-placement round 0) ...
-	int rc = sort_impl<uint32_t, NoVal>(c, d_keys, nullptr, n, 32, false, 0, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 24u);
+	int rc = sort_impl<uint32_t, NoVal>(c, d_keys, nullptr, n, 32, SortJob<uint32_t>::whole(24u));
 	if (rc) return rc;
 	// ... exact counts of all upper halves and the place of every workgroup's share of every bucket
 	HIPCHK(c, hipSetDevice(c->device));
-	Bump sz(nullptr), *bp = &sz;
-	uint64_t *pb = nullptr;
-	uint32_t *wg = nullptr;
-	unsigned long long *base = nullptr;
-	auto carve = [&]() {
-		pb = bp->take<uint64_t>(257);
-		wg = bp->take<uint32_t>((size_t)65536 * kS16Chunks);
-		base = bp->take<unsigned long long>((size_t)65536 * kS16Chunks + 1);
-	};
-	carve();
-	rc = slab_reserve(c, sz.off + 4096);
-	if (rc) return rc;
-	Bump real(c->slab);
-	bp = &real;
-	carve();
-	hipLaunchKernelGGL((bucket_bounds_kernel<uint32_t>), dim3(2), dim3(256), 0, c->stream, (const uint32_t *)d_keys, n, 24u, (uint64_t)0, 256u, pb);
-	hipLaunchKernelGGL(hist16_kernel, dim3(256 * kS16Chunks), dim3(kS16Th), 0, c->stream, (const uint32_t *)d_keys, n, (const uint64_t *)pb, wg);
-	hipLaunchKernelGGL(scan16_kernel, dim3(256), dim3(256), 0, c->stream, (const uint32_t *)wg, (const uint64_t *)pb, (unsigned long long *)d_counts, base);
+	Low16Tables t;
+	if ((rc = slab_carve(c, [&](Bump &b) { t.carve(b); }))) return rc;
+	hipLaunchKernelGGL((bucket_bounds_kernel<uint32_t>), dim3(2), dim3(256), 0, c->stream, (const uint32_t *)d_keys, n, 24u, (uint64_t)0, 256u, t.pb);
+	hipLaunchKernelGGL(hist16_kernel, dim3(256 * kS16Chunks), dim3(kS16Th), 0, c->stream, (const uint32_t *)d_keys, n, (const uint64_t *)t.pb, t.wg);
+	hipLaunchKernelGGL(scan16_kernel, dim3(256), dim3(256), 0, c->stream, (const uint32_t *)t.wg, (const uint64_t *)t.pb, (unsigned long long *)d_counts, t.base);
 	HIPCHK(c, hipGetLastError());
 	c->order_keys = d_keys; // (the tables of the scatter lie in the slab: the scatter must be this context's next call)
 	c->order_n = n;
@@ -1758,12 +1782,12 @@ int msd_order_low16_scatter_u32(msd_ctx *c, const uint32_t *d_keys, uint64_t n, 
 		if (s0 < d1 && d0 < s1) return fail(c, MSD_EINVAL, "order_low16: source and destination overlap");
 	}
 	HIPCHK(c, hipSetDevice(c->device));
-	Bump real(c->slab); // (as carved by msd_order_low16_counts_u32)
-	const uint64_t *pb = real.take<uint64_t>(257);
-	(void)real.take<uint32_t>((size_t)65536 * kS16Chunks);
-	const unsigned long long *base = real.take<unsigned long long>((size_t)65536 * kS16Chunks + 1);
+	Bump real(c->slab); // (as msd_order_low16_counts_u32 left it)
+	Low16Tables t;
+	t.carve(real);
 	if (n)
-		hipLaunchKernelGGL(scatter_low16_kernel, dim3(256 * kS16Chunks), dim3(kS16Th), kS16Lds, c->stream, d_keys, n, pb, base, d_out);
+		hipLaunchKernelGGL(scatter_low16_kernel, dim3(256 * kS16Chunks), dim3(kS16Th), kS16Lds, c->stream, d_keys, n, (const uint64_t *)t.pb,
+				   (const unsigned long long *)t.base, d_out);
 	HIPCHK(c, hipGetLastError());
 	return MSD_OK;
 }
@@ -1794,27 +1818,9 @@ int msd_pack_low16_u32(msd_ctx *c, const uint32_t *d_keys, uint64_t n, uint16_t 
 
 // ---- segmented sort and run gather: what a rank of the multi-GPU sort does with the keys it received
 
-int msd_sort_u32_segments(msd_ctx *c, uint32_t *k, uint64_t n, const uint64_t *seg_off, uint32_t nseg, int end_bit)
-{
-	if (!c) return MSD_EINVAL;
-	if (nseg == 0) return MSD_OK;
-	if (!seg_off) return fail(c, MSD_EINVAL, "segments: null offsets");
-	return sort_impl<uint32_t, NoVal>(c, k, nullptr, n, end_bit, false, 0, 0, nullptr, nullptr, 0, seg_off, nseg);
-}
-int msd_sort_u64_segments(msd_ctx *c, uint64_t *k, uint64_t n, const uint64_t *seg_off, uint32_t nseg, int end_bit)
-{
-	if (!c) return MSD_EINVAL;
-	if (nseg == 0) return MSD_OK;
-	if (!seg_off) return fail(c, MSD_EINVAL, "segments: null offsets");
-	return sort_impl<uint64_t, NoVal>(c, k, nullptr, n, end_bit, false, 0, 0, nullptr, nullptr, 0, seg_off, nseg);
-}
-int msd_sort_pairs_u64_segments(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, const uint64_t *seg_off, uint32_t nseg, int end_bit)
-{
-	if (!c) return MSD_EINVAL;
-	if (nseg == 0) return MSD_OK;
-	if (!seg_off) return fail(c, MSD_EINVAL, "segments: null offsets");
-	return sort_impl<uint64_t, uint64_t>(c, k, r, n, end_bit, false, 0, 0, nullptr, nullptr, 0, seg_off, nseg);
-}
+int msd_sort_u32_segments(msd_ctx *c, uint32_t *k, uint64_t n, const uint64_t *seg_off, uint32_t nseg, int end_bit) { return sort_segments<uint32_t, NoVal>(c, k, nullptr, n, seg_off, nseg, end_bit); }
+int msd_sort_u64_segments(msd_ctx *c, uint64_t *k, uint64_t n, const uint64_t *seg_off, uint32_t nseg, int end_bit) { return sort_segments<uint64_t, NoVal>(c, k, nullptr, n, seg_off, nseg, end_bit); }
+int msd_sort_pairs_u64_segments(msd_ctx *c, uint64_t *k, uint64_t *r, uint64_t n, const uint64_t *seg_off, uint32_t nseg, int end_bit) { return sort_segments<uint64_t, uint64_t>(c, k, r, n, seg_off, nseg, end_bit); }
 
 int msd_gather_runs_u32(msd_ctx *c, uint32_t *dst, const uint32_t *src, const uint64_t *src_off, const uint64_t *dst_off, const uint64_t *len, uint32_t nruns)
 {
@@ -1863,10 +1869,8 @@ static int range_partition_impl(msd_ctx *c, K *k, uint64_t *r, uint64_t n, const
 	if (parts == 1) { // one range: nothing moves; its size goes to the device on the context's stream (ordered with the caller's work there)
 		if (cnt) {
 			int rcp = pinned_reserve(c, 64);
+			if (!rcp) rcp = upload(c, { { cnt, &n, sizeof n } });
 			if (rcp) return rcp;
-			HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
-			memcpy(c->pinned, &n, sizeof n);
-			HIPCHK(c, hipMemcpyAsync(cnt, c->pinned, sizeof n, hipMemcpyHostToDevice, c->stream));
 			HIPCHK(c, hipStreamSynchronize(c->stream));
 		}
 		return MSD_OK;
@@ -1875,7 +1879,7 @@ static int range_partition_impl(msd_ctx *c, K *k, uint64_t *r, uint64_t n, const
 	unsigned width = 1;
 	while ((1u << width) < parts) ++width;
 	// one in-place round whose buckets are the ranges (parts - 1 delimiters; the buckets beyond `parts` stay empty)
-	return sort_impl<K, V>(c, k, r, n, (int)sizeof(K) * 8, true, 0, width, cnt, delims, parts - 1);
+	return sort_impl<K, V>(c, k, r, n, (int)sizeof(K) * 8, SortJob<K>::ranges(delims, parts - 1, width, cnt));
 }
 
 extern "C" {
@@ -2093,16 +2097,11 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 		c->count16 = (int)value;
 	} else if (!strcmp(name, "leaf17")) {
 		c->leaf17 = value != 0;
-	} else if (!strcmp(name, "stream_kernel")) {
-		if (value < 1 || value > 2) return fail(c, MSD_EINVAL, "stream_kernel must be 1 or 2");
-		c->stream_kernel = (int)value;
 	} else if (!strcmp(name, "mid_leaf")) {
 		c->mid_leaf = value != 0;
 	} else if (!strcmp(name, "merge_leaf")) {
 		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "merge_leaf must be 0, 1 or 2");
 		c->merge_leaf = (int)value;
-	} else if (!strcmp(name, "direct_kernel")) {
-		(void)value; // (round 1's kernel is gone; the option is accepted for old callers)
 	} else if (!strcmp(name, "direct_min_parent")) {
 		if (value < 1) return fail(c, MSD_EINVAL, "direct_min_parent must be positive");
 		c->direct_min_parent = (uint64_t)value;

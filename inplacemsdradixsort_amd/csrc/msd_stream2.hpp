@@ -2,7 +2,7 @@
 // or run-structured input, range partitioning by splitters) with the lean tile loop of classify_direct2_kernel
 // (included by msd_device.hpp).
 //
-// Same contract as classify_kernel (msd_device.hpp): one workgroup per stripe, keys stream through registers into 256
+// Same contract as round 2's classify_kernel, which it replaced: one workgroup per stripe, keys stream through registers into 256
 // per-bucket LDS buffers of one block each, every completed block is flushed to the next slot BEHIND the workgroup's own
 // read cursor (cf. range_partition_to_blocks, src/msb_64.c:611-667), block_map records the bucket of every slot, partial
 // buffers and head keys go to the stripe's leftover area, the digit histogram falls out of the pass.  What differs is
@@ -21,7 +21,7 @@
 //   * 512-thread workgroups, two per CU, 128 VGPRs (tuples: 1024 threads, one per CU); all fetch-adds of a tile are
 //     issued before the first result is used; the refill loads are unconditional for whole tiles.
 // A bucket that took more than a sixteenth of the previous tile is counted per wave in this one (the lanes of a wave
-// that hold one of its keys take ONE fetch-add together), as in classify_kernel.
+// that hold one of its keys take ONE fetch-add together), as in round 2's classify_kernel.
 #pragma once
 
 namespace msd {

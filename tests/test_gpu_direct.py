@@ -213,7 +213,8 @@ def test_direct_off_matches(dctx):
 
 
 def test_set_option_rejects_unknown(ctx):
-    with pytest.raises(Exception):
-        ctx.set_option("no_such_option", 1)
+    for name in ("no_such_option", "stream_kernel", "direct_kernel"):  # (the last two: retired options)
+        with pytest.raises(Exception):
+            ctx.set_option(name, 1)
     with pytest.raises(Exception):
         ctx.set_option("direct_mode", 7)
