@@ -218,6 +218,35 @@ int msd_partition_by_splitters_u64(msd_ctx *ctx, uint64_t *d_keys, uint64_t n, c
 int msd_partition_by_splitters_pairs_u64(msd_ctx *ctx, uint64_t *d_keys, uint64_t *d_rids, uint64_t n,
 					 const uint64_t *d_delims, unsigned parts, uint64_t *d_count);
 
+/* ---- radix select and top-k (no counterpart in the reference): ORDER BY key LIMIT k, the k-th value, a percentile ----
+ * With S = the input sorted ascending:
+ *   msd_topk_*:   d_out[0 .. k) = S[0 .. k) (MSD_SMALLEST) or S[n-k .. n) (MSD_LARGEST), in ASCENDING order in both cases
+ *     (a slice of the sorted array), keys bit-exact.  Tuples: unstable like the sort -- the out keys are that slice, every
+ *     (key, rid) written is a tuple of the input, no input position is used twice; which of several tuples with the
+ *     boundary key are taken is unspecified.  k == 0 is a successful no-op (n == 0 too).
+ *   msd_select_*: *value (HOST memory) = S[k] (MSD_SMALLEST) or S[n-1-k] (MSD_LARGEST), k < n.  Synchronous like msd_check_*.
+ * The input is read only (two passes over it for evenly spread keys: a digit histogram and a filter; one more histogram
+ * pass per further digit while the bucket that holds rank k is larger than "select_cap") and NOT modified.  The output
+ * must not overlap the input; inputs and outputs must be aligned to 16 bytes (the outputs are sorted with the sort).
+ * k > n (top-k), k >= n (select), a null pointer, an unknown `which`, overlap or misalignment give MSD_EINVAL and touch nothing.
+ * Threading as msd_sort_*: kernels on the context's stream; the call blocks the calling thread for ONE readback of the
+ * search state (about 100 bytes) behind the filter pass, then for the readbacks of the internal sorts (of the candidates, if
+ * only some of them belong to the answer, and of the k output elements: one per round each, none for what fits one
+ * leaf), and msd_select_* for one more of the value; top-k data are final once the stream has drained.
+ * Workspace (part of msd_workspace_bytes, grown on demand, reused, independent of n): the search state + one
+ * 4096-bin uint64 histogram per possible pass (3 for u32, 6 for u64 keys: 96 / 192 KiB) + the candidate buffer of
+ * "select_cap" elements (keys, and rids for tuples: 4 / 8 / 16 MiB at the default), next to what sorting
+ * max(candidates, k) elements needs.  msd_stat afterwards: "select_hist_passes" (histogram passes over the input, a
+ * first one that only found shared leading bits included), "select_skipped_bits" (leading key bits all keys share: skipped, not counted), "select_candidates"
+ * (size of the final pivot bucket), "select_below" (keys written straight to the output). */
+enum { MSD_SMALLEST = 0, MSD_LARGEST = 1 };
+int msd_topk_u32(msd_ctx *ctx, const uint32_t *d_keys, uint64_t n, uint64_t k, int which, uint32_t *d_out);
+int msd_topk_u64(msd_ctx *ctx, const uint64_t *d_keys, uint64_t n, uint64_t k, int which, uint64_t *d_out);
+int msd_topk_pairs_u64(msd_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_rids, uint64_t n, uint64_t k, int which,
+		       uint64_t *d_out_keys, uint64_t *d_out_rids);
+int msd_select_u32(msd_ctx *ctx, const uint32_t *d_keys, uint64_t n, uint64_t k, int which, uint32_t *value);
+int msd_select_u64(msd_ctx *ctx, const uint64_t *d_keys, uint64_t n, uint64_t k, int which, uint64_t *value);
+
 /* Verifier, the device form of check() (src/msb_64.c:2432-2505): counts order
  * violations (key[i] < key[i-1]) and, when d_rids != NULL, key != rid
  * mismatches; returns wrap-around sum and xor of the keys.  Synchronous (the
@@ -278,7 +307,10 @@ int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, 
  *   keys, crowded ones) are finished by the 16-bit-counter leaf (merge_count_kernel) instead of count_walk_kernel; 0 = never.
  * "merge_leaf": msd_merge_buckets_u32: 0 (default) = by bucket size, 1 = the register-resident leaf, 2 = the 16-bit-counter leaf.
  * "regpart": u64 keys / tuples: 1 (default) = segments of <= 17408 elements take the register-resident
- *   partition pass (csrc/msd_regpart.hpp) instead of a general round, 0 = never. */
+ *   partition pass (csrc/msd_regpart.hpp) instead of a general round, 0 = never.
+ * "select_cap": msd_topk_* / msd_select_*: capacity of the candidate buffer in elements (default 2^20, 1 .. 2^28): the
+ *   search adds histogram passes until the bucket that holds rank k fits.  The 12-bit bucket of 2^30 evenly spread keys
+ *   has 2^18 keys: one histogram pass; tests set it low to force the deep path on small inputs. */
 int msd_set_option(msd_ctx *ctx, const char *name, int64_t value);
 
 /* ---- phase report (reference: description[]/times[], src/msb_64.c:2402-2412) */

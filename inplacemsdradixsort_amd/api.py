@@ -290,6 +290,40 @@ class MsdContext:
             self._ok(self._L.msd_check_u64(self._h, self._ptr(keys, 8), rp, keys.numel(), C.byref(v), C.byref(s), C.byref(x)))
         return int(v.value), int(s.value), int(x.value)
 
+    # ---- radix select and top-k (read-only on ``keys``)
+    def topk(self, keys, k: int, largest: bool = False, rids=None, out=None, out_rids=None):
+        """The ``k`` smallest (``largest``: largest) keys in ascending order: a slice of the sorted array.  ``keys`` (int32 /
+        int64 tensors holding u32 / u64 keys) and ``rids`` are not modified.  Returns ``out`` (allocated when not given), or
+        ``(out, out_rids)`` for tuples."""
+        torch = _torch()
+        es = keys.element_size()
+        which = 1 if largest else 0
+        if rids is not None and (es != 8 or rids.numel() != keys.numel()):
+            raise MsdError("tuples are (u64 key, u64 rid) arrays of equal length")
+        if out is None:
+            out = torch.empty(max(int(k), 0), dtype=keys.dtype, device=keys.device)
+        if rids is not None and out_rids is None:
+            out_rids = torch.empty(max(int(k), 0), dtype=rids.dtype, device=rids.device)
+        if out.numel() < k or (rids is not None and out_rids.numel() < k):
+            raise MsdError("output tensor shorter than k")
+        if rids is not None:
+            self._ok(self._L.msd_topk_pairs_u64(self._h, self._ptr(keys, 8), self._ptr(rids, 8), keys.numel(), k, which,
+                                                self._ptr(out, 8), self._ptr(out_rids, 8)))
+            return out, out_rids
+        f = self._L.msd_topk_u32 if es == 4 else self._L.msd_topk_u64
+        self._ok(f(self._h, self._ptr(keys, es), keys.numel(), k, which, self._ptr(out, es)))
+        return out
+
+    def select(self, keys, k: int, largest: bool = False) -> int:
+        """The key of rank ``k`` (0-based) from the small end, or from the large end with ``largest``; ``keys`` is not modified."""
+        if keys.element_size() == 4:
+            v = C.c_uint32()
+            self._ok(self._L.msd_select_u32(self._h, self._ptr(keys, 4), keys.numel(), k, 1 if largest else 0, C.byref(v)))
+        else:
+            v = C.c_uint64()
+            self._ok(self._L.msd_select_u64(self._h, self._ptr(keys, 8), keys.numel(), k, 1 if largest else 0, C.byref(v)))
+        return int(v.value)
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))
@@ -311,7 +345,7 @@ class MsdContext:
         self._ok(self._L.msd_gen_iota_u64(self._h, self._ptr(vals, 8), vals.numel(), first))
 
     def set_option(self, name: str, value: int) -> None:
-        """Tuning knob of include/msd_radix_hip.h (``direct_mode``, ``direct_min``)."""
+        """Tuning knob of include/msd_radix_hip.h (``direct_mode``, ``direct_min``, ``select_cap``, ...)."""
         self._ok(self._L.msd_set_option(self._h, name.encode(), int(value)))
 
     # ---- phase report
@@ -326,7 +360,8 @@ class MsdContext:
         out = {}
         for name in ("rounds", "parents", "stripes", "children", "slots", "holes", "chain_steps",
                      "small_segments", "count_segments", "big_count_segments", "direct_rounds", "regpart_rounds", "skipped_bits", "bit_skip_restarts", "bit_skip_checked_by_histogram",
-                     "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes"):
+                     "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes",
+                     "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below"):
             v = C.c_uint64()
             if self._L.msd_stat(self._h, name.encode(), C.byref(v)) == 0:
                 out[name] = int(v.value)

@@ -4,6 +4,7 @@
 // <= 8-bit digits) and launches the kernels of msd_device.hpp; it never touches
 // key data itself and has no CPU fallback.
 #include "msd_device.hpp"
+#include "msd_select.hpp"
 #include "../../include/msd_radix_hip.h"
 
 #include <algorithm>
@@ -57,6 +58,9 @@ struct msd_ctx {
 	const uint32_t *order_keys = nullptr; // msd_order_low16_counts_u32 has run on these keys and its tables are still in the slab
 	uint64_t order_n = 0;
 	int merge_leaf = 0;    // msd_merge_buckets_u32: 0 = by bucket size, 1 = merge_place16_kernel, 2 = merge_count_kernel (tests)
+	char *sel = nullptr;   // msd_topk_* / msd_select_*: search state, per-pass bins, candidate buffer (lives across the internal sorts)
+	size_t sel_bytes = 0;
+	uint64_t select_cap = 1ull << 20; // candidate capacity (elements): the search stops once the pivot bucket fits
 };
 
 static int fail(msd_ctx *c, int code, const char *fmt, ...)
@@ -1502,6 +1506,7 @@ int msd_destroy(msd_ctx *c)
 	if (c->slab) (void)hipFree(c->slab);
 	if (c->keep) (void)hipFree(c->keep);
 	if (c->lists) (void)hipFree(c->lists);
+	if (c->sel) (void)hipFree(c->sel);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	if (c->ev_start) (void)hipEventDestroy(c->ev_start);
 	for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1529,7 +1534,7 @@ int msd_reserve(msd_ctx *c, uint64_t n, int key_bytes, int val_bytes)
 	return fail(c, MSD_EINVAL, "unsupported element layout %d+%d bytes", key_bytes, val_bytes);
 }
 
-uint64_t msd_workspace_bytes(const msd_ctx *c) { return c ? c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment) : 0; }
+uint64_t msd_workspace_bytes(const msd_ctx *c) { return c ? c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment) + c->sel_bytes : 0; }
 const char *msd_last_error(const msd_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
 int msd_sort_u32_bits(msd_ctx *c, uint32_t *k, uint64_t n, int end_bit) { return sort_bits<uint32_t, NoVal>(c, k, nullptr, n, end_bit); }
@@ -1951,6 +1956,167 @@ int msd_exclusive_scan_u64(msd_ctx *c, const uint64_t *in, uint64_t *out, uint64
 
 } // extern "C"
 
+// ------------------------------------------------------------ radix select / top-k (kernels: msd_select.hpp)
+
+static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	return abytes && bbytes && x < y + bbytes && y < x + abytes;
+}
+
+// the phases of an internal sort, added to the ones collected so far (every sort_impl starts its own list)
+static void phases_append(msd_ctx *c, std::vector<std::pair<std::string, double>> &all)
+{
+	for (auto &p : c->phase_us) {
+		bool found = false;
+		for (auto &q : all)
+			if (q.first == p.first) {
+				q.second += p.second;
+				found = true;
+			}
+		if (!found) all.push_back(p);
+	}
+}
+
+// TOPK: out[0 .. k) = the k smallest keys in the order of key ^ flip, sorted ascending as plain keys; otherwise
+// *value = the key of rank k in that order.  One readback of the search state behind the filter pass, the internal
+// sorts' own, and (select) one of the value.
+template <typename K, typename V, bool TOPK>
+static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t n, uint64_t k, int which, K *out, uint64_t *out_rids, K *value)
+{
+	constexpr bool HV = has_val<V>::value;
+	constexpr uint32_t KB = sizeof(K) * 8;
+	constexpr uint32_t PASSES = sel_max_passes<K>();
+	if (!c) return MSD_EINVAL;
+	if (which != MSD_SMALLEST && which != MSD_LARGEST) return fail(c, MSD_EINVAL, "which must be MSD_SMALLEST or MSD_LARGEST");
+	if (TOPK ? k > n : k >= n) return fail(c, MSD_EINVAL, TOPK ? "k must not exceed n" : "k must be smaller than n");
+	if (!TOPK && !value) return fail(c, MSD_EINVAL, "null result pointer");
+	if (TOPK && k == 0) return MSD_OK;
+	if (!keys || (HV && !rids) || (TOPK && !out) || (TOPK && HV && !out_rids)) return fail(c, MSD_EINVAL, "null data pointer");
+	if (((uintptr_t)keys & 15) || (HV && ((uintptr_t)rids & 15)) || (TOPK && ((uintptr_t)out & 15)) || (TOPK && HV && ((uintptr_t)out_rids & 15)))
+		return fail(c, MSD_EINVAL, "input and output buffers must be 16-byte aligned");
+	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large");
+	if (TOPK) {
+		const size_t ib = n * sizeof(K), ob = k * sizeof(K), rb = HV ? n * 8 : 0, orb = HV ? k * 8 : 0;
+		if (ranges_overlap(keys, ib, out, ob) || ranges_overlap(keys, ib, out_rids, orb) || ranges_overlap(rids, rb, out, ob) ||
+		    ranges_overlap(rids, rb, out_rids, orb) || ranges_overlap(out, ob, out_rids, orb))
+			return fail(c, MSD_EINVAL, "the output must not overlap the input");
+	}
+	HIPCHK(c, hipSetDevice(c->device));
+	const uint64_t cap = c->select_cap;
+	const K flip = which == MSD_LARGEST ? (K)~(K)0 : (K)0;
+	// the workspace of the search: state | one histogram per pass | candidate keys | candidate rids
+	Bump b(nullptr);
+	b.take<SelectState>(1);
+	b.take<unsigned long long>((size_t)PASSES * kSelBins);
+	const size_t zero_bytes = b.off;
+	b.take<K>(cap);
+	if (HV) b.take<uint64_t>(cap);
+	int rc = dev_reserve(c, c->sel, c->sel_bytes, b.off, true);
+	if (!rc) rc = pinned_reserve(c, 4096);
+	if (rc) return rc;
+	Bump r(c->sel);
+	SelectState *st = r.take<SelectState>(1);
+	unsigned long long *bins = r.take<unsigned long long>((size_t)PASSES * kSelBins);
+	K *cand = r.take<K>(cap);
+	uint64_t *cand_rids = HV ? r.take<uint64_t>(cap) : nullptr;
+
+	c->stats.clear();
+	phase_begin(c);
+	HIPCHK(c, hipMemsetAsync(c->sel, 0, zero_bytes, c->stream));
+	const uint64_t nvec = n / Vec16<K>::N;
+	const unsigned hist_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * 8, (nvec + kSelTh * kSelHistU - 1) / (kSelTh * kSelHistU)));
+	const uint64_t rank = TOPK ? k - 1 : k;
+	for (uint32_t p = 0; p < PASSES; ++p) {
+		if (p == 0)
+			hipLaunchKernelGGL((select_hist_kernel<K, true>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, bins);
+		else
+			hipLaunchKernelGGL((select_hist_kernel<K, false>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, bins + (size_t)p * kSelBins);
+		hipLaunchKernelGGL((select_pivot_kernel<K>), dim3(1), dim3(kSelPivotTh), 0, c->stream, st, bins + (size_t)p * kSelBins, p, n, rank, cap);
+	}
+	HIPCHK(c, hipGetLastError());
+	phase_mark(c, "select_hist");
+	const uint64_t tile_vecs = (uint64_t)kSelTh * kSelFilterU;
+	const unsigned filter_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * 4, (nvec + tile_vecs - 1) / tile_vecs));
+	// staging buffers of the filter: long runs per reservation where much of the input goes to the output (more than 1/32 of it)
+	constexpr uint32_t elem = sizeof(K) + (HV ? 8 : 0);
+	// (the candidates too: when the bits run out on a heavy value they go to the output as well)
+	const bool dense = TOPK && k > n / 32;
+	const uint32_t stage_cand = (dense ? kSelStageLargeCand : kSelStageSmall) / elem;
+	const uint32_t stage_below = !TOPK ? 0 : (dense ? kSelStageLargeBelow : kSelStageSmall) / elem;
+	hipLaunchKernelGGL((select_filter_kernel<K, V, TOPK>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem, c->stream, keys,
+			   rids, n, flip, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
+	HIPCHK(c, hipGetLastError());
+	phase_mark(c, "select_filter");
+	HIPCHK(c, hipMemcpyAsync(c->pinned, st, sizeof(SelectState), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	const SelectState h = *(const SelectState *)c->pinned;
+	phase_end(c);
+	std::vector<std::pair<std::string, double>> phases = c->phase_us;
+	const uint64_t needed = h.rank + 1; // candidates that belong to the answer (top-k)
+	if (!h.done || h.consumed > KB || h.rank >= h.bucket || (!h.exhausted && h.bucket > cap) || (TOPK && h.below + needed != k) ||
+	    (TOPK && h.out_cursor != h.below) || (!h.exhausted && h.cand_cursor != h.bucket))
+		return fail(c, MSD_EINTERNAL, "select: inconsistent search state (bucket %llu, below %llu, rank %llu, consumed %u, cursors %llu/%llu)",
+			    h.bucket, h.below, h.rank, h.consumed, h.out_cursor, h.cand_cursor);
+	const int open = (int)(KB - h.consumed);
+	const bool smallest = which == MSD_SMALLEST;
+	if (TOPK) {
+		if (!h.exhausted) {
+			// only the order of the candidates decides which of them belong to the answer
+			if (needed < h.bucket && open > 0) {
+				if ((rc = sort_impl<K, V>(c, cand, cand_rids, h.bucket, open, SortJob<K>::whole()))) return rc;
+				phases_append(c, phases);
+			}
+			const uint64_t from = smallest ? 0 : h.bucket - needed;
+			HIPCHK(c, hipMemcpyAsync(out + h.below, cand + from, needed * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
+			if (HV) HIPCHK(c, hipMemcpyAsync(out_rids + h.below, cand_rids + from, needed * 8, hipMemcpyDeviceToDevice, c->stream));
+		}
+		if ((rc = sort_impl<K, V>(c, out, out_rids, k, KB, SortJob<K>::whole()))) return rc;
+		phases_append(c, phases);
+	} else if (h.exhausted || open == 0) {
+		*value = (K)h.prefix ^ flip; // every bit is decided: the prefix is the key
+	} else {
+		if (h.bucket > 1) {
+			if ((rc = sort_impl<K, V>(c, cand, nullptr, h.bucket, open, SortJob<K>::whole()))) return rc;
+			phases_append(c, phases);
+		}
+		HIPCHK(c, hipMemcpyAsync(c->pinned, cand + (smallest ? h.rank : h.bucket - 1 - h.rank), sizeof(K), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipStreamSynchronize(c->stream));
+		*value = *(const K *)c->pinned;
+	}
+	c->phase_us = phases;
+	set_stat(c, "select_hist_passes", h.passes);
+	set_stat(c, "select_skipped_bits", h.skipped);
+	set_stat(c, "select_candidates", h.bucket);
+	set_stat(c, "select_below", TOPK ? h.below : 0);
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_topk_u32(msd_ctx *c, const uint32_t *k, uint64_t n, uint64_t kk, int which, uint32_t *out)
+{
+	return select_impl<uint32_t, NoVal, true>(c, k, nullptr, n, kk, which, out, nullptr, nullptr);
+}
+int msd_topk_u64(msd_ctx *c, const uint64_t *k, uint64_t n, uint64_t kk, int which, uint64_t *out)
+{
+	return select_impl<uint64_t, NoVal, true>(c, k, nullptr, n, kk, which, out, nullptr, nullptr);
+}
+int msd_topk_pairs_u64(msd_ctx *c, const uint64_t *k, const uint64_t *r, uint64_t n, uint64_t kk, int which, uint64_t *out, uint64_t *out_rids)
+{
+	return select_impl<uint64_t, uint64_t, true>(c, k, r, n, kk, which, out, out_rids, nullptr);
+}
+int msd_select_u32(msd_ctx *c, const uint32_t *k, uint64_t n, uint64_t kk, int which, uint32_t *value)
+{
+	return select_impl<uint32_t, NoVal, false>(c, k, nullptr, n, kk, which, nullptr, nullptr, value);
+}
+int msd_select_u64(msd_ctx *c, const uint64_t *k, uint64_t n, uint64_t kk, int which, uint64_t *value)
+{
+	return select_impl<uint64_t, NoVal, false>(c, k, nullptr, n, kk, which, nullptr, nullptr, value);
+}
+
+} // extern "C"
+
 template <typename K>
 static int check_impl(msd_ctx *c, const K *k, const uint64_t *r, uint64_t n, uint64_t *viol, uint64_t *sum, uint64_t *xr)
 {
@@ -2102,6 +2268,9 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 	} else if (!strcmp(name, "merge_leaf")) {
 		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "merge_leaf must be 0, 1 or 2");
 		c->merge_leaf = (int)value;
+	} else if (!strcmp(name, "select_cap")) {
+		if (value < 1 || value > ((int64_t)1 << 28)) return fail(c, MSD_EINVAL, "select_cap must be 1 .. 2^28 elements");
+		c->select_cap = (uint64_t)value;
 	} else if (!strcmp(name, "direct_min_parent")) {
 		if (value < 1) return fail(c, MSD_EINVAL, "direct_min_parent must be positive");
 		c->direct_min_parent = (uint64_t)value;
