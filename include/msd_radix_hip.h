@@ -247,6 +247,38 @@ int msd_topk_pairs_u64(msd_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_r
 int msd_select_u32(msd_ctx *ctx, const uint32_t *d_keys, uint64_t n, uint64_t k, int which, uint32_t *value);
 int msd_select_u64(msd_ctx *ctx, const uint64_t *d_keys, uint64_t n, uint64_t k, int which, uint64_t *value);
 
+/* ---- top-k with indices, top-k and select for signed and float keys ----
+ * The key type says how the bit patterns are ordered: MSD_KEY_U* as msd_topk_u*, MSD_KEY_I* as two's-complement integers,
+ * MSD_KEY_F* as IEEE-754 floats in totalOrder:
+ *     -NaN < -inf < ... < -denormal < -0 < +0 < +denormal < ... < +inf < +NaN      (NaNs of one sign: by payload)
+ * Keys are returned BIT-EXACT (NaN payloads, the sign of zero).  torch.topk / torch.sort differ only for NaNs with the sign
+ * bit set (torch puts every NaN on top) and in that they do not tell -0 from +0.
+ * The search runs on order-preserving unsigned CODES of the keys (msd_key_encode; three more integer operations per key and
+ * pass); the filter writes codes, which the library's plain unsigned sort orders, and a finishing pass over the k output
+ * elements turns them back into keys (phase "select_finish").  Nothing of the sort itself is typed.
+ *   msd_topk_keys: d_out_keys[0 .. k) = the k smallest / largest keys in the key type's order, ASCENDING in both cases (a slice
+ *     of the sorted array, as msd_topk_*).  d_out_idx (may be NULL; k uint64): d_out_idx[j] = a position i with d_keys[i]
+ *     bit-equal to d_out_keys[j]; no position twice; which of several keys equal to the boundary key are taken is
+ *     unspecified.  The positions are generated by the filter pass: no rid array of n elements is read or allocated.
+ *     64-bit key types: (code, position) tuples through the tuple path.  32-bit key types: ONE 64-bit element
+ *     code << 32 | position per selected key, which needs n <= 2^32; d_out_idx itself is the buffer these elements are
+ *     filtered to and sorted in (equal keys therefore come out with ascending positions), so the workspace stays
+ *     independent of n and k: as for msd_topk_*, with a candidate buffer of 8 bytes per element for them.
+ *   msd_select_key: *value (HOST memory, 4 or 8 bytes by key type) = the key of rank k from the small / large end.
+ *   msd_key_encode / msd_key_decode: the codec itself; host only, no context, no device.  32-bit types: bits and code in
+ *     the low 32 bits (upper bits of the argument ignored, of the result zero).
+ * Arguments as msd_topk_* / msd_select_*: MSD_EINVAL, before any launch and touching nothing, for a null context or pointer,
+ * k > n (top-k), k >= n (select), an unknown `which` or `key_type`, buffers not aligned to 16 bytes, overlap of any output with
+ * the input or of the two outputs, and n > 2^32 with indices on a 32-bit key type.  k == 0 is a successful no-op.
+ * MSD_KEY_U32 / MSD_KEY_U64 without indices ARE msd_topk_u32 / msd_topk_u64 (msd_select_u32 / _u64).  msd_stat and the phases
+ * as msd_topk_*. */
+enum { MSD_KEY_U32 = 0, MSD_KEY_I32 = 1, MSD_KEY_F32 = 2, MSD_KEY_U64 = 3, MSD_KEY_I64 = 4, MSD_KEY_F64 = 5 };
+int msd_topk_keys(msd_ctx *ctx, const void *d_keys, int key_type, uint64_t n, uint64_t k, int which,
+		  void *d_out_keys, uint64_t *d_out_idx);
+int msd_select_key(msd_ctx *ctx, const void *d_keys, int key_type, uint64_t n, uint64_t k, int which, void *value);
+int msd_key_encode(int key_type, uint64_t bits, uint64_t *code);
+int msd_key_decode(int key_type, uint64_t code, uint64_t *bits);
+
 /* Verifier, the device form of check() (src/msb_64.c:2432-2505): counts order
  * violations (key[i] < key[i-1]) and, when d_rids != NULL, key != rid
  * mismatches; returns wrap-around sum and xor of the keys.  Synchronous (the

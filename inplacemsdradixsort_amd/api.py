@@ -324,6 +324,57 @@ class MsdContext:
             self._ok(self._L.msd_select_u64(self._h, self._ptr(keys, 8), keys.numel(), k, 1 if largest else 0, C.byref(v)))
         return int(v.value)
 
+    # ---- top-k with indices, signed and float keys: the tensor's dtype says how its bit patterns are ordered
+    KEY_U32, KEY_I32, KEY_F32, KEY_U64, KEY_I64, KEY_F64 = range(6)   # MSD_KEY_* of include/msd_radix_hip.h
+
+    def _key_type(self, keys) -> int:
+        torch = _torch()
+        table = {torch.int32: self.KEY_I32, torch.float32: self.KEY_F32, torch.int64: self.KEY_I64, torch.float64: self.KEY_F64}
+        for name, kt in (("uint32", self.KEY_U32), ("uint64", self.KEY_U64)):   # (not in every torch)
+            if hasattr(torch, name):
+                table[getattr(torch, name)] = kt
+        if keys.dtype not in table:
+            raise MsdError(f"no key order for dtype {keys.dtype}: float32, int32, float64, int64, uint32 or uint64")
+        return table[keys.dtype]
+
+    def topk_typed(self, keys, k: int, largest: bool = False, indices: bool = False, out=None, out_indices=None):
+        """The ``k`` smallest (``largest``: largest) keys of ``keys`` in the order of its dtype, ascending in both cases: a
+        slice of the sorted array, bit-exact.  Floats are ordered by IEEE-754 totalOrder (-NaN < -inf < ... < -0 < +0 < ...
+        < +inf < +NaN), which differs from ``torch.topk`` only for NaNs with the sign bit set and in telling -0 from +0.
+        With ``indices`` (or ``out_indices``) returns ``(values, positions)``: int64 positions with
+        ``keys[positions[j]]`` bit-equal to ``values[j]``, none twice; which of several keys equal to the boundary key
+        are taken is unspecified.  ``keys`` is not modified."""
+        torch = _torch()
+        kt = self._key_type(keys)
+        es = keys.element_size()
+        want_idx = indices or out_indices is not None
+        if out is None:
+            out = torch.empty(max(int(k), 0), dtype=keys.dtype, device=keys.device)
+        if want_idx and out_indices is None:
+            out_indices = torch.empty(max(int(k), 0), dtype=torch.int64, device=keys.device)
+        if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
+            raise MsdError("the values have the keys' dtype, the indices are int64")
+        if out.numel() < k or (want_idx and out_indices.numel() < k):
+            raise MsdError("output tensor shorter than k")
+        self._ok(self._L.msd_topk_keys(self._h, self._ptr(keys, es), kt, keys.numel(), k, 1 if largest else 0, self._ptr(out, es),
+                                       self._ptr(out_indices, 8) if want_idx else C.c_void_p(0)))
+        return (out, out_indices) if want_idx else out
+
+    def select_typed(self, keys, k: int, largest: bool = False):
+        """The key of rank ``k`` (0-based) from the small end, or from the large end with ``largest``, in the order of the
+        tensor's dtype, as a python float / int (-0.0 stays -0.0 and a NaN keeps its sign; the payload of a float32 NaN is
+        only exact through ``msd_select_key`` itself, a python float being a double)."""
+        kt = self._key_type(keys)
+        es = keys.element_size()
+        v = (C.c_uint32 if es == 4 else C.c_uint64)()
+        self._ok(self._L.msd_select_key(self._h, self._ptr(keys, es), kt, keys.numel(), k, 1 if largest else 0, C.byref(v)))
+        raw = np.array([v.value], dtype=np.uint32 if es == 4 else np.uint64)
+        if kt in (self.KEY_F32, self.KEY_F64):
+            return float(raw.view(np.float32 if es == 4 else np.float64)[0])
+        if kt in (self.KEY_I32, self.KEY_I64):
+            return int(raw.view(np.int32 if es == 4 else np.int64)[0])
+        return int(v.value)
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))

@@ -1958,6 +1958,10 @@ int msd_exclusive_scan_u64(msd_ctx *c, const uint64_t *in, uint64_t *out, uint64
 
 // ------------------------------------------------------------ radix select / top-k (kernels: msd_select.hpp)
 
+#ifndef MSD_TOPK_PACKED_STOP // (overridable for experiments: 0 or 32)
+#define MSD_TOPK_PACKED_STOP 0
+#endif
+
 static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
 {
 	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -1981,10 +1985,20 @@ static void phases_append(msd_ctx *c, std::vector<std::pair<std::string, double>
 // TOPK: out[0 .. k) = the k smallest keys in the order of key ^ flip, sorted ascending as plain keys; otherwise
 // *value = the key of rank k in that order.  One readback of the search state behind the filter pass, the internal
 // sorts' own, and (select) one of the value.
-template <typename K, typename V, bool TOPK>
-static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t n, uint64_t k, int which, K *out, uint64_t *out_rids, K *value)
+// EMIT (msd_select.hpp) != kSelRaw: typed keys (msd_topk_keys / msd_select_key).  The search, the candidates and the
+// output work on the keys' codes under `codec`; `out` holds the elements the filter writes (codes, or packed
+// code << 32 | position elements in the caller's index array) and is sorted as plain unsigned keys; `rids` is not used
+// (positions are generated); a finishing pass decodes the k elements -- into `final_keys` for packed elements, in place
+// otherwise.
+template <typename K, typename V, bool TOPK, int EMIT = kSelRaw>
+static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t n, uint64_t k, int which, typename sel_elem<K, EMIT>::type *out,
+		       uint64_t *out_rids, K *value, KeyCodec<K> codec = KeyCodec<K>{ 0, 0 }, K *final_keys = nullptr)
 {
+	typedef typename sel_elem<K, EMIT>::type E;
 	constexpr bool HV = has_val<V>::value;
+	constexpr bool LOADS_RIDS = HV && EMIT == kSelRaw;
+	constexpr bool PACKED = EMIT == kSelPacked;
+	constexpr int EB = sizeof(E) * 8;
 	constexpr uint32_t KB = sizeof(K) * 8;
 	constexpr uint32_t PASSES = sel_max_passes<K>();
 	if (!c) return MSD_EINVAL;
@@ -1992,14 +2006,18 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	if (TOPK ? k > n : k >= n) return fail(c, MSD_EINVAL, TOPK ? "k must not exceed n" : "k must be smaller than n");
 	if (!TOPK && !value) return fail(c, MSD_EINVAL, "null result pointer");
 	if (TOPK && k == 0) return MSD_OK;
-	if (!keys || (HV && !rids) || (TOPK && !out) || (TOPK && HV && !out_rids)) return fail(c, MSD_EINVAL, "null data pointer");
-	if (((uintptr_t)keys & 15) || (HV && ((uintptr_t)rids & 15)) || (TOPK && ((uintptr_t)out & 15)) || (TOPK && HV && ((uintptr_t)out_rids & 15)))
+	if (!keys || (LOADS_RIDS && !rids) || (TOPK && !out) || (TOPK && HV && !out_rids) || (PACKED && !final_keys))
+		return fail(c, MSD_EINVAL, "null data pointer");
+	if (((uintptr_t)keys & 15) || (LOADS_RIDS && ((uintptr_t)rids & 15)) || (TOPK && ((uintptr_t)out & 15)) || (TOPK && HV && ((uintptr_t)out_rids & 15)) ||
+	    (PACKED && ((uintptr_t)final_keys & 15)))
 		return fail(c, MSD_EINVAL, "input and output buffers must be 16-byte aligned");
 	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large");
+	if (PACKED && n > ((uint64_t)1 << 32)) return fail(c, MSD_EINVAL, "indices of a 32-bit key type need n <= 2^32 (the position travels in 32 bits)");
 	if (TOPK) {
-		const size_t ib = n * sizeof(K), ob = k * sizeof(K), rb = HV ? n * 8 : 0, orb = HV ? k * 8 : 0;
+		const size_t ib = n * sizeof(K), ob = k * sizeof(E), rb = LOADS_RIDS ? n * 8 : 0, orb = HV ? k * 8 : 0, fb = PACKED ? k * sizeof(K) : 0;
 		if (ranges_overlap(keys, ib, out, ob) || ranges_overlap(keys, ib, out_rids, orb) || ranges_overlap(rids, rb, out, ob) ||
-		    ranges_overlap(rids, rb, out_rids, orb) || ranges_overlap(out, ob, out_rids, orb))
+		    ranges_overlap(rids, rb, out_rids, orb) || ranges_overlap(out, ob, out_rids, orb) || ranges_overlap(keys, ib, final_keys, fb) ||
+		    ranges_overlap(out, ob, final_keys, fb))
 			return fail(c, MSD_EINVAL, "the output must not overlap the input");
 	}
 	HIPCHK(c, hipSetDevice(c->device));
@@ -2010,7 +2028,7 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	b.take<SelectState>(1);
 	b.take<unsigned long long>((size_t)PASSES * kSelBins);
 	const size_t zero_bytes = b.off;
-	b.take<K>(cap);
+	b.take<E>(cap);
 	if (HV) b.take<uint64_t>(cap);
 	int rc = dev_reserve(c, c->sel, c->sel_bytes, b.off, true);
 	if (!rc) rc = pinned_reserve(c, 4096);
@@ -2018,7 +2036,7 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	Bump r(c->sel);
 	SelectState *st = r.take<SelectState>(1);
 	unsigned long long *bins = r.take<unsigned long long>((size_t)PASSES * kSelBins);
-	K *cand = r.take<K>(cap);
+	E *cand = r.take<E>(cap);
 	uint64_t *cand_rids = HV ? r.take<uint64_t>(cap) : nullptr;
 
 	c->stats.clear();
@@ -2028,10 +2046,18 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	const unsigned hist_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * 8, (nvec + kSelTh * kSelHistU - 1) / (kSelTh * kSelHistU)));
 	const uint64_t rank = TOPK ? k - 1 : k;
 	for (uint32_t p = 0; p < PASSES; ++p) {
-		if (p == 0)
-			hipLaunchKernelGGL((select_hist_kernel<K, true>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, bins);
-		else
-			hipLaunchKernelGGL((select_hist_kernel<K, false>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, bins + (size_t)p * kSelBins);
+		unsigned long long *const pb = bins + (size_t)p * kSelBins;
+		if constexpr (EMIT == kSelRaw) {
+			if (p == 0)
+				hipLaunchKernelGGL((select_hist_kernel<K, true>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, pb);
+			else
+				hipLaunchKernelGGL((select_hist_kernel<K, false>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, pb);
+		} else {
+			if (p == 0)
+				hipLaunchKernelGGL((select_hist_codes_kernel<K, true>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, codec, st, pb);
+			else
+				hipLaunchKernelGGL((select_hist_codes_kernel<K, false>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, codec, st, pb);
+		}
 		hipLaunchKernelGGL((select_pivot_kernel<K>), dim3(1), dim3(kSelPivotTh), 0, c->stream, st, bins + (size_t)p * kSelBins, p, n, rank, cap);
 	}
 	HIPCHK(c, hipGetLastError());
@@ -2039,13 +2065,17 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	const uint64_t tile_vecs = (uint64_t)kSelTh * kSelFilterU;
 	const unsigned filter_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * 4, (nvec + tile_vecs - 1) / tile_vecs));
 	// staging buffers of the filter: long runs per reservation where much of the input goes to the output (more than 1/32 of it)
-	constexpr uint32_t elem = sizeof(K) + (HV ? 8 : 0);
+	constexpr uint32_t elem = sizeof(E) + (HV ? 8 : 0);
 	// (the candidates too: when the bits run out on a heavy value they go to the output as well)
 	const bool dense = TOPK && k > n / 32;
 	const uint32_t stage_cand = (dense ? kSelStageLargeCand : kSelStageSmall) / elem;
 	const uint32_t stage_below = !TOPK ? 0 : (dense ? kSelStageLargeBelow : kSelStageSmall) / elem;
-	hipLaunchKernelGGL((select_filter_kernel<K, V, TOPK>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem, c->stream, keys,
-			   rids, n, flip, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
+	if constexpr (EMIT == kSelRaw)
+		hipLaunchKernelGGL((select_filter_kernel<K, V, TOPK>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem, c->stream, keys,
+				   rids, n, flip, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
+	else
+		hipLaunchKernelGGL((select_filter_codes_kernel<K, V, TOPK, EMIT>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem,
+				   c->stream, keys, n, flip, codec, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
 	HIPCHK(c, hipGetLastError());
 	phase_mark(c, "select_filter");
 	HIPCHK(c, hipMemcpyAsync(c->pinned, st, sizeof(SelectState), hipMemcpyDeviceToHost, c->stream));
@@ -2060,29 +2090,45 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 			    h.bucket, h.below, h.rank, h.consumed, h.out_cursor, h.cand_cursor);
 	const int open = (int)(KB - h.consumed);
 	const bool smallest = which == MSD_SMALLEST;
+	// (packed elements: the code is the upper half.  MSD_TOPK_PACKED_STOP = 0 sorts the whole element: equal keys come out
+	// in the order of their positions; 32 orders by the code alone and stops there, which measured no faster: DESIGN.md
+	// section 10)
+	const SortJob<E> job = SortJob<E>::whole(PACKED ? MSD_TOPK_PACKED_STOP : 0);
 	if (TOPK) {
 		if (!h.exhausted) {
 			// only the order of the candidates decides which of them belong to the answer
 			if (needed < h.bucket && open > 0) {
-				if ((rc = sort_impl<K, V>(c, cand, cand_rids, h.bucket, open, SortJob<K>::whole()))) return rc;
+				if ((rc = sort_impl<E, V>(c, cand, cand_rids, h.bucket, open + (EB - (int)KB), job))) return rc;
 				phases_append(c, phases);
 			}
 			const uint64_t from = smallest ? 0 : h.bucket - needed;
-			HIPCHK(c, hipMemcpyAsync(out + h.below, cand + from, needed * sizeof(K), hipMemcpyDeviceToDevice, c->stream));
+			HIPCHK(c, hipMemcpyAsync(out + h.below, cand + from, needed * sizeof(E), hipMemcpyDeviceToDevice, c->stream));
 			if (HV) HIPCHK(c, hipMemcpyAsync(out_rids + h.below, cand_rids + from, needed * 8, hipMemcpyDeviceToDevice, c->stream));
 		}
-		if ((rc = sort_impl<K, V>(c, out, out_rids, k, KB, SortJob<K>::whole()))) return rc;
+		if ((rc = sort_impl<E, V>(c, out, out_rids, k, EB, job))) return rc;
 		phases_append(c, phases);
+		if constexpr (EMIT != kSelRaw) {
+			phase_begin(c);
+			const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (k + kSelFinishTh - 1) / kSelFinishTh);
+			if constexpr (PACKED)
+				hipLaunchKernelGGL((select_finish_kernel<K, true>), dim3(grid), dim3(kSelFinishTh), 0, c->stream, out, final_keys, k, codec);
+			else
+				hipLaunchKernelGGL((select_finish_kernel<K, false>), dim3(grid), dim3(kSelFinishTh), 0, c->stream, (uint64_t *)nullptr, out, k, codec);
+			HIPCHK(c, hipGetLastError());
+			phase_mark(c, "select_finish");
+			phase_end(c);
+			phases_append(c, phases);
+		}
 	} else if (h.exhausted || open == 0) {
-		*value = (K)h.prefix ^ flip; // every bit is decided: the prefix is the key
+		*value = codec.dec((K)h.prefix ^ flip); // every bit is decided: the prefix is the key (its code)
 	} else {
 		if (h.bucket > 1) {
-			if ((rc = sort_impl<K, V>(c, cand, nullptr, h.bucket, open, SortJob<K>::whole()))) return rc;
+			if ((rc = sort_impl<E, V>(c, cand, nullptr, h.bucket, open, SortJob<E>::whole()))) return rc;
 			phases_append(c, phases);
 		}
 		HIPCHK(c, hipMemcpyAsync(c->pinned, cand + (smallest ? h.rank : h.bucket - 1 - h.rank), sizeof(K), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(c, hipStreamSynchronize(c->stream));
-		*value = *(const K *)c->pinned;
+		*value = codec.dec(*(const K *)c->pinned);
 	}
 	c->phase_us = phases;
 	set_stat(c, "select_hist_passes", h.passes);
@@ -2113,6 +2159,56 @@ int msd_select_u32(msd_ctx *c, const uint32_t *k, uint64_t n, uint64_t kk, int w
 int msd_select_u64(msd_ctx *c, const uint64_t *k, uint64_t n, uint64_t kk, int which, uint64_t *value)
 {
 	return select_impl<uint64_t, NoVal, false>(c, k, nullptr, n, kk, which, nullptr, nullptr, value);
+}
+
+// ---- typed keys and indices (codec: msd_keycodec.hpp)
+
+static bool key_type_ok(int key_type) { return key_type >= 0 && key_type < kKeyTypes; }
+
+int msd_key_encode(int key_type, uint64_t bits, uint64_t *code)
+{
+	if (!key_type_ok(key_type) || !code) return MSD_EINVAL;
+	*code = key_type_bytes(key_type) == 4 ? (uint64_t)key_codec<uint32_t>(key_type).enc((uint32_t)bits) : key_codec<uint64_t>(key_type).enc(bits);
+	return MSD_OK;
+}
+int msd_key_decode(int key_type, uint64_t code, uint64_t *bits)
+{
+	if (!key_type_ok(key_type) || !bits) return MSD_EINVAL;
+	*bits = key_type_bytes(key_type) == 4 ? (uint64_t)key_codec<uint32_t>(key_type).dec((uint32_t)code) : key_codec<uint64_t>(key_type).dec(code);
+	return MSD_OK;
+}
+
+int msd_topk_keys(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, uint64_t k, int which, void *d_out_keys, uint64_t *d_out_idx)
+{
+	if (!c) return MSD_EINVAL;
+	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
+	if (key_type_bytes(key_type) == 4) {
+		const uint32_t *keys = (const uint32_t *)d_keys;
+		uint32_t *out = (uint32_t *)d_out_keys;
+		if (d_out_idx) // the index array is where the packed elements are filtered to and sorted
+			return select_impl<uint32_t, NoVal, true, kSelPacked>(c, keys, nullptr, n, k, which, d_out_idx, nullptr, nullptr, key_codec<uint32_t>(key_type), out);
+		if (key_type == kKeyU32) return select_impl<uint32_t, NoVal, true>(c, keys, nullptr, n, k, which, out, nullptr, nullptr);
+		return select_impl<uint32_t, NoVal, true, kSelCodes>(c, keys, nullptr, n, k, which, out, nullptr, nullptr, key_codec<uint32_t>(key_type));
+	}
+	const uint64_t *keys = (const uint64_t *)d_keys;
+	uint64_t *out = (uint64_t *)d_out_keys;
+	if (d_out_idx) return select_impl<uint64_t, uint64_t, true, kSelPos>(c, keys, nullptr, n, k, which, out, d_out_idx, nullptr, key_codec<uint64_t>(key_type));
+	if (key_type == kKeyU64) return select_impl<uint64_t, NoVal, true>(c, keys, nullptr, n, k, which, out, nullptr, nullptr);
+	return select_impl<uint64_t, NoVal, true, kSelCodes>(c, keys, nullptr, n, k, which, out, nullptr, nullptr, key_codec<uint64_t>(key_type));
+}
+
+int msd_select_key(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, uint64_t k, int which, void *value)
+{
+	if (!c) return MSD_EINVAL;
+	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
+	if (key_type_bytes(key_type) == 4) {
+		if (key_type == kKeyU32) return select_impl<uint32_t, NoVal, false>(c, (const uint32_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint32_t *)value);
+		return select_impl<uint32_t, NoVal, false, kSelCodes>(c, (const uint32_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint32_t *)value,
+								      key_codec<uint32_t>(key_type));
+	}
+	if (key_type == kKeyU64) return select_impl<uint64_t, NoVal, false>(c, (const uint64_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint64_t *)value);
+	return select_impl<uint64_t, NoVal, false, kSelCodes>(c, (const uint64_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint64_t *)value,
+							      key_codec<uint64_t>(key_type));
 }
 
 } // extern "C"
