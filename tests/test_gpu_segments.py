@@ -117,6 +117,10 @@ def test_gather_runs(ctx, dt):
     ctx.gather_runs(d[3:] if dt == np.uint32 else d[1:-2], dev(src), src_off.reshape(-1).tolist(), dst_off.reshape(-1).tolist(),
                     lens.reshape(-1).tolist())
     got = host(d[3:] if dt == np.uint32 else d[1:-2], dt)[:n]
+    whole = host(d, dt)                                    # the -1 elements around the destination are still there
+    lead = 3 if dt == np.uint32 else 1
+    ones = np.iinfo(dt).max
+    assert (whole[:lead] == ones).all() and (whole[lead + n:] == ones).all() and whole.size == n + 3
     want = np.empty(n, dtype=dt)
     for s in range(sources):
         for b in range(buckets):
