@@ -279,6 +279,30 @@ int msd_select_key(msd_ctx *ctx, const void *d_keys, int key_type, uint64_t n, u
 int msd_key_encode(int key_type, uint64_t bits, uint64_t *code);
 int msd_key_decode(int key_type, uint64_t code, uint64_t *bits);
 
+/* ---- per-row (batched) top-k: torch.topk(x, k, dim=-1) for a matrix of keys ----
+ * Row r is d_keys[r * row_stride .. r * row_stride + row_len) (counts in elements, row_stride >= row_len; the elements
+ * between two rows are never read).  key_type and which as msd_topk_keys.
+ *   d_out_keys[r * k .. r * k + k) = the k smallest / largest keys of row r, ASCENDING in both cases, bit-exact.
+ *   d_out_idx (may be NULL; rows * k uint64): d_out_idx[r * k + j] = a position WITHIN ROW r whose key is bit-equal to
+ *     d_out_keys[r * k + j]; no position twice within a row; which of several keys equal to the boundary key are taken is
+ *     unspecified.
+ * The input is read only.  rows == 0 or k == 0 is a successful no-op.  The three pointers need only the alignment of their
+ * element type: rows of real matrices do not start on 16-byte boundaries.
+ * Inside the envelope msd_topk_rows_limits reports (row_len <= max_row_len, k <= max_k; host only, no context) ONE kernel
+ * launch answers all rows: a workgroup (long rows), or a wave of it (rows of up to 512 keys), owns a row and keeps the
+ * state of the search in LDS.  The call enqueues on the context's stream and returns: no readback, no workspace.
+ * Outside it, and for fewer than 4 rows of rows * 2^18 keys or more (one workgroup per row leaves the chip idle), the rows go one by one through
+ * msd_topk_keys -- host-blocking as that call is; rows or output rows that are not 16-byte aligned are staged through the
+ * context's workspace (one row + k output elements, grown on demand).  "topk_rows_mode" (msd_set_option) forces either way.
+ * msd_stat afterwards: "topk_rows_kernel_rows" + "topk_rows_looped_rows" = rows: who produced the result.  Phase: "select_rows".
+ * MSD_EINVAL, before any launch and touching nothing: null context or pointer (d_out_idx excepted), unknown which / key_type,
+ * k > row_len, row_stride < row_len, a pointer not aligned to its element size, rows * row_stride or rows * k overflowing,
+ * an output overlapping the input's extent ((rows - 1) * row_stride + row_len elements) or the other output, row_len > 2^32
+ * with indices on a 32-bit key type, "topk_rows_mode" 2 outside the envelope.  msd_topk_rows_limits: unknown key type, null pointers. */
+int msd_topk_rows(msd_ctx *ctx, const void *d_keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t row_stride,
+		  uint64_t k, int which, void *d_out_keys, uint64_t *d_out_idx);
+int msd_topk_rows_limits(int key_type, int with_idx, uint64_t *max_row_len, uint64_t *max_k);
+
 /* Verifier, the device form of check() (src/msb_64.c:2432-2505): counts order
  * violations (key[i] < key[i-1]) and, when d_rids != NULL, key != rid
  * mismatches; returns wrap-around sum and xor of the keys.  Synchronous (the
@@ -342,7 +366,12 @@ int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, 
  *   partition pass (csrc/msd_regpart.hpp) instead of a general round, 0 = never.
  * "select_cap": msd_topk_* / msd_select_*: capacity of the candidate buffer in elements (default 2^20, 1 .. 2^28): the
  *   search adds histogram passes until the bucket that holds rank k fits.  The 12-bit bucket of 2^30 evenly spread keys
- *   has 2^18 keys: one histogram pass; tests set it low to force the deep path on small inputs. */
+ *   has 2^18 keys: one histogram pass; tests set it low to force the deep path on small inputs.
+ * "topk_rows_mode": msd_topk_rows: 0 (default) = the library chooses between the row kernel and the loop over msd_topk_keys,
+ *   1 = always the loop, 2 = always the row kernel (MSD_EINVAL outside its envelope).
+ * "topk_rows_lanes": the row kernel's lanes per row: 0 (default) = by shape (a wave up to 512 keys; 256 lanes below 8192 keys
+ *   and for more rows than 2 per CU of up to 1 MiB; a 1024-thread workgroup otherwise), 64 / 256 / 1024 = that shape wherever
+ *   the row fits it (A/B comparisons). */
 int msd_set_option(msd_ctx *ctx, const char *name, int64_t value);
 
 /* ---- phase report (reference: description[]/times[], src/msb_64.c:2402-2412) */

@@ -25,6 +25,7 @@ EXPORTS = [
     "msd_sort_u32_segments", "msd_sort_u64_segments", "msd_sort_pairs_u64_segments", "msd_gather_runs_u32", "msd_gather_runs_u64",
     "msd_topk_u32", "msd_topk_u64", "msd_topk_pairs_u64", "msd_select_u32", "msd_select_u64",
     "msd_topk_keys", "msd_select_key", "msd_key_encode", "msd_key_decode",
+    "msd_topk_rows", "msd_topk_rows_limits",
     "msd_check_u32", "msd_check_u64",
     "msd_gen_uniform_u32", "msd_gen_uniform_u64", "msd_gen_zipf_u32", "msd_gen_iota_u64",
     "msd_gen_dup_u32", "msd_gen_mt19937_64",
@@ -127,6 +128,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.msd_select_key.argtypes = [_vp, _vp, C.c_int, _u64, _u64, C.c_int, _vp]
     L.msd_key_encode.argtypes = [C.c_int, _u64, _u64p]
     L.msd_key_decode.argtypes = [C.c_int, _u64, _u64p]
+    L.msd_topk_rows.argtypes = [_vp, _vp, C.c_int, _u64, _u64, _u64, _u64, C.c_int, _vp, _vp]
+    L.msd_topk_rows_limits.argtypes = [C.c_int, C.c_int, _u64p, _u64p]
     L.msd_check_u32.argtypes = [_vp, _vp, _u64, _u64p, _u64p, _u64p]
     L.msd_check_u64.argtypes = [_vp, _vp, _vp, _u64, _u64p, _u64p, _u64p]
     L.msd_gen_uniform_u32.argtypes = [_vp, _vp, _u64, _u64, _u64]

@@ -375,6 +375,67 @@ class MsdContext:
             return int(raw.view(np.int32 if es == 4 else np.int64)[0])
         return int(v.value)
 
+    # ---- per-row (batched) top-k: torch.topk(x, k, dim=-1)
+    @staticmethod
+    def _rows_layout(keys) -> Tuple[int, int, int]:
+        """``(rows, row_len, row_stride)`` of a tensor whose last dimension holds the rows, or :class:`MsdError`: the last
+        dimension must have stride 1 and the leading dimensions must collapse to ONE row stride >= row_len (a contiguous
+        tensor, or a 2-D one with ``stride(0) >= size(1)``).  Needs no device; nothing is copied."""
+        if keys.dim() < 1:
+            raise MsdError("topk_rows needs a tensor with at least one dimension")
+        sizes, strides = list(keys.shape), list(keys.stride())
+        row_len = int(sizes[-1])
+        if row_len > 1 and strides[-1] != 1:
+            raise MsdError(f"the last dimension must have stride 1, not {strides[-1]} (no hidden copy is made: pass a contiguous tensor)")
+        lead = [(int(n), int(st)) for n, st in zip(sizes[:-1], strides[:-1]) if n != 1]   # (a dimension of size 1 has no stride to speak of)
+        rows = 1
+        for n, _ in lead:
+            rows *= n
+        if rows <= 1 or not lead:
+            return rows, row_len, row_len
+        for (_, outer), (n, inner) in zip(lead[:-1], lead[1:]):
+            if outer != n * inner:
+                raise MsdError("the leading dimensions do not collapse to one row stride (no hidden copy is made: pass a contiguous tensor)")
+        row_stride = lead[-1][1]
+        if row_stride < row_len:
+            raise MsdError(f"rows overlap: row stride {row_stride} < row length {row_len}")
+        return rows, row_len, row_stride
+
+    def topk_rows_limits(self, keys_or_key_type, indices: bool = False) -> Tuple[int, int]:
+        """``(max_row_len, max_k)``: the envelope of the one-launch row kernel (``msd_topk_rows_limits``)."""
+        kt = keys_or_key_type if isinstance(keys_or_key_type, int) else self._key_type(keys_or_key_type)
+        a, b = C.c_uint64(), C.c_uint64()
+        if self._L.msd_topk_rows_limits(kt, int(indices), C.byref(a), C.byref(b)) != 0:
+            raise MsdError(f"error -1: unknown key type {kt}")
+        return int(a.value), int(b.value)
+
+    def topk_rows(self, keys, k: int, largest: bool = False, indices: bool = False, out=None, out_indices=None):
+        """Top-k along the LAST dimension: for every row the ``k`` smallest (``largest``: largest) keys in the order of the
+        dtype, ascending in both cases and bit-exact, as :meth:`topk_typed` gives them for one array.  Returns values of
+        shape ``[..., k]``; with ``indices`` (or ``out_indices``) also int64 positions within the row, of the same shape.
+        ``keys`` is not modified and never copied: a layout that is not rows of stride 1 with one row stride is refused.
+        Inside :meth:`topk_rows_limits` one kernel launch answers all rows and nothing blocks the host."""
+        torch = _torch()
+        kt = self._key_type(keys)
+        rows, row_len, row_stride = self._rows_layout(keys)
+        if not keys.is_cuda or keys.device.index != self.device:
+            raise MsdError("tensor must live on the context's GPU")
+        k = int(k)
+        want_idx = indices or out_indices is not None
+        shape = tuple(keys.shape[:-1]) + (max(k, 0),)
+        if out is None:
+            out = torch.empty(shape, dtype=keys.dtype, device=keys.device)
+        if want_idx and out_indices is None:
+            out_indices = torch.empty(shape, dtype=torch.int64, device=keys.device)
+        if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
+            raise MsdError("the values have the keys' dtype, the indices are int64")
+        for t in (out, out_indices) if want_idx else (out,):
+            if tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device:
+                raise MsdError(f"an output must be a contiguous tensor of shape {shape} on the context's GPU")
+        self._ok(self._L.msd_topk_rows(self._h, C.c_void_p(keys.data_ptr()), kt, rows, row_len, row_stride, k, 1 if largest else 0,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
+        return (out, out_indices) if want_idx else out
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))
@@ -396,7 +457,7 @@ class MsdContext:
         self._ok(self._L.msd_gen_iota_u64(self._h, self._ptr(vals, 8), vals.numel(), first))
 
     def set_option(self, name: str, value: int) -> None:
-        """Tuning knob of include/msd_radix_hip.h (``direct_mode``, ``direct_min``, ``select_cap``, ...)."""
+        """Tuning knob of include/msd_radix_hip.h (``direct_mode``, ``direct_min``, ``select_cap``, ``topk_rows_mode``, ...)."""
         self._ok(self._L.msd_set_option(self._h, name.encode(), int(value)))
 
     # ---- phase report
@@ -412,7 +473,8 @@ class MsdContext:
         for name in ("rounds", "parents", "stripes", "children", "slots", "holes", "chain_steps",
                      "small_segments", "count_segments", "big_count_segments", "direct_rounds", "regpart_rounds", "skipped_bits", "bit_skip_restarts", "bit_skip_checked_by_histogram",
                      "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes",
-                     "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below"):
+                     "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below",
+                     "topk_rows_kernel_rows", "topk_rows_looped_rows"):
             v = C.c_uint64()
             if self._L.msd_stat(self._h, name.encode(), C.byref(v)) == 0:
                 out[name] = int(v.value)

@@ -5,6 +5,7 @@
 // key data itself and has no CPU fallback.
 #include "msd_device.hpp"
 #include "msd_select.hpp"
+#include "msd_select_rows.hpp"
 #include "../../include/msd_radix_hip.h"
 
 #include <algorithm>
@@ -61,6 +62,10 @@ struct msd_ctx {
 	char *sel = nullptr;   // msd_topk_* / msd_select_*: search state, per-pass bins, candidate buffer (lives across the internal sorts)
 	size_t sel_bytes = 0;
 	uint64_t select_cap = 1ull << 20; // candidate capacity (elements): the search stops once the pivot bucket fits
+	int topk_rows_mode = 0; // msd_topk_rows: 0 = the library chooses, 1 = always the loop over msd_topk_keys, 2 = always the row kernel
+	int topk_rows_lanes = 0; // the row kernel's lanes per row: 0 = by row length, 64 / 256 / 1024 = forced where the row fits (A/B comparisons)
+	char *rows_stage = nullptr; // msd_topk_rows, looped path: one row + k output elements for rows that are not 16-byte aligned
+	size_t rows_stage_bytes = 0;
 };
 
 static int fail(msd_ctx *c, int code, const char *fmt, ...)
@@ -1374,6 +1379,22 @@ template <typename F> static hipError_t max_lds(F *kernel, size_t bytes)
 	return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+template <typename K, bool IDX> static int set_rows_lds_attrs_for(msd_ctx *c)
+{
+	HIPCHK(c, max_lds(&topk_rows_kernel<K, IDX, 64>, RowsLds<K, IDX, 64>::bytes));
+	HIPCHK(c, max_lds(&topk_rows_kernel<K, IDX, 256>, RowsLds<K, IDX, 256>::bytes));
+	HIPCHK(c, max_lds(&topk_rows_kernel<K, IDX, 1024>, RowsLds<K, IDX, 1024>::bytes));
+	return MSD_OK;
+}
+static int set_rows_lds_attrs(msd_ctx *c)
+{
+	int rc = set_rows_lds_attrs_for<uint32_t, false>(c);
+	if (!rc) rc = set_rows_lds_attrs_for<uint32_t, true>(c);
+	if (!rc) rc = set_rows_lds_attrs_for<uint64_t, false>(c);
+	if (!rc) rc = set_rows_lds_attrs_for<uint64_t, true>(c);
+	return rc;
+}
+
 template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
 {
 	{ // the block permutation is launched with exactly the workgroups the chip holds at once (see chains_grid)
@@ -1489,6 +1510,7 @@ int msd_create(msd_ctx **out, int device, void *stream)
 	int rc = set_lds_attrs<uint32_t, NoVal>(c);
 	if (!rc) rc = set_lds_attrs<uint64_t, NoVal>(c);
 	if (!rc) rc = set_lds_attrs<uint64_t, uint64_t>(c);
+	if (!rc) rc = set_rows_lds_attrs(c);
 	if (rc) {
 		fprintf(stderr, "msd_create: %s\n", c->err.c_str());
 		delete c;
@@ -1507,6 +1529,7 @@ int msd_destroy(msd_ctx *c)
 	if (c->keep) (void)hipFree(c->keep);
 	if (c->lists) (void)hipFree(c->lists);
 	if (c->sel) (void)hipFree(c->sel);
+	if (c->rows_stage) (void)hipFree(c->rows_stage);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	if (c->ev_start) (void)hipEventDestroy(c->ev_start);
 	for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1534,7 +1557,7 @@ int msd_reserve(msd_ctx *c, uint64_t n, int key_bytes, int val_bytes)
 	return fail(c, MSD_EINVAL, "unsupported element layout %d+%d bytes", key_bytes, val_bytes);
 }
 
-uint64_t msd_workspace_bytes(const msd_ctx *c) { return c ? c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment) + c->sel_bytes : 0; }
+uint64_t msd_workspace_bytes(const msd_ctx *c) { return c ? c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment) + c->sel_bytes + c->rows_stage_bytes : 0; }
 const char *msd_last_error(const msd_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
 int msd_sort_u32_bits(msd_ctx *c, uint32_t *k, uint64_t n, int end_bit) { return sort_bits<uint32_t, NoVal>(c, k, nullptr, n, end_bit); }
@@ -2213,6 +2236,159 @@ int msd_select_key(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, uin
 
 } // extern "C"
 
+// ---- per-row top-k (msd_select_rows.hpp)
+
+static bool rows_in_envelope(uint64_t row_len, uint64_t k) { return row_len <= kRowsMaxLen && k <= kRowsMaxK; }
+
+// Mode 0: does the row kernel beat the loop over msd_topk_keys?  One workgroup per row: with a few rows a call costs what ONE
+// row costs one workgroup -- 0.41 ms per 2^20 float32 keys, 0.52 ms per 2^20 int64 keys, whatever k -- and the loop 0.11 to
+// 0.15 ms per row whatever its length (profiles/topk_rows_sweep.jsonl; DESIGN.md section 10.2, "Dispatch").  From 4 rows on
+// the kernel wins up to the envelope's longest row.
+static bool rows_kernel_wins(uint64_t rows, uint64_t row_len) { return rows >= 4 || row_len < (rows << 18); }
+
+template <typename K, bool IDX, int LANES>
+static void rows_launch(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec, K *out,
+			uint64_t *out_idx)
+{
+	typedef RowsCfg<LANES> C;
+	constexpr uint64_t groups = C::BLOCK / LANES;
+	const uint64_t per_cu = LANES == 1024 ? 8 : 64; // (workgroups beyond what the chip holds at once walk the rows in a loop)
+	const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * per_cu, (rows + groups - 1) / groups));
+	constexpr size_t lds = RowsLds<K, IDX, LANES>::bytes;
+	hipLaunchKernelGGL((topk_rows_kernel<K, IDX, LANES>), dim3(grid), dim3(C::BLOCK), lds, c->stream, keys, rows,
+			   (uint32_t)row_len, stride, (uint32_t)k, flip, codec, out, out_idx);
+}
+
+// Lanes per row (profiles/topk_rows_sweep.jsonl, the `lanes*` columns): a wave where the row fits its registers; 256 lanes
+// for rows below 8192 keys and wherever there are more rows than the chip holds 1024-thread workgroups (2 per CU: six
+// 256-thread workgroups per CU then move more bytes), measured up to rows of 1 MiB; the 1024-thread workgroup otherwise --
+// with few rows it finishes ONE row 1.3 to 2.6 times sooner.
+static int rows_lanes(const msd_ctx *c, uint64_t rows, uint64_t row_len, uint64_t key_bytes)
+{
+	int by_shape = 1024;
+	if (row_len <= kRowsWaveMaxLen)
+		by_shape = 64;
+	else if (row_len < kRowsMidMaxLen || (rows > 2 * (uint64_t)c->sm_count && row_len * key_bytes <= (1u << 20)))
+		by_shape = 256;
+	if (c->topk_rows_lanes == 0 || (c->topk_rows_lanes == 64 && row_len > kRowsWaveMaxLen)) return by_shape; // (a wave's buffer holds its whole row)
+	return c->topk_rows_lanes;
+}
+
+template <typename K, bool IDX>
+static void rows_launch_by_length(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec,
+				  K *out, uint64_t *out_idx)
+{
+	const int lanes = rows_lanes(c, rows, row_len, sizeof(K));
+	if (lanes == 64)
+		rows_launch<K, IDX, 64>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	else if (lanes == 256)
+		rows_launch<K, IDX, 256>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	else
+		rows_launch<K, IDX, 1024>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+}
+
+template <typename K>
+static int rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, int which, K *out,
+			    uint64_t *out_idx)
+{
+	const K flip = which == MSD_LARGEST ? (K)~(K)0 : (K)0;
+	const KeyCodec<K> codec = key_codec<K>(key_type);
+	phase_begin(c);
+	if (out_idx)
+		rows_launch_by_length<K, true>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	else
+		rows_launch_by_length<K, false>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	HIPCHK(c, hipGetLastError());
+	phase_mark(c, "select_rows");
+	phase_end(c);
+	return MSD_OK;
+}
+
+// row by row through msd_topk_keys; what is not aligned to 16 bytes (which msd_topk_keys refuses) goes through the stage
+static int rows_looped_path(msd_ctx *c, const char *keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, int which,
+			    char *out, uint64_t *out_idx)
+{
+	const size_t es = (size_t)key_type_bytes(key_type);
+	const size_t row_b = align_up(row_len * es, 256), out_b = align_up(k * es, 256), idx_b = align_up(k * 8, 256);
+	const bool many = rows > 1;
+	const bool stage = ((uintptr_t)keys & 15) || (many && ((stride * es) & 15)) || ((uintptr_t)out & 15) || (many && ((k * es) & 15)) ||
+			   (out_idx && (((uintptr_t)out_idx & 15) || (many && ((k * 8) & 15))));
+	if (stage)
+		if (int rc = dev_reserve(c, c->rows_stage, c->rows_stage_bytes, row_b + out_b + idx_b)) return rc;
+	for (uint64_t r = 0; r < rows; ++r) {
+		const char *in = keys + r * stride * es;
+		char *o = out + r * k * es;
+		uint64_t *ix = out_idx ? out_idx + r * k : nullptr;
+		const bool in_st = (uintptr_t)in & 15, o_st = (uintptr_t)o & 15, ix_st = ix && ((uintptr_t)ix & 15);
+		if (in_st) HIPCHK(c, hipMemcpyAsync(c->rows_stage, in, row_len * es, hipMemcpyDeviceToDevice, c->stream));
+		char *const so = c->rows_stage + row_b;
+		uint64_t *const sx = (uint64_t *)(c->rows_stage + row_b + out_b);
+		if (int rc = msd_topk_keys(c, in_st ? c->rows_stage : in, key_type, row_len, k, which, o_st ? so : o, ix_st ? sx : ix)) return rc;
+		if (o_st) HIPCHK(c, hipMemcpyAsync(o, so, k * es, hipMemcpyDeviceToDevice, c->stream));
+		if (ix_st) HIPCHK(c, hipMemcpyAsync(ix, sx, k * 8, hipMemcpyDeviceToDevice, c->stream));
+	}
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_topk_rows_limits(int key_type, int with_idx, uint64_t *max_row_len, uint64_t *max_k)
+{
+	(void)with_idx; // (the LDS buffers are sized for the widest element: one envelope for all)
+	if (!key_type_ok(key_type) || !max_row_len || !max_k) return MSD_EINVAL;
+	*max_row_len = kRowsMaxLen;
+	*max_k = kRowsMaxK;
+	return MSD_OK;
+}
+
+int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t row_stride, uint64_t k, int which,
+		  void *d_out_keys, uint64_t *d_out_idx)
+{
+	if (!c) return MSD_EINVAL;
+	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
+	if (which != MSD_SMALLEST && which != MSD_LARGEST) return fail(c, MSD_EINVAL, "which must be MSD_SMALLEST or MSD_LARGEST");
+	if (k > row_len) return fail(c, MSD_EINVAL, "k must not exceed row_len");
+	if (row_stride < row_len) return fail(c, MSD_EINVAL, "row_stride must not be smaller than row_len");
+	const uint64_t es = (uint64_t)key_type_bytes(key_type);
+	uint64_t in_elems = 0, out_elems = 0, in_bytes = 0, out_bytes = 0, idx_bytes = 0;
+	if (__builtin_mul_overflow(rows, row_stride, &in_elems) || __builtin_mul_overflow(in_elems, es, &in_bytes))
+		return fail(c, MSD_EINVAL, "rows * row_stride overflows");
+	if (__builtin_mul_overflow(rows, k, &out_elems) || __builtin_mul_overflow(out_elems, (uint64_t)8, &idx_bytes))
+		return fail(c, MSD_EINVAL, "rows * k overflows");
+	if (rows == 0 || k == 0) return MSD_OK;
+	if (!d_keys || !d_out_keys) return fail(c, MSD_EINVAL, "null data pointer");
+	if (((uintptr_t)d_keys & (es - 1)) || ((uintptr_t)d_out_keys & (es - 1)) || ((uintptr_t)d_out_idx & 7))
+		return fail(c, MSD_EINVAL, "input and output buffers must be aligned to their element size");
+	if (d_out_idx && es == 4 && row_len > ((uint64_t)1 << 32))
+		return fail(c, MSD_EINVAL, "indices of a 32-bit key type need row_len <= 2^32 (the position travels in 32 bits)");
+	in_bytes = ((rows - 1) * row_stride + row_len) * es; // the input's extent: the padding behind the last row is not part of it
+	out_bytes = out_elems * es;
+	if (!d_out_idx) idx_bytes = 0;
+	if (ranges_overlap(d_keys, in_bytes, d_out_keys, out_bytes) || ranges_overlap(d_keys, in_bytes, d_out_idx, idx_bytes) ||
+	    ranges_overlap(d_out_keys, out_bytes, d_out_idx, idx_bytes))
+		return fail(c, MSD_EINVAL, "the outputs must not overlap the input or each other");
+	const bool inside = rows_in_envelope(row_len, k);
+	if (c->topk_rows_mode == 2 && !inside)
+		return fail(c, MSD_EINVAL, "topk_rows_mode 2: the row kernel takes row_len <= %llu and k <= %u", (unsigned long long)kRowsMaxLen, kRowsMaxK);
+	const bool kernel = inside && (c->topk_rows_mode == 2 || (c->topk_rows_mode == 0 && rows_kernel_wins(rows, row_len)));
+	HIPCHK(c, hipSetDevice(c->device));
+	int rc;
+	if (kernel) {
+		c->stats.clear();
+		if (es == 4)
+			rc = rows_kernel_path<uint32_t>(c, (const uint32_t *)d_keys, key_type, rows, row_len, row_stride, k, which, (uint32_t *)d_out_keys, d_out_idx);
+		else
+			rc = rows_kernel_path<uint64_t>(c, (const uint64_t *)d_keys, key_type, rows, row_len, row_stride, k, which, (uint64_t *)d_out_keys, d_out_idx);
+	} else
+		rc = rows_looped_path(c, (const char *)d_keys, key_type, rows, row_len, row_stride, k, which, (char *)d_out_keys, d_out_idx);
+	if (rc) return rc;
+	set_stat(c, "topk_rows_kernel_rows", kernel ? rows : 0);
+	set_stat(c, "topk_rows_looped_rows", kernel ? 0 : rows);
+	return MSD_OK;
+}
+
+} // extern "C"
+
 template <typename K>
 static int check_impl(msd_ctx *c, const K *k, const uint64_t *r, uint64_t n, uint64_t *viol, uint64_t *sum, uint64_t *xr)
 {
@@ -2367,6 +2543,12 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 	} else if (!strcmp(name, "select_cap")) {
 		if (value < 1 || value > ((int64_t)1 << 28)) return fail(c, MSD_EINVAL, "select_cap must be 1 .. 2^28 elements");
 		c->select_cap = (uint64_t)value;
+	} else if (!strcmp(name, "topk_rows_mode")) {
+		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "topk_rows_mode must be 0, 1 or 2");
+		c->topk_rows_mode = (int)value;
+	} else if (!strcmp(name, "topk_rows_lanes")) {
+		if (value != 0 && value != 64 && value != 256 && value != 1024) return fail(c, MSD_EINVAL, "topk_rows_lanes must be 0, 64, 256 or 1024");
+		c->topk_rows_lanes = (int)value;
 	} else if (!strcmp(name, "direct_min_parent")) {
 		if (value < 1) return fail(c, MSD_EINVAL, "direct_min_parent must be positive");
 		c->direct_min_parent = (uint64_t)value;
