@@ -16,7 +16,9 @@
 //     per 64 words, which keeps 16-byte alignment and makes the b128 accesses bank-conflict free);
 //   * fetch-adds, position look-ups and output writes are branch-free and issued back to back; an element
 //     outside the segment uses the lane's junk words;
-//   * 512-thread workgroups, two per CU, 128 VGPRs.
+//   * 512-thread workgroups, two per CU, 128 VGPRs;
+//   * two sets of key registers: the next segment's keys are requested as soon as the counter registers are dead,
+//     in front of the position look-ups and the LDS output phase; the store phase leaves the counters clear.
 // What this kernel does not take -- other bit counts, longer segments, a thread with more than 255 keys, an
 // overflowing byte -- is queued untouched for count_place_kernel / count_walk_kernel.
 #pragma once
@@ -27,6 +29,12 @@ namespace msd {
 #define MSD_C16_TH 512
 #endif
 constexpr int kC16Th = MSD_C16_TH;
+#ifndef MSD_C16_EARLY_TICKET // work tickets drawn a segment ahead
+#define MSD_C16_EARLY_TICKET 1
+#endif
+#ifndef MSD_C16_SV // 16-byte vectors of the store phase in flight per thread
+#define MSD_C16_SV 8
+#endif
 constexpr int kC16Vec = 4096 / kC16Th;                       // 16-byte vectors per thread: TH * NV * 4 = 16384 elements
 constexpr int kC16Tail = 1024 / kC16Th;                      // + scalar elements per thread behind them
 constexpr uint32_t kC16Cap = kC16Th * (kC16Vec * 4 + kC16Tail); // 17408 elements on the 16-byte grid
@@ -54,7 +62,18 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 	uint32_t *nexti = wtot + 9, *hi_l = wtot + 10, *crowded = wtot + 11;
 	const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 	if (blockIdx.x >= nsegs) return;
-	if (tid == 0) wtot[13] = 0; // tickets in hand (only thread 0 uses them)
+	// tickets (only thread 0 uses them): two at a time when there are many segments -- fewer fetch-adds on the one
+	// ticket word; those in hand live in LDS, wtot[12] next / wtot[13] how many.  A workgroup that ends may hold
+	// tickets it does not use: they are later ones than the one that ended it, so none is below nsegs.
+	constexpr bool kEarlyTicket = MSD_C16_EARLY_TICKET;
+	const uint32_t ntake = nsegs > 64u * gridDim.x ? 2u : 1u;
+	if (tid == 0) {
+		wtot[13] = 0;
+		if (kEarlyTicket) {
+			wtot[12] = atomicAdd(&ctr->count_ticket3, ntake) + gridDim.x;
+			wtot[13] = ntake;
+		}
+	}
 	// segment descriptors are the same in every lane: keep them in scalar registers (loaded through vector
 	// memory or LDS they would make every address a per-lane 64-bit computation)
 	auto uniform = [](Segment g) -> Segment {
@@ -71,34 +90,55 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 	};
 	Segment sg = uniform(segs[blockIdx.x]);
 
-	// ONE register per key for its whole life: the key (prefetched) -> value | rank << 16 -> value | place << 16 -> dead,
-	// by which time the next segment's keys are loaded into the same registers
-	uint32_t rk[NK];
+	// TWO register sets of one register per key: the key (prefetched) -> value | rank << 16 -> value | place << 16 -> dead.
+	// While one set carries a segment through its position look-ups and the LDS output phase, the other already
+	// receives the next segment's keys (requested as soon as the 32 counter registers are dead); the loop body exists
+	// twice with the sets' roles swapped, so no register is copied and no wait sits between the two segments.
+	uint32_t rka[NK], rkb[NK];
 	// the segment's elements on the 16-byte grid: vector v of thread t = grid elements (v * TH + t) * 4 .. + 3,
-	// tail element s of thread t = grid element NV * TH * 4 + s * TH + t.  Branch-free: lanes beyond the
-	// segment re-read its last vector / element; a segment this kernel will not take is not read.
-	auto prefetch = [&](const Segment &g) {
+	// tail element s of thread t = grid element NV * TH * 4 + s * TH + t.  Branch-free and unconditional (a register
+	// set written on only some paths becomes a loop-carried value and spills): lanes beyond the segment re-read its
+	// last vector / element; of a segment this kernel will not take, and when there is no next segment (!live), only
+	// the first vector is read.  Addresses come from an opaque copy of the thread index (not hoisted out of the loop).
+	auto prefetch = [&](uint32_t (&rk)[NK], const Segment &g, bool live) __attribute__((always_inline)) {
+		uint32_t tp = tid;
+		asm volatile("" : "+v"(tp));
 		const uint32_t off = (uint32_t)(g.start & 3u);
 		const uint32_t *base = keys + (g.start - off);
 		const uint64_t tot = g.count + off;
 		// (the only other access of this kernel that can leave the array: the 16-byte vector holding the LAST elements of
 		// the array's last segment may extend up to 12 bytes behind the allocation -- such a segment is not taken, n_total
 		// is the array's length)
-		const bool take = g.bits >= kC16MinBits && g.bits <= 16 && tot <= (uint64_t)kC16Cap && ((g.start - off + tot + 3) & ~3ull) <= n_total;
+		const bool take = live && g.bits >= kC16MinBits && g.bits <= 16 && tot <= (uint64_t)kC16Cap && ((g.start - off + tot + 3) & ~3ull) <= n_total;
 		const uint32_t totc = take ? (uint32_t)tot : 1u;
 		const uint32_t lastv = (totc - 1u) >> 2;
 #pragma unroll
 		for (int v = 0; v < NV; ++v) {
-			const u32x4 q = *reinterpret_cast<const u32x4 *>(base + min((uint32_t)(v * TH) + tid, lastv) * 4u);
+			const u32x4 q = *reinterpret_cast<const u32x4 *>(base + min((uint32_t)(v * TH) + tp, lastv) * 4u);
 			rk[v * 4 + 0] = q.x; rk[v * 4 + 1] = q.y; rk[v * 4 + 2] = q.z; rk[v * 4 + 3] = q.w;
 		}
 #pragma unroll
-		for (int s = 0; s < NT; ++s) rk[NV * 4 + s] = base[min((uint32_t)(NV * TH * 4 + s * TH) + tid, totc - 1u)];
+		for (int s = 0; s < NT; ++s) rk[NV * 4 + s] = base[min((uint32_t)(NV * TH * 4 + s * TH) + tp, totc - 1u)];
 	};
-	prefetch(sg);
+	// the whole counter / output area to zero (16-byte stores): before the first segment and behind a rejected one;
+	// behind a sorted segment the store phase leaves the area cleared
+	auto clear_all = [&]() __attribute__((always_inline)) {
+		uint32_t zero = 0, tc = tid;
+		asm volatile("" : "+v"(zero), "+v"(tc));
+#pragma unroll
+		for (uint32_t j = 0; j < (kC16Cap / 4 + TH - 1) / TH; ++j) {
+			const uint32_t q = j * TH + tc;
+			if (q < kC16Cap / 4) reinterpret_cast<u32x4 *>(cw)[q] = u32x4{ zero, zero, zero, zero };
+		}
+	};
+	prefetch(rka, sg, true);
+	clear_all();
+	__syncthreads();
 	MSD_STAMP_DECL(2);
 	MSD_STAMP_START();
-	for (;;) {
+	// one segment: its keys are in rk (requested during the segment before), the next segment's go to rn.
+	// Returns false behind the workgroup's last segment.
+	auto segment = [&](uint32_t (&rk)[NK], uint32_t (&rn)[NK]) __attribute__((always_inline)) -> bool {
 		const uint32_t off = (uint32_t)(sg.start & 3u);
 		const uint32_t tot = (uint32_t)min(sg.count + off, (uint64_t)0xFFFFFFFFu), n = tot - off;
 		const bool fits = sg.bits >= kC16MinBits && sg.bits <= 16 && sg.count + off <= (uint64_t)kC16Cap && ((sg.start + sg.count + 3) & ~3ull) <= n_total;
@@ -106,33 +146,24 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		uint32_t *segb = keys + (sg.start - off); // 16-byte aligned
 		MSD_STAMP(9);
 		MSD_STAMP_TICK(11);
-		// ---- clear the counters (16-byte stores)
 		// (loop invariants of one use per segment -- a vector of zeros, a lane's slot in the wave totals -- are made
 		// opaque: hoisted out of the loop they are spilled, and their reload waits for the stores in flight)
 		uint32_t zero = 0, tq = tid;
 		asm volatile("" : "+v"(zero), "+v"(tq));
-#pragma unroll
-		for (uint32_t j = 0; j < (kC16Cap / 4 + TH - 1) / TH; ++j) {
-			const uint32_t q = j * TH + tq;
-			if (q < kC16Cap / 4) reinterpret_cast<u32x4 *>(cw)[q] = u32x4{ zero, zero, zero, zero };
-		}
+		// (the counters are clear: the store phase of the segment before, or clear_all, left them so)
 		if (tid == 0) {
-			// (tickets two at a time when there are many segments: fewer fetch-adds on the one ticket word; the pair
-			// in hand lives in LDS, wtot[12] next / wtot[13] how many)
-			if (wtot[13] == 0) {
-				const uint32_t take = nsegs > 64u * gridDim.x ? 2u : 1u;
-				wtot[12] = atomicAdd(&ctr->count_ticket3, take) + gridDim.x;
-				wtot[13] = take;
+			if (!kEarlyTicket && wtot[13] == 0) {
+				wtot[12] = atomicAdd(&ctr->count_ticket3, ntake) + gridDim.x;
+				wtot[13] = ntake;
 			}
-			*nexti = wtot[12];
+			*nexti = wtot[12]; // (a ticket is in hand: drawn before the loop or during the segment before)
 			wtot[12] += 1;
 			wtot[13] -= 1;
 			*crowded = 0;
 			const uint32_t k0 = off == 0 ? rk[0] : off == 1 ? rk[1] : off == 2 ? rk[2] : rk[3]; // first key
 			*hi_l = k0 & ~((1u << sg.bits) - 1u); // common prefix of the whole segment
 		}
-		MSD_STAMP(0); // clear
-		__syncthreads();
+		MSD_STAMP(0); // ticket, first key
 		MSD_STAMP(1);
 		// ---- one fetch-add per key: value (low 16 bits) | rank among equal keys << 16; elements outside the segment
 		// bump the lane's junk counter
@@ -165,9 +196,16 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		__syncthreads();
 		MSD_STAMP(3);
 		const uint32_t nxt = (uint32_t)__builtin_amdgcn_readfirstlane(*nexti), hi = (uint32_t)__builtin_amdgcn_readfirstlane(*hi_l);
+		const bool more = nxt < nsegs;
 		// the next segment's descriptor travels during the counter phases (loaded where its keys are prefetched,
 		// its whole memory latency would sit in front of that prefetch)
-		const Segment nraw = segs[nxt < nsegs ? nxt : blockIdx.x];
+		const Segment nraw = segs[more ? nxt : blockIdx.x];
+		// thread 0 draws the tickets of the segments after the next one here, where nothing waits for them: the
+		// fetch-add's answer is stored behind the prefetch (drawn at the segment's start, every wave stood at the
+		// first barrier for the round trip to the one ticket word)
+		const bool refill = kEarlyTicket && tid == 0 && wtot[13] == 0;
+		uint32_t drawn = 0;
+		if (refill) drawn = atomicAdd(&ctr->count_ticket3, ntake);
 		// ---- the thread's 32 counter words, once: byte sums -> scan over the workgroup -> byte prefixes
 		constexpr int WPT = (int)(kC16Words / TH); // counter words per thread (32 or 16: whole 16-byte vectors, inside one 64-word group)
 		u32x4 *cq = reinterpret_cast<u32x4 *>(cw + c16_at(tid * (uint32_t)WPT)); // (16-byte aligned)
@@ -210,7 +248,22 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 				cq[j] = u32x4{ cr[4 * j + 0], cr[4 * j + 1], cr[4 * j + 2], cr[4 * j + 3] };
 			}
 			tbase[tid] = pos + off; // (output positions are on the array's 16-byte grid)
-			MSD_STAMP(6); // byte prefixes
+		} else if (tid == 0)
+			rejected[atomicAdd(&ctr->nslow16, 1u)] = sg; // untouched
+		// ---- the counter registers are dead: the next segment's keys are requested HERE (segments are disjoint and
+		// handed out by ticket, nobody writes that one before this workgroup does), so that the look-ups, the LDS
+		// output phase and their barriers run under the loads' latency and this segment's stores queue behind
+		// nothing.  (The scheduler must not lift the loads into the counter phases: 32 more live registers.)
+		__builtin_amdgcn_sched_barrier(0);
+		const Segment nsg = uniform(nraw);
+		prefetch(rn, nsg, more);
+		__builtin_amdgcn_sched_barrier(0);
+		if (refill) {
+			wtot[12] = drawn + gridDim.x;
+			wtot[13] = ntake;
+		}
+		if (ok) {
+			MSD_STAMP(6); // byte prefixes, prefetch issue
 			__syncthreads();
 			// ---- place of every key: base[owner of its value] + prefix[value] + rank
 			// (the place, < 2^15, replaces the rank in bits 16..30)
@@ -244,43 +297,53 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 			}
 			__syncthreads();
 			MSD_STAMP(8); // output into LDS
-		} else if (tid == 0)
-			rejected[atomicAdd(&ctr->nslow16, 1u)] = sg; // untouched
-		Segment nsg = sg;
-		if (nxt < nsegs) { // the next segment's keys travel while this one is stored
-			nsg = uniform(nraw);
-			prefetch(nsg);
-		}
-		if (ok) {
-			// whole vectors inside [off, tot) leave as 16-byte stores, the first and the last vector element-wise
+			// ---- LDS -> array.  Whole vectors inside [off, tot) leave as 16-byte stores, the partial vectors at both
+			// ends element-wise, each by the thread that holds the vector; behind its read every vector of the area is
+			// set to zero: the next segment finds its counters clear (no clear phase, one barrier less per segment).
 			const uint32_t v_first = off ? 1u : 0u, v_end = tot >> 2; // full vectors: [v_first, v_end)
-#pragma unroll
-			for (int v0 = 0; v0 < NV; v0 += 4) { // (four vectors in flight: the next segment's keys occupy 34 registers by now)
-				u32x4 t4[4];
-#pragma unroll
-				for (int i = 0; i < 4; ++i) t4[i] = reinterpret_cast<const u32x4 *>(out)[(uint32_t)((v0 + i) * TH) + tid];
-#pragma unroll
-				for (int i = 0; i < 4; ++i) {
-					const uint32_t q = (uint32_t)((v0 + i) * TH) + tid;
-					if (q >= v_first && q < v_end) reinterpret_cast<u32x4 *>(segb)[q] = t4[i];
+			auto put = [&](uint32_t q, const u32x4 &t) __attribute__((always_inline)) {
+				if (q >= v_first && q < v_end)
+					reinterpret_cast<u32x4 *>(segb)[q] = t;
+				else if (q == v_end || q < v_first) { // (one or two vectors per segment)
+					const uint32_t e0 = q << 2;
+					if (e0 + 0 >= off && e0 + 0 < tot) segb[e0 + 0] = t.x;
+					if (e0 + 1 >= off && e0 + 1 < tot) segb[e0 + 1] = t.y;
+					if (e0 + 2 >= off && e0 + 2 < tot) segb[e0 + 2] = t.z;
+					if (e0 + 3 >= off && e0 + 3 < tot) segb[e0 + 3] = t.w;
 				}
+			};
+			constexpr int SV = MSD_C16_SV < NV ? MSD_C16_SV : NV; // vectors in flight (the counter registers are dead: eight fit beside the next segment's keys)
+#pragma unroll
+			for (int v0 = 0; v0 < NV; v0 += SV) {
+				u32x4 t4[SV];
+#pragma unroll
+				for (int i = 0; i < SV; ++i) t4[i] = reinterpret_cast<const u32x4 *>(out)[(uint32_t)((v0 + i) * TH) + tq];
+#pragma unroll
+				for (int i = 0; i < SV; ++i) reinterpret_cast<u32x4 *>(out)[(uint32_t)((v0 + i) * TH) + tq] = u32x4{ zero, zero, zero, zero };
+#pragma unroll
+				for (int i = 0; i < SV; ++i) put((uint32_t)((v0 + i) * TH) + tq, t4[i]);
 				__builtin_amdgcn_sched_barrier(0);
 			}
-			// tail elements of full-size segments are a run of whole vectors too
+			// the rest of the area (tail elements of full-size segments: at most kC16Cap / 4 - NV * TH = 256 vectors)
 			{
-				const uint32_t q = (uint32_t)(NV * TH) + tq; // (at most kC16Cap / 4 - NV * TH = 256 of them)
-				if (q < v_end) reinterpret_cast<u32x4 *>(segb)[q] = reinterpret_cast<const u32x4 *>(out)[q];
+				const uint32_t q = (uint32_t)(NV * TH) + tq;
+				if (q < kC16Cap / 4) {
+					const u32x4 t = reinterpret_cast<const u32x4 *>(out)[q];
+					reinterpret_cast<u32x4 *>(out)[q] = u32x4{ zero, zero, zero, zero };
+					put(q, t);
+				}
 			}
-			if (tq < 4) { // the partial vectors at both ends
-				if (off && tq >= off && tq < tot) segb[tq] = out[tq];
-				const uint32_t el = (v_end << 2) + tq;
-				if (el < tot && el >= off && (el >= 4u || !off)) segb[el] = out[el];
-			}
-		}
-		MSD_STAMP(10); // prefetch issue + store
-		if (nxt >= nsegs) break;
+		} else if (fits)
+			clear_all(); // (the counters of a rejected segment; one that does not fit was not counted)
+		MSD_STAMP(10); // store + clear
+		if (!more) return false;
 		sg = nsg;
-		__syncthreads(); // the output buffer is cleared next
+		__syncthreads(); // the area is clear for everybody
+		return true;
+	};
+	for (;;) {
+		if (!segment(rka, rkb)) break;
+		if (!segment(rkb, rka)) break;
 	}
 	MSD_STAMP_FLUSH(TH / 64);
 }
