@@ -274,6 +274,16 @@ static void phase_mark(msd_ctx *c, const char *name)
 	(void)hipEventRecord(e, c->stream);
 	c->phases.push_back({ name, e });
 }
+// add to the entry of that name, or append one
+static void phase_add(std::vector<std::pair<std::string, double>> &list, const std::string &name, double us)
+{
+	for (auto &q : list)
+		if (q.first == name) {
+			q.second += us;
+			return;
+		}
+	list.emplace_back(name, us);
+}
 static void phase_end(msd_ctx *c)
 {
 	if (!c->profiling) return;
@@ -282,13 +292,7 @@ static void phase_end(msd_ctx *c)
 	for (auto &p : c->phases) {
 		float ms = 0;
 		(void)hipEventElapsedTime(&ms, prev, p.ev);
-		bool found = false;
-		for (auto &q : c->phase_us)
-			if (q.first == p.name) {
-				q.second += ms * 1000.0;
-				found = true;
-			}
-		if (!found) c->phase_us.emplace_back(p.name, ms * 1000.0);
+		phase_add(c->phase_us, p.name, ms * 1000.0);
 		prev = p.ev;
 	}
 }
@@ -1994,15 +1998,7 @@ static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t b
 // the phases of an internal sort, added to the ones collected so far (every sort_impl starts its own list)
 static void phases_append(msd_ctx *c, std::vector<std::pair<std::string, double>> &all)
 {
-	for (auto &p : c->phase_us) {
-		bool found = false;
-		for (auto &q : all)
-			if (q.first == p.first) {
-				q.second += p.second;
-				found = true;
-			}
-		if (!found) all.push_back(p);
-	}
+	for (auto &p : c->phase_us) phase_add(all, p.first, p.second);
 }
 
 // TOPK: out[0 .. k) = the k smallest keys in the order of key ^ flip, sorted ascending as plain keys; otherwise
@@ -2046,6 +2042,11 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	HIPCHK(c, hipSetDevice(c->device));
 	const uint64_t cap = c->select_cap;
 	const K flip = which == MSD_LARGEST ? (K)~(K)0 : (K)0;
+	// what the kernels do with a key (msd_select.hpp): plain keys have instances of their own
+	typedef typename std::conditional<EMIT == kSelRaw, SelPlain<K>, SelCoded<K>>::type HOW;
+	HOW how;
+	how.flip = flip;
+	if constexpr (EMIT != kSelRaw) how.codec = codec;
 	// the workspace of the search: state | one histogram per pass | candidate keys | candidate rids
 	Bump b(nullptr);
 	b.take<SelectState>(1);
@@ -2070,17 +2071,10 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	const uint64_t rank = TOPK ? k - 1 : k;
 	for (uint32_t p = 0; p < PASSES; ++p) {
 		unsigned long long *const pb = bins + (size_t)p * kSelBins;
-		if constexpr (EMIT == kSelRaw) {
-			if (p == 0)
-				hipLaunchKernelGGL((select_hist_kernel<K, true>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, pb);
-			else
-				hipLaunchKernelGGL((select_hist_kernel<K, false>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, st, pb);
-		} else {
-			if (p == 0)
-				hipLaunchKernelGGL((select_hist_codes_kernel<K, true>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, codec, st, pb);
-			else
-				hipLaunchKernelGGL((select_hist_codes_kernel<K, false>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, flip, codec, st, pb);
-		}
+		if (p == 0)
+			hipLaunchKernelGGL((select_hist_kernel<K, true, HOW>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, how, st, pb);
+		else
+			hipLaunchKernelGGL((select_hist_kernel<K, false, HOW>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, how, st, pb);
 		hipLaunchKernelGGL((select_pivot_kernel<K>), dim3(1), dim3(kSelPivotTh), 0, c->stream, st, bins + (size_t)p * kSelBins, p, n, rank, cap);
 	}
 	HIPCHK(c, hipGetLastError());
@@ -2093,12 +2087,8 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	const bool dense = TOPK && k > n / 32;
 	const uint32_t stage_cand = (dense ? kSelStageLargeCand : kSelStageSmall) / elem;
 	const uint32_t stage_below = !TOPK ? 0 : (dense ? kSelStageLargeBelow : kSelStageSmall) / elem;
-	if constexpr (EMIT == kSelRaw)
-		hipLaunchKernelGGL((select_filter_kernel<K, V, TOPK>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem, c->stream, keys,
-				   rids, n, flip, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
-	else
-		hipLaunchKernelGGL((select_filter_codes_kernel<K, V, TOPK, EMIT>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem,
-				   c->stream, keys, n, flip, codec, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
+	hipLaunchKernelGGL((select_filter_kernel<K, V, TOPK, EMIT, HOW>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem, c->stream,
+			   keys, rids, n, how, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
 	HIPCHK(c, hipGetLastError());
 	phase_mark(c, "select_filter");
 	HIPCHK(c, hipMemcpyAsync(c->pinned, st, sizeof(SelectState), hipMemcpyDeviceToHost, c->stream));

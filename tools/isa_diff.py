@@ -5,7 +5,9 @@
 
 Takes the gfx950 code object out of each library (llvm-objcopy + clang-offload-bundler), disassembles it (llvm-objdump)
 and compares the instruction text kernel by kernel (comments, which carry addresses, dropped).  Prints the kernels that
-are missing, changed and added; exit status 1 if an old kernel is missing or changed.  Needs no GPU."""
+are missing, changed and added; exit status 1 if an old kernel is missing or changed.  An old kernel whose name is gone
+but whose instruction text is that of exactly one added kernel (and of no other old kernel that is gone) counts as
+renamed, not as missing.  Needs no GPU."""
 import hashlib
 import os
 import re
@@ -42,11 +44,21 @@ def main():
     missing = sorted(k for k in old if k not in new)
     changed = sorted(k for k in old if k in new and old[k] != new[k])
     added = sorted(k for k in new if k not in old)
+    renamed = {}
+    for k in missing:
+        same = [a for a in added if new[a] == old[k]]
+        if len(same) == 1 and sum(old[m] == old[k] for m in missing) == 1:
+            renamed[k] = same[0]
+    missing = [k for k in missing if k not in renamed]
+    added = [a for a in added if a not in renamed.values()]
     print(f"{len(old)} kernels in {old_lib}, {len(new)} in {new_lib}")
     for title, names in (("missing", missing), ("changed", changed), ("added", added)):
         print(f"{title}: {len(names)}")
         for k in names:
             print("   ", k)
+    print(f"renamed (same code): {len(renamed)}")
+    for k in sorted(renamed):
+        print("   ", k, "->", renamed[k])
     return 1 if missing or changed else 0
 
 
