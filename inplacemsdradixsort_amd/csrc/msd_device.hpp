@@ -1177,6 +1177,24 @@ __global__ __launch_bounds__(64) void excess_kernel(uint32_t nchildren, ChildArr
 	}
 }
 
+// Where a finished child goes.  One rule for collect_kernel and for the segments a caller hands in
+// (SortRun::route_to_leaves): host and device use the same function, like regpart_width.
+enum Route : int { kRouteDone = -1, kRouteSmall = 0, kRouteCount = 1, kRouteBig = 2, kRouteNext = 3 }; // (>= 0: collect_kernel's list)
+// `bits`: the child's open bits; `count_bits`: the most one counting pass takes (0: no counting leaves); `med_max`: the
+// largest segment one workgroup counts by itself; `has_big`: there is a list for the multi-workgroup counting sort (a full
+// one is the caller's affair: another round instead)
+__host__ __device__ inline Route route_child(uint64_t count, uint32_t bits, uint32_t stop_bits, uint32_t count_bits, uint64_t small_max,
+	uint64_t med_max, bool has_big)
+{
+	// a sort that stops early (msd_sort_*_top: the keys are to be ordered by key >> stop_bits only): children whose open
+	// bits all lie below stop_bits are done
+	if (count <= 1 || bits <= stop_bits) return kRouteDone;
+	const bool countable = bits <= count_bits; // all open bits fit one counting pass
+	if (countable && count >= 64 && count <= med_max) return kRouteCount; // one workgroup: LDS byte counters
+	if (count > small_max) return has_big && countable && count < 0xFFFF0000ull ? kRouteBig : kRouteNext; // no further round: the multi-workgroup counting sort
+	return kRouteSmall;
+}
+
 // children -> next round's parents / the small-segment lists / done.  A workgroup serves 256 >> wmax parents (wmax:
 // the round's widest digit) and takes its places in each list with ONE fetch-add per list: the list counters are single
 // words, and a fetch-add per wave on one word is what the device serialises (65536 narrow parents of a register-resident
@@ -1184,10 +1202,7 @@ __global__ __launch_bounds__(64) void excess_kernel(uint32_t nchildren, ChildArr
 __global__ __launch_bounds__(256) void collect_kernel(const Parent *__restrict__ parents, uint32_t nparents, uint32_t wmax, ChildArrays ca,
 	uint64_t small_max, uint64_t med_max, uint32_t small_cap, uint32_t count_bits, Segment *__restrict__ next_parents,
 	Segment *__restrict__ small, Segment *__restrict__ small_count, Segment *__restrict__ big, uint32_t big_cap,
-	Counters *__restrict__ ctr, uint64_t *__restrict__ count_out, uint32_t count_n,
-	// a sort that stops early (msd_sort_*_top: the keys are to be ordered by key >> stop_bits only): children whose open
-	// bits all lie below stop_bits are done
-	uint32_t stop_bits = 0)
+	Counters *__restrict__ ctr, uint64_t *__restrict__ count_out, uint32_t count_n, uint32_t stop_bits)
 {
 	__shared__ uint32_t s_n[4], s_base[4], s_max; // lists: 0 small, 1 counting leaf, 2 big counting sort, 3 next parents
 	const uint32_t tid = threadIdx.x;
@@ -1204,18 +1219,12 @@ __global__ __launch_bounds__(256) void collect_kernel(const Parent *__restrict__
 			const uint32_t ci = pa.child_base + d;
 			const uint64_t c = ca.count[ci];
 			if (count_out && ci < count_n) count_out[ci] = c;
-			if (c > 1 && pa.shift > stop_bits) {
+			which = route_child(c, pa.shift, stop_bits, count_bits, small_max, med_max, big != nullptr);
+			if (which >= 0) {
 				s.start = ca.start[ci];
 				s.count = c;
 				s.bits = pa.shift;
 				s.pad = 0;
-				const bool countable = pa.shift <= count_bits; // all open bits fit one counting pass
-				if (countable && c >= 64 && c <= med_max)
-					which = 1; // one workgroup: LDS byte counters
-				else if (c > small_max)
-					which = (big && countable && c < 0xFFFF0000ull) ? 2 : 3; // no further round: the multi-workgroup counting sort
-				else
-					which = 0;
 				rank = atomicAdd(&s_n[which], 1u);
 				if (which == 3) atomicMax(&s_max, (uint32_t)(c < 0xFFFFFFFFull ? c : 0xFFFFFFFFull));
 			}
@@ -1281,14 +1290,6 @@ __device__ __forceinline__ uint32_t cw_at(uint32_t i) { return i + (i >> 5); }
 //    keys, a byte overflow) are queued untouched for
 //  * count_walk_kernel: no ranks; every thread walks its own counters and re-generates its run of the
 //    output window by window (the windows grow into the counter words already consumed).
-struct CountLds {
-	uint32_t *cw;     // packed byte counters (padded layout)
-	uint32_t *wtot;   // 16 wave totals
-	uint32_t *nexti;  // next ticket
-	uint32_t *tfree;  // walk: the thread cut by the window's end
-	uint32_t *crowded; // place: some thread owns more than 255 keys
-};
-
 template <typename K>
 __global__ __launch_bounds__(kCountTh, 8) void count_place_kernel(K *__restrict__ keys,
 	const Segment *__restrict__ segs, uint32_t nsegs_host, const uint32_t *__restrict__ nsegs_dev,
@@ -1594,7 +1595,7 @@ template <typename K, typename V>
 __global__ __launch_bounds__((Cfg<K, V>::SORT_TH)) void leaf_count_sort_kernel(K *__restrict__ keys,
 	uint64_t *__restrict__ vals, const Segment *__restrict__ segs, uint32_t nsegs,
 	Segment *__restrict__ fallback, Counters *__restrict__ ctr, uint32_t *__restrict__ ticket,
-	const uint32_t *__restrict__ nsegs_dev = nullptr)
+	const uint32_t *__restrict__ nsegs_dev)
 {
 	if (nsegs_dev) nsegs = *nsegs_dev; // (the list was written by the launch before this one)
 	// Persistent workgroups (one per CU fits the LDS): segments by ticket; the next segment's elements are

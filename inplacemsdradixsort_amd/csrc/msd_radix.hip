@@ -87,6 +87,34 @@ static int fail(msd_ctx *c, int code, const char *fmt, ...)
 				    hipGetErrorString(e_), __FILE__, __LINE__);           \
 	} while (0)
 
+// Every kernel of this file is launched here: on the context's stream, the launch checked at once (reported with the call
+// site's file and line, like HIPCHK).  The arguments are converted to the kernel's own parameter types: a call site
+// needs no casts, and an argument the kernel cannot take does not compile.
+template <typename... P, typename... A>
+static int launch_at(msd_ctx *c, const char *what, const char *file, int line, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A &...args)
+{
+	hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, static_cast<P>(args)...);
+	const hipError_t e = hipGetLastError();
+	return e == hipSuccess ? MSD_OK : fail(c, MSD_EHIP, "launch of %s failed: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+}
+// (a statement, like HIPCHK: returns the error from the calling function)
+#define LAUNCH(c, kernel, grid, block, lds, ...)                                                                      \
+	do {                                                                                                          \
+		if (int rc_ = launch_at(c, #kernel, __FILE__, __LINE__, kernel, dim3(grid), dim3(block), lds, __VA_ARGS__)) return rc_; \
+	} while (0)
+
+// ---- argument rules, each stated once
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// Do the byte ranges [a, a + abytes) and [b, b + bbytes) share an address?  An empty range strictly inside the other one
+// counts as sharing (a pointer into the other buffer was handed in); a null pointer with 0 bytes -- an absent optional
+// buffer, the only empty range the select entry points pass -- shares nothing with any range.
+static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	return x < y + bbytes && y < x + abytes;
+}
+
 static void set_stat(msd_ctx *c, const char *name, uint64_t v)
 {
 	for (auto &s : c->stats)
@@ -647,8 +675,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (int rc = vres_init()) return rc;
 		const uint64_t cnt = (n + stride - 1) / stride;
 		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (cnt + 255) / 256);
-		hipLaunchKernelGGL((vary_kernel<K>), dim3(grid), dim3(256), 0, c->stream, keys, n, stride, vres);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, (vary_kernel<K>), grid, 256, 0, keys, n, stride, vres);
 		HIPCHK(c, hipMemcpyAsync(c->pinned, vres, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(c, hipStreamSynchronize(c->stream));
 		const unsigned long long *h = (const unsigned long long *)c->pinned;
@@ -699,16 +726,14 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	// ---- segments that need no partition round go to the leaf lists at once
 	int route_to_leaves()
 	{
-		if (job.segmented() && !cur.empty()) { // by collect_kernel's rules
+		if (job.segmented() && !cur.empty()) {
+			// collect_kernel's rule (route_child), with the limits of a keys-only round; tuples: no counting leaves here
 			std::vector<Segment> l_small, l_count, l_big, parents;
 			for (auto &sg : cur) {
-				const bool countable = !HV && sg.bits <= count_bits;
-				if (countable && sg.count >= 64 && sg.count <= std::max<uint64_t>(small_max, kCountMedMax))
-					l_count.push_back(sg);
-				else if (sg.count > small_max) {
-					if (countable && sg.count < 0xFFFF0000ull && l_big.size() < big_cap) l_big.push_back(sg); else parents.push_back(sg);
-				} else
-					l_small.push_back(sg);
+				Route to = route_child(sg.count, sg.bits, job.stop_bits, HV ? 0u : count_bits, small_max, std::max<uint64_t>(small_max, kCountMedMax), !HV);
+				if (to == kRouteDone) continue;
+				if (to == kRouteBig && l_big.size() >= big_cap) to = kRouteNext; // the big list is full: a round instead
+				(to == kRouteSmall ? l_small : to == kRouteCount ? l_count : to == kRouteBig ? l_big : parents).push_back(sg);
 			}
 			int rc = lists_reserve(c, std::max(l_small.size(), l_count.size()) + 16, 0, 0);
 			if (!rc) rc = pinned_reserve(c, (l_small.size() + l_count.size() + l_big.size()) * sizeof(Segment) + sizeof(Counters));
@@ -797,9 +822,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		HIPCHK(c, hipMemsetAsync(&ctr->nslow2, 0, sizeof(uint32_t), c->stream));
 		HIPCHK(c, hipMemsetAsync(&ctr->l17_slow, 0, sizeof(uint32_t), c->stream));
 		phase_mark(c, "plan+upload");
-		hipLaunchKernelGGL((leaf17_kernel<V>), dim3(std::min<uint32_t>(np, (uint32_t)c->sm_count)), dim3(kL17Th), kL17Lds, c->stream,
-				   (uint64_t *)keys, vals, (const Segment *)d_segs, np, d_rej, &ctr->nslow2, ctr, 0u);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, (leaf17_kernel<V>), std::min<uint32_t>(np, (uint32_t)c->sm_count), kL17Th, kL17Lds, keys, vals, d_segs, np, d_rej, &ctr->nslow2, ctr, 0);
 		phase_mark(c, "leaf17");
 		Counters hc;
 		if ((rc = read_counters(c, ctr, hc))) return rc;
@@ -846,21 +869,17 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (!rc) rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + nc + 16, nsmall_host, ncount_host);
 		if (!rc) rc = pinned_reserve(c, std::max<size_t>(on_device ? 0 : np * sizeof(Parent), 256 + 2048 * sizeof(Segment)));
 		if (rc) return rc;
-		hipLaunchKernelGGL(round_init_kernel, dim3(1), dim3(256), 0, c->stream, ctr, d_scr + 16, (uint64_t)0,
-				   reinterpret_cast<unsigned long long *>(d_scr + 32), (uint64_t)0, d_scr);
+		LAUNCH(c, round_init_kernel, 1, 256, 0, ctr, d_scr + 16, 0, reinterpret_cast<unsigned long long *>(d_scr + 32), 0, d_scr);
 		if (on_device)
-			hipLaunchKernelGGL(regpart_plan_kernel, dim3((np + 255) / 256), dim3(256), 0, c->stream, (const Segment *)dev_list, np,
-					   small_max, d_parents, ctr);
+			LAUNCH(c, regpart_plan_kernel, (np + 255) / 256, 256, 0, dev_list, np, small_max, d_parents, ctr);
 		else if ((rc = upload(c, { { d_parents, ps.data(), np * sizeof(Parent) } })))
 			return rc;
 		phase_mark(c, "plan+upload");
-		hipLaunchKernelGGL((regpart_kernel<V>), dim3(std::min<uint32_t>(np, (uint32_t)c->sm_count)), dim3(kRpTh), kRpLds, c->stream,
-				   (uint64_t *)keys, vals, (const Parent *)d_parents, np, ca, ctr);
+		LAUNCH(c, (regpart_kernel<V>), std::min<uint32_t>(np, (uint32_t)c->sm_count), kRpTh, kRpLds, keys, vals, d_parents, np, ca, ctr);
 		phase_mark(c, "A register partition");
-		hipLaunchKernelGGL(collect_kernel, dim3((np + (256u >> wmax) - 1) / (256u >> wmax)), dim3(256), 0, c->stream, (const Parent *)d_parents, np, wmax, ca, small_max, small_max,
-				   (uint32_t)std::min<size_t>(c->lists_cap, 0xFFFFFFFFu), count_bits, d_next, small(), small_count(),
-				   HV ? (Segment *)nullptr : big, big_cap, ctr, (uint64_t *)nullptr, nc, job.stop_bits);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, collect_kernel, (np + (256u >> wmax) - 1) / (256u >> wmax), 256, 0, d_parents, np, wmax, ca, small_max, small_max,
+		       std::min<size_t>(c->lists_cap, 0xFFFFFFFFu), count_bits, d_next, small(), small_count(), HV ? nullptr : big, big_cap, ctr,
+		       nullptr, nc, job.stop_bits);
 		phase_mark(c, "C cleanup");
 		Counters hc;
 		const size_t ahead = std::min<size_t>(next_cap, 2048); // (next parents that travel with the counters)
@@ -903,8 +922,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			const uint64_t plan_words = (r.np <= kDirectMaxParents ? r.np : 1) * sizeof(DirectPlan) / sizeof(uint32_t);
 			const uint64_t ntiles = (r.nc + kScanTile - 1) / kScanTile + 1;
 			const unsigned grid = (unsigned)std::min<uint64_t>(1024, (std::max(plan_words, ntiles) + 255) / 256 + 1);
-			hipLaunchKernelGGL(round_init_kernel, dim3(grid), dim3(256), 0, c->stream, ctr, reinterpret_cast<uint32_t *>(r.rb.plans),
-					   plan_words, r.rb.scan_state, ntiles, r.rb.scan_ctr);
+			LAUNCH(c, round_init_kernel, grid, 256, 0, ctr, reinterpret_cast<uint32_t *>(r.rb.plans), plan_words, r.rb.scan_state, ntiles, r.rb.scan_ctr);
 		}
 		if ((rc = pinned_reserve(c, r.np * sizeof(Parent) + r.ns * sizeof(Stripe))) ||
 		    (rc = upload(c, { { r.rb.parents, r.rp.parents.data(), r.np * sizeof(Parent) }, { r.rb.stripes, r.rp.stripes.data(), r.ns * sizeof(Stripe) } })))
@@ -942,7 +960,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			const uint64_t nruns = rp.parents[0].count / 256;
 			const uint32_t every = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, nruns / 16384));
 			const uint32_t sgrid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, nruns / every / 4));
-			hipLaunchKernelGGL((direct_sample_kernel<K>), dim3(sgrid), dim3(256), 0, c->stream, (const K *)keys, rb.parents, rb.plans, every);
+			LAUNCH(c, (direct_sample_kernel<K>), sgrid, 256, 0, keys, rb.parents, rb.plans, every);
 		} else {
 			// (the exact check behind a sampled leading-bit skip rides on this pass if it reads every key)
 			r.hist_checks = unverified && rp.round_keys == n;
@@ -950,21 +968,17 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				if (int rc = vres_init()) return rc;
 				add_stat(c, "bit_skip_checked_by_histogram", 1);
 			}
-			hipLaunchKernelGGL((direct_hist_kernel<K>), dim3(ns), dim3(1024), 0, c->stream, (const K *)keys, rb.stripes, rb.parents, rb.plans,
-					   r.hist_checks ? vres : (unsigned long long *)nullptr);
+			LAUNCH(c, (direct_hist_kernel<K>), ns, 1024, 0, keys, rb.stripes, rb.parents, rb.plans, r.hist_checks ? vres : nullptr);
 		}
-		hipLaunchKernelGGL((direct_plan_kernel<B>), dim3(np), dim3(256), 0, c->stream, rb.parents, rb.plans, ctr);
+		LAUNCH(c, (direct_plan_kernel<B>), np, 256, 0, rb.parents, rb.plans, ctr);
 		phase_mark(c, np == 1 ? "A sample" : "A histogram");
 		// The plan's verdict (Counters::direct_uneven: some parent's children are too unequal, or its keys come in
 		// runs) stays on the device: the direct kernel returns at once if it is non-zero, the streaming kernel
 		// launched behind it if it is zero.  The host learns it with the round's summary.
 		r.tried_direct = true;
 		const uint32_t force = c->direct_mode == 2 ? 1u : 0u;
-		constexpr size_t direct_lds = Direct2Lds<K, V>::bytes;
-		hipLaunchKernelGGL((classify_direct2_kernel<K, V>), dim3(ns), dim3(Direct2Cfg<K, V>::TH), direct_lds, c->stream,
-				   keys, vals, rb.stripes, rb.parents, (const DirectPlan *)rb.plans, block_map, slot_full,
-				   rb.fb, rb.lo_cnt, rb.lo_off, (K *)rb.lo_keys, rb.lo_vals, rb.nfull, ctr, force);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, (classify_direct2_kernel<K, V>), ns, (Direct2Cfg<K, V>::TH), (Direct2Lds<K, V>::bytes), keys, vals, rb.stripes, rb.parents, rb.plans,
+		       block_map, slot_full, rb.fb, rb.lo_cnt, rb.lo_off, rb.lo_keys, rb.lo_vals, rb.nfull, ctr, force);
 		phase_mark(c, "A classify direct");
 		return MSD_OK;
 	}
@@ -976,17 +990,13 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (int rc = classify_direct(r)) return rc;
 		if (!r.tried_direct || c->direct_mode != 2) {
 			const RoundBufs &rb = r.rb;
-			const uint32_t *run_if = r.tried_direct ? (const uint32_t *)&ctr->direct_uneven : (const uint32_t *)nullptr;
-			constexpr size_t s2_lds = Stream2Lds<K, V>::bytes;
+			const uint32_t *run_if = r.tried_direct ? &ctr->direct_uneven : nullptr;
 			if (job.splitters)
-				hipLaunchKernelGGL((classify_stream2_kernel<K, V, true>), dim3(r.ns), dim3(Stream2Cfg<K, V>::TH), s2_lds + kP * sizeof(K), c->stream,
-						   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
-						   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, job.splitters, run_if);
+				LAUNCH(c, (classify_stream2_kernel<K, V, true>), r.ns, (Stream2Cfg<K, V>::TH), (Stream2Lds<K, V>::range_bytes), keys, vals, rb.stripes,
+				       rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off, rb.lo_keys, rb.lo_vals, rb.nfull, job.splitters, run_if);
 			else
-				hipLaunchKernelGGL((classify_stream2_kernel<K, V, false>), dim3(r.ns), dim3(Stream2Cfg<K, V>::TH), s2_lds, c->stream,
-						   keys, vals, rb.stripes, rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off,
-						   (K *)rb.lo_keys, rb.lo_vals, rb.nfull, (const K *)nullptr, run_if);
-			HIPCHK(c, hipGetLastError());
+				LAUNCH(c, (classify_stream2_kernel<K, V, false>), r.ns, (Stream2Cfg<K, V>::TH), (Stream2Lds<K, V>::bytes), keys, vals, rb.stripes,
+				       rb.parents, block_map, rb.fb, rb.lo_cnt, rb.lo_off, rb.lo_keys, rb.lo_vals, rb.nfull, nullptr, run_if);
 		}
 		phase_mark(c, "A classify");
 		return MSD_OK;
@@ -997,24 +1007,20 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	{
 		const RoundBufs &rb = r.rb;
 		const uint32_t np = r.np, ns = r.ns, nc = r.nc;
-		const uint8_t *full_map = r.tried_direct ? (const uint8_t *)slot_full : (const uint8_t *)nullptr;
+		const uint8_t *full_map = r.tried_direct ? slot_full : nullptr;
 		const uint32_t force_map = c->direct_mode == 2 ? 1u : 0u;
-		hipLaunchKernelGGL((child_scan_kernel<B>), dim3(np), dim3(1024), 0, c->stream, rb.parents, rb.fb, rb.lo_cnt, rb.lo_dst, rb.ca);
-		hipLaunchKernelGGL((slot_classify_kernel<false>), dim3(ns * kSlotParts), dim3(256), 0, c->stream, rb.stripes, rb.parents,
-				   block_map, rb.nfull, rb.ca, rb.list, rb.holes, ctr, full_map, force_map);
-		hipLaunchKernelGGL(list_prepare_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca, ctr,
-				   (uint32_t)std::min<uint64_t>(r.rp.nslots, 0xFFFFFFFFu), (uint32_t)(2 * nc + kMinChains));
-		hipLaunchKernelGGL(scan_lookback_kernel, dim3((unsigned)((nc + kScanTile - 1) / kScanTile)), dim3(kScanTh), 0, c->stream, // (its state: round_init_kernel)
-				   (const uint64_t *)rb.ca.list_len, rb.ca.list_base, (uint64_t)nc, rb.scan_state, rb.scan_ctr, &ctr->errors);
-		HIPCHK(c, hipGetLastError());
-		hipLaunchKernelGGL((slot_classify_kernel<true>), dim3(ns * kSlotParts), dim3(256), 0, c->stream, rb.stripes, rb.parents,
-				   block_map, rb.nfull, rb.ca, rb.list, rb.holes, ctr, full_map, force_map);
+		LAUNCH(c, (child_scan_kernel<B>), np, 1024, 0, rb.parents, rb.fb, rb.lo_cnt, rb.lo_dst, rb.ca);
+		LAUNCH(c, (slot_classify_kernel<false>), ns * kSlotParts, 256, 0, rb.stripes, rb.parents, block_map, rb.nfull, rb.ca, rb.list, rb.holes, ctr,
+		       full_map, force_map);
+		LAUNCH(c, list_prepare_kernel, (nc + 255) / 256, 256, 0, nc, rb.ca, ctr, std::min<uint64_t>(r.rp.nslots, 0xFFFFFFFFu), 2 * nc + kMinChains);
+		LAUNCH(c, scan_lookback_kernel, (unsigned)((nc + kScanTile - 1) / kScanTile), kScanTh, 0, // (its state: round_init_kernel)
+		       rb.ca.list_len, rb.ca.list_base, nc, rb.scan_state, rb.scan_ctr, &ctr->errors);
+		LAUNCH(c, (slot_classify_kernel<true>), ns * kSlotParts, 256, 0, rb.stripes, rb.parents, block_map, rb.nfull, rb.ca, rb.list, rb.holes, ctr,
+		       full_map, force_map);
 		// per child: up to 64 waves when there are few children, one thread when there are very many
 		const uint32_t evict_waves = nc > 16384 ? 0u : (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, 16384 / nc));
 		const unsigned evict_grid = evict_waves ? (unsigned)(((uint64_t)nc * evict_waves + 3) / 4) : (unsigned)((nc + 255) / 256);
-		hipLaunchKernelGGL((evict_kernel<K, V>), dim3(evict_grid), dim3(256), 0, c->stream, nc, rb.ca,
-				   rb.list, rb.holes, ctr, keys, vals, (K *)rb.xkeys, rb.xvals, evict_waves);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, (evict_kernel<K, V>), evict_grid, 256, 0, nc, rb.ca, rb.list, rb.holes, ctr, keys, vals, rb.xkeys, rb.xvals, evict_waves);
 		phase_mark(c, "B metadata");
 
 		// Exactly the workgroups the chip holds at once: a wave's first 64 chain starts are its own by position and the
@@ -1023,11 +1029,9 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		// -- 2^30 Zipf keys: 1.3 ms where a wave's own work takes 0.7.)
 		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * c->chains_per_cu[HV ? 2 : sizeof(K) == 8 ? 1 : 0],
 								 std::max<uint64_t>(1, (r.rp.nslots + 255) / 256));
-		hipLaunchKernelGGL(list_pack_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca);
-		hipLaunchKernelGGL((chains_kernel<K, V>), dim3(grid), dim3(256), 0, c->stream, rb.ca, rb.list, rb.holes, ctr,
-				   keys, vals, (K *)rb.xkeys, rb.xvals, (uint32_t)(n / B), (uint32_t)(4 * nc + kMinChains));
-		hipLaunchKernelGGL(chains_verify_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, rb.ca, ctr);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, list_pack_kernel, (nc + 255) / 256, 256, 0, nc, rb.ca);
+		LAUNCH(c, (chains_kernel<K, V>), grid, 256, 0, rb.ca, rb.list, rb.holes, ctr, keys, vals, rb.xkeys, rb.xvals, n / B, 4 * nc + kMinChains);
+		LAUNCH(c, chains_verify_kernel, (nc + 255) / 256, 256, 0, nc, rb.ca, ctr);
 		phase_mark(c, "B block permute");
 		return MSD_OK;
 	}
@@ -1038,18 +1042,16 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		const RoundBufs &rb = r.rb;
 		const uint32_t np = r.np, nc = r.nc;
 		const bool sp = job.single_pass();
-		hipLaunchKernelGGL((cleanup_kernel<K, V>), dim3(r.ns), dim3(256), 0, c->stream, rb.stripes, rb.parents, rb.lo_cnt,
-				   rb.lo_off, rb.lo_dst, rb.ca, (const K *)rb.lo_keys, rb.lo_vals, keys, vals);
-		hipLaunchKernelGGL((excess_kernel<K, V>), dim3(nc), dim3(64), 0, c->stream, nc, rb.ca, (const K *)rb.xkeys, rb.xvals, keys, vals);
+		LAUNCH(c, (cleanup_kernel<K, V>), r.ns, 256, 0, rb.stripes, rb.parents, rb.lo_cnt, rb.lo_off, rb.lo_dst, rb.ca, rb.lo_keys, rb.lo_vals, keys, vals);
+		LAUNCH(c, (excess_kernel<K, V>), nc, 64, 0, nc, rb.ca, rb.xkeys, rb.xvals, keys, vals);
 		uint32_t wmax = 1;
 		for (size_t i = 0; i < np; ++i) wmax = std::max(wmax, r.rp.parents[i].width);
 		const uint32_t small_cap = (uint32_t)std::min<size_t>(c->lists_cap, 0xFFFFFFFFu);
-		hipLaunchKernelGGL(collect_kernel, dim3((np + (256u >> wmax) - 1) / (256u >> wmax)), dim3(256), 0, c->stream, (const Parent *)rb.parents, np, wmax, rb.ca,
-				   sp ? ~0ull : small_max, (HV || sp) ? small_max : std::max<uint64_t>(small_max, kCountMedMax),
-				   small_cap, sp ? 0u : count_bits,
-				   rb.next_parents, small(), small_count(), (HV || sp) ? (Segment *)nullptr : big, big_cap, ctr,
-				   (sp && job.counts) ? job.counts : (uint64_t *)nullptr, job.splitters ? job.nsplit + 1u : nc, job.stop_bits);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, collect_kernel, (np + (256u >> wmax) - 1) / (256u >> wmax), 256, 0, rb.parents, np, wmax, rb.ca,
+		       sp ? ~0ull : small_max, (HV || sp) ? small_max : std::max<uint64_t>(small_max, kCountMedMax),
+		       small_cap, sp ? 0u : count_bits,
+		       rb.next_parents, small(), small_count(), (HV || sp) ? nullptr : big, big_cap, ctr,
+		       (sp && job.counts) ? job.counts : nullptr, job.splitters ? job.nsplit + 1u : nc, job.stop_bits);
 		phase_mark(c, "C cleanup");
 		return MSD_OK;
 	}
@@ -1157,11 +1159,9 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// 2^16 counters dominates and 1024-thread workgroups hide its latency better: 1.15 vs 1.44 ms at 2^28)
 			const bool c16 = sizeof(K) == 4 && (c->count16 == 2 || (c->count16 == 1 && n / ncount_host >= 12000));
 			if constexpr (sizeof(K) == 4)
-				if (c16)
-					hipLaunchKernelGGL(count_place16_kernel, dim3(count_grid), dim3(kC16Th), kC16Lds, c->stream,
-							   keys, small_count(), ncount_host, rej16, ctr, n);
-			hipLaunchKernelGGL((count_place_kernel<K>), dim3(count_grid), dim3(kCountTh), kCountLds, c->stream,
-					   keys, c16 ? rej16 : small_count(), c16 ? 0u : ncount_host, c16 ? (const uint32_t *)&ctr->nslow16 : (const uint32_t *)nullptr, slow, ctr);
+				if (c16) LAUNCH(c, count_place16_kernel, count_grid, kC16Th, kC16Lds, keys, small_count(), ncount_host, rej16, ctr, n);
+			LAUNCH(c, (count_place_kernel<K>), count_grid, kCountTh, kCountLds, keys, c16 ? rej16 : small_count(), c16 ? 0u : ncount_host,
+			       c16 ? &ctr->nslow16 : nullptr, slow, ctr);
 			const uint32_t *walk_n = &ctr->nslow;
 			const Segment *walk_list = slow;
 			if constexpr (sizeof(K) == 4) {
@@ -1170,17 +1170,13 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				// segment, all of it counted before the first key is written back, so the sort is in place); only what that
 				// does not take either (a key with >= 2^16 copies, a 256-value group with >= 2^16 keys) walks its counters.
 				if (c->mid_leaf) {
-					hipLaunchKernelGGL((merge_count_kernel<true>), dim3(std::min<uint32_t>(ncount_host, (uint32_t)c->sm_count)), dim3(kMcTh), kMcLds, c->stream,
-							   (const uint32_t *)keys, (uint32_t *)keys, (const uint32_t *)nullptr, (const uint64_t *)nullptr, (const uint64_t *)nullptr,
-							   0u, 0u, 0u, 0u, (const Segment *)slow, (const uint32_t *)&ctr->nslow, slow2, &ctr->nslow2, &ctr->count_ticket4,
-							   (const uint32_t *)nullptr);
+					LAUNCH(c, (merge_count_kernel<true>), std::min<uint32_t>(ncount_host, (uint32_t)c->sm_count), kMcTh, kMcLds, keys, keys, nullptr,
+					       nullptr, nullptr, 0, 0, 0, 0, slow, &ctr->nslow, slow2, &ctr->nslow2, &ctr->count_ticket4, nullptr);
 					walk_n = &ctr->nslow2;
 					walk_list = slow2;
 				}
 			}
-			hipLaunchKernelGGL((count_walk_kernel<K>), dim3(count_grid), dim3(kCountTh), kCountLds, c->stream,
-					   keys, walk_list, walk_n, small(), nsmall_host, (uint32_t)small_max, big, big_cap, ctr);
-			HIPCHK(c, hipGetLastError());
+			LAUNCH(c, (count_walk_kernel<K>), count_grid, kCountTh, kCountLds, keys, walk_list, walk_n, small(), nsmall_host, small_max, big, big_cap, ctr);
 			phase_mark(c, "count sort");
 			// byte-counter overflows of segments above the LDS-sort capacity joined the big list
 			Counters hc;
@@ -1229,14 +1225,10 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				if (!rc) rc = upload(c, { { d_first, first.data(), first.size() * sizeof(uint32_t) } });
 				if (rc) return rc;
 				HIPCHK(c, hipMemsetAsync(ghist, 0, (size_t)nb * 65536 * sizeof(uint32_t), c->stream));
-				hipLaunchKernelGGL((bigcount_hist_kernel<K>), dim3((unsigned)std::min<uint64_t>(nchunks, (uint64_t)c->sm_count)), dim3(kBigHistTh), kBigHistLds, c->stream,
-						   (const K *)keys, big + b0, (const uint32_t *)d_first, nb, ghist);
-				hipLaunchKernelGGL((bigcount_scan_kernel<K>), dim3(nb), dim3(1024), 0, c->stream,
-						   (const K *)keys, big + b0, (const uint32_t *)(d_first + nb + 1), ghist, seg_hi, tile_v, ctr);
-				hipLaunchKernelGGL((bigcount_write_kernel<K>), dim3((unsigned)ntiles), dim3(kBigWriteTh), kBigWriteLds, c->stream,
-						   keys, big + b0, (const uint32_t *)(d_first + nb + 1), nb, (const uint32_t *)ghist, (const K *)seg_hi,
-						   (const uint16_t *)tile_v);
-				HIPCHK(c, hipGetLastError());
+				LAUNCH(c, (bigcount_hist_kernel<K>), (unsigned)std::min<uint64_t>(nchunks, (uint64_t)c->sm_count), kBigHistTh, kBigHistLds, keys, big + b0,
+				       d_first, nb, ghist);
+				LAUNCH(c, (bigcount_scan_kernel<K>), nb, 1024, 0, keys, big + b0, d_first + nb + 1, ghist, seg_hi, tile_v, ctr);
+				LAUNCH(c, (bigcount_write_kernel<K>), (unsigned)ntiles, kBigWriteTh, kBigWriteLds, keys, big + b0, d_first + nb + 1, nb, ghist, seg_hi, tile_v);
 			}
 			phase_mark(c, "big count sort");
 			Counters hc;
@@ -1255,6 +1247,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		// persistent workgroups with prefetch of the next segment: as many per CU as the LDS holds
 		constexpr size_t leaf_lds = LeafCountLds<K, V>::bytes;
 		const uint32_t leaf_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2048 / C::SORT_TH, (160 * 1024) / (leaf_lds + 512)));
+		const auto leaf_grid = [&](uint32_t nsegs) { return std::min<uint32_t>(nsegs, (uint32_t)c->sm_count * leaf_per_cu); };
 		bool small_done = false;
 		if constexpr (!HV && sizeof(K) == 8) {
 			// u64 keys, segments of about 2^14 (what two 8-bit rounds leave of 2^30 keys): leaf17_kernel -- counters for up to
@@ -1265,34 +1258,26 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				Segment *d_rej = reinterpret_cast<Segment *>(c->slab);
 				HIPCHK(c, hipMemsetAsync(&ctr->nslow2, 0, sizeof(uint32_t), c->stream));
 				HIPCHK(c, hipMemsetAsync(&ctr->l17_slow, 0, sizeof(uint32_t), c->stream));
-				hipLaunchKernelGGL((leaf17_kernel<NoVal>), dim3(std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count)), dim3(kL17Th), kL17Lds, c->stream,
-						   (uint64_t *)keys, (uint64_t *)nullptr, (const Segment *)small(), nsmall_host, d_rej, &ctr->nslow2, ctr, 4096u);
-				hipLaunchKernelGGL((leaf_count_sort_kernel<K, V>), dim3(std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count * leaf_per_cu)), dim3(C::SORT_TH), leaf_lds, c->stream,
-						   keys, vals, (const Segment *)d_rej, nsmall_host, small() + nsmall_host, ctr, &ctr->leaf_ticket[0], (const uint32_t *)&ctr->nslow2);
-				HIPCHK(c, hipGetLastError());
+				LAUNCH(c, (leaf17_kernel<NoVal>), std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count), kL17Th, kL17Lds, keys, nullptr, small(), nsmall_host,
+				       d_rej, &ctr->nslow2, ctr, 4096);
+				LAUNCH(c, (leaf_count_sort_kernel<K, V>), leaf_grid(nsmall_host), C::SORT_TH, leaf_lds, keys, vals, d_rej, nsmall_host, small() + nsmall_host,
+				       ctr, &ctr->leaf_ticket[0], &ctr->nslow2);
 				add_stat(c, "leaf17_launches", 1);
 				small_done = true;
 			}
 		}
-		if (nsmall_host && !small_done) {
-			hipLaunchKernelGGL((leaf_count_sort_kernel<K, V>), dim3(std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count * leaf_per_cu)), dim3(C::SORT_TH), leaf_lds, c->stream,
-					   keys, vals, small(), nsmall_host, small() + nsmall_host, ctr, &ctr->leaf_ticket[0]);
-			HIPCHK(c, hipGetLastError());
-		}
-		if (HV && ncount_host) { // (tuples whose last <= 16 bits are open -- 5b after its rounds: same kernel, its own ticket)
-			hipLaunchKernelGGL((leaf_count_sort_kernel<K, V>), dim3(std::min<uint32_t>(ncount_host, (uint32_t)c->sm_count * leaf_per_cu)), dim3(C::SORT_TH), leaf_lds, c->stream,
-					   keys, vals, small_count(), ncount_host, small() + nsmall_host, ctr, &ctr->leaf_ticket[1]);
-			HIPCHK(c, hipGetLastError());
-		}
+		if (nsmall_host && !small_done)
+			LAUNCH(c, (leaf_count_sort_kernel<K, V>), leaf_grid(nsmall_host), C::SORT_TH, leaf_lds, keys, vals, small(), nsmall_host, small() + nsmall_host, ctr,
+			       &ctr->leaf_ticket[0], nullptr);
+		if (HV && ncount_host) // (tuples whose last <= 16 bits are open -- 5b after its rounds: same kernel, its own ticket)
+			LAUNCH(c, (leaf_count_sort_kernel<K, V>), leaf_grid(ncount_host), C::SORT_TH, leaf_lds, keys, vals, small_count(), ncount_host, small() + nsmall_host,
+			       ctr, &ctr->leaf_ticket[1], nullptr);
 		// (keys only, no small segments, and the counting leaves are known to have handed nothing on: no launch -- 2^30 uniform
 		// u32 keys: 0.03 ms for workgroups that look at an empty list)
 		const bool may_fall_back = HV || nsmall_host != 0 || nfallback_known != 0;
-		if (may_fall_back && nsmall_host + ncount_host) {
-			constexpr size_t sort_lds = SortLds<K, V>::bytes;
-			hipLaunchKernelGGL((lds_sort_kernel<K, V>), dim3(std::min<uint32_t>(nsmall_host + ncount_host, 2 * c->sm_count)), dim3(C::SORT_TH), sort_lds, c->stream,
-					   keys, vals, small() + nsmall_host, 0u, (const uint32_t *)&ctr->nfallback);
-			HIPCHK(c, hipGetLastError());
-		}
+		if (may_fall_back && nsmall_host + ncount_host)
+			LAUNCH(c, (lds_sort_kernel<K, V>), std::min<uint32_t>(nsmall_host + ncount_host, 2 * c->sm_count), C::SORT_TH, (SortLds<K, V>::bytes), keys, vals,
+			       small() + nsmall_host, 0, &ctr->nfallback);
 		phase_mark(c, "LDS sort");
 		return MSD_OK;
 	}
@@ -1306,7 +1291,7 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 	constexpr bool HV = has_val<V>::value;
 	if (n == 0) return MSD_OK;
 	if (!keys || (HV && !vals)) return fail(c, MSD_EINVAL, "null data pointer");
-	if (((uintptr_t)keys & 15) || (HV && ((uintptr_t)vals & 15)))
+	if (!aligned16(keys) || (HV && !aligned16(vals)))
 		return fail(c, MSD_EINVAL, "keys/rids must be 16-byte aligned (the reference asserts the same, src/msb_64.c:2273)");
 	if (end_bit < 0 || end_bit > (int)sizeof(K) * 8) return fail(c, MSD_EINVAL, "end_bit out of range");
 	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large for 32-bit block slots");
@@ -1346,6 +1331,16 @@ template <typename K, typename V> static int reserve_for(msd_ctx *c, uint64_t n)
 	if (!rc) rc = pinned_reserve(c, 1 << 20);
 	if (!rc) rc = lists_reserve(c, leaf_list_guess<K, V>(n), 0, 0, true);
 	return rc;
+}
+
+// (key_bytes, val_bytes) -> the element layout: f(K(), V()), or kNoLayout (not an MSD_ code) where there is none
+constexpr int kNoLayout = 1;
+template <typename F> static int with_layout(int key_bytes, int val_bytes, F &&f)
+{
+	if (key_bytes == 4 && val_bytes == 0) return f(uint32_t(), NoVal());
+	if (key_bytes == 8 && val_bytes == 0) return f(uint64_t(), NoVal());
+	if (key_bytes == 8 && val_bytes == 8) return f(uint64_t(), uint64_t());
+	return kNoLayout;
 }
 
 // ---- the entry points' jobs (the C ABI below: one instance per element type)
@@ -1407,7 +1402,7 @@ template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
 		c->chains_per_cu[has_val<V>::value ? 2 : sizeof(K) == 8 ? 1 : 0] = std::max(1, per_cu);
 	}
 	HIPCHK(c, max_lds(&classify_stream2_kernel<K, V, false>, Stream2Lds<K, V>::bytes));
-	HIPCHK(c, max_lds(&classify_stream2_kernel<K, V, true>, Stream2Lds<K, V>::bytes + kP * sizeof(K)));
+	HIPCHK(c, max_lds(&classify_stream2_kernel<K, V, true>, Stream2Lds<K, V>::range_bytes));
 	HIPCHK(c, max_lds(&lds_sort_kernel<K, V>, SortLds<K, V>::bytes));
 	HIPCHK(c, max_lds(&classify_direct2_kernel<K, V>, Direct2Lds<K, V>::bytes));
 	if constexpr (sizeof(K) == 8) {
@@ -1473,9 +1468,7 @@ static int gather_impl(msd_ctx *c, K *dst, const K *src, const uint64_t *src_off
 	HIPCHK(c, hipMemcpyAsync(d_runs, c->pinned, bytes, hipMemcpyHostToDevice, c->stream));
 	// (one workgroup per 8 KiB chunk, no loop: 4.3-4.5 TB/s; persistent workgroups with larger chunks: 3.6)
 	const unsigned grid = (unsigned)nchunks;
-	hipLaunchKernelGGL((gather_runs_kernel<K>), dim3(grid), dim3(256), 0, c->stream, dst, src, (const GatherRun *)d_runs,
-			   (uint32_t)runs.size() - 1, (uint32_t)nchunks, d_coarse);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (gather_runs_kernel<K>), grid, 256, 0, dst, src, d_runs, runs.size() - 1, nchunks, d_coarse);
 	return MSD_OK;
 }
 
@@ -1511,9 +1504,10 @@ int msd_create(msd_ctx **out, int device, void *stream)
 		const long x = strtol(v, &end, 10);
 		if (end == v || *end || msd_set_option(c, name, x) != MSD_OK) fprintf(stderr, "msd_create: ignoring %s=%s\n", env, v);
 	}
-	int rc = set_lds_attrs<uint32_t, NoVal>(c);
-	if (!rc) rc = set_lds_attrs<uint64_t, NoVal>(c);
-	if (!rc) rc = set_lds_attrs<uint64_t, uint64_t>(c);
+	const auto attrs = [c](auto k, auto v) { return set_lds_attrs<decltype(k), decltype(v)>(c); };
+	int rc = with_layout(4, 0, attrs);
+	if (!rc) rc = with_layout(8, 0, attrs);
+	if (!rc) rc = with_layout(8, 8, attrs);
 	if (!rc) rc = set_rows_lds_attrs(c);
 	if (rc) {
 		fprintf(stderr, "msd_create: %s\n", c->err.c_str());
@@ -1555,10 +1549,8 @@ int msd_reserve(msd_ctx *c, uint64_t n, int key_bytes, int val_bytes)
 {
 	if (!c) return MSD_EINVAL;
 	HIPCHK(c, hipSetDevice(c->device));
-	if (key_bytes == 4 && val_bytes == 0) return reserve_for<uint32_t, NoVal>(c, n);
-	if (key_bytes == 8 && val_bytes == 0) return reserve_for<uint64_t, NoVal>(c, n);
-	if (key_bytes == 8 && val_bytes == 8) return reserve_for<uint64_t, uint64_t>(c, n);
-	return fail(c, MSD_EINVAL, "unsupported element layout %d+%d bytes", key_bytes, val_bytes);
+	const int rc = with_layout(key_bytes, val_bytes, [&](auto k, auto v) { return reserve_for<decltype(k), decltype(v)>(c, n); });
+	return rc != kNoLayout ? rc : fail(c, MSD_EINVAL, "unsupported element layout %d+%d bytes", key_bytes, val_bytes);
 }
 
 uint64_t msd_workspace_bytes(const msd_ctx *c) { return c ? c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment) + c->sel_bytes + c->rows_stage_bytes : 0; }
@@ -1590,8 +1582,7 @@ static int bounds_impl(msd_ctx *c, const K *k, uint64_t n, unsigned shift, uint6
 	if (!bounds || (n && !k)) return fail(c, MSD_EINVAL, "bucket_bounds: null pointer");
 	if (shift >= sizeof(K) * 8 || nbuckets == 0 || nbuckets > (1u << 24)) return fail(c, MSD_EINVAL, "bucket_bounds: shift or bucket count out of range");
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL((bucket_bounds_kernel<K>), dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, c->stream, k, n, (uint32_t)shift, first, nbuckets, bounds);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (bucket_bounds_kernel<K>), (nbuckets + 1 + 255) / 256, 256, 0, k, n, shift, first, nbuckets, bounds);
 	return MSD_OK;
 }
 
@@ -1608,13 +1599,11 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	if (open_bits < 1 || open_bits > 16) return fail(c, MSD_EINVAL, "merge_buckets: 1..16 open bits");
 	if ((IN16 || HIST) && open_bits != 16) return fail(c, MSD_EINVAL, "merge_buckets: extents of low halves need 16 open bits");
 	if (HIST && src_cap < (uint64_t)nsrc * nb * kH2Rec) return fail(c, MSD_EINVAL, "merge_buckets: %u x %u records of %u bytes do not fit the source buffer", nsrc, nb, kH2Rec);
-	if (((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return fail(c, MSD_EINVAL, "merge_buckets: buffers must be 16-byte aligned");
+	if (!aligned16(src) || !aligned16(dst)) return fail(c, MSD_EINVAL, "merge_buckets: buffers must be 16-byte aligned");
 	if (n_expected > dst_cap) return fail(c, MSD_EINVAL, "merge_buckets: the output buffer is too small");
 	if ((uint64_t)first_prefix + nb > (1ull << (32 - open_bits))) return fail(c, MSD_EINVAL, "merge_buckets: bucket numbers exceed the key's prefix");
-	{ // the buffers must not overlap (the leaf reads extents while other workgroups write finished buckets)
-		const uintptr_t s0 = (uintptr_t)src, s1 = s0 + src_cap * sizeof(IN), d0 = (uintptr_t)dst, d1 = d0 + dst_cap * 4;
-		if (s0 < d1 && d0 < s1) return fail(c, MSD_EINVAL, "merge_buckets: source and destination overlap");
-	}
+	// (the leaf reads extents while other workgroups write finished buckets)
+	if (ranges_overlap(src, src_cap * sizeof(IN), dst, dst_cap * 4)) return fail(c, MSD_EINVAL, "merge_buckets: source and destination overlap");
 	HIPCHK(c, hipSetDevice(c->device));
 	c->stats.clear();
 	phase_begin(c);
@@ -1636,32 +1625,23 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	HIPCHK(c, hipMemsetAsync(ctr, 0, (char *)(status + 64) - (char *)ctr, c->stream));
 	MergeBase mb = {};
 	for (uint32_t x = 0; x < nsrc; ++x) mb.b[x] = src_base[x];
-	hipLaunchKernelGGL(merge_plan_kernel, dim3(nsrc + 1), dim3(1024), 0, c->stream, d_counts, mb, nsrc, nb, n_expected, cnt32, soff, doff, status);
+	LAUNCH(c, merge_plan_kernel, nsrc + 1, 1024, 0, d_counts, mb, nsrc, nb, n_expected, cnt32, soff, doff, status);
 	// buckets that fit the registers of a workgroup (shards of <= 2^27 keys at 8 ranks) take merge_place16_kernel, larger
 	// ones (2^30 keys per rank: nsrc x 2^14 keys per bucket) merge_count_kernel
 	// (low halves: merge_count_kernel at every bucket size -- shorter buckets cost it more per key, the exchange it follows
 	// cost half)
 	const bool in_regs = !IN16 && !HIST && (c->merge_leaf == 1 || (c->merge_leaf == 0 && n_expected / nb <= 12000 && open_bits >= (int)kC16MinBits));
-	if constexpr (IN16 || HIST) {
-		const unsigned grid = (unsigned)std::min<uint64_t>(nb, (uint64_t)c->sm_count);
-		hipLaunchKernelGGL((merge_count_kernel<false, IN>), dim3(grid), dim3(kMcTh), kMcLds, c->stream, src, dst, (const uint32_t *)cnt32,
-				   (const uint64_t *)soff, (const uint64_t *)doff, nsrc, nb, (uint32_t)open_bits, first_prefix, (const Segment *)nullptr,
-				   (const uint32_t *)nullptr, rej, &ctr->nslow16, &ctr->count_ticket3, (const uint32_t *)status);
-	} else if (in_regs) {
-		const unsigned grid = (unsigned)std::min<uint64_t>(nb, (uint64_t)c->sm_count * 2);
-		const uint32_t G = nsrc <= 2 ? 2 : nsrc <= 4 ? 4 : 8;
-#define MSD_MERGE_LAUNCH(GG)                                                                                                              \
-	hipLaunchKernelGGL((merge_place16_kernel<GG>), dim3(grid), dim3(kC16Th), kC16Lds, c->stream, (const uint32_t *)src, src_cap, dst, (const uint32_t *)cnt32, \
-			   (const uint64_t *)soff, (const uint64_t *)doff, nsrc, nb, (uint32_t)open_bits, first_prefix, rej, ctr, (const uint32_t *)status)
-		if (G == 2) MSD_MERGE_LAUNCH(2); else if (G == 4) MSD_MERGE_LAUNCH(4); else MSD_MERGE_LAUNCH(8);
-#undef MSD_MERGE_LAUNCH
+	if (in_regs) {
+		if constexpr (!IN16 && !HIST) { // (whole keys only)
+			const unsigned grid = (unsigned)std::min<uint64_t>(nb, (uint64_t)c->sm_count * 2);
+			const auto place16 = nsrc <= 2 ? merge_place16_kernel<2> : nsrc <= 4 ? merge_place16_kernel<4> : merge_place16_kernel<8>;
+			LAUNCH(c, place16, grid, kC16Th, kC16Lds, src, src_cap, dst, cnt32, soff, doff, nsrc, nb, open_bits, first_prefix, rej, ctr, status);
+		}
 	} else {
 		const unsigned grid = (unsigned)std::min<uint64_t>(nb, (uint64_t)c->sm_count);
-		hipLaunchKernelGGL((merge_count_kernel<false, uint32_t>), dim3(grid), dim3(kMcTh), kMcLds, c->stream, (const uint32_t *)src, dst, (const uint32_t *)cnt32,
-				   (const uint64_t *)soff, (const uint64_t *)doff, nsrc, nb, (uint32_t)open_bits, first_prefix, (const Segment *)nullptr,
-				   (const uint32_t *)nullptr, rej, &ctr->nslow16, &ctr->count_ticket3, (const uint32_t *)status);
+		LAUNCH(c, (merge_count_kernel<false, IN>), grid, kMcTh, kMcLds, src, dst, cnt32, soff, doff, nsrc, nb, open_bits, first_prefix, nullptr, nullptr,
+		       rej, &ctr->nslow16, &ctr->count_ticket3, status);
 	}
-	HIPCHK(c, hipGetLastError());
 	phase_mark(c, "merge leaf");
 	// what the leaf did not take (rare: long or crowded buckets) lies unsorted at its place in dst: the general leaves finish it
 	Counters hc;
@@ -1713,36 +1693,14 @@ static int hist2_pack_impl(msd_ctx *c, const IN *d_keys, uint64_t n, const uint6
 	if (!c) return MSD_EINVAL;
 	if (!d_keys || !d_bounds || !d_rec || !d_overflow) return fail(c, MSD_EINVAL, "hist2_pack: null pointer");
 	if (nbuckets == 0 || nbuckets > 65536) return fail(c, MSD_EINVAL, "hist2_pack: 1..65536 buckets");
-	if (((uintptr_t)d_keys & 15) || ((uintptr_t)d_rec & 15)) return fail(c, MSD_EINVAL, "hist2_pack: buffers must be 16-byte aligned");
+	if (!aligned16(d_keys) || !aligned16(d_rec)) return fail(c, MSD_EINVAL, "hist2_pack: buffers must be 16-byte aligned");
 	if (rec_bytes < (uint64_t)nbuckets * kH2Rec) return fail(c, MSD_EINVAL, "hist2_pack: %u records of %u bytes do not fit the output buffer", nbuckets, kH2Rec);
-	{
-		const uintptr_t s0 = (uintptr_t)d_keys, s1 = s0 + n * sizeof(IN), d0 = (uintptr_t)d_rec, d1 = d0 + (uint64_t)nbuckets * kH2Rec;
-		if (s0 < d1 && d0 < s1) return fail(c, MSD_EINVAL, "hist2_pack: source and destination overlap");
-	}
+	if (ranges_overlap(d_keys, n * sizeof(IN), d_rec, (uint64_t)nbuckets * kH2Rec)) return fail(c, MSD_EINVAL, "hist2_pack: source and destination overlap");
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipMemsetAsync(d_overflow, 0, sizeof(uint32_t), c->stream));
 	const unsigned grid = (unsigned)std::min<uint64_t>(nbuckets, (uint64_t)c->sm_count * 2);
-	hipLaunchKernelGGL((hist2_pack_kernel<IN>), dim3(grid), dim3(kH2Th), kH2Lds, c->stream, d_keys, d_bounds, nbuckets, (unsigned char *)d_rec, d_overflow);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (hist2_pack_kernel<IN>), grid, kH2Th, kH2Lds, d_keys, d_bounds, nbuckets, d_rec, d_overflow);
 	return MSD_OK;
-}
-// starts[b] = sum of counts[0 .. b), b = 0 .. 65536 (one workgroup)
-__global__ __launch_bounds__(1024) void bounds16_kernel(const uint64_t *__restrict__ counts, uint64_t *__restrict__ bounds)
-{
-	__shared__ uint64_t wsum[16];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-	uint64_t mine = 0;
-	for (uint32_t j = 0; j < 64; ++j) mine += counts[tid * 64u + j];
-	const uint64_t inc = wave_incl_scan64(mine);
-	if (lane == 63) wsum[w] = inc;
-	__syncthreads();
-	uint64_t at = inc - mine;
-	for (uint32_t ww = 0; ww < w; ++ww) at += wsum[ww];
-	for (uint32_t j = 0; j < 64; ++j) {
-		bounds[tid * 64u + j] = at;
-		at += counts[tid * 64u + j];
-	}
-	if (tid == 1023) bounds[65536] = at;
 }
 namespace {
 // the tables msd_order_low16_counts_u32 leaves in the slab for msd_order_low16_scatter_u32
@@ -1774,8 +1732,7 @@ int msd_bounds_from_counts16(msd_ctx *c, const uint64_t *d_counts, uint64_t *d_b
 	if (!c) return MSD_EINVAL;
 	if (!d_counts || !d_bounds) return fail(c, MSD_EINVAL, "bounds_from_counts16: null pointer");
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL(bounds16_kernel, dim3(1), dim3(1024), 0, c->stream, d_counts, d_bounds);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, bounds16_kernel, 1, 1024, 0, d_counts, d_bounds);
 	return MSD_OK;
 }
 // msd_order_low16_u32 in two halves: the counts are ready (asynchronously) after the first, so that the caller can start its
@@ -1785,7 +1742,7 @@ int msd_order_low16_counts_u32(msd_ctx *c, uint32_t *d_keys, uint64_t n, uint64_
 	if (!c) return MSD_EINVAL;
 	c->order_keys = nullptr;
 	if (!d_counts || (n && !d_keys)) return fail(c, MSD_EINVAL, "order_low16: null pointer");
-	if ((uintptr_t)d_keys & 15) return fail(c, MSD_EINVAL, "order_low16: buffers must be 16-byte aligned");
+	if (!aligned16(d_keys)) return fail(c, MSD_EINVAL, "order_low16: buffers must be 16-byte aligned");
 	if (n >= (1ull << 40)) return fail(c, MSD_EINVAL, "order_low16: too many keys");
 	// one in-place round on the top 8 bits (the direct-placement round 0) ...
 	int rc = sort_impl<uint32_t, NoVal>(c, d_keys, nullptr, n, 32, SortJob<uint32_t>::whole(24u));
@@ -1794,10 +1751,9 @@ int msd_order_low16_counts_u32(msd_ctx *c, uint32_t *d_keys, uint64_t n, uint64_
 	HIPCHK(c, hipSetDevice(c->device));
 	Low16Tables t;
 	if ((rc = slab_carve(c, [&](Bump &b) { t.carve(b); }))) return rc;
-	hipLaunchKernelGGL((bucket_bounds_kernel<uint32_t>), dim3(2), dim3(256), 0, c->stream, (const uint32_t *)d_keys, n, 24u, (uint64_t)0, 256u, t.pb);
-	hipLaunchKernelGGL(hist16_kernel, dim3(256 * kS16Chunks), dim3(kS16Th), 0, c->stream, (const uint32_t *)d_keys, n, (const uint64_t *)t.pb, t.wg);
-	hipLaunchKernelGGL(scan16_kernel, dim3(256), dim3(256), 0, c->stream, (const uint32_t *)t.wg, (const uint64_t *)t.pb, (unsigned long long *)d_counts, t.base);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (bucket_bounds_kernel<uint32_t>), 2, 256, 0, d_keys, n, 24, 0, 256, t.pb);
+	LAUNCH(c, hist16_kernel, 256 * kS16Chunks, kS16Th, 0, d_keys, n, t.pb, t.wg);
+	LAUNCH(c, scan16_kernel, 256, 256, 0, t.wg, t.pb, reinterpret_cast<unsigned long long *>(d_counts), t.base);
 	c->order_keys = d_keys; // (the tables of the scatter lie in the slab: the scatter must be this context's next call)
 	c->order_n = n;
 	return MSD_OK;
@@ -1808,19 +1764,13 @@ int msd_order_low16_scatter_u32(msd_ctx *c, const uint32_t *d_keys, uint64_t n, 
 	if (!d_out || (n && !d_keys)) return fail(c, MSD_EINVAL, "order_low16: null pointer");
 	if (c->order_keys != d_keys || c->order_n != n) return fail(c, MSD_EINVAL, "order_low16_scatter: not preceded by msd_order_low16_counts_u32 on the same keys");
 	c->order_keys = nullptr;
-	if ((uintptr_t)d_out & 15) return fail(c, MSD_EINVAL, "order_low16: buffers must be 16-byte aligned");
-	{
-		const uintptr_t s0 = (uintptr_t)d_keys, s1 = s0 + n * 4, d0 = (uintptr_t)d_out, d1 = d0 + n * 2;
-		if (s0 < d1 && d0 < s1) return fail(c, MSD_EINVAL, "order_low16: source and destination overlap");
-	}
+	if (!aligned16(d_out)) return fail(c, MSD_EINVAL, "order_low16: buffers must be 16-byte aligned");
+	if (ranges_overlap(d_keys, n * 4, d_out, n * 2)) return fail(c, MSD_EINVAL, "order_low16: source and destination overlap");
 	HIPCHK(c, hipSetDevice(c->device));
 	Bump real(c->slab); // (as msd_order_low16_counts_u32 left it)
 	Low16Tables t;
 	t.carve(real);
-	if (n)
-		hipLaunchKernelGGL(scatter_low16_kernel, dim3(256 * kS16Chunks), dim3(kS16Th), kS16Lds, c->stream, d_keys, n, (const uint64_t *)t.pb,
-				   (const unsigned long long *)t.base, d_out);
-	HIPCHK(c, hipGetLastError());
+	if (n) LAUNCH(c, scatter_low16_kernel, 256 * kS16Chunks, kS16Th, kS16Lds, d_keys, n, t.pb, t.base, d_out);
 	return MSD_OK;
 }
 int msd_order_low16_u32(msd_ctx *c, uint32_t *d_keys, uint64_t n, uint16_t *d_out, uint64_t *d_counts)
@@ -1836,15 +1786,11 @@ int msd_pack_low16_u32(msd_ctx *c, const uint32_t *d_keys, uint64_t n, uint16_t 
 	if (!c) return MSD_EINVAL;
 	if (n == 0) return MSD_OK;
 	if (!d_keys || !d_out) return fail(c, MSD_EINVAL, "pack_low16: null pointer");
-	if (((uintptr_t)d_keys & 15) || ((uintptr_t)d_out & 15)) return fail(c, MSD_EINVAL, "pack_low16: buffers must be 16-byte aligned");
-	{
-		const uintptr_t s0 = (uintptr_t)d_keys, s1 = s0 + n * 4, d0 = (uintptr_t)d_out, d1 = d0 + n * 2;
-		if (s0 < d1 && d0 < s1) return fail(c, MSD_EINVAL, "pack_low16: source and destination overlap");
-	}
+	if (!aligned16(d_keys) || !aligned16(d_out)) return fail(c, MSD_EINVAL, "pack_low16: buffers must be 16-byte aligned");
+	if (ranges_overlap(d_keys, n * 4, d_out, n * 2)) return fail(c, MSD_EINVAL, "pack_low16: source and destination overlap");
 	HIPCHK(c, hipSetDevice(c->device));
 	const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 16, (n / 8 + 255) / 256 + 1);
-	hipLaunchKernelGGL(pack_low16_kernel, dim3(grid), dim3(256), 0, c->stream, d_keys, n, d_out);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, pack_low16_kernel, grid, 256, 0, d_keys, n, d_out);
 	return MSD_OK;
 }
 
@@ -1874,8 +1820,7 @@ template <typename K> static int sample_impl(msd_ctx *c, const K *k, uint64_t n,
 	HIPCHK(c, hipSetDevice(c->device));
 	if (m == 0) return MSD_OK;
 	const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (m + 255) / 256);
-	hipLaunchKernelGGL((sample_kernel<K>), dim3(grid), dim3(256), 0, c->stream, k, n, m, seed, out);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (sample_kernel<K>), grid, 256, 0, k, n, m, seed, out);
 	return MSD_OK;
 }
 
@@ -1886,8 +1831,7 @@ template <typename K> static int splitters_impl(msd_ctx *c, const K *sorted_samp
 	if (parts == 1) return MSD_OK;
 	if (!sorted_sample || !delims || m == 0) return fail(c, MSD_EINVAL, "splitters: null pointer or empty sample");
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL((splitters_kernel<K>), dim3(1), dim3(256), 0, c->stream, sorted_sample, m, parts, delims);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (splitters_kernel<K>), 1, 256, 0, sorted_sample, m, parts, delims);
 	return MSD_OK;
 }
 
@@ -1942,14 +1886,12 @@ static int histogram_impl(msd_ctx *c, const K *k, uint64_t n, unsigned shift, un
 	if (!c) return MSD_EINVAL;
 	if (!cnt || (n && !k)) return fail(c, MSD_EINVAL, "null pointer");
 	if (rb < 1 || rb > 12 || shift + rb > sizeof(K) * 8) return fail(c, MSD_EINVAL, "radix_bits must be 1..12 and shift+radix_bits within the key");
-	if ((uintptr_t)k & 15) return fail(c, MSD_EINVAL, "keys must be 16-byte aligned");
+	if (!aligned16(k)) return fail(c, MSD_EINVAL, "keys must be 16-byte aligned");
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint64_t) << rb, c->stream));
 	if (n == 0) return MSD_OK;
 	const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (n + 4095) / 4096);
-	hipLaunchKernelGGL((histogram_kernel<K>), dim3(grid), dim3(256), sizeof(uint32_t) << rb, c->stream, k, n, shift, rb,
-			   (unsigned long long *)cnt);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (histogram_kernel<K>), grid, 256, sizeof(uint32_t) << rb, k, n, shift, rb, reinterpret_cast<unsigned long long *>(cnt));
 	return MSD_OK;
 }
 extern "C" {
@@ -1970,8 +1912,7 @@ int msd_exclusive_scan_u64(msd_ctx *c, const uint64_t *in, uint64_t *out, uint64
 	uint32_t *ctr = (uint32_t *)c->slab; // [0] tile counter, [2] error flag
 	HIPCHK(c, hipMemsetAsync(c->slab, 0, 256, c->stream));
 	HIPCHK(c, hipMemsetAsync(state, 0, ntiles * 8, c->stream));
-	hipLaunchKernelGGL(scan_lookback_kernel, dim3((unsigned)ntiles), dim3(kScanTh), 0, c->stream, in, out, n, state, ctr, ctr + 2);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, scan_lookback_kernel, (unsigned)ntiles, kScanTh, 0, in, out, n, state, ctr, ctr + 2);
 	// the look-back gives up after a bounded number of polls and sets a flag: report it (one small readback)
 	rc = pinned_reserve(c, 64);
 	if (rc) return rc;
@@ -1989,10 +1930,12 @@ int msd_exclusive_scan_u64(msd_ctx *c, const uint64_t *in, uint64_t *out, uint64
 #define MSD_TOPK_PACKED_STOP 0
 #endif
 
-static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+// key_type (valid) -> the unsigned type that carries the key and whether the key is its own code (raw):
+// f(K(), std::true_type or std::false_type)
+template <typename F> static int with_key_type(int key_type, F &&f)
 {
-	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return abytes && bbytes && x < y + bbytes && y < x + abytes;
+	if (key_type_bytes(key_type) == 4) return key_type == kKeyU32 ? f(uint32_t(), std::true_type()) : f(uint32_t(), std::false_type());
+	return key_type == kKeyU64 ? f(uint64_t(), std::true_type()) : f(uint64_t(), std::false_type());
 }
 
 // the phases of an internal sort, added to the ones collected so far (every sort_impl starts its own list)
@@ -2027,8 +1970,7 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	if (TOPK && k == 0) return MSD_OK;
 	if (!keys || (LOADS_RIDS && !rids) || (TOPK && !out) || (TOPK && HV && !out_rids) || (PACKED && !final_keys))
 		return fail(c, MSD_EINVAL, "null data pointer");
-	if (((uintptr_t)keys & 15) || (LOADS_RIDS && ((uintptr_t)rids & 15)) || (TOPK && ((uintptr_t)out & 15)) || (TOPK && HV && ((uintptr_t)out_rids & 15)) ||
-	    (PACKED && ((uintptr_t)final_keys & 15)))
+	if (!aligned16(keys) || (LOADS_RIDS && !aligned16(rids)) || (TOPK && !aligned16(out)) || (TOPK && HV && !aligned16(out_rids)) || (PACKED && !aligned16(final_keys)))
 		return fail(c, MSD_EINVAL, "input and output buffers must be 16-byte aligned");
 	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large");
 	if (PACKED && n > ((uint64_t)1 << 32)) return fail(c, MSD_EINVAL, "indices of a 32-bit key type need n <= 2^32 (the position travels in 32 bits)");
@@ -2071,13 +2013,9 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	const uint64_t rank = TOPK ? k - 1 : k;
 	for (uint32_t p = 0; p < PASSES; ++p) {
 		unsigned long long *const pb = bins + (size_t)p * kSelBins;
-		if (p == 0)
-			hipLaunchKernelGGL((select_hist_kernel<K, true, HOW>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, how, st, pb);
-		else
-			hipLaunchKernelGGL((select_hist_kernel<K, false, HOW>), dim3(hist_grid), dim3(kSelTh), 0, c->stream, keys, n, how, st, pb);
-		hipLaunchKernelGGL((select_pivot_kernel<K>), dim3(1), dim3(kSelPivotTh), 0, c->stream, st, bins + (size_t)p * kSelBins, p, n, rank, cap);
+		LAUNCH(c, (p == 0 ? select_hist_kernel<K, true, HOW> : select_hist_kernel<K, false, HOW>), hist_grid, kSelTh, 0, keys, n, how, st, pb);
+		LAUNCH(c, (select_pivot_kernel<K>), 1, kSelPivotTh, 0, st, pb, p, n, rank, cap);
 	}
-	HIPCHK(c, hipGetLastError());
 	phase_mark(c, "select_hist");
 	const uint64_t tile_vecs = (uint64_t)kSelTh * kSelFilterU;
 	const unsigned filter_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * 4, (nvec + tile_vecs - 1) / tile_vecs));
@@ -2087,9 +2025,8 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	const bool dense = TOPK && k > n / 32;
 	const uint32_t stage_cand = (dense ? kSelStageLargeCand : kSelStageSmall) / elem;
 	const uint32_t stage_below = !TOPK ? 0 : (dense ? kSelStageLargeBelow : kSelStageSmall) / elem;
-	hipLaunchKernelGGL((select_filter_kernel<K, V, TOPK, EMIT, HOW>), dim3(filter_grid), dim3(kSelTh), (size_t)(stage_cand + stage_below) * elem, c->stream,
-			   keys, rids, n, how, st, out, out_rids, cand, cand_rids, stage_cand, stage_below);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, (select_filter_kernel<K, V, TOPK, EMIT, HOW>), filter_grid, kSelTh, (size_t)(stage_cand + stage_below) * elem, keys, rids, n, how, st, out,
+	       out_rids, cand, cand_rids, stage_cand, stage_below);
 	phase_mark(c, "select_filter");
 	HIPCHK(c, hipMemcpyAsync(c->pinned, st, sizeof(SelectState), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2124,10 +2061,9 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 			phase_begin(c);
 			const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (k + kSelFinishTh - 1) / kSelFinishTh);
 			if constexpr (PACKED)
-				hipLaunchKernelGGL((select_finish_kernel<K, true>), dim3(grid), dim3(kSelFinishTh), 0, c->stream, out, final_keys, k, codec);
+				LAUNCH(c, (select_finish_kernel<K, true>), grid, kSelFinishTh, 0, out, final_keys, k, codec);
 			else
-				hipLaunchKernelGGL((select_finish_kernel<K, false>), dim3(grid), dim3(kSelFinishTh), 0, c->stream, (uint64_t *)nullptr, out, k, codec);
-			HIPCHK(c, hipGetLastError());
+				LAUNCH(c, (select_finish_kernel<K, false>), grid, kSelFinishTh, 0, nullptr, out, k, codec);
 			phase_mark(c, "select_finish");
 			phase_end(c);
 			phases_append(c, phases);
@@ -2177,6 +2113,10 @@ int msd_select_u64(msd_ctx *c, const uint64_t *k, uint64_t n, uint64_t kk, int w
 // ---- typed keys and indices (codec: msd_keycodec.hpp)
 
 static bool key_type_ok(int key_type) { return key_type >= 0 && key_type < kKeyTypes; }
+static int check_key_type(msd_ctx *c, int key_type)
+{
+	return key_type_ok(key_type) ? MSD_OK : fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
+}
 
 int msd_key_encode(int key_type, uint64_t bits, uint64_t *code)
 {
@@ -2194,34 +2134,32 @@ int msd_key_decode(int key_type, uint64_t code, uint64_t *bits)
 int msd_topk_keys(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, uint64_t k, int which, void *d_out_keys, uint64_t *d_out_idx)
 {
 	if (!c) return MSD_EINVAL;
-	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
-	if (key_type_bytes(key_type) == 4) {
-		const uint32_t *keys = (const uint32_t *)d_keys;
-		uint32_t *out = (uint32_t *)d_out_keys;
-		if (d_out_idx) // the index array is where the packed elements are filtered to and sorted
-			return select_impl<uint32_t, NoVal, true, kSelPacked>(c, keys, nullptr, n, k, which, d_out_idx, nullptr, nullptr, key_codec<uint32_t>(key_type), out);
-		if (key_type == kKeyU32) return select_impl<uint32_t, NoVal, true>(c, keys, nullptr, n, k, which, out, nullptr, nullptr);
-		return select_impl<uint32_t, NoVal, true, kSelCodes>(c, keys, nullptr, n, k, which, out, nullptr, nullptr, key_codec<uint32_t>(key_type));
-	}
-	const uint64_t *keys = (const uint64_t *)d_keys;
-	uint64_t *out = (uint64_t *)d_out_keys;
-	if (d_out_idx) return select_impl<uint64_t, uint64_t, true, kSelPos>(c, keys, nullptr, n, k, which, out, d_out_idx, nullptr, key_codec<uint64_t>(key_type));
-	if (key_type == kKeyU64) return select_impl<uint64_t, NoVal, true>(c, keys, nullptr, n, k, which, out, nullptr, nullptr);
-	return select_impl<uint64_t, NoVal, true, kSelCodes>(c, keys, nullptr, n, k, which, out, nullptr, nullptr, key_codec<uint64_t>(key_type));
+	if (int rc = check_key_type(c, key_type)) return rc;
+	return with_key_type(key_type, [&](auto k0, auto raw) {
+		typedef decltype(k0) K;
+		const K *keys = (const K *)d_keys;
+		K *out = (K *)d_out_keys;
+		const KeyCodec<K> codec = key_codec<K>(key_type);
+		if (d_out_idx) {
+			if constexpr (sizeof(K) == 4) // the index array is where the packed elements are filtered to and sorted
+				return select_impl<K, NoVal, true, kSelPacked>(c, keys, nullptr, n, k, which, d_out_idx, nullptr, nullptr, codec, out);
+			else
+				return select_impl<K, uint64_t, true, kSelPos>(c, keys, nullptr, n, k, which, out, d_out_idx, nullptr, codec);
+		}
+		if constexpr (decltype(raw)::value) return select_impl<K, NoVal, true>(c, keys, nullptr, n, k, which, out, nullptr, nullptr);
+		else return select_impl<K, NoVal, true, kSelCodes>(c, keys, nullptr, n, k, which, out, nullptr, nullptr, codec);
+	});
 }
 
 int msd_select_key(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, uint64_t k, int which, void *value)
 {
 	if (!c) return MSD_EINVAL;
-	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
-	if (key_type_bytes(key_type) == 4) {
-		if (key_type == kKeyU32) return select_impl<uint32_t, NoVal, false>(c, (const uint32_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint32_t *)value);
-		return select_impl<uint32_t, NoVal, false, kSelCodes>(c, (const uint32_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint32_t *)value,
-								      key_codec<uint32_t>(key_type));
-	}
-	if (key_type == kKeyU64) return select_impl<uint64_t, NoVal, false>(c, (const uint64_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint64_t *)value);
-	return select_impl<uint64_t, NoVal, false, kSelCodes>(c, (const uint64_t *)d_keys, nullptr, n, k, which, nullptr, nullptr, (uint64_t *)value,
-							      key_codec<uint64_t>(key_type));
+	if (int rc = check_key_type(c, key_type)) return rc;
+	return with_key_type(key_type, [&](auto k0, auto raw) {
+		typedef decltype(k0) K;
+		if constexpr (decltype(raw)::value) return select_impl<K, NoVal, false>(c, (const K *)d_keys, nullptr, n, k, which, nullptr, nullptr, (K *)value);
+		else return select_impl<K, NoVal, false, kSelCodes>(c, (const K *)d_keys, nullptr, n, k, which, nullptr, nullptr, (K *)value, key_codec<K>(key_type));
+	});
 }
 
 } // extern "C"
@@ -2237,16 +2175,15 @@ static bool rows_in_envelope(uint64_t row_len, uint64_t k) { return row_len <= k
 static bool rows_kernel_wins(uint64_t rows, uint64_t row_len) { return rows >= 4 || row_len < (rows << 18); }
 
 template <typename K, bool IDX, int LANES>
-static void rows_launch(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec, K *out,
+static int rows_launch(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec, K *out,
 			uint64_t *out_idx)
 {
 	typedef RowsCfg<LANES> C;
 	constexpr uint64_t groups = C::BLOCK / LANES;
 	const uint64_t per_cu = LANES == 1024 ? 8 : 64; // (workgroups beyond what the chip holds at once walk the rows in a loop)
 	const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * per_cu, (rows + groups - 1) / groups));
-	constexpr size_t lds = RowsLds<K, IDX, LANES>::bytes;
-	hipLaunchKernelGGL((topk_rows_kernel<K, IDX, LANES>), dim3(grid), dim3(C::BLOCK), lds, c->stream, keys, rows,
-			   (uint32_t)row_len, stride, (uint32_t)k, flip, codec, out, out_idx);
+	LAUNCH(c, (topk_rows_kernel<K, IDX, LANES>), grid, C::BLOCK, (RowsLds<K, IDX, LANES>::bytes), keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	return MSD_OK;
 }
 
 // Lanes per row (profiles/topk_rows_sweep.jsonl, the `lanes*` columns): a wave where the row fits its registers; 256 lanes
@@ -2265,16 +2202,13 @@ static int rows_lanes(const msd_ctx *c, uint64_t rows, uint64_t row_len, uint64_
 }
 
 template <typename K, bool IDX>
-static void rows_launch_by_length(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec,
+static int rows_launch_by_length(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec,
 				  K *out, uint64_t *out_idx)
 {
 	const int lanes = rows_lanes(c, rows, row_len, sizeof(K));
-	if (lanes == 64)
-		rows_launch<K, IDX, 64>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-	else if (lanes == 256)
-		rows_launch<K, IDX, 256>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-	else
-		rows_launch<K, IDX, 1024>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	if (lanes == 64) return rows_launch<K, IDX, 64>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	if (lanes == 256) return rows_launch<K, IDX, 256>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+	return rows_launch<K, IDX, 1024>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
 }
 
 template <typename K>
@@ -2284,11 +2218,9 @@ static int rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64_t ro
 	const K flip = which == MSD_LARGEST ? (K)~(K)0 : (K)0;
 	const KeyCodec<K> codec = key_codec<K>(key_type);
 	phase_begin(c);
-	if (out_idx)
-		rows_launch_by_length<K, true>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-	else
-		rows_launch_by_length<K, false>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-	HIPCHK(c, hipGetLastError());
+	if (int rc = out_idx ? rows_launch_by_length<K, true>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx)
+			     : rows_launch_by_length<K, false>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx))
+		return rc;
 	phase_mark(c, "select_rows");
 	phase_end(c);
 	return MSD_OK;
@@ -2301,15 +2233,15 @@ static int rows_looped_path(msd_ctx *c, const char *keys, int key_type, uint64_t
 	const size_t es = (size_t)key_type_bytes(key_type);
 	const size_t row_b = align_up(row_len * es, 256), out_b = align_up(k * es, 256), idx_b = align_up(k * 8, 256);
 	const bool many = rows > 1;
-	const bool stage = ((uintptr_t)keys & 15) || (many && ((stride * es) & 15)) || ((uintptr_t)out & 15) || (many && ((k * es) & 15)) ||
-			   (out_idx && (((uintptr_t)out_idx & 15) || (many && ((k * 8) & 15))));
+	const bool stage = !aligned16(keys) || (many && ((stride * es) & 15)) || !aligned16(out) || (many && ((k * es) & 15)) ||
+			   (out_idx && (!aligned16(out_idx) || (many && ((k * 8) & 15))));
 	if (stage)
 		if (int rc = dev_reserve(c, c->rows_stage, c->rows_stage_bytes, row_b + out_b + idx_b)) return rc;
 	for (uint64_t r = 0; r < rows; ++r) {
 		const char *in = keys + r * stride * es;
 		char *o = out + r * k * es;
 		uint64_t *ix = out_idx ? out_idx + r * k : nullptr;
-		const bool in_st = (uintptr_t)in & 15, o_st = (uintptr_t)o & 15, ix_st = ix && ((uintptr_t)ix & 15);
+		const bool in_st = !aligned16(in), o_st = !aligned16(o), ix_st = ix && !aligned16(ix);
 		if (in_st) HIPCHK(c, hipMemcpyAsync(c->rows_stage, in, row_len * es, hipMemcpyDeviceToDevice, c->stream));
 		char *const so = c->rows_stage + row_b;
 		uint64_t *const sx = (uint64_t *)(c->rows_stage + row_b + out_b);
@@ -2335,7 +2267,7 @@ int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 		  void *d_out_keys, uint64_t *d_out_idx)
 {
 	if (!c) return MSD_EINVAL;
-	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
+	if (int rc = check_key_type(c, key_type)) return rc;
 	if (which != MSD_SMALLEST && which != MSD_LARGEST) return fail(c, MSD_EINVAL, "which must be MSD_SMALLEST or MSD_LARGEST");
 	if (k > row_len) return fail(c, MSD_EINVAL, "k must not exceed row_len");
 	if (row_stride < row_len) return fail(c, MSD_EINVAL, "row_stride must not be smaller than row_len");
@@ -2365,10 +2297,10 @@ int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 	int rc;
 	if (kernel) {
 		c->stats.clear();
-		if (es == 4)
-			rc = rows_kernel_path<uint32_t>(c, (const uint32_t *)d_keys, key_type, rows, row_len, row_stride, k, which, (uint32_t *)d_out_keys, d_out_idx);
-		else
-			rc = rows_kernel_path<uint64_t>(c, (const uint64_t *)d_keys, key_type, rows, row_len, row_stride, k, which, (uint64_t *)d_out_keys, d_out_idx);
+		rc = with_key_type(key_type, [&](auto k0, auto) { // (the 4-byte / 8-byte choice only: the row kernel decodes every type)
+			typedef decltype(k0) K;
+			return rows_kernel_path<K>(c, (const K *)d_keys, key_type, rows, row_len, row_stride, k, which, (K *)d_out_keys, d_out_idx);
+		});
 	} else
 		rc = rows_looped_path(c, (const char *)d_keys, key_type, rows, row_len, row_stride, k, which, (char *)d_out_keys, d_out_idx);
 	if (rc) return rc;
@@ -2391,8 +2323,7 @@ static int check_impl(msd_ctx *c, const K *k, const uint64_t *r, uint64_t n, uin
 	HIPCHK(c, hipMemsetAsync(res, 0, sizeof *res, c->stream));
 	if (n) {
 		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (n + 255) / 256);
-		hipLaunchKernelGGL((check_kernel<K>), dim3(grid), dim3(256), 0, c->stream, k, r, n, res);
-		HIPCHK(c, hipGetLastError());
+		LAUNCH(c, (check_kernel<K>), grid, 256, 0, k, r, n, res);
 	}
 	HIPCHK(c, hipMemcpyAsync(c->pinned, res, sizeof *res, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2413,24 +2344,21 @@ int msd_gen_uniform_u32(msd_ctx *c, uint32_t *k, uint64_t n, uint64_t seed, uint
 {
 	if (!c) return MSD_EINVAL;
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL(gen_uniform_u32_kernel, dim3(gen_grid(c, n)), dim3(256), 0, c->stream, k, n, seed + first);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, gen_uniform_u32_kernel, gen_grid(c, n), 256, 0, k, n, seed + first);
 	return MSD_OK;
 }
 int msd_gen_uniform_u64(msd_ctx *c, uint64_t *k, uint64_t n, uint64_t seed, uint64_t first, int shr)
 {
 	if (!c) return MSD_EINVAL;
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL(gen_uniform_u64_kernel, dim3(gen_grid(c, n)), dim3(256), 0, c->stream, k, n, seed + first, shr);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, gen_uniform_u64_kernel, gen_grid(c, n), 256, 0, k, n, seed + first, shr);
 	return MSD_OK;
 }
 int msd_gen_zipf_u32(msd_ctx *c, uint32_t *k, uint64_t n, uint64_t seed, uint64_t first)
 {
 	if (!c) return MSD_EINVAL;
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL(gen_zipf_u32_kernel, dim3(gen_grid(c, n)), dim3(256), 0, c->stream, k, n, seed + first);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, gen_zipf_u32_kernel, gen_grid(c, n), 256, 0, k, n, seed + first);
 	return MSD_OK;
 }
 int msd_gen_dup_u32(msd_ctx *c, uint32_t *k, uint64_t n, uint64_t seed, uint64_t first, uint64_t distinct)
@@ -2438,8 +2366,7 @@ int msd_gen_dup_u32(msd_ctx *c, uint32_t *k, uint64_t n, uint64_t seed, uint64_t
 	if (!c) return MSD_EINVAL;
 	if (distinct == 0) return fail(c, MSD_EINVAL, "gen_dup: distinct must be positive");
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL(gen_dup_u32_kernel, dim3(gen_grid(c, n)), dim3(256), 0, c->stream, k, n, seed + first, distinct);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, gen_dup_u32_kernel, gen_grid(c, n), 256, 0, k, n, seed + first, distinct);
 	return MSD_OK;
 }
 int msd_gen_mt19937_64(msd_ctx *c, uint64_t *k, uint64_t n, uint64_t seed, int shr)
@@ -2448,16 +2375,14 @@ int msd_gen_mt19937_64(msd_ctx *c, uint64_t *k, uint64_t n, uint64_t seed, int s
 	if (shr < 0 || shr > 63) return fail(c, MSD_EINVAL, "gen_mt19937_64: shift_right must be 0..63");
 	HIPCHK(c, hipSetDevice(c->device));
 	if (n == 0) return MSD_OK;
-	hipLaunchKernelGGL(gen_mt19937_64_kernel, dim3(1), dim3(320), 0, c->stream, k, n, seed, shr);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, gen_mt19937_64_kernel, 1, 320, 0, k, n, seed, shr);
 	return MSD_OK;
 }
 int msd_gen_iota_u64(msd_ctx *c, uint64_t *v, uint64_t n, uint64_t first)
 {
 	if (!c) return MSD_EINVAL;
 	HIPCHK(c, hipSetDevice(c->device));
-	hipLaunchKernelGGL(gen_iota_u64_kernel, dim3(gen_grid(c, n)), dim3(256), 0, c->stream, v, n, first);
-	HIPCHK(c, hipGetLastError());
+	LAUNCH(c, gen_iota_u64_kernel, gen_grid(c, n), 256, 0, v, n, first);
 	return MSD_OK;
 }
 
@@ -2503,10 +2428,8 @@ extern "C" {
 int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, int cus, msd_plan *out)
 {
 	if (!out || cus <= 0 || end_bit < 0 || end_bit > key_bytes * 8) return MSD_EINVAL;
-	if (key_bytes == 4 && val_bytes == 0) return plan_describe<uint32_t, NoVal>(n, end_bit, cus, out);
-	if (key_bytes == 8 && val_bytes == 0) return plan_describe<uint64_t, NoVal>(n, end_bit, cus, out);
-	if (key_bytes == 8 && val_bytes == 8) return plan_describe<uint64_t, uint64_t>(n, end_bit, cus, out);
-	return MSD_EINVAL;
+	const int rc = with_layout(key_bytes, val_bytes, [&](auto k, auto v) { return plan_describe<decltype(k), decltype(v)>(n, end_bit, cus, out); });
+	return rc != kNoLayout ? rc : MSD_EINVAL;
 }
 
 int msd_set_option(msd_ctx *c, const char *name, int64_t value)

@@ -122,6 +122,26 @@ __global__ __launch_bounds__(256) void scan16_kernel(const uint32_t *__restrict_
 	if (p == 255u && c == 255u) base[(size_t)65536 * kS16Chunks] = at; // (one behind the last: a share ends where the next begins)
 }
 
+// what the receiver of those counts needs (msd_bounds_from_counts16):
+// starts[b] = sum of counts[0 .. b), b = 0 .. 65536 (one workgroup)
+__global__ __launch_bounds__(1024) void bounds16_kernel(const uint64_t *__restrict__ counts, uint64_t *__restrict__ bounds)
+{
+	__shared__ uint64_t wsum[16];
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+	uint64_t mine = 0;
+	for (uint32_t j = 0; j < 64; ++j) mine += counts[tid * 64u + j];
+	const uint64_t inc = wave_incl_scan64(mine);
+	if (lane == 63) wsum[w] = inc;
+	__syncthreads();
+	uint64_t at = inc - mine;
+	for (uint32_t ww = 0; ww < w; ++ww) at += wsum[ww];
+	for (uint32_t j = 0; j < 64; ++j) {
+		bounds[tid * 64u + j] = at;
+		at += counts[tid * 64u + j];
+	}
+	if (tid == 1023) bounds[65536] = at;
+}
+
 // Write alignment.  A workgroup's share of a bucket starts wherever the shares before it end -- at any 2-byte address --, and
 // 128-byte blocks written from there straddle three 64-byte granules instead of two (PMC: 2.99 GB written per 2^30 keys
 // where 2.15 are stored; 2.18 GB since -- profiles/r03_pmc_order_low16.txt).  So a ring starts its life as if it already held k values, k = the share's distance from the

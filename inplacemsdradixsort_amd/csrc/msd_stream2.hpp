@@ -45,6 +45,7 @@ template <typename K, typename V> struct Stream2Lds {
 	// cnt, hc, loff, meta : 4 kP ; jobs ; multi 64 ; spare 64 ; tmp 32
 	static constexpr size_t small = (size_t)(4 * kP + JOBS + 64 + 64 + 32) * sizeof(uint32_t);
 	static constexpr size_t bytes = kbuf + vbuf + head + small;
+	static constexpr size_t range_bytes = bytes + kP * sizeof(K); // RANGE: the delimiters behind it
 };
 
 template <typename K, typename V, bool RANGE = false>
@@ -53,9 +54,9 @@ __global__ __launch_bounds__((Stream2Cfg<K, V>::TH), (Stream2Cfg<K, V>::WPE)) vo
 	const Parent *__restrict__ parents, uint8_t *__restrict__ block_map,
 	uint32_t *__restrict__ fb, uint32_t *__restrict__ lo_cnt, uint32_t *__restrict__ lo_off,
 	K *__restrict__ lo_keys, uint64_t *__restrict__ lo_vals, uint32_t *__restrict__ nfull,
-	const K *__restrict__ splitters = nullptr,
+	const K *__restrict__ splitters,
 	// launched behind a direct-placement attempt: runs only if that declined (Counters::direct_uneven != 0)
-	const uint32_t *__restrict__ run_if_nonzero = nullptr)
+	const uint32_t *__restrict__ run_if_nonzero)
 {
 	if (run_if_nonzero && *run_if_nonzero == 0) return;
 	using C = Cfg<K, V>;
@@ -86,7 +87,7 @@ __global__ __launch_bounds__((Stream2Cfg<K, V>::TH), (Stream2Cfg<K, V>::WPE)) vo
 	K *headk = reinterpret_cast<K *>(smem + L::small + (HV ? (size_t)B * sizeof(uint64_t) : 0));
 	K *kbuf = reinterpret_cast<K *>(smem + L::small + L::head);
 	uint64_t *vbuf = reinterpret_cast<uint64_t *>(smem + L::small + L::head + L::kbuf);
-	K *spl = reinterpret_cast<K *>(smem + L::bytes); // RANGE only: the delimiters (the launch adds kP keys of LDS)
+	K *spl = reinterpret_cast<K *>(smem + L::bytes); // RANGE only: the delimiters (the launch asks for L::range_bytes)
 
 	const uint32_t tid = threadIdx.x, lane = tid & 63;
 	const uint32_t junk = (uint32_t)PB + lane; // this lane's junk word behind the buffers

@@ -34,6 +34,15 @@ def kernels(lib, tmp):
             out[cur] = []
         elif cur:
             out[cur].append(re.sub(r"\s*//.*$", "", line.strip()))
+    # A kernel ends at the s_endpgm that padding follows: the s_nop fill up to the next symbol's alignment -- and, behind
+    # the last named kernel, whatever unnamed code comes next -- depends on the neighbours, not on the kernel.
+    for v in out.values():
+        for i in range(len(v) - 1):
+            if v[i] == "s_endpgm" and v[i + 1] == "s_nop 0":
+                del v[i + 1:]
+                break
+        while v and v[-1] == "":
+            v.pop()
     return {k: hashlib.sha1("\n".join(v).encode()).hexdigest() for k, v in out.items() if v}
 
 
