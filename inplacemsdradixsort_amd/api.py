@@ -87,6 +87,42 @@ class MsdContext:
             raise MsdError("keys and rids differ in length")
         self._ok(self._L.msd_sort_pairs_u64_bits(self._h, self._ptr(keys, 8), self._ptr(rids, 8), keys.numel(), end_bit))
 
+    # ---- the sort for every key type and both directions (include/msd_sort_keys_hip.h)
+    REVERSE_TILE = {4: 4092, 8: 2046}   # elements one workgroup of the reversal kernel takes from each end of a range
+
+    def sort_typed(self, keys, descending: bool = False, rids=None) -> None:
+        """Sorts the 1-D contiguous tensor ``keys`` in place in the order of its dtype (float32, int32, float64, int64,
+        uint32, uint64), ascending or ``descending``; floats in IEEE-754 totalOrder as :meth:`topk_typed`, every key
+        bit-exact.  ``rids`` (int64, same length; 64-bit keys only) move with their keys; tuples with equal keys come out
+        in any order."""
+        torch = _torch()
+        kt = self._key_type(keys)
+        es = keys.element_size()
+        if keys.dim() != 1 or (rids is not None and rids.dim() != 1):
+            raise MsdError("sort_typed takes 1-D tensors")
+        order = 1 if descending else 0
+        if rids is not None and es != 8:
+            raise MsdError("tuples have 64-bit keys: float64, int64 or uint64")
+        if rids is not None and (rids.dtype != torch.int64 or rids.numel() != keys.numel()):
+            raise MsdError("rids must be int64 and as many as the keys")
+        kp = self._ptr(keys, es)   # (a tensor that is not on the context's GPU is refused here, before the library is touched)
+        if rids is None:
+            self._ok(self._L.msd_sort_keys(self._h, kp, kt, keys.numel(), order))
+        else:
+            self._ok(self._L.msd_sort_pairs_keys(self._h, kp, kt, self._ptr(rids, 8), keys.numel(), order))
+
+    def reverse(self, t, first: int = 0, count: Optional[int] = None) -> None:
+        """Reverses elements ``[first, first + count)`` (``count`` None: to the end) of the 1-D contiguous tensor ``t`` of
+        4- or 8-byte elements in place; asynchronous."""
+        es = t.element_size()
+        if es not in (4, 8) or t.dim() != 1:
+            raise MsdError("reverse takes a 1-D tensor of 4- or 8-byte elements")
+        count = t.numel() - first if count is None else count
+        if first < 0 or count < 0 or first + count > t.numel():
+            raise MsdError("reverse: the range lies outside the tensor")
+        p = self._ptr(t, es)
+        self._ok(self._L.msd_reverse(self._h, p, es, first, count))
+
     # ---- fine-grained sharding (include/msd_radix_hip.h): top digits before the exchange, open bits after it
     def sort_top(self, keys, begin_bit: int, end_bit: Optional[int] = None, rids=None) -> None:
         """Orders ``keys`` by ``key >> begin_bit`` only (keys that agree above ``begin_bit`` end up adjacent, in any order)."""
@@ -474,7 +510,8 @@ class MsdContext:
                      "small_segments", "count_segments", "big_count_segments", "direct_rounds", "regpart_rounds", "skipped_bits", "bit_skip_restarts", "bit_skip_checked_by_histogram",
                      "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes",
                      "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below",
-                     "topk_rows_kernel_rows", "topk_rows_looped_rows"):
+                     "topk_rows_kernel_rows", "topk_rows_looped_rows",
+                     "sort_keys_split", "sort_keys_reversed"):   # (these two wait for the stream: include/msd_sort_keys_hip.h)
             v = C.c_uint64()
             if self._L.msd_stat(self._h, name.encode(), C.byref(v)) == 0:
                 out[name] = int(v.value)

@@ -6,7 +6,9 @@
 #include "msd_device.hpp"
 #include "msd_select.hpp"
 #include "msd_select_rows.hpp"
+#include "msd_reverse.hpp"
 #include "../../include/msd_radix_hip.h"
+#include "../../include/msd_sort_keys_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -66,6 +68,9 @@ struct msd_ctx {
 	int topk_rows_lanes = 0; // the row kernel's lanes per row: 0 = by row length, 64 / 256 / 1024 = forced where the row fits (A/B comparisons)
 	char *rows_stage = nullptr; // msd_topk_rows, looped path: one row + k output elements for rows that are not 16-byte aligned
 	size_t rows_stage_bytes = 0;
+	uint64_t *fix_plan = nullptr; // msd_sort_keys: the plan words of msd_reverse.hpp (kFixWords), allocated by msd_create
+	int fix_stats = 0;            // "sort_keys_split" / "sort_keys_reversed" of the last typed sort: 0 none yet, 1 fix_split and 0 (nothing was launched), 2 in the plan words
+	uint64_t fix_split = 0;
 };
 
 static int fail(msd_ctx *c, int code, const char *fmt, ...)
@@ -1509,6 +1514,7 @@ int msd_create(msd_ctx **out, int device, void *stream)
 	if (!rc) rc = with_layout(8, 0, attrs);
 	if (!rc) rc = with_layout(8, 8, attrs);
 	if (!rc) rc = set_rows_lds_attrs(c);
+	if (!rc && hipMalloc((void **)&c->fix_plan, kFixWords * sizeof(uint64_t)) != hipSuccess) rc = fail(c, MSD_ENOMEM, "plan words hipMalloc failed");
 	if (rc) {
 		fprintf(stderr, "msd_create: %s\n", c->err.c_str());
 		delete c;
@@ -1528,6 +1534,7 @@ int msd_destroy(msd_ctx *c)
 	if (c->lists) (void)hipFree(c->lists);
 	if (c->sel) (void)hipFree(c->sel);
 	if (c->rows_stage) (void)hipFree(c->rows_stage);
+	if (c->fix_plan) (void)hipFree(c->fix_plan);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	if (c->ev_start) (void)hipEventDestroy(c->ev_start);
 	for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -2164,6 +2171,88 @@ int msd_select_key(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, uin
 
 } // extern "C"
 
+// ---- typed and descending sort: the unsigned sort, then range reversals (msd_reverse.hpp)
+
+template <typename E> static int reverse_launch(msd_ctx *c, E *data, uint64_t n, const uint64_t *plan, uint64_t a, uint64_t b)
+{
+	LAUNCH(c, (reverse_ranges_kernel<E>), (unsigned)rev_grid_for<E>(n), kRevTh, 0, data, plan, a, b);
+	return MSD_OK;
+}
+
+template <typename K> static int sort_keys_impl(msd_ctx *c, K *keys, uint64_t *rids, int key_type, uint64_t n, int order)
+{
+	const int kind = key_type % 3; // 0 unsigned, 1 signed, 2 float
+	int rc;
+	if constexpr (sizeof(K) == 8) // (tuples exist for 64-bit keys only)
+		rc = rids ? sort_impl<K, uint64_t>(c, keys, rids, n, 64, SortJob<K>::whole()) : sort_impl<K, NoVal>(c, keys, nullptr, n, 64, SortJob<K>::whole());
+	else
+		rc = sort_impl<K, NoVal>(c, keys, nullptr, n, 32, SortJob<K>::whole());
+	if (rc) return rc;
+	if (n == 0 || (kind == 0 && order == MSD_ASCENDING)) { // the unsigned sort is the answer
+		c->fix_stats = 1;
+		c->fix_split = kind == 0 ? n : 0;
+		return MSD_OK;
+	}
+	std::vector<std::pair<std::string, double>> phases = c->phase_us;
+	phase_begin(c);
+	LAUNCH(c, (sign_split_kernel<K>), 1, 64, 0, keys, n, kind, order, c->fix_plan);
+	c->fix_stats = 2;
+	if (n >= 2) {
+		// descending needs one stage, ascending two; a stage without work is a launch whose workgroups leave at once
+		for (int stage = 0; stage < (order == MSD_DESCENDING ? 1 : 2); ++stage) {
+			const uint64_t *plan = c->fix_plan + (stage ? kFixStage2 : kFixStage1);
+			if (int r = reverse_launch<K>(c, keys, n, plan, 0, 0)) return r;
+			if (rids)
+				if (int r = reverse_launch<uint64_t>(c, rids, n, plan, 0, 0)) return r;
+		}
+	}
+	phase_mark(c, "sort_fixup");
+	phase_end(c);
+	phases_append(c, phases);
+	c->phase_us = phases;
+	return MSD_OK;
+}
+
+static int sort_keys_entry(msd_ctx *c, void *d_keys, int key_type, uint64_t *d_rids, bool pairs, uint64_t n, int order)
+{
+	if (!c) return MSD_EINVAL;
+	if (int rc = check_key_type(c, key_type)) return rc;
+	if (order != MSD_ASCENDING && order != MSD_DESCENDING) return fail(c, MSD_EINVAL, "order must be MSD_ASCENDING or MSD_DESCENDING");
+	if (pairs && key_type_bytes(key_type) != 8) return fail(c, MSD_EINVAL, "tuples have 64-bit keys (MSD_KEY_U64 / I64 / F64)");
+	if (n && (!d_keys || (pairs && !d_rids))) return fail(c, MSD_EINVAL, "null data pointer");
+	if (!aligned16(d_keys) || (pairs && !aligned16(d_rids))) return fail(c, MSD_EINVAL, "keys/rids must be 16-byte aligned");
+	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large for 32-bit block slots");
+	if (pairs && n && ranges_overlap(d_keys, n * 8, d_rids, n * 8)) return fail(c, MSD_EINVAL, "keys and rids overlap");
+	HIPCHK(c, hipSetDevice(c->device));
+	return with_key_type(key_type, [&](auto k0, auto) {
+		typedef decltype(k0) K;
+		return sort_keys_impl<K>(c, (K *)d_keys, pairs ? d_rids : nullptr, key_type, n, order);
+	});
+}
+
+extern "C" {
+
+int msd_sort_keys(msd_ctx *c, void *d_keys, int key_type, uint64_t n, int order) { return sort_keys_entry(c, d_keys, key_type, nullptr, false, n, order); }
+int msd_sort_pairs_keys(msd_ctx *c, void *d_keys, int key_type, uint64_t *d_rids, uint64_t n, int order)
+{
+	return sort_keys_entry(c, d_keys, key_type, d_rids, true, n, order);
+}
+
+int msd_reverse(msd_ctx *c, void *d_data, int elem_bytes, uint64_t first, uint64_t count)
+{
+	if (!c) return MSD_EINVAL;
+	if (elem_bytes != 4 && elem_bytes != 8) return fail(c, MSD_EINVAL, "elem_bytes must be 4 or 8");
+	if (count && !d_data) return fail(c, MSD_EINVAL, "null data pointer");
+	if ((uintptr_t)d_data % (unsigned)elem_bytes) return fail(c, MSD_EINVAL, "data must be aligned to its element size");
+	if (first + count < first || first + count > UINT64_MAX / (unsigned)elem_bytes) return fail(c, MSD_EINVAL, "first + count overflows");
+	HIPCHK(c, hipSetDevice(c->device));
+	if (count < 2) return MSD_OK;
+	return elem_bytes == 4 ? reverse_launch<uint32_t>(c, (uint32_t *)d_data, count, nullptr, first, first + count)
+			       : reverse_launch<uint64_t>(c, (uint64_t *)d_data, count, nullptr, first, first + count);
+}
+
+} // extern "C"
+
 // ---- per-row top-k (msd_select_rows.hpp)
 
 static bool rows_in_envelope(uint64_t row_len, uint64_t k) { return row_len <= kRowsMaxLen && k <= kRowsMaxK; }
@@ -2495,6 +2584,17 @@ double msd_phase_us(const msd_ctx *c, int i) { return (c && i >= 0 && i < (int)c
 int msd_stat(const msd_ctx *c, const char *name, uint64_t *v)
 {
 	if (!c || !name || !v) return MSD_EINVAL;
+	// the typed sort's two counters live in device words: these two names wait for the context's stream
+	const int fix_word = !strcmp(name, "sort_keys_split") ? kFixSplit : !strcmp(name, "sort_keys_reversed") ? kFixReversed : -1;
+	if (fix_word >= 0) {
+		if (c->fix_stats == 0) return MSD_EINVAL;
+		*v = fix_word == kFixSplit ? c->fix_split : 0;
+		if (c->fix_stats == 1) return MSD_OK;
+		if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+		    hipMemcpy(v, c->fix_plan + fix_word, sizeof *v, hipMemcpyDeviceToHost) != hipSuccess)
+			return MSD_EHIP;
+		return MSD_OK;
+	}
 	for (auto &s : c->stats)
 		if (s.first == name) {
 			*v = s.second;

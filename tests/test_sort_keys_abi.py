@@ -1,0 +1,116 @@
+"""The typed, two-way sort (include/msd_sort_keys_hip.h: msd_sort_keys, msd_sort_pairs_keys, msd_reverse; MsdContext.sort_typed
+/ reverse) without a GPU: the header declares the three functions with the agreed argument lists, the library exports
+them, the binding lists them apart from the surface of msd_radix_hip.h, a null context is refused first, and the Python
+wrapper refuses what never needs a device to be refused."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIGNATURES = {
+    "msd_sort_keys": ["msd_ctx *ctx", "void *d_keys", "int key_type", "uint64_t n", "int order"],
+    "msd_sort_pairs_keys": ["msd_ctx *ctx", "void *d_keys", "int key_type", "uint64_t *d_rids", "uint64_t n", "int order"],
+    "msd_reverse": ["msd_ctx *ctx", "void *d_data", "int elem_bytes", "uint64_t first", "uint64_t count"],
+}
+
+
+def _header():
+    text = open(os.path.join(ROOT, "include", "msd_sort_keys_hip.h")).read()
+    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def test_header_declares_the_three_functions():
+    flat = _header()
+    assert '#include "msd_radix_hip.h"' in flat
+    for name, value in (("MSD_ASCENDING", 0), ("MSD_DESCENDING", 1)):
+        assert re.search(r"\b%s\s*=\s*%d\b" % (name, value), flat), name
+    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
+    assert sorted(declared) == sorted(SIGNATURES), declared
+    for f, want in SIGNATURES.items():
+        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
+        assert m, f
+        assert [a.strip() for a in m.group(1).split(",")] == want, f
+
+
+def test_library_exports_and_binding_lists_them_apart():
+    from inplacemsdradixsort_amd import _build, _lib
+    L = _lib.load()
+    assert sorted(_lib.SORT_KEYS_EXPORTS) == sorted(SIGNATURES)
+    for f in SIGNATURES:
+        assert hasattr(L, f), f
+        assert f not in _lib.EXPORTS, f
+        assert getattr(L, f).argtypes is not None and len(getattr(L, f).argtypes) == len(SIGNATURES[f]), f
+        assert list(getattr(L, f).argtypes) == list(_lib.SORT_KEYS_EXPORTS[f]), f
+    assert any(d.endswith("msd_sort_keys_hip.h") for d in _build.DEPS)
+    assert "msd_reverse.hpp" in _build.DEPS
+
+
+def test_null_context_is_refused_with_every_other_argument_zero():
+    from inplacemsdradixsort_amd import _lib
+    L = _lib.load()
+    for f in SIGNATURES:
+        fn = getattr(L, f)
+        zeros = [t() for t in fn.argtypes[1:]]      # the zero value of each argtype
+        assert fn(None, *zeros) == -1, f
+    # ... and whatever the other arguments are: the context is looked at first
+    assert L.msd_sort_keys(None, None, 99, 10, 99) == -1
+    assert L.msd_sort_pairs_keys(None, None, 0, None, 10, 0) == -1
+    assert L.msd_reverse(None, None, 3, 1 << 63, 1 << 63) == -1
+
+
+def test_stat_names_are_unknown_to_a_null_context():
+    from inplacemsdradixsort_amd import _lib
+    L = _lib.load()
+    v = C.c_uint64(77)
+    for name in (b"sort_keys_split", b"sort_keys_reversed"):
+        assert L.msd_stat(None, name, C.byref(v)) == -1 and v.value == 77
+
+
+def _ctx():
+    from inplacemsdradixsort_amd import MsdContext
+    return MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
+
+
+def test_sort_typed_refuses_before_the_library_is_touched():
+    import torch
+    from inplacemsdradixsort_amd import MsdError
+    ctx = _ctx()
+    for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
+        with pytest.raises(MsdError):                   # a CPU tensor
+            ctx.sort_typed(torch.zeros(8, dtype=dt))
+        with pytest.raises(MsdError):
+            ctx.sort_typed(torch.zeros(8, dtype=dt), descending=True)
+    for dt in (torch.float16, torch.bfloat16, torch.int16, torch.uint8, torch.bool):
+        with pytest.raises(MsdError):                   # a dtype without a key order
+            ctx.sort_typed(torch.zeros(8).to(dt))
+    rids = torch.arange(8, dtype=torch.int64)
+    for dt in (torch.float32, torch.int32):
+        with pytest.raises(MsdError, match="64-bit"):   # 32-bit keys with rids
+            ctx.sort_typed(torch.zeros(8, dtype=dt), rids=rids)
+    with pytest.raises(MsdError):                       # rids of another type or length
+        ctx.sort_typed(torch.zeros(8, dtype=torch.int64), rids=rids.to(torch.int32))
+    with pytest.raises(MsdError):
+        ctx.sort_typed(torch.zeros(8, dtype=torch.float64), rids=rids[:7])
+    with pytest.raises(MsdError):                       # not 1-D
+        ctx.sort_typed(torch.zeros(4, 2))
+
+
+def test_reverse_refuses_before_the_library_is_touched():
+    import torch
+    from inplacemsdradixsort_amd import MsdError
+    ctx = _ctx()
+    for t, args in ((torch.zeros(8), ()),                                       # a CPU tensor
+                    (torch.zeros(8, dtype=torch.int16), ()), (torch.zeros(4, 2), ()),
+                    (torch.zeros(8), (5, 4)), (torch.zeros(8), (-1, 2)), (torch.zeros(8), (9,))):
+        with pytest.raises(MsdError):
+            ctx.reverse(t, *args)
+
+
+def test_stats_names_are_listed():
+    from inplacemsdradixsort_amd import MsdContext
+    src = inspect.getsource(MsdContext.stats)
+    assert "sort_keys_split" in src and "sort_keys_reversed" in src
+    assert MsdContext.REVERSE_TILE == {4: 4092, 8: 2046}
