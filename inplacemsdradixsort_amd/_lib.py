@@ -41,6 +41,12 @@ SORT_KEYS_EXPORTS = {
     "msd_reverse": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64],
 }
 
+# every symbol include/msd_sort_rows_hip.h declares (the same library): name -> argtypes, set in load()
+SORT_ROWS_EXPORTS = {
+    "msd_sort_rows": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p],
+    "msd_sort_rows_limits": [C.c_int, C.c_int, C.POINTER(C.c_uint64)],
+}
+
 # every symbol include/msd_sharded_hip.h declares (libinpmsdradix_hip_rccl.so)
 RCCL_EXPORTS = ["msd_shard_create", "msd_shard_destroy", "msd_shard_set_option", "msd_shard_rank", "msd_shard_world", "msd_shard_last_error",
                 "msd_sort_u32_sharded", "msd_sort_pairs_u64_sharded", "msd_sort_u32_multi"]
@@ -155,6 +161,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.msd_phase_us.restype = C.c_double
     L.msd_stat.argtypes = [_vp, C.c_char_p, _u64p]
     for f, argtypes in SORT_KEYS_EXPORTS.items():
+        getattr(L, f).argtypes = argtypes
+    for f, argtypes in SORT_ROWS_EXPORTS.items():
         getattr(L, f).argtypes = argtypes
     # reference surface (include/msb_64.h)
     L.sort.argtypes = [C.POINTER(_u64p), C.POINTER(_u64p), _u64p, C.c_int, C.c_int, C.c_double,

@@ -472,6 +472,44 @@ class MsdContext:
                                        C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
         return (out, out_indices) if want_idx else out
 
+    # ---- per-row (batched) sort: torch.sort(x, dim=-1)
+    def sort_rows_limits(self, keys_or_key_type, indices: bool = False) -> int:
+        """``max_row_len``: the longest row the one-launch row kernel takes (``msd_sort_rows_limits``); longer rows go
+        through the segment sort."""
+        kt = keys_or_key_type if isinstance(keys_or_key_type, int) else self._key_type(keys_or_key_type)
+        a = C.c_uint64()
+        if self._L.msd_sort_rows_limits(kt, int(indices), C.byref(a)) != 0:
+            raise MsdError(f"error -1: unknown key type {kt}")
+        return int(a.value)
+
+    def sort_rows(self, keys, descending: bool = False, indices: bool = False, out=None, out_indices=None):
+        """Sorts along the LAST dimension: every row in the order of the dtype (floats in IEEE-754 totalOrder, as
+        :meth:`topk_typed`), ascending or ``descending``, bit-exact.  Returns values of the input's shape; with ``indices``
+        (or ``out_indices``) also int64 positions within the row, of the same shape: ``keys[..., positions[..., j]]`` is
+        bit-equal to ``values[..., j]`` and every row's positions are a permutation; the order among equal keys is
+        unspecified.  ``keys`` is never copied: a layout that is not rows of stride 1 with one row stride is refused.
+        ``out=keys`` sorts a contiguous tensor in place; otherwise ``keys`` is not modified.  Inside
+        :meth:`sort_rows_limits` one kernel launch sorts all rows and nothing blocks the host."""
+        torch = _torch()
+        kt = self._key_type(keys)
+        rows, row_len, row_stride = self._rows_layout(keys)
+        want_idx = indices or out_indices is not None
+        shape = tuple(keys.shape)
+        if out is None:
+            out = torch.empty(shape, dtype=keys.dtype, device=keys.device)
+        if want_idx and out_indices is None:
+            out_indices = torch.empty(shape, dtype=torch.int64, device=keys.device)
+        outs = (out, out_indices) if want_idx else (out,)
+        if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
+            raise MsdError("the values have the keys' dtype, the indices are int64")
+        if any(tuple(t.shape) != shape or not t.is_contiguous() for t in outs):
+            raise MsdError(f"an output must be a contiguous tensor of shape {shape}")
+        if any(not t.is_cuda or t.device.index != self.device for t in (keys,) + outs):
+            raise MsdError("the tensors must live on the context's GPU")
+        self._ok(self._L.msd_sort_rows(self._h, C.c_void_p(keys.data_ptr()), kt, rows, row_len, row_stride, 1 if descending else 0,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
+        return (out, out_indices) if want_idx else out
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))
@@ -493,7 +531,9 @@ class MsdContext:
         self._ok(self._L.msd_gen_iota_u64(self._h, self._ptr(vals, 8), vals.numel(), first))
 
     def set_option(self, name: str, value: int) -> None:
-        """Tuning knob of include/msd_radix_hip.h (``direct_mode``, ``direct_min``, ``select_cap``, ``topk_rows_mode``, ...)."""
+        """Tuning knob of include/msd_radix_hip.h (``direct_mode``, ``direct_min``, ``select_cap``, ``topk_rows_mode``, ...) or
+        of include/msd_sort_rows_hip.h: ``sort_rows_mode`` (0 the library chooses, 1 always the segment path, 2 always the
+        row kernel) and ``sort_rows_lanes`` (0 by the shape of the matrix, 64 / 256 / 1024 forced where the row fits)."""
         self._ok(self._L.msd_set_option(self._h, name.encode(), int(value)))
 
     # ---- phase report
@@ -511,6 +551,7 @@ class MsdContext:
                      "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes",
                      "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below",
                      "topk_rows_kernel_rows", "topk_rows_looped_rows",
+                     "sort_rows_kernel_rows", "sort_rows_segment_rows", "sort_rows_lanes",
                      "sort_keys_split", "sort_keys_reversed"):   # (these two wait for the stream: include/msd_sort_keys_hip.h)
             v = C.c_uint64()
             if self._L.msd_stat(self._h, name.encode(), C.byref(v)) == 0:

@@ -7,8 +7,10 @@
 #include "msd_select.hpp"
 #include "msd_select_rows.hpp"
 #include "msd_reverse.hpp"
+#include "msd_sort_rows.hpp"
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
+#include "../../include/msd_sort_rows_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -68,6 +70,8 @@ struct msd_ctx {
 	int topk_rows_lanes = 0; // the row kernel's lanes per row: 0 = by row length, 64 / 256 / 1024 = forced where the row fits (A/B comparisons)
 	char *rows_stage = nullptr; // msd_topk_rows, looped path: one row + k output elements for rows that are not 16-byte aligned
 	size_t rows_stage_bytes = 0;
+	int sort_rows_mode = 0; // msd_sort_rows: 0 = the library chooses, 1 = always the segment path, 2 = always the row kernel
+	int sort_rows_lanes = 0; // the row kernel's lanes per row: 0 = by row length, 64 / 256 / 1024 = forced where the row fits (A/B comparisons)
 	uint64_t *fix_plan = nullptr; // msd_sort_keys: the plan words of msd_reverse.hpp (kFixWords), allocated by msd_create
 	int fix_stats = 0;            // "sort_keys_split" / "sort_keys_reversed" of the last typed sort: 0 none yet, 1 fix_split and 0 (nothing was launched), 2 in the plan words
 	uint64_t fix_split = 0;
@@ -1399,6 +1403,22 @@ static int set_rows_lds_attrs(msd_ctx *c)
 	return rc;
 }
 
+template <typename K, bool IDX> static int set_sort_rows_lds_attrs_for(msd_ctx *c)
+{
+	HIPCHK(c, max_lds(&sort_rows_kernel<K, IDX, 64>, SortRowsLds<K, IDX, 64>::bytes));
+	HIPCHK(c, max_lds(&sort_rows_kernel<K, IDX, 256>, SortRowsLds<K, IDX, 256>::bytes));
+	HIPCHK(c, max_lds(&sort_rows_kernel<K, IDX, 1024>, SortRowsLds<K, IDX, 1024>::bytes));
+	return MSD_OK;
+}
+static int set_sort_rows_lds_attrs(msd_ctx *c)
+{
+	int rc = set_sort_rows_lds_attrs_for<uint32_t, false>(c);
+	if (!rc) rc = set_sort_rows_lds_attrs_for<uint32_t, true>(c);
+	if (!rc) rc = set_sort_rows_lds_attrs_for<uint64_t, false>(c);
+	if (!rc) rc = set_sort_rows_lds_attrs_for<uint64_t, true>(c);
+	return rc;
+}
+
 template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
 {
 	{ // the block permutation is launched with exactly the workgroups the chip holds at once (see chains_grid)
@@ -1514,6 +1534,7 @@ int msd_create(msd_ctx **out, int device, void *stream)
 	if (!rc) rc = with_layout(8, 0, attrs);
 	if (!rc) rc = with_layout(8, 8, attrs);
 	if (!rc) rc = set_rows_lds_attrs(c);
+	if (!rc) rc = set_sort_rows_lds_attrs(c);
 	if (!rc && hipMalloc((void **)&c->fix_plan, kFixWords * sizeof(uint64_t)) != hipSuccess) rc = fail(c, MSD_ENOMEM, "plan words hipMalloc failed");
 	if (rc) {
 		fprintf(stderr, "msd_create: %s\n", c->err.c_str());
@@ -2400,6 +2421,176 @@ int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 
 } // extern "C"
 
+// ---- per-row sort (msd_sort_rows.hpp)
+
+// the envelope: what the 1024-lane shape holds
+static uint64_t sort_rows_max_len(int key_bytes, bool idx)
+{
+	if (key_bytes == 4) return idx ? sort_rows_cap<uint32_t, true, 1024>() : sort_rows_cap<uint32_t, false, 1024>();
+	return idx ? sort_rows_cap<uint64_t, true, 1024>() : sort_rows_cap<uint64_t, false, 1024>();
+}
+
+// Mode 0 inside the envelope: does the row kernel beat the segment path?  (profiles/sort_rows_sweep.jsonl; DESIGN.md section
+// 10.4, "Dispatch".)  32-bit keys: always, by 1.3 to 40 times.  64-bit keys (measured on random bits, where the row kernel
+// needs all eight passes and the segment sort's leaves two): up to 512 keys per row always; with positions not beyond that
+// ([8192, 1024]: 0.41 against 0.20 ms), without them below 4096 keys ([65536, 4096]: 4.9 against 4.1 ms; [16384, 16384]: 6.5
+// against 3.0 ms).  The segment path has its own rules for the outputs (16-byte aligned): where they do not hold, the kernel.
+static bool sort_rows_kernel_wins(uint64_t key_bytes, bool idx, uint64_t row_len, bool segments_possible)
+{
+	if (key_bytes == 4 || !segments_possible) return true;
+	return idx ? row_len <= 512 : row_len < 4096;
+}
+
+template <typename K, bool IDX, int LANES>
+static int sort_rows_launch(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, K flip, KeyCodec<K> codec, K *out, uint64_t *out_idx)
+{
+	typedef SortRowsCfg<K, IDX, LANES> C;
+	constexpr uint64_t groups = C::BLOCK / LANES;
+	// workgroups a CU holds at once (LDS: 160 KiB; registers: one 1024-thread workgroup); the rest of the rows in a loop
+	const uint64_t per_cu = LANES == 1024 ? 1 : LANES == 256 ? 4 : 6;
+	const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * per_cu, (rows + groups - 1) / groups));
+	LAUNCH(c, (sort_rows_kernel<K, IDX, LANES>), grid, C::BLOCK, (SortRowsLds<K, IDX, LANES>::bytes), keys, rows, row_len, stride, flip, codec, out, out_idx);
+	return MSD_OK;
+}
+
+// Lanes per row: the smallest group that holds the row -- a wave up to 512 keys, 256 lanes up to 4096, 1024 lanes beyond
+// (profiles/sort_rows_sweep.jsonl, the `lanes*` columns: at every row length a narrower group that holds the row beats a
+// wider one, by 1.4 to 50 times at 64 MiB).  A forced shape holds where the row fits it.
+template <typename K, bool IDX> static int sort_rows_lanes(const msd_ctx *c, uint64_t row_len)
+{
+	constexpr uint64_t cap64 = sort_rows_cap<K, IDX, 64>(), cap256 = sort_rows_cap<K, IDX, 256>();
+	const int by_shape = row_len <= cap64 ? 64 : row_len <= cap256 ? 256 : 1024;
+	const int forced = c->sort_rows_lanes;
+	if (forced == 0 || (forced == 64 && row_len > cap64) || (forced == 256 && row_len > cap256)) return by_shape;
+	return forced;
+}
+
+template <typename K, bool IDX>
+static int sort_rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t stride, int order, K *out, uint64_t *out_idx)
+{
+	const K flip = order == MSD_DESCENDING ? (K)~(K)0 : (K)0;
+	const KeyCodec<K> codec = key_codec<K>(key_type);
+	const int lanes = sort_rows_lanes<K, IDX>(c, row_len);
+	c->stats.clear();
+	phase_begin(c);
+	int rc;
+	if (lanes == 64)
+		rc = sort_rows_launch<K, IDX, 64>(c, keys, rows, row_len, stride, flip, codec, out, out_idx);
+	else if (lanes == 256)
+		rc = sort_rows_launch<K, IDX, 256>(c, keys, rows, row_len, stride, flip, codec, out, out_idx);
+	else
+		rc = sort_rows_launch<K, IDX, 1024>(c, keys, rows, row_len, stride, flip, codec, out, out_idx);
+	if (rc) return rc;
+	phase_mark(c, "sort_rows");
+	phase_end(c);
+	set_stat(c, "sort_rows_lanes", (uint64_t)lanes);
+	return MSD_OK;
+}
+
+// Rows of any length: codes of the rows, contiguous, in the output; the segment sort on them (host-blocking, as
+// msd_sort_*_segments); keys again.  32-bit keys with positions are sorted as (code << 32 | position) in the index array.
+template <typename K>
+static int sort_rows_segments(msd_ctx *c, const K *keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t stride, int order, K *out, uint64_t *out_idx)
+{
+	const K flip = order == MSD_DESCENDING ? (K)~(K)0 : (K)0;
+	const KeyCodec<K> fcodec = key_codec<K>(key_type).flipped(flip);
+	const uint64_t total = rows * row_len;
+	const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * 16, (total + 255) / 256));
+	std::vector<uint64_t> off(rows + 1);
+	for (uint64_t r = 0; r <= rows; ++r) off[r] = r * row_len;
+	constexpr bool PACK = sizeof(K) == 4;
+	bool packed = false;
+	int rc;
+	if (!out_idx) {
+		LAUNCH(c, (rows_encode_kernel<K, false>), grid, 256, 0, keys, rows, row_len, stride, fcodec, out, out_idx);
+		rc = sort_segments<K, NoVal>(c, out, nullptr, total, off.data(), (uint32_t)rows, (int)sizeof(K) * 8);
+	} else if constexpr (PACK) {
+		packed = true;
+		LAUNCH(c, rows_pack_kernel, grid, 256, 0, keys, rows, row_len, stride, fcodec, out_idx);
+		rc = sort_segments<uint64_t, NoVal>(c, out_idx, nullptr, total, off.data(), (uint32_t)rows, 64);
+	} else {
+		LAUNCH(c, (rows_encode_kernel<K, true>), grid, 256, 0, keys, rows, row_len, stride, fcodec, out, out_idx);
+		rc = sort_segments<uint64_t, uint64_t>(c, out, out_idx, total, off.data(), (uint32_t)rows, 64);
+	}
+	if (rc) return rc; // (the outputs hold codes)
+	std::vector<std::pair<std::string, double>> phases = c->phase_us;
+	phase_begin(c);
+	if (packed) {
+		if constexpr (PACK) LAUNCH(c, rows_unpack_kernel, grid, 256, 0, out_idx, total, fcodec, out);
+	} else
+		LAUNCH(c, (rows_decode_kernel<K>), grid, 256, 0, out, total, fcodec);
+	phase_mark(c, "sort_rows");
+	phase_end(c);
+	phases_append(c, phases);
+	c->phase_us = phases;
+	set_stat(c, "sort_rows_lanes", 0);
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_sort_rows_limits(int key_type, int with_idx, uint64_t *max_row_len)
+{
+	if (!key_type_ok(key_type) || !max_row_len) return MSD_EINVAL;
+	*max_row_len = sort_rows_max_len(key_type_bytes(key_type), with_idx != 0);
+	return MSD_OK;
+}
+
+int msd_sort_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t row_stride, int order, void *d_out_keys,
+		  uint64_t *d_out_idx)
+{
+	if (!c) return MSD_EINVAL;
+	if (int rc = check_key_type(c, key_type)) return rc;
+	if (order != MSD_ASCENDING && order != MSD_DESCENDING) return fail(c, MSD_EINVAL, "order must be MSD_ASCENDING or MSD_DESCENDING");
+	if (row_stride < row_len) return fail(c, MSD_EINVAL, "row_stride must not be smaller than row_len");
+	const uint64_t es = (uint64_t)key_type_bytes(key_type);
+	uint64_t in_elems = 0, out_elems = 0, in_bytes = 0, out_bytes = 0, idx_bytes = 0;
+	if (__builtin_mul_overflow(rows, row_stride, &in_elems) || __builtin_mul_overflow(in_elems, es, &in_bytes))
+		return fail(c, MSD_EINVAL, "rows * row_stride overflows");
+	if (__builtin_mul_overflow(rows, row_len, &out_elems) || __builtin_mul_overflow(out_elems, (uint64_t)8, &idx_bytes))
+		return fail(c, MSD_EINVAL, "rows * row_len overflows");
+	if (rows == 0 || row_len == 0) return MSD_OK;
+	if (!d_keys || !d_out_keys) return fail(c, MSD_EINVAL, "null data pointer");
+	if (((uintptr_t)d_keys & (es - 1)) || ((uintptr_t)d_out_keys & (es - 1)) || ((uintptr_t)d_out_idx & 7))
+		return fail(c, MSD_EINVAL, "input and output buffers must be aligned to their element size");
+	in_bytes = ((rows - 1) * row_stride + row_len) * es; // the input's extent: the padding behind the last row is not part of it
+	out_bytes = out_elems * es;
+	if (!d_out_idx) idx_bytes = 0;
+	const bool in_place = d_out_keys == d_keys && row_stride == row_len;
+	if ((!in_place && ranges_overlap(d_keys, in_bytes, d_out_keys, out_bytes)) || ranges_overlap(d_keys, in_bytes, d_out_idx, idx_bytes) ||
+	    ranges_overlap(d_out_keys, out_bytes, d_out_idx, idx_bytes))
+		return fail(c, MSD_EINVAL, "the outputs must not overlap the input (but d_out_keys == d_keys with row_stride == row_len) or each other");
+	const uint64_t max_len = sort_rows_max_len((int)es, d_out_idx != nullptr);
+	const bool inside = row_len <= max_len;
+	if (c->sort_rows_mode == 2 && !inside)
+		return fail(c, MSD_EINVAL, "sort_rows_mode 2: the row kernel takes row_len <= %llu for this key type", (unsigned long long)max_len);
+	const bool seg_ok = aligned16(d_out_keys) && (!d_out_idx || aligned16(d_out_idx)) && rows < ((uint64_t)1 << 32) && out_elems < ((uint64_t)1 << 36);
+	const bool kernel = inside && (c->sort_rows_mode == 2 || (c->sort_rows_mode == 0 && sort_rows_kernel_wins(es, d_out_idx != nullptr, row_len, seg_ok)));
+	if (!kernel) {
+		if (!aligned16(d_out_keys) || (d_out_idx && !aligned16(d_out_idx)))
+			return fail(c, MSD_EINVAL, "rows beyond the row kernel (row_len > %llu, or sort_rows_mode 1) go through the segment sort, whose rule this is: "
+						   "d_out_keys and d_out_idx must be 16-byte aligned",
+				    (unsigned long long)max_len);
+		if (rows >= ((uint64_t)1 << 32) || out_elems >= ((uint64_t)1 << 36))
+			return fail(c, MSD_EINVAL, "the segment sort takes fewer than 2^32 rows and 2^36 elements");
+	}
+	HIPCHK(c, hipSetDevice(c->device));
+	const int rc = with_key_type(key_type, [&](auto k0, auto) { // (the 4-byte / 8-byte choice only: the codec is two run-time words)
+		typedef decltype(k0) K;
+		const K *in = (const K *)d_keys;
+		K *out = (K *)d_out_keys;
+		if (!kernel) return sort_rows_segments<K>(c, in, key_type, rows, row_len, row_stride, order, out, d_out_idx);
+		return d_out_idx ? sort_rows_kernel_path<K, true>(c, in, key_type, rows, row_len, row_stride, order, out, d_out_idx)
+				 : sort_rows_kernel_path<K, false>(c, in, key_type, rows, row_len, row_stride, order, out, d_out_idx);
+	});
+	if (rc) return rc;
+	set_stat(c, "sort_rows_kernel_rows", kernel ? rows : 0);
+	set_stat(c, "sort_rows_segment_rows", kernel ? 0 : rows);
+	return MSD_OK;
+}
+
+} // extern "C"
+
 template <typename K>
 static int check_impl(msd_ctx *c, const K *k, const uint64_t *r, uint64_t n, uint64_t *viol, uint64_t *sum, uint64_t *xr)
 {
@@ -2551,6 +2742,12 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 	} else if (!strcmp(name, "topk_rows_lanes")) {
 		if (value != 0 && value != 64 && value != 256 && value != 1024) return fail(c, MSD_EINVAL, "topk_rows_lanes must be 0, 64, 256 or 1024");
 		c->topk_rows_lanes = (int)value;
+	} else if (!strcmp(name, "sort_rows_mode")) {
+		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "sort_rows_mode must be 0, 1 or 2");
+		c->sort_rows_mode = (int)value;
+	} else if (!strcmp(name, "sort_rows_lanes")) {
+		if (value != 0 && value != 64 && value != 256 && value != 1024) return fail(c, MSD_EINVAL, "sort_rows_lanes must be 0, 64, 256 or 1024");
+		c->sort_rows_lanes = (int)value;
 	} else if (!strcmp(name, "direct_min_parent")) {
 		if (value < 1) return fail(c, MSD_EINVAL, "direct_min_parent must be positive");
 		c->direct_min_parent = (uint64_t)value;
