@@ -510,6 +510,88 @@ class MsdContext:
                                        C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
         return (out, out_indices) if want_idx else out
 
+    # ---- run-length encode and unique (include/msd_runs_hip.h)
+    def run_encode_limits(self, elem_bytes: int) -> Tuple[int, int]:
+        """``(tile, scan_tile)``: the elements one workgroup takes per tile for that element width, and how many tile
+        counts one workgroup of the tile-count scan takes at once (``msd_run_encode_limits``)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        if self._L.msd_run_encode_limits(int(elem_bytes), C.byref(a), C.byref(b)) != 0:
+            raise MsdError(f"error -1: elem_bytes must be 4 or 8, not {elem_bytes}")
+        return int(a.value), int(b.value)
+
+    def run_encode(self, t, cap: Optional[int] = None, values: bool = True, starts: bool = True, inverse: bool = False, positions=None):
+        """Run-length encodes the 1-D contiguous tensor ``t`` of 4- or 8-byte elements (``torch.unique_consecutive``; on a
+        sorted tensor the runs are the groups of equal keys).  A run is a maximal stretch of consecutive elements with
+        equal BIT PATTERNS: -0.0 and +0.0 are two values, NaNs with equal sign and payload are one value, NaNs with
+        different payloads differ -- unlike ``torch.unique``, which keeps every NaN apart.
+
+        Returns ``(num_runs, values, starts, inverse)``; an output that was not asked for is ``None``.  ``num_runs`` is a
+        one-element int64 tensor on the device: the true number of runs m, also when m > ``cap`` (default
+        ``t.numel()``).  ``values`` (``cap`` elements, the dtype of ``t``) holds the value of run j and ``starts``
+        (``cap + 1`` int64) the index of its first element, for j < min(m, cap); ``starts[min(m, cap)]`` closes the last
+        stored run (``t.numel()`` if m <= cap), so counts are ``starts[1:] - starts[:-1]``; the rest of both is not
+        written.  ``inverse`` (``t.numel()`` int64) holds the run number of every element; with ``positions`` (int64, a
+        permutation of the indices as :meth:`sort_rows` or :meth:`sort_typed` with rids produce it)
+        ``inverse[positions[i]]`` is the run of element i.  Nothing waits on the host."""
+        torch = _torch()
+        if t.dim() != 1 or not t.is_contiguous():
+            raise MsdError("run_encode takes a 1-D contiguous tensor")
+        es = t.element_size()
+        if es not in (4, 8):
+            raise MsdError(f"run_encode takes 4- or 8-byte elements, not {t.dtype}")
+        n = t.numel()
+        if positions is not None:
+            if positions.dtype != torch.int64 or positions.dim() != 1 or positions.numel() != n or not positions.is_contiguous():
+                raise MsdError("positions must be a contiguous int64 tensor, as many as the elements")
+            if not inverse:
+                raise MsdError("positions without inverse")
+        cap = n if cap is None else int(cap)
+        if cap < 0:
+            raise MsdError("cap must not be negative")
+        if any(not x.is_cuda or x.device.index != self.device for x in (t, positions) if x is not None):
+            raise MsdError("the tensors must live on the context's GPU")
+        pp = C.c_void_p(positions.data_ptr() if positions is not None else 0)
+        num = torch.empty(1, dtype=torch.int64, device=t.device)
+        vals = torch.empty(cap, dtype=t.dtype, device=t.device) if values else None
+        st = torch.empty(cap + 1, dtype=torch.int64, device=t.device) if starts else None
+        inv = torch.empty(n, dtype=torch.int64, device=t.device) if inverse else None
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+        self._ok(self._L.msd_run_encode(self._h, C.c_void_p(t.data_ptr()), es, n, cap, ptr(vals), ptr(st), pp, ptr(inv), ptr(num)))
+        return num, vals, st, inv
+
+    def unique(self, keys, return_inverse: bool = False, return_counts: bool = False):
+        """``torch.unique(keys, sorted=True, return_inverse=..., return_counts=...)`` for a 1-D tensor of float32, int32,
+        float64, int64, uint32 or uint64: the distinct values in the dtype's order, then the inverse (int64:
+        ``values[inverse]`` is ``keys``) and the counts (int64) where asked for.  Floats are ordered by IEEE-754
+        totalOrder and told apart by their BITS, as everywhere in this library: -0.0 and +0.0 are two values and NaNs
+        with equal bits are one, where ``torch.unique`` merges the zeros and keeps every NaN apart.  ``keys`` is not
+        modified.  One host wait beyond the sort's own: the number of distinct values sizes the results."""
+        torch = _torch()
+        self._key_type(keys)   # (a dtype without a key order is refused here)
+        if keys.dim() != 1 or not keys.is_contiguous():
+            raise MsdError("unique takes a 1-D contiguous tensor")
+        if not keys.is_cuda or keys.device.index != self.device:
+            raise MsdError("tensor must live on the context's GPU")
+        n = keys.numel()
+        positions = None
+        if not return_inverse:
+            s = keys.clone()
+            self.sort_typed(s)
+        elif keys.element_size() == 4:
+            s, positions = self.sort_rows(keys, indices=True)
+        else:
+            s = keys.clone()
+            positions = torch.arange(n, dtype=torch.int64, device=keys.device)
+            self.sort_typed(s, rids=positions)
+        num, vals, st, inv = self.run_encode(s, starts=return_counts, inverse=return_inverse, positions=positions)
+        m = int(num.item())
+        out = (vals[:m],)
+        if return_inverse:
+            out += (inv,)
+        if return_counts:
+            out += (st[1:m + 1] - st[:m],)
+        return out if len(out) > 1 else out[0]
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))

@@ -8,9 +8,11 @@
 #include "msd_select_rows.hpp"
 #include "msd_reverse.hpp"
 #include "msd_sort_rows.hpp"
+#include "msd_runs.hpp"
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
 #include "../../include/msd_sort_rows_hip.h"
+#include "../../include/msd_runs_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -2587,6 +2589,97 @@ int msd_sort_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 	set_stat(c, "sort_rows_kernel_rows", kernel ? rows : 0);
 	set_stat(c, "sort_rows_segment_rows", kernel ? 0 : rows);
 	return MSD_OK;
+}
+
+} // extern "C"
+
+// ---- run-length encode (msd_runs.hpp)
+
+template <typename E, bool INV, bool POS>
+static int run_write_launch(msd_ctx *c, const E *data, uint64_t n, uint64_t cap, uint64_t tiles, const uint64_t *tile_base, const uint64_t *piece_base, E *values,
+			    uint64_t *starts, const uint64_t *positions, uint64_t *inverse)
+{
+	LAUNCH(c, (runs_write_kernel<E, INV, POS>), (unsigned)tiles, kRunsTh, 0, data, n, cap, tile_base, piece_base, values, starts, positions, inverse);
+	return MSD_OK;
+}
+
+// Count, scan, write: four launches one behind the other on the stream, nothing read back.  The scratch -- one word per
+// tile, one per scan piece -- is the slab's, like a sort round's: the next call on the context overwrites it, in stream order.
+template <typename E>
+static int run_encode_impl(msd_ctx *c, const E *data, uint64_t n, uint64_t cap, E *values, uint64_t *starts, const uint64_t *positions, uint64_t *inverse,
+			   uint64_t *num_runs)
+{
+	if (n == 0) {
+		phase_begin(c);
+		LAUNCH(c, runs_empty_kernel, 1, 64, 0, num_runs, starts);
+		phase_mark(c, "run_encode");
+		phase_end(c);
+		return MSD_OK;
+	}
+	const uint64_t tiles = runs_tiles(data, n), pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile; // (tiles <= 2^25 + 1)
+	uint64_t *tile_counts = nullptr, *piece_sums = nullptr;
+	if (int rc = slab_carve(c, [&](Bump &b) {
+		    tile_counts = b.take<uint64_t>(tiles);
+		    piece_sums = b.take<uint64_t>(pieces);
+	    }))
+		return rc;
+	phase_begin(c);
+	LAUNCH(c, (runs_count_kernel<E>), (unsigned)tiles, kRunsTh, 0, data, n, tile_counts);
+	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
+	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_runs);
+	int rc = MSD_OK;
+	if (inverse && positions)
+		rc = run_write_launch<E, true, true>(c, data, n, cap, tiles, tile_counts, piece_sums, values, starts, positions, inverse);
+	else if (inverse)
+		rc = run_write_launch<E, true, false>(c, data, n, cap, tiles, tile_counts, piece_sums, values, starts, positions, inverse);
+	else if (values || starts)
+		rc = run_write_launch<E, false, false>(c, data, n, cap, tiles, tile_counts, piece_sums, values, starts, positions, inverse);
+	if (rc) return rc;
+	phase_mark(c, "run_encode");
+	phase_end(c);
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_run_encode_limits(int elem_bytes, uint64_t *tile, uint64_t *scan_tile)
+{
+	if ((elem_bytes != 4 && elem_bytes != 8) || !tile || !scan_tile) return MSD_EINVAL;
+	*tile = elem_bytes == 4 ? RunsCfg<uint32_t>::TILE : RunsCfg<uint64_t>::TILE;
+	*scan_tile = kRunsScanTile;
+	return MSD_OK;
+}
+
+int msd_run_encode(msd_ctx *c, const void *d_data, int elem_bytes, uint64_t n, uint64_t cap, void *d_values, uint64_t *d_starts, const uint64_t *d_positions,
+		   uint64_t *d_inverse, uint64_t *d_num_runs)
+{
+	if (!c) return MSD_EINVAL;
+	if (elem_bytes != 4 && elem_bytes != 8) return fail(c, MSD_EINVAL, "elem_bytes must be 4 or 8");
+	if (!d_num_runs) return fail(c, MSD_EINVAL, "d_num_runs is required");
+	if (n && !d_data) return fail(c, MSD_EINVAL, "null data pointer");
+	const uintptr_t es = (uintptr_t)elem_bytes;
+	if ((uintptr_t)d_data % es || (uintptr_t)d_values % es || ((uintptr_t)d_starts | (uintptr_t)d_positions | (uintptr_t)d_inverse | (uintptr_t)d_num_runs) % 8)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_data, d_values: elem_bytes; the others: 8)");
+	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
+	if (d_positions && !d_inverse) return fail(c, MSD_EINVAL, "d_positions without d_inverse");
+	// the extents: inputs first, then the outputs; at most min(cap, n) runs are stored
+	const uint64_t stored = std::min(cap, n);
+	const struct { const void *p; size_t bytes; } buf[6] = {
+		{ d_data, (size_t)(n * es) },
+		{ d_positions, d_positions ? (size_t)(n * 8) : 0 },
+		{ d_values, d_values ? (size_t)(stored * es) : 0 },
+		{ d_starts, d_starts ? (size_t)((stored + 1) * 8) : 0 },
+		{ d_inverse, d_inverse ? (size_t)(n * 8) : 0 },
+		{ d_num_runs, 8 },
+	};
+	for (int o = 2; o < 6; ++o)
+		for (int i = 0; i < o; ++i)
+			if (ranges_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes))
+				return fail(c, MSD_EINVAL, "the outputs must not overlap the input, d_positions or each other (in-place compaction is not offered)");
+	HIPCHK(c, hipSetDevice(c->device));
+	if (elem_bytes == 4)
+		return run_encode_impl<uint32_t>(c, (const uint32_t *)d_data, n, cap, (uint32_t *)d_values, d_starts, d_positions, d_inverse, d_num_runs);
+	return run_encode_impl<uint64_t>(c, (const uint64_t *)d_data, n, cap, (uint64_t *)d_values, d_starts, d_positions, d_inverse, d_num_runs);
 }
 
 } // extern "C"
