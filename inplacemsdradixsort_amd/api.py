@@ -592,6 +592,96 @@ class MsdContext:
             out += (st[1:m + 1] - st[:m],)
         return out if len(out) > 1 else out[0]
 
+    # ---- reduce-by-key over runs and group-by (include/msd_reduce_hip.h)
+    REDUCE_OPS = {"sum": 0, "min": 1, "max": 2}   # MSD_REDUCE_* of include/msd_reduce_hip.h
+
+    def reduce_runs_limits(self, key_bytes: int) -> Tuple[int, int]:
+        """``(tile, scan_tile)`` of ``msd_reduce_runs_limits``: the geometry of :meth:`run_encode_limits`."""
+        a, b = C.c_uint64(), C.c_uint64()
+        if self._L.msd_reduce_runs_limits(int(key_bytes), C.byref(a), C.byref(b)) != 0:
+            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
+        return int(a.value), int(b.value)
+
+    def reduce_runs(self, keys, vals, op: str = "sum", positions=None, cap: Optional[int] = None):
+        """One number per run of ``keys``: the ``"sum"``, ``"min"`` or ``"max"`` of the values of its elements.  The runs
+        are those of :meth:`run_encode` on the same tensor (maximal stretches of equal BIT patterns; 4- or 8-byte
+        elements), so run j here is run j there.  The value of element i is ``vals[i]``, or ``vals[positions[i]]`` with
+        ``positions`` (int64, as :meth:`sort_rows` or :meth:`sort_typed` with rids produce them): the group-by case,
+        where the keys were sorted and the value column stayed where it was.  ``vals`` is float32, int32, float64,
+        int64, uint32 or uint64, whatever the keys are.  All tensors are 1-D and contiguous.
+
+        Returns ``(num_runs, out)``.  ``num_runs`` is a one-element int64 tensor on the device: the true number of runs
+        m, also when m > ``cap`` (default ``keys.numel()``).  ``out`` has ``cap`` elements, of which the first
+        min(m, cap) are written.  A sum is int64 for integer values (uint64 for unsigned ones where torch has that
+        dtype), exact modulo 2^64, and float64 for float values: summed in double, without atomics and in an order
+        that the sizes and addresses alone fix, so the same call gives the same bits every time -- but not the bits of
+        a sequential sum.  ``min`` / ``max`` have the values' dtype and are bit-exact, floats in IEEE-754 totalOrder
+        as everywhere in this library: -0.0 is below +0.0, a NaN is the maximum of its run (the minimum, if its sign
+        bit is set), unlike ``torch.amax`` / ``torch.amin``, which propagate any NaN.  Nothing waits on the host."""
+        torch = _torch()
+        if op not in self.REDUCE_OPS:
+            raise MsdError(f"op must be one of {sorted(self.REDUCE_OPS)}, not {op!r}")
+        if keys.dim() != 1 or vals.dim() != 1 or not keys.is_contiguous() or not vals.is_contiguous():
+            raise MsdError("reduce_runs takes 1-D contiguous tensors")
+        ks = keys.element_size()
+        if ks not in (4, 8):
+            raise MsdError(f"reduce_runs takes 4- or 8-byte keys, not {keys.dtype}")
+        vt = self._key_type(vals)   # (a value dtype without an order is refused here)
+        n = keys.numel()
+        if vals.numel() != n:
+            raise MsdError("keys and vals differ in length")
+        if positions is not None and (positions.dtype != torch.int64 or positions.dim() != 1 or positions.numel() != n or not positions.is_contiguous()):
+            raise MsdError("positions must be a contiguous int64 tensor, as many as the elements")
+        cap = n if cap is None else int(cap)
+        if cap < 0:
+            raise MsdError("cap must not be negative")
+        if any(not x.is_cuda or x.device.index != self.device for x in (keys, vals, positions) if x is not None):
+            raise MsdError("the tensors must live on the context's GPU")
+        if op != "sum":
+            odt = vals.dtype
+        elif vt in (self.KEY_F32, self.KEY_F64):
+            odt = torch.float64
+        elif vt in (self.KEY_U32, self.KEY_U64) and hasattr(torch, "uint64"):
+            odt = torch.uint64
+        else:
+            odt = torch.int64
+        num = torch.empty(1, dtype=torch.int64, device=keys.device)
+        out = torch.empty(cap, dtype=odt, device=keys.device)
+        self._ok(self._L.msd_reduce_runs(self._h, C.c_void_p(keys.data_ptr()), ks, n, C.c_void_p(vals.data_ptr()), vt,
+                                         C.c_void_p(positions.data_ptr() if positions is not None else 0), self.REDUCE_OPS[op], cap,
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(num.data_ptr())))
+        return num, out
+
+    def group_reduce(self, keys, vals, op: str = "sum"):
+        """Group-by: ``(distinct_keys, aggregates)`` for UNSORTED 1-D ``keys`` of float32, int32, float64, int64, uint32
+        or uint64 -- the distinct keys in the dtype's order (floats in totalOrder and told apart by their bits, as
+        :meth:`unique`) and per distinct key the ``"sum"``, ``"min"`` or ``"max"`` of the ``vals`` of its elements, with
+        the dtypes and the rules of :meth:`reduce_runs`.  The keys are sorted with positions, the value column is read
+        through them where it lies.  ``keys`` and ``vals`` are not modified.  One host wait beyond the sort's own: the
+        number of distinct keys sizes the results."""
+        torch = _torch()
+        if op not in self.REDUCE_OPS:
+            raise MsdError(f"op must be one of {sorted(self.REDUCE_OPS)}, not {op!r}")
+        self._key_type(keys)
+        self._key_type(vals)
+        if keys.dim() != 1 or vals.dim() != 1 or not keys.is_contiguous() or not vals.is_contiguous():
+            raise MsdError("group_reduce takes 1-D contiguous tensors")
+        n = keys.numel()
+        if vals.numel() != n:
+            raise MsdError("keys and vals differ in length")
+        if any(not x.is_cuda or x.device.index != self.device for x in (keys, vals)):
+            raise MsdError("the tensors must live on the context's GPU")
+        if keys.element_size() == 4:
+            s, positions = self.sort_rows(keys, indices=True)
+        else:
+            s = keys.clone()
+            positions = torch.arange(n, dtype=torch.int64, device=keys.device)
+            self.sort_typed(s, rids=positions)
+        _, distinct, _, _ = self.run_encode(s, starts=False)
+        num, out = self.reduce_runs(s, vals, op=op, positions=positions)
+        m = int(num.item())
+        return distinct[:m], out[:m]
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))

@@ -9,10 +9,12 @@
 #include "msd_reverse.hpp"
 #include "msd_sort_rows.hpp"
 #include "msd_runs.hpp"
+#include "msd_reduce.hpp"
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
 #include "../../include/msd_sort_rows_hip.h"
 #include "../../include/msd_runs_hip.h"
+#include "../../include/msd_reduce_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -2680,6 +2682,111 @@ int msd_run_encode(msd_ctx *c, const void *d_data, int elem_bytes, uint64_t n, u
 	if (elem_bytes == 4)
 		return run_encode_impl<uint32_t>(c, (const uint32_t *)d_data, n, cap, (uint32_t *)d_values, d_starts, d_positions, d_inverse, d_num_runs);
 	return run_encode_impl<uint64_t>(c, (const uint64_t *)d_data, n, cap, (uint64_t *)d_values, d_starts, d_positions, d_inverse, d_num_runs);
+}
+
+} // extern "C"
+
+// ---- reduce-by-key over runs (msd_reduce.hpp)
+
+// Count, scan, reduce, carry, apply: seven launches one behind the other on the stream, nothing read back.  The scratch --
+// per tile the count, the lead and the heads, and the same per scan piece -- is the slab's, as for msd_run_encode.
+template <typename E, typename P>
+static int reduce_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *vals, const uint64_t *positions, uint64_t cap, void *out, uint64_t *num_runs,
+			    KeyCodec<typename P::R::O> cd)
+{
+	typedef typename P::R R;
+	if (n == 0) {
+		phase_begin(c);
+		LAUNCH(c, runs_empty_kernel, 1, 64, 0, num_runs, nullptr);
+		phase_mark(c, "reduce_runs");
+		phase_end(c);
+		return MSD_OK;
+	}
+	const uint64_t tiles = runs_tiles(keys, n), pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile; // (tiles <= 2^25 + 1)
+	uint64_t *tile_counts = nullptr, *piece_sums = nullptr;
+	ReduceRecord rec{ nullptr, nullptr }, piece{ nullptr, nullptr };
+	if (int rc = slab_carve(c, [&](Bump &b) {
+		    tile_counts = b.take<uint64_t>(tiles);
+		    piece_sums = b.take<uint64_t>(pieces);
+		    rec.lead = b.take<uint64_t>(tiles);
+		    rec.heads = b.take<uint32_t>(tiles);
+		    piece.lead = b.take<uint64_t>(pieces);
+		    piece.heads = b.take<uint32_t>(pieces);
+	    }))
+		return rc;
+	phase_begin(c);
+	LAUNCH(c, (runs_count_kernel<E>), (unsigned)tiles, kRunsTh, 0, keys, n, tile_counts);
+	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
+	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_runs);
+	if (cap) { // (cap == 0 only counts)
+		if (positions)
+			LAUNCH(c, (reduce_tile_kernel<E, P, true>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, positions, cap, tile_counts, piece_sums, cd, out, rec);
+		else
+			LAUNCH(c, (reduce_tile_kernel<E, P, false>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, positions, cap, tile_counts, piece_sums, cd, out, rec);
+		LAUNCH(c, (reduce_carry_pieces_kernel<R>), (unsigned)pieces, kRunsScanTh, 0, rec, tiles, cd, piece);
+		LAUNCH(c, (reduce_carry_top_kernel<R>), 1, kRunsScanTh, 0, piece, pieces, cd);
+		LAUNCH(c, (reduce_apply_kernel<R>), (unsigned)((tiles + 255) / 256), 256, 0, rec, piece, tiles, cap, tile_counts, piece_sums, cd, out);
+	}
+	phase_mark(c, "reduce_runs");
+	phase_end(c);
+	return MSD_OK;
+}
+
+template <typename E>
+static int reduce_runs_typed(msd_ctx *c, const E *keys, uint64_t n, const void *vals, int val_type, const uint64_t *positions, int op, uint64_t cap, void *out,
+			     uint64_t *num_runs)
+{
+	const KeyCodec<uint64_t> none{ 0, 0 };
+	if (op == MSD_REDUCE_SUM) {
+		switch (val_type) {
+		case kKeyU32: return reduce_runs_impl<E, SumU32>(c, keys, n, vals, positions, cap, out, num_runs, none);
+		case kKeyI32: return reduce_runs_impl<E, SumI32>(c, keys, n, vals, positions, cap, out, num_runs, none);
+		case kKeyF32: return reduce_runs_impl<E, SumF32>(c, keys, n, vals, positions, cap, out, num_runs, none);
+		case kKeyF64: return reduce_runs_impl<E, SumF64>(c, keys, n, vals, positions, cap, out, num_runs, none);
+		default: return reduce_runs_impl<E, SumX64>(c, keys, n, vals, positions, cap, out, num_runs, none); // (U64, I64: the same sum modulo 2^64)
+		}
+	}
+	// a maximum is the minimum of the complemented codes
+	const bool mx = op == MSD_REDUCE_MAX;
+	if (key_type_bytes(val_type) == 4)
+		return reduce_runs_impl<E, MinOf<uint32_t>>(c, keys, n, vals, positions, cap, out, num_runs, key_codec<uint32_t>(val_type).flipped(mx ? ~0u : 0u));
+	return reduce_runs_impl<E, MinOf<uint64_t>>(c, keys, n, vals, positions, cap, out, num_runs, key_codec<uint64_t>(val_type).flipped(mx ? ~0ull : 0ull));
+}
+
+extern "C" {
+
+int msd_reduce_runs_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile) { return msd_run_encode_limits(key_bytes, tile, scan_tile); }
+
+int msd_reduce_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, const void *d_vals, int val_type, const uint64_t *d_positions, int op, uint64_t cap,
+		    void *d_out, uint64_t *d_num_runs)
+{
+	if (!c) return MSD_EINVAL;
+	if (key_bytes != 4 && key_bytes != 8) return fail(c, MSD_EINVAL, "key_bytes must be 4 or 8");
+	if (val_type < 0 || val_type >= kKeyTypes) return fail(c, MSD_EINVAL, "unknown val_type");
+	if (op != MSD_REDUCE_SUM && op != MSD_REDUCE_MIN && op != MSD_REDUCE_MAX) return fail(c, MSD_EINVAL, "unknown op");
+	if (!d_num_runs) return fail(c, MSD_EINVAL, "d_num_runs is required");
+	if (n && (!d_keys || !d_vals)) return fail(c, MSD_EINVAL, "null keys or values pointer");
+	if (n && cap && !d_out) return fail(c, MSD_EINVAL, "null d_out pointer");
+	const uintptr_t ks = (uintptr_t)key_bytes, vs = (uintptr_t)key_type_bytes(val_type), os = op == MSD_REDUCE_SUM ? 8 : vs;
+	if ((uintptr_t)d_keys % ks || (uintptr_t)d_vals % vs || (uintptr_t)d_out % os || ((uintptr_t)d_positions | (uintptr_t)d_num_runs) % 8)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_keys: key_bytes; d_vals: the value's; d_out: 8 for a sum, else the value's; the others: 8)");
+	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
+	// the extents: inputs first, then the outputs; at most min(cap, n) runs are stored
+	const uint64_t stored = std::min(cap, n);
+	const struct { const void *p; size_t bytes; } buf[5] = {
+		{ d_keys, (size_t)(n * ks) },
+		{ d_vals, (size_t)(n * vs) },
+		{ d_positions, d_positions ? (size_t)(n * 8) : 0 },
+		{ d_out, d_out ? (size_t)(stored * os) : 0 },
+		{ d_num_runs, 8 },
+	};
+	for (int o = 3; o < 5; ++o)
+		for (int i = 0; i < o; ++i)
+			if (ranges_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes))
+				return fail(c, MSD_EINVAL, "d_out and d_num_runs must not overlap the keys, the values, d_positions or each other");
+	HIPCHK(c, hipSetDevice(c->device));
+	if (key_bytes == 4) return reduce_runs_typed<uint32_t>(c, (const uint32_t *)d_keys, n, d_vals, val_type, d_positions, op, cap, d_out, d_num_runs);
+	return reduce_runs_typed<uint64_t>(c, (const uint64_t *)d_keys, n, d_vals, val_type, d_positions, op, cap, d_out, d_num_runs);
 }
 
 } // extern "C"
