@@ -682,6 +682,80 @@ class MsdContext:
         m = int(num.item())
         return distinct[:m], out[:m]
 
+    # ---- sorted search (include/msd_search_hip.h)
+    def search_sorted_limits(self, key_bytes: int) -> Tuple[int, int]:
+        """``(tile, direct_tile)`` of ``msd_search_sorted_limits``: the elements (keys plus needles together) one
+        workgroup of the merge path takes for that key width, and the needles one workgroup of the direct path takes."""
+        a, b = C.c_uint64(), C.c_uint64()
+        if self._L.msd_search_sorted_limits(int(key_bytes), C.byref(a), C.byref(b)) != 0:
+            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
+        return int(a.value), int(b.value)
+
+    def searchsorted(self, sorted_keys, needles, right: bool = False, needles_sorted: bool = False, sort_needles: bool = False,
+                     positions=None, out=None):
+        """``torch.searchsorted(sorted_keys, needles, right=right)`` in the key order of this library: for every needle
+        the number of keys that are smaller (``right``: not larger), an int64 tensor of the needles' shape.
+        ``sorted_keys`` is 1-D and contiguous, of float32, int32, float64, int64, uint32 or uint64, and ascending as
+        :meth:`sort_typed` leaves it (trusted); ``needles`` is contiguous, of any shape and the same dtype.
+
+        Where the results differ from ``torch.searchsorted``: floats are ordered by IEEE-754 totalOrder on their bits,
+        as everywhere in this library.  -0.0 lies below +0.0, so the left bound of +0.0 points behind the -0.0s; a NaN
+        is an ordinary key, a +NaN above +inf, a -NaN (sign bit set) below -inf, among NaNs by payload.  A tensor sorted
+        by ``torch.sort`` is in this order only if it holds no -NaN and no zeros of both signs.
+
+        ``needles_sorted=True`` promises needles that are ascending in the same order (flat): the library may then
+        merge the two arrays, reading each once, instead of one binary search per needle (``set_option("search_mode",
+        ...)``).  ``positions`` (int64, 1-D, a permutation of the needles' flat indices) stores the result of needle j
+        at flat index ``positions[j]``.  ``sort_needles=True`` does both for unsorted needles: it sorts a copy of them
+        with positions (:meth:`sort_rows` for 32-bit keys, :meth:`sort_typed` with rids for 64-bit keys) and searches
+        through those, without one random load into ``sorted_keys``.  Measured on 2^30 sorted keys (DESIGN.md section
+        10.7) that is 2 to 4 times faster than the default from 2^24 needles on (89.9 against 332 ms at 2^30 needles) and
+        slower at 2^20 needles and fewer (0.51 against 0.45 ms), so the default stays ``False``.  ``out`` (int64, contiguous, the
+        needles' shape) receives the result.  ``sorted_keys`` and ``needles`` are not modified.  Nothing waits on the
+        host."""
+        torch = _torch()
+        kt = self._key_type(sorted_keys)
+        if needles.dtype != sorted_keys.dtype:
+            raise MsdError(f"sorted_keys and needles differ in dtype: {sorted_keys.dtype} and {needles.dtype}")
+        if sorted_keys.dim() != 1:
+            raise MsdError("searchsorted takes 1-D sorted_keys")
+        if not sorted_keys.is_contiguous() or not needles.is_contiguous():
+            raise MsdError("searchsorted takes contiguous tensors")
+        m = needles.numel()
+        if positions is not None:
+            if positions.dtype != torch.int64 or positions.dim() != 1 or positions.numel() != m or not positions.is_contiguous():
+                raise MsdError("positions must be a contiguous 1-D int64 tensor, as many as the needles")
+            if sort_needles:
+                raise MsdError("positions together with sort_needles: the sort makes positions of its own")
+        shape = tuple(needles.shape)
+        if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise MsdError(f"out must be a contiguous int64 tensor of shape {shape}")
+        if any(not x.is_cuda or x.device.index != self.device for x in (sorted_keys, needles, positions, out) if x is not None):
+            raise MsdError("the tensors must live on the context's GPU")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=needles.device)
+        if m == 0:
+            return out
+        if sort_needles:
+            flat = needles.reshape(-1)
+            if needles.element_size() == 4:
+                needles, positions = self.sort_rows(flat, indices=True)
+            else:
+                needles = flat.clone()
+                positions = torch.arange(m, dtype=torch.int64, device=needles.device)
+                self.sort_typed(needles, rids=positions)
+            needles_sorted = True
+        self._ok(self._L.msd_search_sorted(self._h, C.c_void_p(sorted_keys.data_ptr()), kt, sorted_keys.numel(), C.c_void_p(needles.data_ptr()), m,
+                                           1 if needles_sorted else 0, 1 if right else 0,
+                                           C.c_void_p(positions.data_ptr() if positions is not None else 0), C.c_void_p(out.data_ptr())))
+        return out
+
+    def bucketize(self, values, boundaries, right: bool = False):
+        """``torch.bucketize(values, boundaries, right=right)``: :meth:`searchsorted` ``(boundaries, values, right=right)``,
+        with its order -- where results differ from torch: -0.0 lies below +0.0 and a NaN is an ordinary key (+NaN above
+        +inf, -NaN below -inf).  ``boundaries`` is 1-D, contiguous and ascending as :meth:`sort_typed` leaves it."""
+        return self.searchsorted(boundaries, values, right=right)
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))
@@ -705,7 +779,9 @@ class MsdContext:
     def set_option(self, name: str, value: int) -> None:
         """Tuning knob of include/msd_radix_hip.h (``direct_mode``, ``direct_min``, ``select_cap``, ``topk_rows_mode``, ...) or
         of include/msd_sort_rows_hip.h: ``sort_rows_mode`` (0 the library chooses, 1 always the segment path, 2 always the
-        row kernel) and ``sort_rows_lanes`` (0 by the shape of the matrix, 64 / 256 / 1024 forced where the row fits)."""
+        row kernel) and ``sort_rows_lanes`` (0 by the shape of the matrix, 64 / 256 / 1024 forced where the row fits); of
+        include/msd_search_hip.h: ``search_mode`` (sorted needles: 0 the library chooses, 1 always the direct path, 2 always
+        the merge path) and ``search_merge_ratio`` (R >= 1: the library chooses the merge path when m >= n / R)."""
         self._ok(self._L.msd_set_option(self._h, name.encode(), int(value)))
 
     # ---- phase report

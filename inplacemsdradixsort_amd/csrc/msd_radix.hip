@@ -10,11 +10,13 @@
 #include "msd_sort_rows.hpp"
 #include "msd_runs.hpp"
 #include "msd_reduce.hpp"
+#include "msd_search.hpp"
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
 #include "../../include/msd_sort_rows_hip.h"
 #include "../../include/msd_runs_hip.h"
 #include "../../include/msd_reduce_hip.h"
+#include "../../include/msd_search_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -79,6 +81,8 @@ struct msd_ctx {
 	uint64_t *fix_plan = nullptr; // msd_sort_keys: the plan words of msd_reverse.hpp (kFixWords), allocated by msd_create
 	int fix_stats = 0;            // "sort_keys_split" / "sort_keys_reversed" of the last typed sort: 0 none yet, 1 fix_split and 0 (nothing was launched), 2 in the plan words
 	uint64_t fix_split = 0;
+	int search_mode = 0;               // msd_search_sorted with sorted needles: 0 = the library chooses, 1 = always direct, 2 = always merge
+	uint64_t search_merge_ratio = 32;  // R: the library chooses merge when m >= n / R (the measured crossover lies near n / 37 for 4-byte and n / 24 for 8-byte keys: DESIGN.md section 10.7)
 };
 
 static int fail(msd_ctx *c, int code, const char *fmt, ...)
@@ -2791,6 +2795,78 @@ int msd_reduce_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, c
 
 } // extern "C"
 
+// ---- sorted search (msd_search.hpp)
+
+// Direct: one launch.  Merge: the splits, then the tiles, one behind the other on the stream; the scratch -- one split per
+// tile plus one -- is the slab's, as for msd_run_encode.  Nothing is read back.
+template <typename K>
+static int search_sorted_impl(msd_ctx *c, const K *keys, int key_type, uint64_t n, const K *needles, uint64_t m, bool merge, uint32_t right,
+			      const uint64_t *positions, uint64_t *out)
+{
+	const KeyCodec<K> cd = key_codec<K>(key_type);
+	if (!merge) {
+		const unsigned grid = (unsigned)((m + kSearchDirectTile - 1) / kSearchDirectTile); // (m < 2^36: at most 2^26)
+		phase_begin(c);
+		if (positions)
+			LAUNCH(c, (search_direct_kernel<K, true>), grid, kSearchTh, 0, keys, n, needles, m, right, cd, positions, out);
+		else
+			LAUNCH(c, (search_direct_kernel<K, false>), grid, kSearchTh, 0, keys, n, needles, m, right, cd, positions, out);
+		phase_mark(c, "search_sorted");
+		phase_end(c);
+		return MSD_OK;
+	}
+	const uint64_t tiles = (n + m + SearchCfg<K>::TILE - 1) / SearchCfg<K>::TILE; // (n + m < 2^37: at most 2^26)
+	uint64_t *splits = nullptr;
+	if (int rc = slab_carve(c, [&](Bump &b) { splits = b.take<uint64_t>(tiles + 1); })) return rc;
+	phase_begin(c);
+	LAUNCH(c, (search_split_kernel<K>), (unsigned)((tiles + 1 + kSearchTh - 1) / kSearchTh), kSearchTh, 0, keys, n, needles, m, right, cd, tiles, splits);
+	if (positions)
+		LAUNCH(c, (search_tile_kernel<K, true>), (unsigned)tiles, kSearchTh, 0, keys, n, needles, m, right, cd, splits, positions, out);
+	else
+		LAUNCH(c, (search_tile_kernel<K, false>), (unsigned)tiles, kSearchTh, 0, keys, n, needles, m, right, cd, splits, positions, out);
+	phase_mark(c, "search_sorted");
+	phase_end(c);
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_search_sorted_limits(int key_bytes, uint64_t *tile, uint64_t *direct_tile)
+{
+	if ((key_bytes != 4 && key_bytes != 8) || !tile || !direct_tile) return MSD_EINVAL;
+	*tile = key_bytes == 4 ? SearchCfg<uint32_t>::TILE : SearchCfg<uint64_t>::TILE;
+	*direct_tile = kSearchDirectTile;
+	return MSD_OK;
+}
+
+int msd_search_sorted(msd_ctx *c, const void *d_sorted, int key_type, uint64_t n, const void *d_needles, uint64_t m, int needles_sorted, int side,
+		      const uint64_t *d_positions, uint64_t *d_out)
+{
+	if (!c) return MSD_EINVAL;
+	if (key_type < 0 || key_type >= kKeyTypes) return fail(c, MSD_EINVAL, "unknown key_type");
+	if (side != MSD_SEARCH_LEFT && side != MSD_SEARCH_RIGHT) return fail(c, MSD_EINVAL, "side must be MSD_SEARCH_LEFT or MSD_SEARCH_RIGHT");
+	if (needles_sorted != 0 && needles_sorted != 1) return fail(c, MSD_EINVAL, "needles_sorted must be 0 or 1");
+	if (m && !d_out) return fail(c, MSD_EINVAL, "null d_out pointer");
+	if (m && !d_needles) return fail(c, MSD_EINVAL, "null d_needles pointer");
+	if (m && n && !d_sorted) return fail(c, MSD_EINVAL, "null d_sorted pointer");
+	const uintptr_t es = (uintptr_t)key_type_bytes(key_type);
+	if ((uintptr_t)d_sorted % es || (uintptr_t)d_needles % es || ((uintptr_t)d_positions | (uintptr_t)d_out) % 8)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_sorted, d_needles: the key's width; d_positions, d_out: 8)");
+	if (n >= ((uint64_t)1 << 36) || m >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^36 elements each");
+	const size_t out_bytes = (size_t)(m * 8);
+	if (m && (ranges_overlap(d_out, out_bytes, d_sorted, d_sorted ? (size_t)(n * es) : 0) || ranges_overlap(d_out, out_bytes, d_needles, (size_t)(m * es)) ||
+		  ranges_overlap(d_out, out_bytes, d_positions, d_positions ? out_bytes : 0)))
+		return fail(c, MSD_EINVAL, "d_out must not overlap d_sorted, d_needles or d_positions");
+	if (m == 0) return MSD_OK; // nothing to write
+	const bool merge = needles_sorted && c->search_mode != 1 && (c->search_mode == 2 || n / c->search_merge_ratio <= m);
+	HIPCHK(c, hipSetDevice(c->device));
+	if (es == 4)
+		return search_sorted_impl<uint32_t>(c, (const uint32_t *)d_sorted, key_type, n, (const uint32_t *)d_needles, m, merge, (uint32_t)side, d_positions, d_out);
+	return search_sorted_impl<uint64_t>(c, (const uint64_t *)d_sorted, key_type, n, (const uint64_t *)d_needles, m, merge, (uint32_t)side, d_positions, d_out);
+}
+
+} // extern "C"
+
 template <typename K>
 static int check_impl(msd_ctx *c, const K *k, const uint64_t *r, uint64_t n, uint64_t *viol, uint64_t *sum, uint64_t *xr)
 {
@@ -2948,6 +3024,12 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 	} else if (!strcmp(name, "sort_rows_lanes")) {
 		if (value != 0 && value != 64 && value != 256 && value != 1024) return fail(c, MSD_EINVAL, "sort_rows_lanes must be 0, 64, 256 or 1024");
 		c->sort_rows_lanes = (int)value;
+	} else if (!strcmp(name, "search_mode")) {
+		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "search_mode must be 0, 1 or 2");
+		c->search_mode = (int)value;
+	} else if (!strcmp(name, "search_merge_ratio")) {
+		if (value < 1) return fail(c, MSD_EINVAL, "search_merge_ratio must be at least 1");
+		c->search_merge_ratio = (uint64_t)value;
 	} else if (!strcmp(name, "direct_min_parent")) {
 		if (value < 1) return fail(c, MSD_EINVAL, "direct_min_parent must be positive");
 		c->direct_min_parent = (uint64_t)value;
