@@ -56,13 +56,60 @@ class MsdContext:
         if rc != 0:
             raise MsdError(f"error {rc}: {self._L.msd_last_error(self._h).decode()}")
 
+    def _on_gpu(self, *tensors) -> None:
+        """Refuses a tensor that does not live on the context's GPU (``None``: an absent one); the library is not touched."""
+        if any(not t.is_cuda or t.device.index != self.device for t in tensors if t is not None):
+            raise MsdError("the tensors must live on the context's GPU")
+
     def _ptr(self, t, dtype_size: int) -> C.c_void_p:
-        torch = _torch()
-        if not t.is_cuda or t.device.index != self.device:
-            raise MsdError("tensor must live on the context's GPU")
+        self._on_gpu(t)
         if not t.is_contiguous() or t.element_size() != dtype_size:
             raise MsdError("tensor must be contiguous with the expected element size")
         return C.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _check_positions(positions, n: int, what: str = "elements") -> None:
+        """Refuses ``positions`` (``None``: absent) that are not ``n`` contiguous int64 in one dimension."""
+        if positions is not None and (positions.dtype != _torch().int64 or positions.dim() != 1 or positions.numel() != n or not positions.is_contiguous()):
+            raise MsdError(f"positions must be a contiguous 1-D int64 tensor, as many as the {what}")
+
+    def _value_index_outputs(self, shape, keys, out, out_indices, want_idx: bool, exact: bool = True):
+        """``(out, out_indices)``: the values (the keys' dtype) and, with ``want_idx``, the int64 positions, allocated with
+        ``shape`` where not given.  ``exact``: contiguous tensors of exactly that shape on the context's GPU; otherwise 1-D
+        tensors of at least ``shape[0]`` elements (:meth:`_ptr` looks at the rest)."""
+        torch = _torch()
+        if out is None:
+            out = torch.empty(shape, dtype=keys.dtype, device=keys.device)
+        if want_idx and out_indices is None:
+            out_indices = torch.empty(shape, dtype=torch.int64, device=keys.device)
+        outs = (out, out_indices) if want_idx else (out,)
+        if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
+            raise MsdError("the values have the keys' dtype, the indices are int64")
+        if not exact and any(t.numel() < shape[0] for t in outs):
+            raise MsdError("output tensor shorter than k")
+        if exact and any(tuple(t.shape) != shape or not t.is_contiguous() for t in outs):
+            raise MsdError(f"an output must be a contiguous tensor of shape {shape}")
+        if exact:
+            self._on_gpu(keys, *outs)
+        return out, out_indices
+
+    def _sorted_with_positions(self, flat):
+        """``(sorted copy, positions)`` of a 1-D tensor: :meth:`sort_rows` for 32-bit, :meth:`sort_typed` with rids for 64-bit keys."""
+        if flat.element_size() == 4:
+            return self.sort_rows(flat, indices=True)
+        torch = _torch()
+        s = flat.clone()
+        positions = torch.arange(flat.numel(), dtype=torch.int64, device=flat.device)
+        self.sort_typed(s, rids=positions)
+        return s, positions
+
+    @staticmethod
+    def _limits2(fn, arg: int, what: str) -> Tuple[int, int]:
+        """The two words of a ``*_limits`` call that takes an element width."""
+        a, b = C.c_uint64(), C.c_uint64()
+        if fn(int(arg), C.byref(a), C.byref(b)) != 0:
+            raise MsdError(f"error -1: {what} must be 4 or 8, not {arg}")
+        return int(a.value), int(b.value)
 
     def use_torch_stream(self) -> None:
         torch = _torch()
@@ -380,18 +427,10 @@ class MsdContext:
         With ``indices`` (or ``out_indices``) returns ``(values, positions)``: int64 positions with
         ``keys[positions[j]]`` bit-equal to ``values[j]``, none twice; which of several keys equal to the boundary key
         are taken is unspecified.  ``keys`` is not modified."""
-        torch = _torch()
         kt = self._key_type(keys)
         es = keys.element_size()
         want_idx = indices or out_indices is not None
-        if out is None:
-            out = torch.empty(max(int(k), 0), dtype=keys.dtype, device=keys.device)
-        if want_idx and out_indices is None:
-            out_indices = torch.empty(max(int(k), 0), dtype=torch.int64, device=keys.device)
-        if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
-            raise MsdError("the values have the keys' dtype, the indices are int64")
-        if out.numel() < k or (want_idx and out_indices.numel() < k):
-            raise MsdError("output tensor shorter than k")
+        out, out_indices = self._value_index_outputs((max(int(k), 0),), keys, out, out_indices, want_idx, exact=False)
         self._ok(self._L.msd_topk_keys(self._h, self._ptr(keys, es), kt, keys.numel(), k, 1 if largest else 0, self._ptr(out, es),
                                        self._ptr(out_indices, 8) if want_idx else C.c_void_p(0)))
         return (out, out_indices) if want_idx else out
@@ -451,23 +490,12 @@ class MsdContext:
         shape ``[..., k]``; with ``indices`` (or ``out_indices``) also int64 positions within the row, of the same shape.
         ``keys`` is not modified and never copied: a layout that is not rows of stride 1 with one row stride is refused.
         Inside :meth:`topk_rows_limits` one kernel launch answers all rows and nothing blocks the host."""
-        torch = _torch()
         kt = self._key_type(keys)
         rows, row_len, row_stride = self._rows_layout(keys)
-        if not keys.is_cuda or keys.device.index != self.device:
-            raise MsdError("tensor must live on the context's GPU")
+        self._on_gpu(keys)
         k = int(k)
         want_idx = indices or out_indices is not None
-        shape = tuple(keys.shape[:-1]) + (max(k, 0),)
-        if out is None:
-            out = torch.empty(shape, dtype=keys.dtype, device=keys.device)
-        if want_idx and out_indices is None:
-            out_indices = torch.empty(shape, dtype=torch.int64, device=keys.device)
-        if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
-            raise MsdError("the values have the keys' dtype, the indices are int64")
-        for t in (out, out_indices) if want_idx else (out,):
-            if tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device:
-                raise MsdError(f"an output must be a contiguous tensor of shape {shape} on the context's GPU")
+        out, out_indices = self._value_index_outputs(tuple(keys.shape[:-1]) + (max(k, 0),), keys, out, out_indices, want_idx)
         self._ok(self._L.msd_topk_rows(self._h, C.c_void_p(keys.data_ptr()), kt, rows, row_len, row_stride, k, 1 if largest else 0,
                                        C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
         return (out, out_indices) if want_idx else out
@@ -490,22 +518,10 @@ class MsdContext:
         unspecified.  ``keys`` is never copied: a layout that is not rows of stride 1 with one row stride is refused.
         ``out=keys`` sorts a contiguous tensor in place; otherwise ``keys`` is not modified.  Inside
         :meth:`sort_rows_limits` one kernel launch sorts all rows and nothing blocks the host."""
-        torch = _torch()
         kt = self._key_type(keys)
         rows, row_len, row_stride = self._rows_layout(keys)
         want_idx = indices or out_indices is not None
-        shape = tuple(keys.shape)
-        if out is None:
-            out = torch.empty(shape, dtype=keys.dtype, device=keys.device)
-        if want_idx and out_indices is None:
-            out_indices = torch.empty(shape, dtype=torch.int64, device=keys.device)
-        outs = (out, out_indices) if want_idx else (out,)
-        if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
-            raise MsdError("the values have the keys' dtype, the indices are int64")
-        if any(tuple(t.shape) != shape or not t.is_contiguous() for t in outs):
-            raise MsdError(f"an output must be a contiguous tensor of shape {shape}")
-        if any(not t.is_cuda or t.device.index != self.device for t in (keys,) + outs):
-            raise MsdError("the tensors must live on the context's GPU")
+        out, out_indices = self._value_index_outputs(tuple(keys.shape), keys, out, out_indices, want_idx)
         self._ok(self._L.msd_sort_rows(self._h, C.c_void_p(keys.data_ptr()), kt, rows, row_len, row_stride, 1 if descending else 0,
                                        C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
         return (out, out_indices) if want_idx else out
@@ -514,10 +530,7 @@ class MsdContext:
     def run_encode_limits(self, elem_bytes: int) -> Tuple[int, int]:
         """``(tile, scan_tile)``: the elements one workgroup takes per tile for that element width, and how many tile
         counts one workgroup of the tile-count scan takes at once (``msd_run_encode_limits``)."""
-        a, b = C.c_uint64(), C.c_uint64()
-        if self._L.msd_run_encode_limits(int(elem_bytes), C.byref(a), C.byref(b)) != 0:
-            raise MsdError(f"error -1: elem_bytes must be 4 or 8, not {elem_bytes}")
-        return int(a.value), int(b.value)
+        return self._limits2(self._L.msd_run_encode_limits, elem_bytes, "elem_bytes")
 
     def run_encode(self, t, cap: Optional[int] = None, values: bool = True, starts: bool = True, inverse: bool = False, positions=None):
         """Run-length encodes the 1-D contiguous tensor ``t`` of 4- or 8-byte elements (``torch.unique_consecutive``; on a
@@ -540,23 +553,19 @@ class MsdContext:
         if es not in (4, 8):
             raise MsdError(f"run_encode takes 4- or 8-byte elements, not {t.dtype}")
         n = t.numel()
-        if positions is not None:
-            if positions.dtype != torch.int64 or positions.dim() != 1 or positions.numel() != n or not positions.is_contiguous():
-                raise MsdError("positions must be a contiguous int64 tensor, as many as the elements")
-            if not inverse:
-                raise MsdError("positions without inverse")
+        self._check_positions(positions, n)
+        if positions is not None and not inverse:
+            raise MsdError("positions without inverse")
         cap = n if cap is None else int(cap)
         if cap < 0:
             raise MsdError("cap must not be negative")
-        if any(not x.is_cuda or x.device.index != self.device for x in (t, positions) if x is not None):
-            raise MsdError("the tensors must live on the context's GPU")
-        pp = C.c_void_p(positions.data_ptr() if positions is not None else 0)
+        self._on_gpu(t, positions)
         num = torch.empty(1, dtype=torch.int64, device=t.device)
         vals = torch.empty(cap, dtype=t.dtype, device=t.device) if values else None
         st = torch.empty(cap + 1, dtype=torch.int64, device=t.device) if starts else None
         inv = torch.empty(n, dtype=torch.int64, device=t.device) if inverse else None
         ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
-        self._ok(self._L.msd_run_encode(self._h, C.c_void_p(t.data_ptr()), es, n, cap, ptr(vals), ptr(st), pp, ptr(inv), ptr(num)))
+        self._ok(self._L.msd_run_encode(self._h, C.c_void_p(t.data_ptr()), es, n, cap, ptr(vals), ptr(st), ptr(positions), ptr(inv), ptr(num)))
         return num, vals, st, inv
 
     def unique(self, keys, return_inverse: bool = False, return_counts: bool = False):
@@ -566,23 +575,15 @@ class MsdContext:
         totalOrder and told apart by their BITS, as everywhere in this library: -0.0 and +0.0 are two values and NaNs
         with equal bits are one, where ``torch.unique`` merges the zeros and keeps every NaN apart.  ``keys`` is not
         modified.  One host wait beyond the sort's own: the number of distinct values sizes the results."""
-        torch = _torch()
         self._key_type(keys)   # (a dtype without a key order is refused here)
         if keys.dim() != 1 or not keys.is_contiguous():
             raise MsdError("unique takes a 1-D contiguous tensor")
-        if not keys.is_cuda or keys.device.index != self.device:
-            raise MsdError("tensor must live on the context's GPU")
-        n = keys.numel()
-        positions = None
-        if not return_inverse:
-            s = keys.clone()
-            self.sort_typed(s)
-        elif keys.element_size() == 4:
-            s, positions = self.sort_rows(keys, indices=True)
+        self._on_gpu(keys)
+        if return_inverse:
+            s, positions = self._sorted_with_positions(keys)
         else:
-            s = keys.clone()
-            positions = torch.arange(n, dtype=torch.int64, device=keys.device)
-            self.sort_typed(s, rids=positions)
+            s, positions = keys.clone(), None
+            self.sort_typed(s)
         num, vals, st, inv = self.run_encode(s, starts=return_counts, inverse=return_inverse, positions=positions)
         m = int(num.item())
         out = (vals[:m],)
@@ -597,10 +598,7 @@ class MsdContext:
 
     def reduce_runs_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, scan_tile)`` of ``msd_reduce_runs_limits``: the geometry of :meth:`run_encode_limits`."""
-        a, b = C.c_uint64(), C.c_uint64()
-        if self._L.msd_reduce_runs_limits(int(key_bytes), C.byref(a), C.byref(b)) != 0:
-            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
-        return int(a.value), int(b.value)
+        return self._limits2(self._L.msd_reduce_runs_limits, key_bytes, "key_bytes")
 
     def reduce_runs(self, keys, vals, op: str = "sum", positions=None, cap: Optional[int] = None):
         """One number per run of ``keys``: the ``"sum"``, ``"min"`` or ``"max"`` of the values of its elements.  The runs
@@ -630,13 +628,11 @@ class MsdContext:
         n = keys.numel()
         if vals.numel() != n:
             raise MsdError("keys and vals differ in length")
-        if positions is not None and (positions.dtype != torch.int64 or positions.dim() != 1 or positions.numel() != n or not positions.is_contiguous()):
-            raise MsdError("positions must be a contiguous int64 tensor, as many as the elements")
+        self._check_positions(positions, n)
         cap = n if cap is None else int(cap)
         if cap < 0:
             raise MsdError("cap must not be negative")
-        if any(not x.is_cuda or x.device.index != self.device for x in (keys, vals, positions) if x is not None):
-            raise MsdError("the tensors must live on the context's GPU")
+        self._on_gpu(keys, vals, positions)
         if op != "sum":
             odt = vals.dtype
         elif vt in (self.KEY_F32, self.KEY_F64):
@@ -659,24 +655,16 @@ class MsdContext:
         the dtypes and the rules of :meth:`reduce_runs`.  The keys are sorted with positions, the value column is read
         through them where it lies.  ``keys`` and ``vals`` are not modified.  One host wait beyond the sort's own: the
         number of distinct keys sizes the results."""
-        torch = _torch()
         if op not in self.REDUCE_OPS:
             raise MsdError(f"op must be one of {sorted(self.REDUCE_OPS)}, not {op!r}")
         self._key_type(keys)
         self._key_type(vals)
         if keys.dim() != 1 or vals.dim() != 1 or not keys.is_contiguous() or not vals.is_contiguous():
             raise MsdError("group_reduce takes 1-D contiguous tensors")
-        n = keys.numel()
-        if vals.numel() != n:
+        if vals.numel() != keys.numel():
             raise MsdError("keys and vals differ in length")
-        if any(not x.is_cuda or x.device.index != self.device for x in (keys, vals)):
-            raise MsdError("the tensors must live on the context's GPU")
-        if keys.element_size() == 4:
-            s, positions = self.sort_rows(keys, indices=True)
-        else:
-            s = keys.clone()
-            positions = torch.arange(n, dtype=torch.int64, device=keys.device)
-            self.sort_typed(s, rids=positions)
+        self._on_gpu(keys, vals)
+        s, positions = self._sorted_with_positions(keys)
         _, distinct, _, _ = self.run_encode(s, starts=False)
         num, out = self.reduce_runs(s, vals, op=op, positions=positions)
         m = int(num.item())
@@ -686,10 +674,7 @@ class MsdContext:
     def search_sorted_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, direct_tile)`` of ``msd_search_sorted_limits``: the elements (keys plus needles together) one
         workgroup of the merge path takes for that key width, and the needles one workgroup of the direct path takes."""
-        a, b = C.c_uint64(), C.c_uint64()
-        if self._L.msd_search_sorted_limits(int(key_bytes), C.byref(a), C.byref(b)) != 0:
-            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
-        return int(a.value), int(b.value)
+        return self._limits2(self._L.msd_search_sorted_limits, key_bytes, "key_bytes")
 
     def searchsorted(self, sorted_keys, needles, right: bool = False, needles_sorted: bool = False, sort_needles: bool = False,
                      positions=None, out=None):
@@ -722,28 +707,19 @@ class MsdContext:
         if not sorted_keys.is_contiguous() or not needles.is_contiguous():
             raise MsdError("searchsorted takes contiguous tensors")
         m = needles.numel()
-        if positions is not None:
-            if positions.dtype != torch.int64 or positions.dim() != 1 or positions.numel() != m or not positions.is_contiguous():
-                raise MsdError("positions must be a contiguous 1-D int64 tensor, as many as the needles")
-            if sort_needles:
-                raise MsdError("positions together with sort_needles: the sort makes positions of its own")
+        self._check_positions(positions, m, "needles")
+        if positions is not None and sort_needles:
+            raise MsdError("positions together with sort_needles: the sort makes positions of its own")
         shape = tuple(needles.shape)
         if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous()):
             raise MsdError(f"out must be a contiguous int64 tensor of shape {shape}")
-        if any(not x.is_cuda or x.device.index != self.device for x in (sorted_keys, needles, positions, out) if x is not None):
-            raise MsdError("the tensors must live on the context's GPU")
+        self._on_gpu(sorted_keys, needles, positions, out)
         if out is None:
             out = torch.empty(shape, dtype=torch.int64, device=needles.device)
         if m == 0:
             return out
         if sort_needles:
-            flat = needles.reshape(-1)
-            if needles.element_size() == 4:
-                needles, positions = self.sort_rows(flat, indices=True)
-            else:
-                needles = flat.clone()
-                positions = torch.arange(m, dtype=torch.int64, device=needles.device)
-                self.sort_typed(needles, rids=positions)
+            needles, positions = self._sorted_with_positions(needles.reshape(-1))
             needles_sorted = True
         self._ok(self._L.msd_search_sorted(self._h, C.c_void_p(sorted_keys.data_ptr()), kt, sorted_keys.numel(), C.c_void_p(needles.data_ptr()), m,
                                            1 if needles_sorted else 0, 1 if right else 0,

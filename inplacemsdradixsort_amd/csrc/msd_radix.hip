@@ -11,6 +11,7 @@
 #include "msd_runs.hpp"
 #include "msd_reduce.hpp"
 #include "msd_search.hpp"
+#include "msd_args.hpp" // the argument rules, each stated once (host only)
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
 #include "../../include/msd_sort_rows_hip.h"
@@ -114,23 +115,13 @@ static int launch_at(msd_ctx *c, const char *what, const char *file, int line, v
 	const hipError_t e = hipGetLastError();
 	return e == hipSuccess ? MSD_OK : fail(c, MSD_EHIP, "launch of %s failed: %s (%s:%d)", what, hipGetErrorString(e), file, line);
 }
+// (an expression: MSD_OK or the error)
+#define LAUNCH_RC(c, kernel, grid, block, lds, ...) launch_at(c, #kernel, __FILE__, __LINE__, kernel, dim3(grid), dim3(block), lds, __VA_ARGS__)
 // (a statement, like HIPCHK: returns the error from the calling function)
-#define LAUNCH(c, kernel, grid, block, lds, ...)                                                                      \
-	do {                                                                                                          \
-		if (int rc_ = launch_at(c, #kernel, __FILE__, __LINE__, kernel, dim3(grid), dim3(block), lds, __VA_ARGS__)) return rc_; \
+#define LAUNCH(c, kernel, grid, block, lds, ...)                                                    \
+	do {                                                                                        \
+		if (int rc_ = LAUNCH_RC(c, kernel, grid, block, lds, __VA_ARGS__)) return rc_;      \
 	} while (0)
-
-// ---- argument rules, each stated once
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-// Do the byte ranges [a, a + abytes) and [b, b + bbytes) share an address?  An empty range strictly inside the other one
-// counts as sharing (a pointer into the other buffer was handed in); a null pointer with 0 bytes -- an absent optional
-// buffer, the only empty range the select entry points pass -- shares nothing with any range.
-static bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return x < y + bbytes && y < x + abytes;
-}
 
 static void set_stat(msd_ctx *c, const char *name, uint64_t v)
 {
@@ -1395,35 +1386,24 @@ template <typename F> static hipError_t max_lds(F *kernel, size_t bytes)
 	return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-template <typename K, bool IDX> static int set_rows_lds_attrs_for(msd_ctx *c)
+// the two row kernels (msd_topk_rows, msd_sort_rows): every K x IDX x LANES instance
+template <typename K, bool IDX, int LANES> static int set_row_kernels_lds_attrs_for(msd_ctx *c)
 {
-	HIPCHK(c, max_lds(&topk_rows_kernel<K, IDX, 64>, RowsLds<K, IDX, 64>::bytes));
-	HIPCHK(c, max_lds(&topk_rows_kernel<K, IDX, 256>, RowsLds<K, IDX, 256>::bytes));
-	HIPCHK(c, max_lds(&topk_rows_kernel<K, IDX, 1024>, RowsLds<K, IDX, 1024>::bytes));
+	HIPCHK(c, max_lds(&topk_rows_kernel<K, IDX, LANES>, RowsLds<K, IDX, LANES>::bytes));
+	HIPCHK(c, max_lds(&sort_rows_kernel<K, IDX, LANES>, SortRowsLds<K, IDX, LANES>::bytes));
 	return MSD_OK;
 }
-static int set_rows_lds_attrs(msd_ctx *c)
+static int set_row_kernels_lds_attrs(msd_ctx *c)
 {
-	int rc = set_rows_lds_attrs_for<uint32_t, false>(c);
-	if (!rc) rc = set_rows_lds_attrs_for<uint32_t, true>(c);
-	if (!rc) rc = set_rows_lds_attrs_for<uint64_t, false>(c);
-	if (!rc) rc = set_rows_lds_attrs_for<uint64_t, true>(c);
-	return rc;
-}
-
-template <typename K, bool IDX> static int set_sort_rows_lds_attrs_for(msd_ctx *c)
-{
-	HIPCHK(c, max_lds(&sort_rows_kernel<K, IDX, 64>, SortRowsLds<K, IDX, 64>::bytes));
-	HIPCHK(c, max_lds(&sort_rows_kernel<K, IDX, 256>, SortRowsLds<K, IDX, 256>::bytes));
-	HIPCHK(c, max_lds(&sort_rows_kernel<K, IDX, 1024>, SortRowsLds<K, IDX, 1024>::bytes));
-	return MSD_OK;
-}
-static int set_sort_rows_lds_attrs(msd_ctx *c)
-{
-	int rc = set_sort_rows_lds_attrs_for<uint32_t, false>(c);
-	if (!rc) rc = set_sort_rows_lds_attrs_for<uint32_t, true>(c);
-	if (!rc) rc = set_sort_rows_lds_attrs_for<uint64_t, false>(c);
-	if (!rc) rc = set_sort_rows_lds_attrs_for<uint64_t, true>(c);
+	int rc = MSD_OK;
+	for (const int key_bytes : { 4, 8 })
+		for (const bool with_idx : { false, true })
+			for (const int lanes_per_row : { 64, 256, 1024 })
+				if (!rc) rc = with_width(key_bytes, [&](auto k0) {
+					return with_flag(with_idx, [&](auto idx) {
+						return with_lanes(lanes_per_row, [&](auto lanes) { return set_row_kernels_lds_attrs_for<decltype(k0), decltype(idx)::value, decltype(lanes)::value>(c); });
+					});
+				});
 	return rc;
 }
 
@@ -1541,8 +1521,7 @@ int msd_create(msd_ctx **out, int device, void *stream)
 	int rc = with_layout(4, 0, attrs);
 	if (!rc) rc = with_layout(8, 0, attrs);
 	if (!rc) rc = with_layout(8, 8, attrs);
-	if (!rc) rc = set_rows_lds_attrs(c);
-	if (!rc) rc = set_sort_rows_lds_attrs(c);
+	if (!rc) rc = set_row_kernels_lds_attrs(c);
 	if (!rc && hipMalloc((void **)&c->fix_plan, kFixWords * sizeof(uint64_t)) != hipSuccess) rc = fail(c, MSD_ENOMEM, "plan words hipMalloc failed");
 	if (rc) {
 		fprintf(stderr, "msd_create: %s\n", c->err.c_str());
@@ -1980,6 +1959,19 @@ static void phases_append(msd_ctx *c, std::vector<std::pair<std::string, double>
 	for (auto &p : c->phase_us) phase_add(all, p.first, p.second);
 }
 
+// A stage behind an internal sort: what `launches` starts is the phase `name`, added to the phases the sort has left
+template <typename F> static int tail_phase(msd_ctx *c, const char *name, F &&launches)
+{
+	std::vector<std::pair<std::string, double>> phases = c->phase_us;
+	phase_begin(c);
+	if (int rc = launches()) return rc;
+	phase_mark(c, name);
+	phase_end(c);
+	phases_append(c, phases);
+	c->phase_us = phases;
+	return MSD_OK;
+}
+
 // TOPK: out[0 .. k) = the k smallest keys in the order of key ^ flip, sorted ascending as plain keys; otherwise
 // *value = the key of rank k in that order.  One readback of the search state behind the filter pass, the internal
 // sorts' own, and (select) one of the value.
@@ -2153,6 +2145,10 @@ static int check_key_type(msd_ctx *c, int key_type)
 {
 	return key_type_ok(key_type) ? MSD_OK : fail(c, MSD_EINVAL, "unknown key type %d (MSD_KEY_U32 .. MSD_KEY_F64)", key_type);
 }
+static int check_order(msd_ctx *c, int order)
+{
+	return order == MSD_ASCENDING || order == MSD_DESCENDING ? MSD_OK : fail(c, MSD_EINVAL, "order must be MSD_ASCENDING or MSD_DESCENDING");
+}
 
 int msd_key_encode(int key_type, uint64_t bits, uint64_t *code)
 {
@@ -2204,8 +2200,7 @@ int msd_select_key(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, uin
 
 template <typename E> static int reverse_launch(msd_ctx *c, E *data, uint64_t n, const uint64_t *plan, uint64_t a, uint64_t b)
 {
-	LAUNCH(c, (reverse_ranges_kernel<E>), (unsigned)rev_grid_for<E>(n), kRevTh, 0, data, plan, a, b);
-	return MSD_OK;
+	return LAUNCH_RC(c, (reverse_ranges_kernel<E>), (unsigned)rev_grid_for<E>(n), kRevTh, 0, data, plan, a, b);
 }
 
 template <typename K> static int sort_keys_impl(msd_ctx *c, K *keys, uint64_t *rids, int key_type, uint64_t n, int order)
@@ -2222,11 +2217,10 @@ template <typename K> static int sort_keys_impl(msd_ctx *c, K *keys, uint64_t *r
 		c->fix_split = kind == 0 ? n : 0;
 		return MSD_OK;
 	}
-	std::vector<std::pair<std::string, double>> phases = c->phase_us;
-	phase_begin(c);
-	LAUNCH(c, (sign_split_kernel<K>), 1, 64, 0, keys, n, kind, order, c->fix_plan);
-	c->fix_stats = 2;
-	if (n >= 2) {
+	return tail_phase(c, "sort_fixup", [&]() -> int {
+		LAUNCH(c, (sign_split_kernel<K>), 1, 64, 0, keys, n, kind, order, c->fix_plan);
+		c->fix_stats = 2;
+		if (n < 2) return MSD_OK;
 		// descending needs one stage, ascending two; a stage without work is a launch whose workgroups leave at once
 		for (int stage = 0; stage < (order == MSD_DESCENDING ? 1 : 2); ++stage) {
 			const uint64_t *plan = c->fix_plan + (stage ? kFixStage2 : kFixStage1);
@@ -2234,24 +2228,21 @@ template <typename K> static int sort_keys_impl(msd_ctx *c, K *keys, uint64_t *r
 			if (rids)
 				if (int r = reverse_launch<uint64_t>(c, rids, n, plan, 0, 0)) return r;
 		}
-	}
-	phase_mark(c, "sort_fixup");
-	phase_end(c);
-	phases_append(c, phases);
-	c->phase_us = phases;
-	return MSD_OK;
+		return MSD_OK;
+	});
 }
 
 static int sort_keys_entry(msd_ctx *c, void *d_keys, int key_type, uint64_t *d_rids, bool pairs, uint64_t n, int order)
 {
 	if (!c) return MSD_EINVAL;
 	if (int rc = check_key_type(c, key_type)) return rc;
-	if (order != MSD_ASCENDING && order != MSD_DESCENDING) return fail(c, MSD_EINVAL, "order must be MSD_ASCENDING or MSD_DESCENDING");
+	if (int rc = check_order(c, order)) return rc;
 	if (pairs && key_type_bytes(key_type) != 8) return fail(c, MSD_EINVAL, "tuples have 64-bit keys (MSD_KEY_U64 / I64 / F64)");
 	if (n && (!d_keys || (pairs && !d_rids))) return fail(c, MSD_EINVAL, "null data pointer");
-	if (!aligned16(d_keys) || (pairs && !aligned16(d_rids))) return fail(c, MSD_EINVAL, "keys/rids must be 16-byte aligned");
-	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large for 32-bit block slots");
-	if (pairs && n && ranges_overlap(d_keys, n * 8, d_rids, n * 8)) return fail(c, MSD_EINVAL, "keys and rids overlap");
+	const Span buf[2] = { span_of(d_keys, n, key_type_bytes(key_type), 16), span_of(pairs ? d_rids : nullptr, n, 8, 16) }; // both sorted in place
+	if (first_misaligned(buf) >= 0) return fail(c, MSD_EINVAL, "keys/rids must be 16-byte aligned");
+	if (n >= kMaxElems) return fail(c, MSD_EINVAL, "n too large for 32-bit block slots");
+	if (outputs_overlap(buf, 1)) return fail(c, MSD_EINVAL, "keys and rids overlap");
 	HIPCHK(c, hipSetDevice(c->device));
 	return with_key_type(key_type, [&](auto k0, auto) {
 		typedef decltype(k0) K;
@@ -2272,12 +2263,11 @@ int msd_reverse(msd_ctx *c, void *d_data, int elem_bytes, uint64_t first, uint64
 	if (!c) return MSD_EINVAL;
 	if (elem_bytes != 4 && elem_bytes != 8) return fail(c, MSD_EINVAL, "elem_bytes must be 4 or 8");
 	if (count && !d_data) return fail(c, MSD_EINVAL, "null data pointer");
-	if ((uintptr_t)d_data % (unsigned)elem_bytes) return fail(c, MSD_EINVAL, "data must be aligned to its element size");
+	if (!aligned_to(d_data, (uint32_t)elem_bytes)) return fail(c, MSD_EINVAL, "data must be aligned to its element size");
 	if (first + count < first || first + count > UINT64_MAX / (unsigned)elem_bytes) return fail(c, MSD_EINVAL, "first + count overflows");
 	HIPCHK(c, hipSetDevice(c->device));
 	if (count < 2) return MSD_OK;
-	return elem_bytes == 4 ? reverse_launch<uint32_t>(c, (uint32_t *)d_data, count, nullptr, first, first + count)
-			       : reverse_launch<uint64_t>(c, (uint64_t *)d_data, count, nullptr, first, first + count);
+	return with_width(elem_bytes, [&](auto e) { return reverse_launch(c, (decltype(e) *)d_data, count, nullptr, first, first + count); });
 }
 
 } // extern "C"
@@ -2291,18 +2281,6 @@ static bool rows_in_envelope(uint64_t row_len, uint64_t k) { return row_len <= k
 // 0.15 ms per row whatever its length (profiles/topk_rows_sweep.jsonl; DESIGN.md section 10.2, "Dispatch").  From 4 rows on
 // the kernel wins up to the envelope's longest row.
 static bool rows_kernel_wins(uint64_t rows, uint64_t row_len) { return rows >= 4 || row_len < (rows << 18); }
-
-template <typename K, bool IDX, int LANES>
-static int rows_launch(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec, K *out,
-			uint64_t *out_idx)
-{
-	typedef RowsCfg<LANES> C;
-	constexpr uint64_t groups = C::BLOCK / LANES;
-	const uint64_t per_cu = LANES == 1024 ? 8 : 64; // (workgroups beyond what the chip holds at once walk the rows in a loop)
-	const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * per_cu, (rows + groups - 1) / groups));
-	LAUNCH(c, (topk_rows_kernel<K, IDX, LANES>), grid, C::BLOCK, (RowsLds<K, IDX, LANES>::bytes), keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-	return MSD_OK;
-}
 
 // Lanes per row (profiles/topk_rows_sweep.jsonl, the `lanes*` columns): a wave where the row fits its registers; 256 lanes
 // for rows below 8192 keys and wherever there are more rows than the chip holds 1024-thread workgroups (2 per CU: six
@@ -2319,16 +2297,6 @@ static int rows_lanes(const msd_ctx *c, uint64_t rows, uint64_t row_len, uint64_
 	return c->topk_rows_lanes;
 }
 
-template <typename K, bool IDX>
-static int rows_launch_by_length(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, K flip, KeyCodec<K> codec,
-				  K *out, uint64_t *out_idx)
-{
-	const int lanes = rows_lanes(c, rows, row_len, sizeof(K));
-	if (lanes == 64) return rows_launch<K, IDX, 64>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-	if (lanes == 256) return rows_launch<K, IDX, 256>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-	return rows_launch<K, IDX, 1024>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx);
-}
-
 template <typename K>
 static int rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64_t rows, uint64_t row_len, uint64_t stride, uint64_t k, int which, K *out,
 			    uint64_t *out_idx)
@@ -2336,9 +2304,18 @@ static int rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64_t ro
 	const K flip = which == MSD_LARGEST ? (K)~(K)0 : (K)0;
 	const KeyCodec<K> codec = key_codec<K>(key_type);
 	phase_begin(c);
-	if (int rc = out_idx ? rows_launch_by_length<K, true>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx)
-			     : rows_launch_by_length<K, false>(c, keys, rows, row_len, stride, k, flip, codec, out, out_idx))
-		return rc;
+	const int rc = with_flag(out_idx != nullptr, [&](auto idx) {
+		return with_lanes(rows_lanes(c, rows, row_len, sizeof(K)), [&](auto lanes) {
+			constexpr bool IDX = decltype(idx)::value;
+			constexpr int LANES = decltype(lanes)::value;
+			typedef RowsCfg<LANES> C;
+			constexpr uint64_t groups = C::BLOCK / LANES;
+			const uint64_t per_cu = LANES == 1024 ? 8 : 64; // (workgroups beyond what the chip holds at once walk the rows in a loop)
+			const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * per_cu, (rows + groups - 1) / groups));
+			return LAUNCH_RC(c, (topk_rows_kernel<K, IDX, LANES>), grid, C::BLOCK, (RowsLds<K, IDX, LANES>::bytes), keys, rows, row_len, stride, k, flip, codec, out, out_idx);
+		});
+	});
+	if (rc) return rc;
 	phase_mark(c, "select_rows");
 	phase_end(c);
 	return MSD_OK;
@@ -2389,24 +2366,16 @@ int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 	if (which != MSD_SMALLEST && which != MSD_LARGEST) return fail(c, MSD_EINVAL, "which must be MSD_SMALLEST or MSD_LARGEST");
 	if (k > row_len) return fail(c, MSD_EINVAL, "k must not exceed row_len");
 	if (row_stride < row_len) return fail(c, MSD_EINVAL, "row_stride must not be smaller than row_len");
-	const uint64_t es = (uint64_t)key_type_bytes(key_type);
-	uint64_t in_elems = 0, out_elems = 0, in_bytes = 0, out_bytes = 0, idx_bytes = 0;
-	if (__builtin_mul_overflow(rows, row_stride, &in_elems) || __builtin_mul_overflow(in_elems, es, &in_bytes))
-		return fail(c, MSD_EINVAL, "rows * row_stride overflows");
-	if (__builtin_mul_overflow(rows, k, &out_elems) || __builtin_mul_overflow(out_elems, (uint64_t)8, &idx_bytes))
-		return fail(c, MSD_EINVAL, "rows * k overflows");
+	const uint32_t es = (uint32_t)key_type_bytes(key_type);
+	const RowsExtents ext = rows_extents(rows, row_len, row_stride, k, es, d_out_idx != nullptr);
+	if (ext.overflow) return fail(c, MSD_EINVAL, ext.overflow == kRowsInputOverflows ? "rows * row_stride overflows" : "rows * k overflows");
 	if (rows == 0 || k == 0) return MSD_OK;
 	if (!d_keys || !d_out_keys) return fail(c, MSD_EINVAL, "null data pointer");
-	if (((uintptr_t)d_keys & (es - 1)) || ((uintptr_t)d_out_keys & (es - 1)) || ((uintptr_t)d_out_idx & 7))
-		return fail(c, MSD_EINVAL, "input and output buffers must be aligned to their element size");
+	const Span buf[3] = { { d_keys, ext.in_bytes, es }, { d_out_keys, ext.out_bytes, es }, { d_out_idx, ext.idx_bytes, 8 } };
+	if (first_misaligned(buf) >= 0) return fail(c, MSD_EINVAL, "input and output buffers must be aligned to their element size");
 	if (d_out_idx && es == 4 && row_len > ((uint64_t)1 << 32))
 		return fail(c, MSD_EINVAL, "indices of a 32-bit key type need row_len <= 2^32 (the position travels in 32 bits)");
-	in_bytes = ((rows - 1) * row_stride + row_len) * es; // the input's extent: the padding behind the last row is not part of it
-	out_bytes = out_elems * es;
-	if (!d_out_idx) idx_bytes = 0;
-	if (ranges_overlap(d_keys, in_bytes, d_out_keys, out_bytes) || ranges_overlap(d_keys, in_bytes, d_out_idx, idx_bytes) ||
-	    ranges_overlap(d_out_keys, out_bytes, d_out_idx, idx_bytes))
-		return fail(c, MSD_EINVAL, "the outputs must not overlap the input or each other");
+	if (outputs_overlap(buf, 1)) return fail(c, MSD_EINVAL, "the outputs must not overlap the input or each other");
 	const bool inside = rows_in_envelope(row_len, k);
 	if (c->topk_rows_mode == 2 && !inside)
 		return fail(c, MSD_EINVAL, "topk_rows_mode 2: the row kernel takes row_len <= %llu and k <= %u", (unsigned long long)kRowsMaxLen, kRowsMaxK);
@@ -2434,8 +2403,7 @@ int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 // the envelope: what the 1024-lane shape holds
 static uint64_t sort_rows_max_len(int key_bytes, bool idx)
 {
-	if (key_bytes == 4) return idx ? sort_rows_cap<uint32_t, true, 1024>() : sort_rows_cap<uint32_t, false, 1024>();
-	return idx ? sort_rows_cap<uint64_t, true, 1024>() : sort_rows_cap<uint64_t, false, 1024>();
+	return with_width(key_bytes, [&](auto k0) { return with_flag(idx, [](auto i) { return (uint64_t)sort_rows_cap<decltype(k0), decltype(i)::value, 1024>(); }); });
 }
 
 // Mode 0 inside the envelope: does the row kernel beat the segment path?  (profiles/sort_rows_sweep.jsonl; DESIGN.md section
@@ -2447,18 +2415,6 @@ static bool sort_rows_kernel_wins(uint64_t key_bytes, bool idx, uint64_t row_len
 {
 	if (key_bytes == 4 || !segments_possible) return true;
 	return idx ? row_len <= 512 : row_len < 4096;
-}
-
-template <typename K, bool IDX, int LANES>
-static int sort_rows_launch(msd_ctx *c, const K *keys, uint64_t rows, uint64_t row_len, uint64_t stride, K flip, KeyCodec<K> codec, K *out, uint64_t *out_idx)
-{
-	typedef SortRowsCfg<K, IDX, LANES> C;
-	constexpr uint64_t groups = C::BLOCK / LANES;
-	// workgroups a CU holds at once (LDS: 160 KiB; registers: one 1024-thread workgroup); the rest of the rows in a loop
-	const uint64_t per_cu = LANES == 1024 ? 1 : LANES == 256 ? 4 : 6;
-	const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * per_cu, (rows + groups - 1) / groups));
-	LAUNCH(c, (sort_rows_kernel<K, IDX, LANES>), grid, C::BLOCK, (SortRowsLds<K, IDX, LANES>::bytes), keys, rows, row_len, stride, flip, codec, out, out_idx);
-	return MSD_OK;
 }
 
 // Lanes per row: the smallest group that holds the row -- a wave up to 512 keys, 256 lanes up to 4096, 1024 lanes beyond
@@ -2481,13 +2437,15 @@ static int sort_rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64
 	const int lanes = sort_rows_lanes<K, IDX>(c, row_len);
 	c->stats.clear();
 	phase_begin(c);
-	int rc;
-	if (lanes == 64)
-		rc = sort_rows_launch<K, IDX, 64>(c, keys, rows, row_len, stride, flip, codec, out, out_idx);
-	else if (lanes == 256)
-		rc = sort_rows_launch<K, IDX, 256>(c, keys, rows, row_len, stride, flip, codec, out, out_idx);
-	else
-		rc = sort_rows_launch<K, IDX, 1024>(c, keys, rows, row_len, stride, flip, codec, out, out_idx);
+	const int rc = with_lanes(lanes, [&](auto l) {
+		constexpr int LANES = decltype(l)::value;
+		typedef SortRowsCfg<K, IDX, LANES> C;
+		constexpr uint64_t groups = C::BLOCK / LANES;
+		// workgroups a CU holds at once (LDS: 160 KiB; registers: one 1024-thread workgroup); the rest of the rows in a loop
+		const uint64_t per_cu = LANES == 1024 ? 1 : LANES == 256 ? 4 : 6;
+		const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->sm_count * per_cu, (rows + groups - 1) / groups));
+		return LAUNCH_RC(c, (sort_rows_kernel<K, IDX, LANES>), grid, C::BLOCK, (SortRowsLds<K, IDX, LANES>::bytes), keys, rows, row_len, stride, flip, codec, out, out_idx);
+	});
 	if (rc) return rc;
 	phase_mark(c, "sort_rows");
 	phase_end(c);
@@ -2521,16 +2479,14 @@ static int sort_rows_segments(msd_ctx *c, const K *keys, int key_type, uint64_t 
 		rc = sort_segments<uint64_t, uint64_t>(c, out, out_idx, total, off.data(), (uint32_t)rows, 64);
 	}
 	if (rc) return rc; // (the outputs hold codes)
-	std::vector<std::pair<std::string, double>> phases = c->phase_us;
-	phase_begin(c);
-	if (packed) {
-		if constexpr (PACK) LAUNCH(c, rows_unpack_kernel, grid, 256, 0, out_idx, total, fcodec, out);
-	} else
-		LAUNCH(c, (rows_decode_kernel<K>), grid, 256, 0, out, total, fcodec);
-	phase_mark(c, "sort_rows");
-	phase_end(c);
-	phases_append(c, phases);
-	c->phase_us = phases;
+	rc = tail_phase(c, "sort_rows", [&]() -> int {
+		if (packed) {
+			if constexpr (PACK) LAUNCH(c, rows_unpack_kernel, grid, 256, 0, out_idx, total, fcodec, out);
+		} else
+			LAUNCH(c, (rows_decode_kernel<K>), grid, 256, 0, out, total, fcodec);
+		return MSD_OK;
+	});
+	if (rc) return rc;
 	set_stat(c, "sort_rows_lanes", 0);
 	return MSD_OK;
 }
@@ -2549,47 +2505,40 @@ int msd_sort_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 {
 	if (!c) return MSD_EINVAL;
 	if (int rc = check_key_type(c, key_type)) return rc;
-	if (order != MSD_ASCENDING && order != MSD_DESCENDING) return fail(c, MSD_EINVAL, "order must be MSD_ASCENDING or MSD_DESCENDING");
+	if (int rc = check_order(c, order)) return rc;
 	if (row_stride < row_len) return fail(c, MSD_EINVAL, "row_stride must not be smaller than row_len");
-	const uint64_t es = (uint64_t)key_type_bytes(key_type);
-	uint64_t in_elems = 0, out_elems = 0, in_bytes = 0, out_bytes = 0, idx_bytes = 0;
-	if (__builtin_mul_overflow(rows, row_stride, &in_elems) || __builtin_mul_overflow(in_elems, es, &in_bytes))
-		return fail(c, MSD_EINVAL, "rows * row_stride overflows");
-	if (__builtin_mul_overflow(rows, row_len, &out_elems) || __builtin_mul_overflow(out_elems, (uint64_t)8, &idx_bytes))
-		return fail(c, MSD_EINVAL, "rows * row_len overflows");
+	const uint32_t es = (uint32_t)key_type_bytes(key_type);
+	const RowsExtents ext = rows_extents(rows, row_len, row_stride, row_len, es, d_out_idx != nullptr);
+	if (ext.overflow) return fail(c, MSD_EINVAL, ext.overflow == kRowsInputOverflows ? "rows * row_stride overflows" : "rows * row_len overflows");
 	if (rows == 0 || row_len == 0) return MSD_OK;
 	if (!d_keys || !d_out_keys) return fail(c, MSD_EINVAL, "null data pointer");
-	if (((uintptr_t)d_keys & (es - 1)) || ((uintptr_t)d_out_keys & (es - 1)) || ((uintptr_t)d_out_idx & 7))
-		return fail(c, MSD_EINVAL, "input and output buffers must be aligned to their element size");
-	in_bytes = ((rows - 1) * row_stride + row_len) * es; // the input's extent: the padding behind the last row is not part of it
-	out_bytes = out_elems * es;
-	if (!d_out_idx) idx_bytes = 0;
+	// in place the input IS the output (the same extent): it has no span of its own
 	const bool in_place = d_out_keys == d_keys && row_stride == row_len;
-	if ((!in_place && ranges_overlap(d_keys, in_bytes, d_out_keys, out_bytes)) || ranges_overlap(d_keys, in_bytes, d_out_idx, idx_bytes) ||
-	    ranges_overlap(d_out_keys, out_bytes, d_out_idx, idx_bytes))
+	const Span buf[3] = { { in_place ? nullptr : d_keys, in_place ? 0 : ext.in_bytes, es }, { d_out_keys, ext.out_bytes, es }, { d_out_idx, ext.idx_bytes, 8 } };
+	if (first_misaligned(buf) >= 0) return fail(c, MSD_EINVAL, "input and output buffers must be aligned to their element size");
+	if (outputs_overlap(buf, 1))
 		return fail(c, MSD_EINVAL, "the outputs must not overlap the input (but d_out_keys == d_keys with row_stride == row_len) or each other");
 	const uint64_t max_len = sort_rows_max_len((int)es, d_out_idx != nullptr);
 	const bool inside = row_len <= max_len;
 	if (c->sort_rows_mode == 2 && !inside)
 		return fail(c, MSD_EINVAL, "sort_rows_mode 2: the row kernel takes row_len <= %llu for this key type", (unsigned long long)max_len);
-	const bool seg_ok = aligned16(d_out_keys) && (!d_out_idx || aligned16(d_out_idx)) && rows < ((uint64_t)1 << 32) && out_elems < ((uint64_t)1 << 36);
-	const bool kernel = inside && (c->sort_rows_mode == 2 || (c->sort_rows_mode == 0 && sort_rows_kernel_wins(es, d_out_idx != nullptr, row_len, seg_ok)));
-	if (!kernel) {
-		if (!aligned16(d_out_keys) || (d_out_idx && !aligned16(d_out_idx)))
-			return fail(c, MSD_EINVAL, "rows beyond the row kernel (row_len > %llu, or sort_rows_mode 1) go through the segment sort, whose rule this is: "
-						   "d_out_keys and d_out_idx must be 16-byte aligned",
-				    (unsigned long long)max_len);
-		if (rows >= ((uint64_t)1 << 32) || out_elems >= ((uint64_t)1 << 36))
-			return fail(c, MSD_EINVAL, "the segment sort takes fewer than 2^32 rows and 2^36 elements");
-	}
+	// the segment path's own rules for the outputs and the sizes (a null d_out_idx is aligned)
+	const bool seg_aligned = aligned16(d_out_keys) && aligned16(d_out_idx), seg_fits = rows < ((uint64_t)1 << 32) && ext.out_elems < kMaxElems;
+	const bool kernel = inside && (c->sort_rows_mode == 2 || (c->sort_rows_mode == 0 && sort_rows_kernel_wins(es, d_out_idx != nullptr, row_len, seg_aligned && seg_fits)));
+	if (!kernel && !seg_aligned)
+		return fail(c, MSD_EINVAL, "rows beyond the row kernel (row_len > %llu, or sort_rows_mode 1) go through the segment sort, whose rule this is: "
+					   "d_out_keys and d_out_idx must be 16-byte aligned",
+			    (unsigned long long)max_len);
+	if (!kernel && !seg_fits) return fail(c, MSD_EINVAL, "the segment sort takes fewer than 2^32 rows and 2^36 elements");
 	HIPCHK(c, hipSetDevice(c->device));
 	const int rc = with_key_type(key_type, [&](auto k0, auto) { // (the 4-byte / 8-byte choice only: the codec is two run-time words)
 		typedef decltype(k0) K;
 		const K *in = (const K *)d_keys;
 		K *out = (K *)d_out_keys;
 		if (!kernel) return sort_rows_segments<K>(c, in, key_type, rows, row_len, row_stride, order, out, d_out_idx);
-		return d_out_idx ? sort_rows_kernel_path<K, true>(c, in, key_type, rows, row_len, row_stride, order, out, d_out_idx)
-				 : sort_rows_kernel_path<K, false>(c, in, key_type, rows, row_len, row_stride, order, out, d_out_idx);
+		return with_flag(d_out_idx != nullptr, [&](auto idx) {
+			return sort_rows_kernel_path<K, decltype(idx)::value>(c, in, key_type, rows, row_len, row_stride, order, out, d_out_idx);
+		});
 	});
 	if (rc) return rc;
 	set_stat(c, "sort_rows_kernel_rows", kernel ? rows : 0);
@@ -2601,46 +2550,50 @@ int msd_sort_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 
 // ---- run-length encode (msd_runs.hpp)
 
-template <typename E, bool INV, bool POS>
-static int run_write_launch(msd_ctx *c, const E *data, uint64_t n, uint64_t cap, uint64_t tiles, const uint64_t *tile_base, const uint64_t *piece_base, E *values,
-			    uint64_t *starts, const uint64_t *positions, uint64_t *inverse)
-{
-	LAUNCH(c, (runs_write_kernel<E, INV, POS>), (unsigned)tiles, kRunsTh, 0, data, n, cap, tile_base, piece_base, values, starts, positions, inverse);
-	return MSD_OK;
-}
-
-// Count, scan, write: four launches one behind the other on the stream, nothing read back.  The scratch -- one word per
-// tile, one per scan piece -- is the slab's, like a sort round's: the next call on the context overwrites it, in stream order.
-template <typename E>
-static int run_encode_impl(msd_ctx *c, const E *data, uint64_t n, uint64_t cap, E *values, uint64_t *starts, const uint64_t *positions, uint64_t *inverse,
-			   uint64_t *num_runs)
+// What msd_run_encode and msd_reduce_runs begin with: the runs counted per tile and the counts scanned, *num_runs written.
+// The scratch -- one word per tile, one per scan piece, then whatever `more` takes from the Bump -- is the slab's, like a
+// sort round's: the next call on the context overwrites it, in stream order.  The caller's phase begins here, behind the
+// carve; an empty array (tiles == 0 afterwards) is one launch that writes 0 runs, and starts[0] = 0 where starts is given.
+struct RunsScratch { uint64_t tiles = 0, pieces = 0, *tile_counts = nullptr, *piece_sums = nullptr; };
+template <typename E, typename F> static int runs_count_scan(msd_ctx *c, const E *data, uint64_t n, uint64_t *num_runs, uint64_t *starts, F &&more, RunsScratch &s)
 {
 	if (n == 0) {
 		phase_begin(c);
 		LAUNCH(c, runs_empty_kernel, 1, 64, 0, num_runs, starts);
-		phase_mark(c, "run_encode");
-		phase_end(c);
 		return MSD_OK;
 	}
-	const uint64_t tiles = runs_tiles(data, n), pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile; // (tiles <= 2^25 + 1)
-	uint64_t *tile_counts = nullptr, *piece_sums = nullptr;
+	s.tiles = runs_tiles(data, n); // (<= 2^25 + 1)
+	s.pieces = (s.tiles + kRunsScanTile - 1) / kRunsScanTile;
 	if (int rc = slab_carve(c, [&](Bump &b) {
-		    tile_counts = b.take<uint64_t>(tiles);
-		    piece_sums = b.take<uint64_t>(pieces);
+		    s.tile_counts = b.take<uint64_t>(s.tiles);
+		    s.piece_sums = b.take<uint64_t>(s.pieces);
+		    more(b);
 	    }))
 		return rc;
 	phase_begin(c);
-	LAUNCH(c, (runs_count_kernel<E>), (unsigned)tiles, kRunsTh, 0, data, n, tile_counts);
-	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
-	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_runs);
-	int rc = MSD_OK;
-	if (inverse && positions)
-		rc = run_write_launch<E, true, true>(c, data, n, cap, tiles, tile_counts, piece_sums, values, starts, positions, inverse);
-	else if (inverse)
-		rc = run_write_launch<E, true, false>(c, data, n, cap, tiles, tile_counts, piece_sums, values, starts, positions, inverse);
-	else if (values || starts)
-		rc = run_write_launch<E, false, false>(c, data, n, cap, tiles, tile_counts, piece_sums, values, starts, positions, inverse);
-	if (rc) return rc;
+	LAUNCH(c, (runs_count_kernel<E>), (unsigned)s.tiles, kRunsTh, 0, data, n, s.tile_counts);
+	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)s.pieces, kRunsScanTh, 0, s.tile_counts, s.tiles, s.piece_sums);
+	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, s.piece_sums, s.pieces, num_runs);
+	return MSD_OK;
+}
+
+// Count, scan, write: four launches one behind the other on the stream, nothing read back.
+template <typename E>
+static int run_encode_impl(msd_ctx *c, const E *data, uint64_t n, uint64_t cap, E *values, uint64_t *starts, const uint64_t *positions, uint64_t *inverse,
+			   uint64_t *num_runs)
+{
+	RunsScratch s;
+	if (int rc = runs_count_scan(c, data, n, num_runs, starts, [](Bump &) {}, s)) return rc;
+	if (s.tiles && (inverse || values || starts)) {
+		// (positions only go with an inverse: there is no <E, false, true> instance)
+		const int rc = with_flag(inverse != nullptr, [&](auto inv) {
+			return with_flag(inverse && positions, [&](auto pos) {
+				constexpr bool INV = decltype(inv)::value, POS = INV && decltype(pos)::value;
+				return LAUNCH_RC(c, (runs_write_kernel<E, INV, POS>), (unsigned)s.tiles, kRunsTh, 0, data, n, cap, s.tile_counts, s.piece_sums, values, starts, positions, inverse);
+			});
+		});
+		if (rc) return rc;
+	}
 	phase_mark(c, "run_encode");
 	phase_end(c);
 	return MSD_OK;
@@ -2651,7 +2604,7 @@ extern "C" {
 int msd_run_encode_limits(int elem_bytes, uint64_t *tile, uint64_t *scan_tile)
 {
 	if ((elem_bytes != 4 && elem_bytes != 8) || !tile || !scan_tile) return MSD_EINVAL;
-	*tile = elem_bytes == 4 ? RunsCfg<uint32_t>::TILE : RunsCfg<uint64_t>::TILE;
+	*tile = with_width(elem_bytes, [](auto e) { return (uint64_t)RunsCfg<decltype(e)>::TILE; });
 	*scan_tile = kRunsScanTile;
 	return MSD_OK;
 }
@@ -2663,29 +2616,22 @@ int msd_run_encode(msd_ctx *c, const void *d_data, int elem_bytes, uint64_t n, u
 	if (elem_bytes != 4 && elem_bytes != 8) return fail(c, MSD_EINVAL, "elem_bytes must be 4 or 8");
 	if (!d_num_runs) return fail(c, MSD_EINVAL, "d_num_runs is required");
 	if (n && !d_data) return fail(c, MSD_EINVAL, "null data pointer");
-	const uintptr_t es = (uintptr_t)elem_bytes;
-	if ((uintptr_t)d_data % es || (uintptr_t)d_values % es || ((uintptr_t)d_starts | (uintptr_t)d_positions | (uintptr_t)d_inverse | (uintptr_t)d_num_runs) % 8)
+	// the extents: inputs first, then the outputs; at most min(cap, n) runs are stored (n at most 2^36 - 1 wherever an extent is looked at)
+	const uint32_t es = (uint32_t)elem_bytes;
+	const uint64_t stored = std::min({ cap, n, kMaxElems });
+	const Span buf[6] = { span_of(d_data, n, es),          span_of(d_positions, n, 8), span_of(d_values, stored, es),
+			      span_of(d_starts, stored + 1, 8), span_of(d_inverse, n, 8),   span_of(d_num_runs, 1, 8) };
+	if (first_misaligned(buf) >= 0)
 		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_data, d_values: elem_bytes; the others: 8)");
-	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
+	if (n >= kMaxElems) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
 	if (d_positions && !d_inverse) return fail(c, MSD_EINVAL, "d_positions without d_inverse");
-	// the extents: inputs first, then the outputs; at most min(cap, n) runs are stored
-	const uint64_t stored = std::min(cap, n);
-	const struct { const void *p; size_t bytes; } buf[6] = {
-		{ d_data, (size_t)(n * es) },
-		{ d_positions, d_positions ? (size_t)(n * 8) : 0 },
-		{ d_values, d_values ? (size_t)(stored * es) : 0 },
-		{ d_starts, d_starts ? (size_t)((stored + 1) * 8) : 0 },
-		{ d_inverse, d_inverse ? (size_t)(n * 8) : 0 },
-		{ d_num_runs, 8 },
-	};
-	for (int o = 2; o < 6; ++o)
-		for (int i = 0; i < o; ++i)
-			if (ranges_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes))
-				return fail(c, MSD_EINVAL, "the outputs must not overlap the input, d_positions or each other (in-place compaction is not offered)");
+	if (outputs_overlap(buf, 2))
+		return fail(c, MSD_EINVAL, "the outputs must not overlap the input, d_positions or each other (in-place compaction is not offered)");
 	HIPCHK(c, hipSetDevice(c->device));
-	if (elem_bytes == 4)
-		return run_encode_impl<uint32_t>(c, (const uint32_t *)d_data, n, cap, (uint32_t *)d_values, d_starts, d_positions, d_inverse, d_num_runs);
-	return run_encode_impl<uint64_t>(c, (const uint64_t *)d_data, n, cap, (uint64_t *)d_values, d_starts, d_positions, d_inverse, d_num_runs);
+	return with_width(elem_bytes, [&](auto e) {
+		typedef decltype(e) E;
+		return run_encode_impl<E>(c, (const E *)d_data, n, cap, (E *)d_values, d_starts, d_positions, d_inverse, d_num_runs);
+	});
 }
 
 } // extern "C"
@@ -2693,43 +2639,29 @@ int msd_run_encode(msd_ctx *c, const void *d_data, int elem_bytes, uint64_t n, u
 // ---- reduce-by-key over runs (msd_reduce.hpp)
 
 // Count, scan, reduce, carry, apply: seven launches one behind the other on the stream, nothing read back.  The scratch --
-// per tile the count, the lead and the heads, and the same per scan piece -- is the slab's, as for msd_run_encode.
+// per tile the count, the lead and the heads, and the same per scan piece -- is the slab's (runs_count_scan).
 template <typename E, typename P>
 static int reduce_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *vals, const uint64_t *positions, uint64_t cap, void *out, uint64_t *num_runs,
 			    KeyCodec<typename P::R::O> cd)
 {
 	typedef typename P::R R;
-	if (n == 0) {
-		phase_begin(c);
-		LAUNCH(c, runs_empty_kernel, 1, 64, 0, num_runs, nullptr);
-		phase_mark(c, "reduce_runs");
-		phase_end(c);
-		return MSD_OK;
-	}
-	const uint64_t tiles = runs_tiles(keys, n), pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile; // (tiles <= 2^25 + 1)
-	uint64_t *tile_counts = nullptr, *piece_sums = nullptr;
+	RunsScratch s;
 	ReduceRecord rec{ nullptr, nullptr }, piece{ nullptr, nullptr };
-	if (int rc = slab_carve(c, [&](Bump &b) {
-		    tile_counts = b.take<uint64_t>(tiles);
-		    piece_sums = b.take<uint64_t>(pieces);
-		    rec.lead = b.take<uint64_t>(tiles);
-		    rec.heads = b.take<uint32_t>(tiles);
-		    piece.lead = b.take<uint64_t>(pieces);
-		    piece.heads = b.take<uint32_t>(pieces);
-	    }))
-		return rc;
-	phase_begin(c);
-	LAUNCH(c, (runs_count_kernel<E>), (unsigned)tiles, kRunsTh, 0, keys, n, tile_counts);
-	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
-	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_runs);
-	if (cap) { // (cap == 0 only counts)
-		if (positions)
-			LAUNCH(c, (reduce_tile_kernel<E, P, true>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, positions, cap, tile_counts, piece_sums, cd, out, rec);
-		else
-			LAUNCH(c, (reduce_tile_kernel<E, P, false>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, positions, cap, tile_counts, piece_sums, cd, out, rec);
-		LAUNCH(c, (reduce_carry_pieces_kernel<R>), (unsigned)pieces, kRunsScanTh, 0, rec, tiles, cd, piece);
-		LAUNCH(c, (reduce_carry_top_kernel<R>), 1, kRunsScanTh, 0, piece, pieces, cd);
-		LAUNCH(c, (reduce_apply_kernel<R>), (unsigned)((tiles + 255) / 256), 256, 0, rec, piece, tiles, cap, tile_counts, piece_sums, cd, out);
+	const auto records = [&](Bump &b) {
+		rec.lead = b.take<uint64_t>(s.tiles);
+		rec.heads = b.take<uint32_t>(s.tiles);
+		piece.lead = b.take<uint64_t>(s.pieces);
+		piece.heads = b.take<uint32_t>(s.pieces);
+	};
+	if (int rc = runs_count_scan(c, keys, n, num_runs, nullptr, records, s)) return rc;
+	if (s.tiles && cap) { // (cap == 0 only counts)
+		const int rc = with_flag(positions != nullptr, [&](auto pos) {
+			return LAUNCH_RC(c, (reduce_tile_kernel<E, P, decltype(pos)::value>), (unsigned)s.tiles, kRunsTh, 0, keys, n, vals, positions, cap, s.tile_counts, s.piece_sums, cd, out, rec);
+		});
+		if (rc) return rc;
+		LAUNCH(c, (reduce_carry_pieces_kernel<R>), (unsigned)s.pieces, kRunsScanTh, 0, rec, s.tiles, cd, piece);
+		LAUNCH(c, (reduce_carry_top_kernel<R>), 1, kRunsScanTh, 0, piece, s.pieces, cd);
+		LAUNCH(c, (reduce_apply_kernel<R>), (unsigned)((s.tiles + 255) / 256), 256, 0, rec, piece, s.tiles, cap, s.tile_counts, s.piece_sums, cd, out);
 	}
 	phase_mark(c, "reduce_runs");
 	phase_end(c);
@@ -2766,31 +2698,22 @@ int msd_reduce_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, c
 {
 	if (!c) return MSD_EINVAL;
 	if (key_bytes != 4 && key_bytes != 8) return fail(c, MSD_EINVAL, "key_bytes must be 4 or 8");
-	if (val_type < 0 || val_type >= kKeyTypes) return fail(c, MSD_EINVAL, "unknown val_type");
+	if (!key_type_ok(val_type)) return fail(c, MSD_EINVAL, "unknown val_type");
 	if (op != MSD_REDUCE_SUM && op != MSD_REDUCE_MIN && op != MSD_REDUCE_MAX) return fail(c, MSD_EINVAL, "unknown op");
 	if (!d_num_runs) return fail(c, MSD_EINVAL, "d_num_runs is required");
 	if (n && (!d_keys || !d_vals)) return fail(c, MSD_EINVAL, "null keys or values pointer");
 	if (n && cap && !d_out) return fail(c, MSD_EINVAL, "null d_out pointer");
-	const uintptr_t ks = (uintptr_t)key_bytes, vs = (uintptr_t)key_type_bytes(val_type), os = op == MSD_REDUCE_SUM ? 8 : vs;
-	if ((uintptr_t)d_keys % ks || (uintptr_t)d_vals % vs || (uintptr_t)d_out % os || ((uintptr_t)d_positions | (uintptr_t)d_num_runs) % 8)
+	// the extents: inputs first, then the outputs; at most min(cap, n) runs are stored, a sum as 8 bytes
+	const uint32_t ks = (uint32_t)key_bytes, vs = (uint32_t)key_type_bytes(val_type), os = op == MSD_REDUCE_SUM ? 8 : vs;
+	const Span buf[5] = { span_of(d_keys, n, ks), span_of(d_vals, n, vs), span_of(d_positions, n, 8), span_of(d_out, std::min(cap, n), os), span_of(d_num_runs, 1, 8) };
+	if (first_misaligned(buf) >= 0)
 		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_keys: key_bytes; d_vals: the value's; d_out: 8 for a sum, else the value's; the others: 8)");
-	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
-	// the extents: inputs first, then the outputs; at most min(cap, n) runs are stored
-	const uint64_t stored = std::min(cap, n);
-	const struct { const void *p; size_t bytes; } buf[5] = {
-		{ d_keys, (size_t)(n * ks) },
-		{ d_vals, (size_t)(n * vs) },
-		{ d_positions, d_positions ? (size_t)(n * 8) : 0 },
-		{ d_out, d_out ? (size_t)(stored * os) : 0 },
-		{ d_num_runs, 8 },
-	};
-	for (int o = 3; o < 5; ++o)
-		for (int i = 0; i < o; ++i)
-			if (ranges_overlap(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes))
-				return fail(c, MSD_EINVAL, "d_out and d_num_runs must not overlap the keys, the values, d_positions or each other");
+	if (n >= kMaxElems) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
+	if (outputs_overlap(buf, 3)) return fail(c, MSD_EINVAL, "d_out and d_num_runs must not overlap the keys, the values, d_positions or each other");
 	HIPCHK(c, hipSetDevice(c->device));
-	if (key_bytes == 4) return reduce_runs_typed<uint32_t>(c, (const uint32_t *)d_keys, n, d_vals, val_type, d_positions, op, cap, d_out, d_num_runs);
-	return reduce_runs_typed<uint64_t>(c, (const uint64_t *)d_keys, n, d_vals, val_type, d_positions, op, cap, d_out, d_num_runs);
+	return with_width(key_bytes, [&](auto k0) {
+		return reduce_runs_typed(c, (const decltype(k0) *)d_keys, n, d_vals, val_type, d_positions, op, cap, d_out, d_num_runs);
+	});
 }
 
 } // extern "C"
@@ -2799,7 +2722,7 @@ int msd_reduce_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, c
 
 // Direct: one launch.  Merge: the splits, then the tiles, one behind the other on the stream; the scratch -- one split per
 // tile plus one -- is the slab's, as for msd_run_encode.  Nothing is read back.
-template <typename K>
+template <typename K, bool POS> // (POS: through positions)
 static int search_sorted_impl(msd_ctx *c, const K *keys, int key_type, uint64_t n, const K *needles, uint64_t m, bool merge, uint32_t right,
 			      const uint64_t *positions, uint64_t *out)
 {
@@ -2807,10 +2730,7 @@ static int search_sorted_impl(msd_ctx *c, const K *keys, int key_type, uint64_t 
 	if (!merge) {
 		const unsigned grid = (unsigned)((m + kSearchDirectTile - 1) / kSearchDirectTile); // (m < 2^36: at most 2^26)
 		phase_begin(c);
-		if (positions)
-			LAUNCH(c, (search_direct_kernel<K, true>), grid, kSearchTh, 0, keys, n, needles, m, right, cd, positions, out);
-		else
-			LAUNCH(c, (search_direct_kernel<K, false>), grid, kSearchTh, 0, keys, n, needles, m, right, cd, positions, out);
+		LAUNCH(c, (search_direct_kernel<K, POS>), grid, kSearchTh, 0, keys, n, needles, m, right, cd, positions, out);
 		phase_mark(c, "search_sorted");
 		phase_end(c);
 		return MSD_OK;
@@ -2820,10 +2740,7 @@ static int search_sorted_impl(msd_ctx *c, const K *keys, int key_type, uint64_t 
 	if (int rc = slab_carve(c, [&](Bump &b) { splits = b.take<uint64_t>(tiles + 1); })) return rc;
 	phase_begin(c);
 	LAUNCH(c, (search_split_kernel<K>), (unsigned)((tiles + 1 + kSearchTh - 1) / kSearchTh), kSearchTh, 0, keys, n, needles, m, right, cd, tiles, splits);
-	if (positions)
-		LAUNCH(c, (search_tile_kernel<K, true>), (unsigned)tiles, kSearchTh, 0, keys, n, needles, m, right, cd, splits, positions, out);
-	else
-		LAUNCH(c, (search_tile_kernel<K, false>), (unsigned)tiles, kSearchTh, 0, keys, n, needles, m, right, cd, splits, positions, out);
+	LAUNCH(c, (search_tile_kernel<K, POS>), (unsigned)tiles, kSearchTh, 0, keys, n, needles, m, right, cd, splits, positions, out);
 	phase_mark(c, "search_sorted");
 	phase_end(c);
 	return MSD_OK;
@@ -2834,7 +2751,7 @@ extern "C" {
 int msd_search_sorted_limits(int key_bytes, uint64_t *tile, uint64_t *direct_tile)
 {
 	if ((key_bytes != 4 && key_bytes != 8) || !tile || !direct_tile) return MSD_EINVAL;
-	*tile = key_bytes == 4 ? SearchCfg<uint32_t>::TILE : SearchCfg<uint64_t>::TILE;
+	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)SearchCfg<decltype(k0)>::TILE; });
 	*direct_tile = kSearchDirectTile;
 	return MSD_OK;
 }
@@ -2843,26 +2760,28 @@ int msd_search_sorted(msd_ctx *c, const void *d_sorted, int key_type, uint64_t n
 		      const uint64_t *d_positions, uint64_t *d_out)
 {
 	if (!c) return MSD_EINVAL;
-	if (key_type < 0 || key_type >= kKeyTypes) return fail(c, MSD_EINVAL, "unknown key_type");
+	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key_type");
 	if (side != MSD_SEARCH_LEFT && side != MSD_SEARCH_RIGHT) return fail(c, MSD_EINVAL, "side must be MSD_SEARCH_LEFT or MSD_SEARCH_RIGHT");
 	if (needles_sorted != 0 && needles_sorted != 1) return fail(c, MSD_EINVAL, "needles_sorted must be 0 or 1");
 	if (m && !d_out) return fail(c, MSD_EINVAL, "null d_out pointer");
 	if (m && !d_needles) return fail(c, MSD_EINVAL, "null d_needles pointer");
 	if (m && n && !d_sorted) return fail(c, MSD_EINVAL, "null d_sorted pointer");
-	const uintptr_t es = (uintptr_t)key_type_bytes(key_type);
-	if ((uintptr_t)d_sorted % es || (uintptr_t)d_needles % es || ((uintptr_t)d_positions | (uintptr_t)d_out) % 8)
+	// the extents: the inputs, then d_out (a null d_sorted is empty)
+	const uint32_t es = (uint32_t)key_type_bytes(key_type);
+	const Span buf[4] = { span_of(d_sorted, n, es), span_of(d_needles, m, es), span_of(d_positions, m, 8), span_of(d_out, m, 8) };
+	if (first_misaligned(buf) >= 0)
 		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_sorted, d_needles: the key's width; d_positions, d_out: 8)");
-	if (n >= ((uint64_t)1 << 36) || m >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^36 elements each");
-	const size_t out_bytes = (size_t)(m * 8);
-	if (m && (ranges_overlap(d_out, out_bytes, d_sorted, d_sorted ? (size_t)(n * es) : 0) || ranges_overlap(d_out, out_bytes, d_needles, (size_t)(m * es)) ||
-		  ranges_overlap(d_out, out_bytes, d_positions, d_positions ? out_bytes : 0)))
-		return fail(c, MSD_EINVAL, "d_out must not overlap d_sorted, d_needles or d_positions");
+	if (n >= kMaxElems || m >= kMaxElems) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^36 elements each");
+	if (m && outputs_overlap(buf, 3)) return fail(c, MSD_EINVAL, "d_out must not overlap d_sorted, d_needles or d_positions");
 	if (m == 0) return MSD_OK; // nothing to write
 	const bool merge = needles_sorted && c->search_mode != 1 && (c->search_mode == 2 || n / c->search_merge_ratio <= m);
 	HIPCHK(c, hipSetDevice(c->device));
-	if (es == 4)
-		return search_sorted_impl<uint32_t>(c, (const uint32_t *)d_sorted, key_type, n, (const uint32_t *)d_needles, m, merge, (uint32_t)side, d_positions, d_out);
-	return search_sorted_impl<uint64_t>(c, (const uint64_t *)d_sorted, key_type, n, (const uint64_t *)d_needles, m, merge, (uint32_t)side, d_positions, d_out);
+	return with_width((int)es, [&](auto k0) {
+		return with_flag(d_positions != nullptr, [&](auto pos) {
+			typedef decltype(k0) K;
+			return search_sorted_impl<K, decltype(pos)::value>(c, (const K *)d_sorted, key_type, n, (const K *)d_needles, m, merge, (uint32_t)side, d_positions, d_out);
+		});
+	});
 }
 
 } // extern "C"

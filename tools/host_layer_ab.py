@@ -6,6 +6,11 @@
 Alternates the two builds in one job, `runs` (default 3) fresh processes each.  A process measures, on one GPU:
   sort_u32_2^16, sort_u32_2^20   msd_sort_u32 on fresh uniform keys: median over 200 calls of the host clock around call + synchronise
   topk_rows_4x4096_f32_k8        msd_topk_rows, 4 rows of 4096 float32, k = 8: the same
+  sort_rows_64x512_f32_idx       msd_sort_rows, 64 rows of 512 float32 with positions: the same, as all of the following
+  run_encode_2^16_i32            msd_run_encode on 2^16 sorted int32 (values, starts)
+  reduce_runs_sum_2^16_i64       msd_reduce_runs, the sum of int64 values over the runs of the same keys
+  searchsorted_2^16_in_2^20_i32  msd_search_sorted, 2^16 unsorted needles in 2^20 sorted int32
+  sort_typed_2^16_f32            msd_sort_keys on 2^16 float32 (a fresh copy of the same keys before every call)
   bench_2^30_u32                 bench.py's default line (ms_per_step of --steps 10 --warmup 2)
 and prints one JSON line per case; the driver appends them to profiles/host_layer_ab.jsonl and prints the comparison:
 per case the parent's min-max over its runs against the median of this build's runs.  The small cases are the ones where
@@ -56,6 +61,22 @@ def child():
     x = torch.randn(4, 4096, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     o = torch.empty(4, 8, device="cuda")
     rows["topk_rows_4x4096_f32_k8"] = timed(lambda: ctx.topk_rows(x, 8, out=o))
+    # the typed entry points: one to four launches and no synchronisation of their own, so the call's time is host time
+    g = torch.Generator("cuda").manual_seed(2)
+    m = torch.randn(64, 512, device="cuda", generator=g)
+    mo, mi = torch.empty_like(m), torch.empty(64, 512, dtype=torch.int64, device="cuda")
+    rows["sort_rows_64x512_f32_idx"] = timed(lambda: ctx.sort_rows(m, out=mo, out_indices=mi))
+    sk = torch.randint(0, 1 << 12, (1 << 16,), dtype=torch.int32, device="cuda", generator=g).sort().values
+    sv = torch.arange(1 << 16, dtype=torch.int64, device="cuda")
+    rows["run_encode_2^16_i32"] = timed(lambda: ctx.run_encode(sk))
+    rows["reduce_runs_sum_2^16_i64"] = timed(lambda: ctx.reduce_runs(sk, sv))
+    hay = torch.randint(-(1 << 30), 1 << 30, (1 << 20,), dtype=torch.int32, device="cuda", generator=g).sort().values
+    needles = torch.randint(-(1 << 30), 1 << 30, (1 << 16,), dtype=torch.int32, device="cuda", generator=g)
+    found = torch.empty(1 << 16, dtype=torch.int64, device="cuda")
+    rows["searchsorted_2^16_in_2^20_i32"] = timed(lambda: ctx.searchsorted(hay, needles, out=found))
+    f = torch.randn(1 << 16, device="cuda", generator=g)
+    ft = torch.empty_like(f)
+    rows["sort_typed_2^16_f32"] = timed(lambda: ctx.sort_typed(ft), lambda i: ft.copy_(f))
     ctx.close()
     buf = io.StringIO()
     sys.argv = ["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "2"]
