@@ -361,6 +361,10 @@ int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, 
  *   leaf_count_sort_kernel (round 2).
  * "mid_leaf": u32 keys: 1 (default) = counting-leaf segments the register-resident kernels do not take (17 Ki .. 128 Ki
  *   keys, crowded ones) are finished by the 16-bit-counter leaf (merge_count_kernel) instead of count_walk_kernel; 0 = never.
+ * "early_leaves": keys without payload: 1 (default) = behind a round that by its plan leaves no parent (every child has at
+ *   most 16 open bits) the counting leaves are enqueued while the round's fix-up still runs -- the lists' lengths come
+ *   from a copy of the counters taken behind collect_kernel -- and the round's summary travels with the leaves' counters;
+ *   0 = every round ends with its own readback (A/B comparisons).  msd_stat "leaves_behind_round" counts such rounds.
  * "merge_leaf": msd_merge_buckets_u32: 0 (default) = by bucket size, 1 = the register-resident leaf, 2 = the 16-bit-counter leaf.
  * "regpart": u64 keys / tuples: 1 (default) = segments of <= 17408 elements take the register-resident
  *   partition pass (csrc/msd_regpart.hpp) instead of a general round, 0 = never.

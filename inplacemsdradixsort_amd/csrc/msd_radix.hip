@@ -48,6 +48,7 @@ struct msd_ctx {
 	size_t lists_cap = 0;
 	void *pinned = nullptr; // small host staging (pinned)
 	size_t pinned_bytes = 0;
+	hipEvent_t ev_early = nullptr; // behind a round's early copy of its counters (SortRun::early_counters)
 	std::string err;
 	bool profiling = false;
 	hipEvent_t ev_start = nullptr;
@@ -67,6 +68,7 @@ struct msd_ctx {
 	int count16 = 1;       // u32 keys: count_place16_kernel in front of count_place_kernel (0: A/B comparisons)
 	int leaf17 = 1;        // u64 keys and tuples: segments of <= 17408 elements are finished by leaf17_kernel (0: tuples: register partition + small leaves, keys: leaf_count_sort_kernel; A/B comparisons)
 	int mid_leaf = 1;      // u32 keys: merge_count_kernel (list mode) in front of count_walk_kernel (0: A/B comparisons)
+	int early_leaves = 1;  // keys only: the counting leaves go behind a last round without waiting for its end (0: A/B comparisons)
 	const uint32_t *order_keys = nullptr; // msd_order_low16_counts_u32 has run on these keys and its tables are still in the slab
 	uint64_t order_n = 0;
 	int merge_leaf = 0;    // msd_merge_buckets_u32: 0 = by bucket size, 1 = merge_place16_kernel, 2 = merge_count_kernel (tests)
@@ -444,7 +446,17 @@ struct RoundBufs {
 	uint32_t *scan_ctr;
 	Segment *next_parents;
 	DirectPlan *plans; // per parent (direct placement)
+	uint32_t *scan_part; // child_scan_part_kernel's sums per (parent, stripe group), where the round's child scan is split
 };
+
+// Workgroups per parent of the round's child scan: 1 = child_scan_kernel, more = the split pair (msd_device.hpp)
+static uint32_t child_scan_groups(const RoundPlan &rp)
+{
+	uint32_t longest = 0;
+	for (const Parent &p : rp.parents) longest = std::max(longest, p.stripe_hi - p.stripe_lo);
+	if (longest < kChildScanSplit || rp.parents.size() > kChildScanSplitParents) return 1;
+	return std::min(kChildScanGroupsMax, (longest + kChildScanGroup - 1) / kChildScanGroup);
+}
 
 // direct placement is tried on rounds of at most this many parents
 constexpr size_t kDirectMaxParents = 4096;
@@ -499,6 +511,8 @@ static void carve_round(Bump &b, const RoundPlan &rp, uint64_t small_max, RoundB
 	// children that stay big: each has > small_max elements
 	rb.next_parents = b.take<Segment>(rp.round_keys / (small_max + 1) + 2);
 	rb.plans = b.take<DirectPlan>(np <= kDirectMaxParents ? np : 1);
+	const uint32_t groups = child_scan_groups(rp);
+	rb.scan_part = b.take<uint32_t>(groups > 1 ? np * groups * 2 * kP : 1);
 }
 
 // ------------------------------------------------------------------ the sort
@@ -803,7 +817,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			}
 			// ---- the general round: plan + upload, A classify, B block metadata + permutation, C cleanup + collect, summary
 			Round r;
-			if ((rc = plan_upload(r)) || (rc = classify(r)) || (rc = permute_blocks(r)) || (rc = cleanup_collect(r)) || (rc = round_summary(r)))
+			if ((rc = plan_upload(r)) || (rc = classify(r)) || (rc = permute_blocks(r)) || (rc = cleanup_collect(r)) ||
+			    (rc = r.leaves_follow ? early_summary(r) : round_summary(r)))
 				return rc;
 		}
 		return MSD_OK;
@@ -877,7 +892,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (!rc) rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + nc + 16, nsmall_host, ncount_host);
 		if (!rc) rc = pinned_reserve(c, std::max<size_t>(on_device ? 0 : np * sizeof(Parent), 256 + 2048 * sizeof(Segment)));
 		if (rc) return rc;
-		LAUNCH(c, round_init_kernel, 1, 256, 0, ctr, d_scr + 16, 0, reinterpret_cast<unsigned long long *>(d_scr + 32), 0, d_scr);
+		LAUNCH(c, round_init_kernel, 1, 256, 0, ctr, d_scr + 16, 0, reinterpret_cast<unsigned long long *>(d_scr + 32), 0, d_scr,
+		       nullptr, nullptr, 0, nullptr, 0); // (this round's plan is uploaded or made on the device below)
 		if (on_device)
 			LAUNCH(c, regpart_plan_kernel, (np + 255) / 256, 256, 0, dev_list, np, small_max, d_parents, ctr);
 		else if ((rc = upload(c, { { d_parents, ps.data(), np * sizeof(Parent) } })))
@@ -914,7 +930,19 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		uint32_t np = 0, ns = 0, nc = 0;
 		bool tried_direct = false; // a direct placement was attempted (its verdict stays on the device until the summary)
 		bool hist_checks = false;  // its exact histogram pass carries the check behind a sampled leading-bit skip
+		bool leaves_follow = false; // by the plan no child can become a parent: the counters travel early, the leaves go behind at once
 	};
+	// where the early copy of a round's counters lands in the staging buffer: behind the summary's own pieces
+	static constexpr size_t kReadAhead = 2048, kSegOff = 256, kVresOff = kSegOff - 2 * sizeof(unsigned long long);
+	static constexpr size_t kEarlyOff = kSegOff + kReadAhead * sizeof(Segment), kStagingBytes = kEarlyOff + sizeof(Counters);
+	static_assert(sizeof(Counters) <= kVresOff, "counters and the OR/AND words share the head of the staging buffer");
+	// a round whose fix-up is still running when the host went on to the leaves: its summary comes with the leaves' counters
+	struct Pending {
+		bool open = false;
+		int round = 0;
+		uint32_t np = 0, ns = 0, nc = 0;
+		uint64_t nslots = 0;
+	} pending;
 	int plan_upload(Round &r)
 	{
 		plan_round<K, V>(cur, small_max, c->sm_count, r.rp, count_bits, job.single_pass() ? job.width : 0u, job.splitters ? job.nsplit : 0u);
@@ -924,17 +952,31 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				    first && !job.single_pass() ? round_bytes_estimate<K, V>(n, c->sm_count) : 0, first);
 		if (rc) return rc;
 		r.np = (uint32_t)r.rp.parents.size(), r.ns = (uint32_t)r.rp.stripes.size(), r.nc = r.rp.nchildren;
+		// A keys-only round in which no parent leaves more open bits than one counting pass takes has no next parents
+		// (route_child; a full big list or a child of 2^32 keys would make one: the early counters show it).  Not behind an
+		// unconfirmed leading-bit skip: no leaf may run before the check.
+		if constexpr (!HV) {
+			r.leaves_follow = !job.single_pass() && !unverified && c->early_leaves;
+			for (size_t i = 0; i < r.np && r.leaves_follow; ++i) r.leaves_follow = r.rp.parents[i].shift <= count_bits;
+		}
 		// every child of this round may become a leaf
 		if ((rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + r.nc + 16, nsmall_host, ncount_host))) return rc;
-		{ // per-round counters, per-parent plans, scan state: one launch
+		{ // per-round counters, per-parent plans, scan state, and the plan itself from the staging buffer: one launch
+			static_assert(sizeof(Parent) % 4 == 0 && sizeof(Stripe) % 4 == 0, "the plan travels as 32-bit words");
 			const uint64_t plan_words = (r.np <= kDirectMaxParents ? r.np : 1) * sizeof(DirectPlan) / sizeof(uint32_t);
 			const uint64_t ntiles = (r.nc + kScanTile - 1) / kScanTile + 1;
-			const unsigned grid = (unsigned)std::min<uint64_t>(1024, (std::max(plan_words, ntiles) + 255) / 256 + 1);
-			LAUNCH(c, round_init_kernel, grid, 256, 0, ctr, reinterpret_cast<uint32_t *>(r.rb.plans), plan_words, r.rb.scan_state, ntiles, r.rb.scan_ctr);
+			const uint64_t parent_words = r.np * sizeof(Parent) / 4, stripe_words = r.ns * sizeof(Stripe) / 4;
+			if ((rc = pinned_reserve(c, std::max(kStagingBytes, r.np * sizeof(Parent) + r.ns * sizeof(Stripe))))) return rc;
+			HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
+			memcpy(c->pinned, r.rp.parents.data(), r.np * sizeof(Parent));
+			memcpy((char *)c->pinned + r.np * sizeof(Parent), r.rp.stripes.data(), r.ns * sizeof(Stripe));
+			void *staged = nullptr; // (pinned memory is mapped: an error here, never a guess at the address)
+			HIPCHK(c, hipHostGetDevicePointer(&staged, c->pinned, 0));
+			const unsigned grid = (unsigned)std::min<uint64_t>(1024, (std::max({ plan_words, ntiles, parent_words, stripe_words }) + 255) / 256 + 1);
+			LAUNCH(c, round_init_kernel, grid, 256, 0, ctr, reinterpret_cast<uint32_t *>(r.rb.plans), plan_words, r.rb.scan_state, ntiles, r.rb.scan_ctr,
+			       static_cast<const uint32_t *>(staged), reinterpret_cast<uint32_t *>(r.rb.parents), parent_words,
+			       reinterpret_cast<uint32_t *>(r.rb.stripes), stripe_words);
 		}
-		if ((rc = pinned_reserve(c, r.np * sizeof(Parent) + r.ns * sizeof(Stripe))) ||
-		    (rc = upload(c, { { r.rb.parents, r.rp.parents.data(), r.np * sizeof(Parent) }, { r.rb.stripes, r.rp.stripes.data(), r.ns * sizeof(Stripe) } })))
-			return rc;
 		phase_mark(c, "plan+upload");
 		return MSD_OK;
 	}
@@ -1017,7 +1059,15 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		const uint32_t np = r.np, ns = r.ns, nc = r.nc;
 		const uint8_t *full_map = r.tried_direct ? slot_full : nullptr;
 		const uint32_t force_map = c->direct_mode == 2 ? 1u : 0u;
-		LAUNCH(c, (child_scan_kernel<B>), np, 1024, 0, rb.parents, rb.fb, rb.lo_cnt, rb.lo_dst, rb.ca);
+		if (const uint32_t groups = child_scan_groups(r.rp); groups > 1) {
+			LAUNCH(c, child_scan_part_kernel, dim3(np, groups), 256, 0, rb.parents, rb.fb, rb.lo_cnt, rb.scan_part);
+			LAUNCH(c, (child_scan_split_kernel<B>), dim3(np, groups), 256, 0, rb.parents, rb.lo_cnt, rb.scan_part, rb.lo_dst, rb.ca);
+			add_stat(c, "child_scan_split_rounds", 1);
+		} else
+			LAUNCH(c, (child_scan_kernel<B>), np, 1024, 0, rb.parents, rb.fb, rb.lo_cnt, rb.lo_dst, rb.ca);
+		// every child's start and count are final: the children go to the next round or the leaf lists now, so that the
+		// host can have the lists' lengths while the fix-up runs
+		if (int rc = collect(r)) return rc;
 		LAUNCH(c, (slot_classify_kernel<false>), ns * kSlotParts, 256, 0, rb.stripes, rb.parents, block_map, rb.nfull, rb.ca, rb.list, rb.holes, ctr,
 		       full_map, force_map);
 		LAUNCH(c, list_prepare_kernel, (nc + 255) / 256, 256, 0, nc, rb.ca, ctr, std::min<uint64_t>(r.rp.nslots, 0xFFFFFFFFu), 2 * nc + kMinChains);
@@ -1037,21 +1087,18 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		// -- 2^30 Zipf keys: 1.3 ms where a wave's own work takes 0.7.)
 		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * c->chains_per_cu[HV ? 2 : sizeof(K) == 8 ? 1 : 0],
 								 std::max<uint64_t>(1, (r.rp.nslots + 255) / 256));
-		LAUNCH(c, list_pack_kernel, (nc + 255) / 256, 256, 0, nc, rb.ca);
 		LAUNCH(c, (chains_kernel<K, V>), grid, 256, 0, rb.ca, rb.list, rb.holes, ctr, keys, vals, rb.xkeys, rb.xvals, n / B, 4 * nc + kMinChains);
-		LAUNCH(c, chains_verify_kernel, (nc + 255) / 256, 256, 0, nc, rb.ca, ctr);
 		phase_mark(c, "B block permute");
 		return MSD_OK;
 	}
 
-	// ---- C: cleanup, then the children to the next round or the leaf lists
-	int cleanup_collect(Round &r)
+	// ---- the children to the next round or the leaf lists (behind the child scan); a round that the leaves follow sends a
+	// copy of the counters to the host behind it -- the kernels behind the copy do not wait for the host
+	int collect(Round &r)
 	{
 		const RoundBufs &rb = r.rb;
 		const uint32_t np = r.np, nc = r.nc;
 		const bool sp = job.single_pass();
-		LAUNCH(c, (cleanup_kernel<K, V>), r.ns, 256, 0, rb.stripes, rb.parents, rb.lo_cnt, rb.lo_off, rb.lo_dst, rb.ca, rb.lo_keys, rb.lo_vals, keys, vals);
-		LAUNCH(c, (excess_kernel<K, V>), nc, 64, 0, nc, rb.ca, rb.xkeys, rb.xvals, keys, vals);
 		uint32_t wmax = 1;
 		for (size_t i = 0; i < np; ++i) wmax = std::max(wmax, r.rp.parents[i].width);
 		const uint32_t small_cap = (uint32_t)std::min<size_t>(c->lists_cap, 0xFFFFFFFFu);
@@ -1060,7 +1107,62 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		       small_cap, sp ? 0u : count_bits,
 		       rb.next_parents, small(), small_count(), (HV || sp) ? nullptr : big, big_cap, ctr,
 		       (sp && job.counts) ? job.counts : nullptr, job.splitters ? job.nsplit + 1u : nc, job.stop_bits);
+		if (r.leaves_follow) {
+			if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
+			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kEarlyOff, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+			HIPCHK(c, hipEventRecord(c->ev_early, c->stream));
+		}
+		return MSD_OK;
+	}
+
+	// ---- C: cleanup (with it: the check that the chains used up every list, the excess blocks)
+	int cleanup_collect(Round &r)
+	{
+		const RoundBufs &rb = r.rb;
+		LAUNCH(c, (cleanup_kernel<K, V>), r.ns, 256, 0, rb.stripes, rb.parents, rb.lo_cnt, rb.lo_off, rb.lo_dst, rb.ca, rb.lo_keys, rb.lo_vals, keys, vals,
+		       rb.xkeys, rb.xvals, ctr);
 		phase_mark(c, "C cleanup");
+		return MSD_OK;
+	}
+
+	// what a round's counters say once its last kernel has run
+	int round_errors(const Counters &hc, int rnd, uint32_t np, uint32_t ns, const char *direct)
+	{
+		return fail(c, MSD_EINTERNAL, "round %d: %u internal invariant violations (checks 0x%x: bit = site of msd_note_error in csrc/; 0 = a scan tile's look-back timed out; "
+					      "%u parents, %u stripes, direct placement %s)",
+			    rnd, hc.errors, hc.err_sites, np, ns, direct);
+	}
+	void round_stats(const Counters &hc, uint32_t np, uint32_t ns, uint32_t nc, uint64_t nslots)
+	{
+		add_stat(c, "rounds", 1);
+		add_stat(c, "parents", np);
+		add_stat(c, "stripes", ns);
+		add_stat(c, "children", nc);
+		add_stat(c, "slots", nslots);
+		add_stat(c, "holes", hc.nholes);
+		set_stat(c, "chain_steps", hc.chain_steps);
+		set_stat(c, "excess_blocks", hc.nexcess);
+	}
+
+	// ---- the summary of a round that the leaves follow: the lists' lengths from the early copy of the counters, while the
+	// round's fix-up still runs; the rest of the summary (errors, holes, chain steps) comes with the leaves' counters
+	// (count_leaves).  If the round left a parent after all, or no counting leaf: the ordinary summary.
+	int early_summary(Round &r)
+	{
+		HIPCHK(c, hipEventSynchronize(c->ev_early));
+		Counters hc;
+		memcpy(&hc, (char *)c->pinned + kEarlyOff, sizeof hc);
+		if (hc.next_parents || hc.ncount == 0 || hc.errors) return round_summary(r);
+		prev_direct = r.tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
+		if (prev_direct) add_stat(c, "direct_rounds", 1);
+		nsmall_host = hc.nsmall;
+		ncount_host = hc.ncount;
+		nbig_host = hc.nbig;
+		pending = { true, round, r.np, r.ns, r.nc, r.rp.nslots };
+		add_stat(c, "leaves_behind_round", 1);
+		cur.clear();
+		phase_mark(c, "readback");
+		++round;
 		return MSD_OK;
 	}
 
@@ -1068,17 +1170,13 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	// first kReadAhead next parents travel with the counters (more than that only on the odd input: fetched then)
 	int round_summary(Round &r)
 	{
-		constexpr size_t kReadAhead = 2048, kSegOff = 256, kVresOff = kSegOff - 2 * sizeof(unsigned long long);
-		static_assert(sizeof(Counters) <= kVresOff, "counters and the OR/AND words share the head of the staging buffer");
 		const size_t np_cap = r.rp.round_keys / (small_max + 1) + 2, ahead = job.single_pass() ? 0 : std::min(np_cap, kReadAhead);
 		Counters hc;
-		int rc = pinned_reserve(c, kSegOff + kReadAhead * sizeof(Segment));
+		int rc = pinned_reserve(c, kStagingBytes);
 		if (rc || (rc = read_counters(c, ctr, hc, { { kSegOff, r.rb.next_parents, ahead * sizeof(Segment) },
 							    { kVresOff, vres, r.hist_checks ? 2 * sizeof(unsigned long long) : 0 } })))
 			return rc;
-		if (hc.errors) return fail(c, MSD_EINTERNAL, "round %d: %u internal invariant violations (checks 0x%x: bit = site of msd_note_error in csrc/; 0 = a scan tile's look-back timed out; "
-						  "%u parents, %u stripes, direct placement %s)",
-					   round, hc.errors, hc.err_sites, r.np, r.ns, r.tried_direct ? (hc.direct_uneven ? "declined" : "used") : "not tried");
+		if (hc.errors) return round_errors(hc, round, r.np, r.ns, r.tried_direct ? (hc.direct_uneven ? "declined" : "used") : "not tried");
 		if (r.hist_checks) {
 			const unsigned long long *h = (const unsigned long long *)((char *)c->pinned + kVresOff);
 			if ((h[0] ^ h[1]) & claimed_const) { // some key differs in a bit the sample found constant
@@ -1093,13 +1191,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		nsmall_host = hc.nsmall;
 		ncount_host = hc.ncount;
 		nbig_host = hc.nbig;
-		add_stat(c, "rounds", 1);
-		add_stat(c, "parents", r.np);
-		add_stat(c, "stripes", r.ns);
-		add_stat(c, "children", r.nc);
-		add_stat(c, "slots", r.rp.nslots);
-		add_stat(c, "holes", hc.nholes);
-		set_stat(c, "chain_steps", hc.chain_steps);
+		round_stats(hc, r.np, r.ns, r.nc, r.rp.nslots);
 		cur.clear();
 		if (job.single_pass()) return MSD_OK;
 		bool stays_on_device = false;
@@ -1145,6 +1237,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (top > 0 && (uint32_t)top > job.stop_bits) cur.push_back({ 0, n, (uint32_t)top, 0 });
 		nsmall_host = ncount_host = nbig_host = dev_np = 0;
 		round = 0;
+		pending.open = false;
 		prev_direct = unverified = false;
 		HIPCHK(c, hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
 		return MSD_OK;
@@ -1189,7 +1282,16 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// byte-counter overflows of segments above the LDS-sort capacity joined the big list
 			Counters hc;
 			if ((rc = read_counters(c, ctr, hc))) return rc;
+			if (pending.open) { // the last round's summary travels with the leaves' counters (early_summary)
+				pending.open = false;
+				// (every check but count_walk_kernel's, site 7, is a round's; a scan tile's time-out leaves no site)
+				if (hc.errors && (hc.err_sites & ~0x80u || !hc.err_sites))
+					return round_errors(hc, pending.round, pending.np, pending.ns, prev_direct ? "used" : "not used");
+				round_stats(hc, pending.np, pending.ns, pending.nc, pending.nslots);
+			}
 			if (hc.errors) return fail(c, MSD_EINTERNAL, "counting leaf: %u segments could not be queued", hc.errors);
+			set_stat(c, "count16_rejected", hc.nslow16);     // segments count_place16_kernel left to count_place_kernel
+			set_stat(c, "count_slow_segments", hc.nslow);     // segments the register-resident kernels left to the 16-bit-counter leaf / the walk
 			nbig_host = hc.nbig;
 			nfallback_known = hc.nfallback;
 		}
@@ -1545,6 +1647,7 @@ int msd_destroy(msd_ctx *c)
 	if (c->fix_plan) (void)hipFree(c->fix_plan);
 	if (c->pinned) (void)hipHostFree(c->pinned);
 	if (c->ev_start) (void)hipEventDestroy(c->ev_start);
+	if (c->ev_early) (void)hipEventDestroy(c->ev_early);
 	for (auto e : c->ev_pool) (void)hipEventDestroy(e);
 	delete c;
 	return MSD_OK;
@@ -2925,6 +3028,8 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 		c->leaf17 = value != 0;
 	} else if (!strcmp(name, "mid_leaf")) {
 		c->mid_leaf = value != 0;
+	} else if (!strcmp(name, "early_leaves")) {
+		c->early_leaves = value != 0;
 	} else if (!strcmp(name, "merge_leaf")) {
 		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "merge_leaf must be 0, 1 or 2");
 		c->merge_leaf = (int)value;
