@@ -732,6 +732,73 @@ class MsdContext:
         +inf, -NaN below -inf).  ``boundaries`` is 1-D, contiguous and ascending as :meth:`sort_typed` leaves it."""
         return self.searchsorted(boundaries, values, right=right)
 
+    # ---- merge of two sorted arrays (include/msd_merge_hip.h)
+    def merge_sorted_limits(self, key_bytes: int) -> int:
+        """``tile`` of ``msd_merge_sorted_limits``: the elements (of both inputs together) one workgroup takes for that
+        key width."""
+        t = C.c_uint64()
+        if self._L.msd_merge_sorted_limits(int(key_bytes), C.byref(t)) != 0:
+            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
+        return int(t.value)
+
+    def merge_sorted(self, a, b, values_a=None, values_b=None, origin: bool = False, out=None, out_values=None, out_origin=None):
+        """The merge of two sorted tensors: ``a`` and ``b`` are 1-D, contiguous, of the same dtype (float32, int32,
+        float64, int64, uint32 or uint64) and each ascending as :meth:`sort_typed` leaves it (trusted); the result holds
+        the ``a.numel() + b.numel()`` keys in ascending order -- what sorting ``torch.cat([a, b])`` gives, but each input
+        is read once and nothing is sorted again.
+
+        The merge is stable: among equal keys all of A's come before all of B's, and within one side equal keys keep
+        their order.  The keys are bit-exact.  Floats are ordered by IEEE-754 totalOrder on their bits, as everywhere in
+        this library: -0.0 lies below +0.0 and the two stay apart, a NaN is an ordinary key (+NaN above +inf, -NaN below
+        -inf) and keeps its payload.
+
+        ``values_a`` and ``values_b`` (both or neither; 1-D, contiguous, 8-byte elements of one dtype -- int64, uint64 or
+        float64 --, as long as their keys) travel with their keys.  ``origin=True`` (or ``out_origin``) also gives, per position of the result, the
+        index in ``torch.cat([a, b])`` of the element that landed there (int64): the stable argsort of the
+        concatenation, which :meth:`reduce_runs` takes as ``positions``.  Returns ``merged``, or the tuple
+        ``(merged[, values][, origin])`` in that order.  ``out``, ``out_values`` and ``out_origin`` (contiguous, shape
+        ``(n + m,)``, the dtype of the keys, of the values, int64) receive the results and must not overlap an input:
+        the merge is not in place.  The inputs are not modified.  Nothing waits on the host."""
+        torch = _torch()
+        kt = self._key_type(a)
+        if b.dtype != a.dtype:
+            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
+        if a.dim() != 1 or b.dim() != 1:
+            raise MsdError("merge_sorted takes 1-D tensors")
+        if (values_a is None) != (values_b is None):
+            raise MsdError("values_a and values_b are given both or neither")
+        tensors = [a, b] + ([values_a, values_b] if values_a is not None else [])
+        if values_a is not None:
+            if values_a.dim() != 1 or values_b.dim() != 1:
+                raise MsdError("merge_sorted takes 1-D tensors")
+            if values_a.dtype != values_b.dtype or values_a.dtype not in [torch.int64, torch.float64] + ([torch.uint64] if hasattr(torch, "uint64") else []):
+                raise MsdError(f"the values must have 8-byte elements of one dtype (int64, uint64 or float64), not {values_a.dtype} and {values_b.dtype}")
+            if values_a.numel() != a.numel() or values_b.numel() != b.numel():
+                raise MsdError("the values must be as long as their keys")
+        elif out_values is not None:
+            raise MsdError("out_values without values_a and values_b")
+        if any(not t.is_contiguous() for t in tensors):
+            raise MsdError("merge_sorted takes contiguous tensors")
+        n, m = a.numel(), b.numel()
+        want_origin = origin or out_origin is not None
+        wanted = [("out", out, a.dtype)]
+        if values_a is not None:
+            wanted.append(("out_values", out_values, values_a.dtype))
+        if want_origin:
+            wanted.append(("out_origin", out_origin, torch.int64))
+        for name, t, dt in wanted:
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (n + m,) or not t.is_contiguous()):
+                raise MsdError(f"{name} must be a contiguous {dt} tensor of shape {(n + m,)}")
+        self._on_gpu(*tensors, out, out_values, out_origin)
+        res = [t if t is not None else torch.empty(n + m, dtype=dt, device=a.device) for _, t, dt in wanted]
+        ptr = {name: C.c_void_p(t.data_ptr()) for (name, _, _), t in zip(wanted, res)}
+        null = C.c_void_p(0)
+        self._ok(self._L.msd_merge_sorted(self._h, C.c_void_p(a.data_ptr()), n, C.c_void_p(b.data_ptr()), m, kt,
+                                          C.c_void_p(values_a.data_ptr()) if values_a is not None else null,
+                                          C.c_void_p(values_b.data_ptr()) if values_b is not None else null,
+                                          ptr["out"], ptr.get("out_values", null), ptr.get("out_origin", null)))
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))

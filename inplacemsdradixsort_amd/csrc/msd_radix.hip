@@ -11,6 +11,7 @@
 #include "msd_runs.hpp"
 #include "msd_reduce.hpp"
 #include "msd_search.hpp"
+#include "msd_merge2.hpp"
 #include "msd_args.hpp" // the argument rules, each stated once (host only)
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
@@ -18,6 +19,7 @@
 #include "../../include/msd_runs_hip.h"
 #include "../../include/msd_reduce_hip.h"
 #include "../../include/msd_search_hip.h"
+#include "../../include/msd_merge_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -2883,6 +2885,70 @@ int msd_search_sorted(msd_ctx *c, const void *d_sorted, int key_type, uint64_t n
 		return with_flag(d_positions != nullptr, [&](auto pos) {
 			typedef decltype(k0) K;
 			return search_sorted_impl<K, decltype(pos)::value>(c, (const K *)d_sorted, key_type, n, (const K *)d_needles, m, merge, (uint32_t)side, d_positions, d_out);
+		});
+	});
+}
+
+} // extern "C"
+
+// ---- merge of two sorted arrays (msd_merge2.hpp)
+
+// The splits, then the tiles, one behind the other on the stream; the scratch -- one split per tile plus one -- is the
+// slab's, as for msd_search_sorted.  Nothing is read back.
+template <typename K, bool VALS, bool ORIGIN>
+static int merge_sorted_impl(msd_ctx *c, const K *a, uint64_t n, const K *b, uint64_t m, int key_type, const uint64_t *vals_a, const uint64_t *vals_b, K *out,
+			     uint64_t *out_vals, uint64_t *out_origin)
+{
+	const KeyCodec<K> cd = key_codec<K>(key_type);
+	const uint64_t tiles = (n + m + MergeCfg<K>::TILE - 1) / MergeCfg<K>::TILE; // (n + m < 2^37: at most 2^26)
+	uint64_t *splits = nullptr;
+	if (int rc = slab_carve(c, [&](Bump &bump) { splits = bump.take<uint64_t>(tiles + 1); })) return rc;
+	phase_begin(c);
+	LAUNCH(c, (merge_split_kernel<K>), (unsigned)((tiles + 1 + kMergeTh - 1) / kMergeTh), kMergeTh, 0, a, n, b, m, cd, tiles, splits);
+	LAUNCH(c, (merge_tile_kernel<K, VALS, ORIGIN>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, splits, vals_a, vals_b, out, out_vals, out_origin);
+	phase_mark(c, "merge_sorted");
+	phase_end(c);
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_merge_sorted_limits(int key_bytes, uint64_t *tile)
+{
+	if ((key_bytes != 4 && key_bytes != 8) || !tile) return MSD_EINVAL;
+	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)MergeCfg<decltype(k0)>::TILE; });
+	return MSD_OK;
+}
+
+int msd_merge_sorted(msd_ctx *c, const void *d_a, uint64_t n, const void *d_b, uint64_t m, int key_type, const uint64_t *d_vals_a, const uint64_t *d_vals_b,
+		     void *d_out, uint64_t *d_out_vals, uint64_t *d_out_origin)
+{
+	if (!c) return MSD_EINVAL;
+	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key_type");
+	if ((n || m) && !d_out) return fail(c, MSD_EINVAL, "null d_out pointer");
+	if (n && !d_a) return fail(c, MSD_EINVAL, "null d_a pointer");
+	if (m && !d_b) return fail(c, MSD_EINVAL, "null d_b pointer");
+	if (d_out_vals && ((n && !d_vals_a) || (m && !d_vals_b))) return fail(c, MSD_EINVAL, "d_out_vals without d_vals_a or d_vals_b");
+	if (!d_out_vals && (d_vals_a || d_vals_b)) return fail(c, MSD_EINVAL, "d_vals_a or d_vals_b without d_out_vals");
+	// the extents: the inputs, then the outputs (a count beyond 2^36 is refused behind the alignment rule; until then n + m saturates)
+	const uint32_t es = (uint32_t)key_type_bytes(key_type);
+	uint64_t total = 0;
+	if (__builtin_add_overflow(n, m, &total)) total = UINT64_MAX;
+	const Span buf[7] = { span_of(d_a, n, es),      span_of(d_b, m, es),          span_of(d_vals_a, n, 8),        span_of(d_vals_b, m, 8),
+			      span_of(d_out, total, es), span_of(d_out_vals, total, 8), span_of(d_out_origin, total, 8) };
+	if (first_misaligned(buf) >= 0)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_a, d_b, d_out: the key's width; the others: 8)");
+	if (n >= kMaxElems || m >= kMaxElems) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^36 elements each");
+	if (total && outputs_overlap(buf, 4)) return fail(c, MSD_EINVAL, "d_out, d_out_vals and d_out_origin must not overlap an input or each other (the merge is not in place)");
+	if (total == 0) return MSD_OK; // nothing to write
+	HIPCHK(c, hipSetDevice(c->device));
+	return with_width((int)es, [&](auto k0) {
+		return with_flag(d_out_vals != nullptr, [&](auto vals) {
+			return with_flag(d_out_origin != nullptr, [&](auto origin) {
+				typedef decltype(k0) K;
+				return merge_sorted_impl<K, decltype(vals)::value, decltype(origin)::value>(c, (const K *)d_a, n, (const K *)d_b, m, key_type, d_vals_a, d_vals_b,
+													 (K *)d_out, d_out_vals, d_out_origin);
+			});
 		});
 	});
 }
