@@ -365,6 +365,12 @@ int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, 
  *   most 16 open bits) the counting leaves are enqueued while the round's fix-up still runs -- the lists' lengths come
  *   from a copy of the counters taken behind collect_kernel -- and the round's summary travels with the leaves' counters;
  *   0 = every round ends with its own readback (A/B comparisons).  msd_stat "leaves_behind_round" counts such rounds.
+ * "early_plan": 1 (default) = behind a round that is not the last the next round is planned from a copy of the counters and
+ *   the first next parents taken behind collect_kernel, and enqueued while the round's fix-up still runs; the round's own
+ *   summary is parked on the device and travels with the next readback.  The round ends with its own readback instead
+ *   if it left no parent or more than travelled, if its next parents stay on the device or take a register-resident
+ *   pass, if it carries the check behind a sampled bit skip, or if a buffer of the next round would have to grow;
+ *   0 = always (A/B comparisons).  msd_stat "rounds_planned_early" counts the rounds planned this way.
  * "merge_leaf": msd_merge_buckets_u32: 0 (default) = by bucket size, 1 = the register-resident leaf, 2 = the 16-bit-counter leaf.
  * "regpart": u64 keys / tuples: 1 (default) = segments of <= 17408 elements take the register-resident
  *   partition pass (csrc/msd_regpart.hpp) instead of a general round, 0 = never.

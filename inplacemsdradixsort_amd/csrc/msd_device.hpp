@@ -699,15 +699,73 @@ __global__ __launch_bounds__(256) void slot_classify_kernel(const Stripe *__rest
 	// aligned 8-byte load per map (byte loads are processed lane by lane: sixteen of them per 8 slots
 	// made the kernel's time), two groups in flight; the few slots before the first 8-aligned one and
 	// after the last whole group go one per thread.
+	const uint32_t lead = min(nsl, (8u - (st.slot_lo & 7u)) & 7u);
+	const uint32_t ngr = (nsl - lead) / 8u, rest = lead + 8u * ngr;
+	// Direct placement leaves nearly every slot where it belongs, and the bodies below do nothing for such a slot -- but
+	// one odd slot (stolen, empty, or in the error zone of a sampled boundary: about one in 64) sends its thread through
+	// the owner search and the fetch-adds, and with 8 slots unrolled per thread and 128 groups per wave iteration some
+	// lane of a wave is on that path at nearly every slot: the sweeps ran at the speed of the rare path.  So one pass
+	// marks the groups that are not SETTLED -- settled: all eight slots full, all eight map bytes one bucket d < W, and
+	// the eight slots inside d's interior, which is exactly when own == d and full hold for each of them, so that no
+	// body counts, records or places anything -- and the sweeps walk the marked groups alone, a slot per lane.
+	// s_grp holds every group of the longest part there is (a stripe has at most 2^20 elements, the last one of a parent
+	// half as many again, a block 32 at least); a longer part would be swept in full like a streaming round's.
+	constexpr uint32_t kMarkCap = (3u << 19) / 32u / 8u / kSlotParts + 2u;
+	static_assert(kMarkCap <= 0x10000u, "group indices are kept in 16 bits");
+	__shared__ uint16_t s_grp[kMarkCap];
+	__shared__ uint32_t s_nmark;
+	const bool marked = slot_full != nullptr && ngr <= kMarkCap; // (uniform) streaming rounds: nearly every block is misplaced
+	if (marked) {
+		if (tid == 0) s_nmark = 0;
+		__syncthreads();
+		const uint8_t *bm0 = block_map + (size_t)st.slot_lo + lead, *sf0 = slot_full + (size_t)st.slot_lo + lead;
+		for (uint32_t base = 0; base < ngr; base += 4 * 256) { // (uniform trip count: the ballots below see whole waves)
+			uint2 bm[4], sf[4];
+#pragma unroll
+			for (int k = 0; k < 4; ++k) { // branch-free: a thread without a k-th group re-reads the last one
+				const uint32_t g = min(base + k * 256u + tid, ngr - 1u);
+				bm[k] = *reinterpret_cast<const uint2 *>(bm0 + 8u * g);
+				sf[k] = *reinterpret_cast<const uint2 *>(sf0 + 8u * g);
+			}
+#pragma unroll
+			for (int k = 0; k < 4; ++k) {
+				const uint32_t g = base + k * 256u + tid, d = bm[k].x & 0xFFu, i0 = st.slot_lo + lead + 8u * g;
+				const uint32_t dd = min(d, W - 1u);
+				const bool same = bm[k].x == d * 0x01010101u && bm[k].y == bm[k].x && d < W;
+				const uint32_t z = ((sf[k].x - 0x01010101u) & ~sf[k].x) | ((sf[k].y - 0x01010101u) & ~sf[k].y); // bit 7 of a byte set: some byte is 0
+				const bool settled = same && (z & 0x80808080u) == 0 && s_is[dd] <= i0 && i0 + 8u <= s_ie[dd];
+				const bool odd = g < ngr && !settled;
+				const uint64_t m = __ballot(odd);
+				if (m) { // (wave-uniform) one fetch-add per wave
+					const uint32_t lane = tid & 63u;
+					uint32_t at = 0;
+					if (lane == 0) at = atomicAdd(&s_nmark, (uint32_t)__popcll(m));
+					at = __shfl(at, 0);
+					if (odd) s_grp[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)g;
+				}
+			}
+		}
+		__syncthreads();
+	}
+	const uint32_t nmarked = marked ? 8u * s_nmark : 0u;
 	auto sweep = [&](auto body) {
-		const uint32_t lead = min(nsl, (8u - (st.slot_lo & 7u)) & 7u);
-		const uint32_t ngr = (nsl - lead) / 8u, rest = lead + 8u * ngr;
 		auto one = [&](uint32_t o) {
 			const uint32_t i = st.slot_lo + o;
 			body(i, (uint32_t)block_map[i], slot_full ? slot_full[i] != 0 : o < nf);
 		};
 		if (tid < lead) one(tid);
 		if (tid < nsl - rest) one(rest + tid);
+		if (marked) { // (uniform) the marked groups, one slot per lane: the aligned word that holds the slot's byte
+			for (uint32_t j = tid; j < nmarked; j += 256) {
+				const uint32_t o = lead + 8u * s_grp[j >> 3] + (j & 7u);
+				const size_t at = ((size_t)st.slot_lo + o) & ~(size_t)3;
+				const uint32_t sh = 8u * (j & 3u); // (slot_lo + lead is a multiple of 8)
+				const uint32_t b = (*reinterpret_cast<const uint32_t *>(block_map + at) >> sh) & 0xFFu;
+				const uint32_t f = (*reinterpret_cast<const uint32_t *>(slot_full + at) >> sh) & 0xFFu;
+				body(st.slot_lo + o, b, f != 0);
+			}
+			return;
+		}
 		for (uint32_t g0 = tid; g0 < ngr; g0 += 2 * 256) {
 			uint2 bm[2], sf[2];
 #pragma unroll
@@ -1224,19 +1282,47 @@ __global__ __launch_bounds__(256) void cleanup_kernel(const Stripe *__restrict__
 		chains_verify(ca, pa.child_base + tid, fl, ctr);
 		if (fl & 2u) s_ex[atomicAdd(&s_nex, 1u)] = tid;
 	}
-	const uint32_t total = s_off[kP];
-	for (uint32_t idx = tid; idx < total; idx += 256) {
-		// last d with s_off[d] <= idx
-		uint32_t lo = 0, hi = kP;
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (s_off[mid] <= idx) lo = mid; else hi = mid;
+	// The leftovers of one bucket are a run, in lo_keys and (but for the step from the child's head to its tail, which
+	// fringe_pos takes per key) at the destination: a half-wave takes a bucket and copies its run, four buckets' loads in
+	// flight per thread before their stores.  (A search for its bucket per key -- eight dependent LDS reads -- made this
+	// kernel's time.)  A run is shorter than B + the head and tail keys; what a half-wave's first step leaves goes in a loop.
+	{
+		constexpr uint32_t LG = 32, NB = 4, NG = 256 / LG;
+		const uint32_t grp = tid / LG, l = tid % LG;
+		for (uint32_t d0 = grp; d0 < kP; d0 += NG * NB) { // (kP is a multiple of NG * NB)
+			K k[NB];
+			uint64_t v[NB];
+			uint32_t off[NB], cnt[NB];
+#pragma unroll
+			for (uint32_t q = 0; q < NB; ++q) {
+				const uint32_t d = d0 + q * NG;
+				off[q] = s_off[d];
+				cnt[q] = s_off[d + 1] - off[q];
+				if (l < cnt[q]) {
+					k[q] = lo_keys[st.lo_base + off[q] + l];
+					if constexpr (HV) v[q] = lo_vals[st.lo_base + off[q] + l];
+				}
+			}
+#pragma unroll
+			for (uint32_t q = 0; q < NB; ++q) {
+				const uint32_t d = d0 + q * NG;
+				if (l < cnt[q]) {
+					const uint64_t p = fringe_pos<B>(s_start[d], s_is[d], s_I[d], (uint64_t)s_dst[d] + l);
+					keys[p] = k[q];
+					if constexpr (HV) vals[p] = v[q];
+				}
+			}
+#pragma unroll
+			for (uint32_t q = 0; q < NB; ++q) {
+				const uint32_t d = d0 + q * NG;
+				for (uint32_t j = l + LG; j < cnt[q]; j += LG) {
+					const uint64_t p = fringe_pos<B>(s_start[d], s_is[d], s_I[d], (uint64_t)s_dst[d] + j);
+					keys[p] = lo_keys[st.lo_base + off[q] + j];
+					if constexpr (HV) vals[p] = lo_vals[st.lo_base + off[q] + j];
+				}
+			}
 		}
-		const uint32_t d = lo;
-		const uint64_t o = (uint64_t)s_dst[d] + (idx - s_off[d]);
-		const uint64_t p = fringe_pos<B>(s_start[d], s_is[d], s_I[d], o);
-		keys[p] = lo_keys[st.lo_base + idx];
-		if constexpr (HV) vals[p] = lo_vals[st.lo_base + idx];
+		static_assert(kP % (NG * NB) == 0, "every bucket has its half-wave");
 	}
 	if (!first) return;
 	__syncthreads();
@@ -1923,13 +2009,17 @@ namespace msd {
 // It also brings the host's plan over: `staged` (pinned host memory, read through its device address; nullptr: nothing to
 // bring) holds the round's parents and behind them its stripes, as 32-bit words.  A copy enqueued between two kernels
 // cost 35 us of idle GPU around it; these few tens of KiB read across the bus take less than the launch.
+// `park` (nullptr: nobody wants them): the round that ended just in front of this launch was not summarised by the host --
+// it planned this round while that one's fix-up ran -- so its counters are put aside before they are cleared; the host
+// reads them with its next readback.
 __global__ __launch_bounds__(256) void round_init_kernel(Counters *__restrict__ ctr, uint32_t *__restrict__ plan_words,
 	uint64_t nplan_words, unsigned long long *__restrict__ scan_state, uint64_t ntiles, uint32_t *__restrict__ scan_ctr,
 	const uint32_t *__restrict__ staged, uint32_t *__restrict__ parents_out, uint64_t parent_words,
-	uint32_t *__restrict__ stripes_out, uint64_t stripe_words)
+	uint32_t *__restrict__ stripes_out, uint64_t stripe_words, Counters *__restrict__ park)
 {
 	const uint64_t i0 = (uint64_t)blockIdx.x * 256 + threadIdx.x, step = (uint64_t)gridDim.x * 256;
 	if (i0 == 0) {
+		if (park) *park = *ctr;
 		ctr->nholes = 0;
 		ctr->hole_cursor = 0;
 		ctr->next_parents = 0;

@@ -71,6 +71,7 @@ struct msd_ctx {
 	int leaf17 = 1;        // u64 keys and tuples: segments of <= 17408 elements are finished by leaf17_kernel (0: tuples: register partition + small leaves, keys: leaf_count_sort_kernel; A/B comparisons)
 	int mid_leaf = 1;      // u32 keys: merge_count_kernel (list mode) in front of count_walk_kernel (0: A/B comparisons)
 	int early_leaves = 1;  // keys only: the counting leaves go behind a last round without waiting for its end (0: A/B comparisons)
+	int early_plan = 1;    // a round that is not the last: the next round is planned and enqueued while its fix-up runs (0: A/B comparisons)
 	const uint32_t *order_keys = nullptr; // msd_order_low16_counts_u32 has run on these keys and its tables are still in the slab
 	uint64_t order_n = 0;
 	int merge_leaf = 0;    // msd_merge_buckets_u32: 0 = by bucket size, 1 = merge_place16_kernel, 2 = merge_count_kernel (tests)
@@ -542,7 +543,7 @@ struct KeepBufs {
 		constexpr uint64_t B = Cfg<K, V>::B, small_max = (uint64_t)Cfg<K, V>::SORT_TH * Cfg<K, V>::SORT_KPT;
 		block_map = b.take<uint8_t>(n / B + 2);
 		slot_full = b.take<uint8_t>(n / B + 2);
-		ctr = b.take<Counters>(2);
+		ctr = b.take<Counters>(3); // ([1]: scratch of the varying-bit reduction, [2]: a finished round's counters, parked by round_init_kernel)
 		big_cap = (uint32_t)std::min<uint64_t>(n / small_max + 16, 0x7FFFFFFFu);
 		big = b.take<Segment>(big_cap);
 		dev_list = sizeof(K) == 8 ? b.take<Segment>(n / (small_max + 1) + 2) : nullptr;
@@ -820,7 +821,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// ---- the general round: plan + upload, A classify, B block metadata + permutation, C cleanup + collect, summary
 			Round r;
 			if ((rc = plan_upload(r)) || (rc = classify(r)) || (rc = permute_blocks(r)) || (rc = cleanup_collect(r)) ||
-			    (rc = r.leaves_follow ? early_summary(r) : round_summary(r)))
+			    (rc = r.leaves_follow ? early_summary(r) : r.plan_ahead ? plan_next_early(r) : round_summary(r)))
 				return rc;
 		}
 		return MSD_OK;
@@ -895,7 +896,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (!rc) rc = pinned_reserve(c, std::max<size_t>(on_device ? 0 : np * sizeof(Parent), 256 + 2048 * sizeof(Segment)));
 		if (rc) return rc;
 		LAUNCH(c, round_init_kernel, 1, 256, 0, ctr, d_scr + 16, 0, reinterpret_cast<unsigned long long *>(d_scr + 32), 0, d_scr,
-		       nullptr, nullptr, 0, nullptr, 0); // (this round's plan is uploaded or made on the device below)
+		       nullptr, nullptr, 0, nullptr, 0, nullptr); // (this round's plan is uploaded or made on the device below)
 		if (on_device)
 			LAUNCH(c, regpart_plan_kernel, (np + 255) / 256, 256, 0, dev_list, np, small_max, d_parents, ctr);
 		else if ((rc = upload(c, { { d_parents, ps.data(), np * sizeof(Parent) } })))
@@ -933,11 +934,18 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		bool tried_direct = false; // a direct placement was attempted (its verdict stays on the device until the summary)
 		bool hist_checks = false;  // its exact histogram pass carries the check behind a sampled leading-bit skip
 		bool leaves_follow = false; // by the plan no child can become a parent: the counters travel early, the leaves go behind at once
+		size_t plan_ahead = 0;      // > 0: the counters and this many next parents travel early, for the next round's plan (plan_next_early)
 	};
 	// where the early copy of a round's counters lands in the staging buffer: behind the summary's own pieces
 	static constexpr size_t kReadAhead = 2048, kSegOff = 256, kVresOff = kSegOff - 2 * sizeof(unsigned long long);
 	static constexpr size_t kEarlyOff = kSegOff + kReadAhead * sizeof(Segment), kStagingBytes = kEarlyOff + sizeof(Counters);
 	static_assert(sizeof(Counters) <= kVresOff, "counters and the OR/AND words share the head of the staging buffer");
+	// behind them, for a round planned while the one before it still runs (early_plan): the early copy of that round's
+	// counters and first next parents, its parked counters once they are read, and a staging region of its own for the
+	// plan -- the first one is only free after a synchronisation
+	static constexpr size_t kPlanCtrOff = (kStagingBytes + 255) / 256 * 256, kPlanSegOff = kPlanCtrOff + 256;
+	static constexpr size_t kParkOff = kPlanSegOff + kReadAhead * sizeof(Segment), kStage2Off = (kParkOff + sizeof(Counters) + 255) / 256 * 256;
+	static_assert(sizeof(Counters) <= 256, "the early copy of the counters has 256 bytes");
 	// a round whose fix-up is still running when the host went on to the leaves: its summary comes with the leaves' counters
 	struct Pending {
 		bool open = false;
@@ -945,9 +953,23 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		uint32_t np = 0, ns = 0, nc = 0;
 		uint64_t nslots = 0;
 	} pending;
+	// a round whose fix-up was still running when the host planned and enqueued the next round (plan_next_early): the next
+	// round's round_init_kernel parks its counters, and they come with the next readback
+	Pending parked;
+	bool parked_direct = false;
+	bool enqueue_ahead = false; // the round being enqueued now goes behind a running one: no synchronisation, no allocation
+	Counters *park() const { return ctr + 2; }
+	// (pinned bytes the second staging region needs for a plan)
+	static size_t stage2_bytes(size_t np, size_t ns) { return kStage2Off + np * sizeof(Parent) + ns * sizeof(Stripe); }
+	void plan_next(const std::vector<Segment> &segs, RoundPlan &rp) const
+	{
+		plan_round<K, V>(segs, small_max, c->sm_count, rp, count_bits, job.single_pass() ? job.width : 0u, job.splitters ? job.nsplit : 0u);
+	}
 	int plan_upload(Round &r)
 	{
-		plan_round<K, V>(cur, small_max, c->sm_count, r.rp, count_bits, job.single_pass() ? job.width : 0u, job.splitters ? job.nsplit : 0u);
+		const bool ahead = enqueue_ahead; // (plan_next_early has made sure that nothing below has to grow)
+		enqueue_ahead = false;
+		plan_next(cur, r.rp);
 		// (between rounds nothing in the slab is live; the first round reserves the usual shapes' worst case at once)
 		const bool first = round == 0;
 		int rc = slab_carve(c, [&](Bump &b) { carve_round<K, V>(b, r.rp, small_max, r.rb); },
@@ -968,16 +990,22 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			const uint64_t plan_words = (r.np <= kDirectMaxParents ? r.np : 1) * sizeof(DirectPlan) / sizeof(uint32_t);
 			const uint64_t ntiles = (r.nc + kScanTile - 1) / kScanTile + 1;
 			const uint64_t parent_words = r.np * sizeof(Parent) / 4, stripe_words = r.ns * sizeof(Stripe) / 4;
-			if ((rc = pinned_reserve(c, std::max(kStagingBytes, r.np * sizeof(Parent) + r.ns * sizeof(Stripe))))) return rc;
-			HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
-			memcpy(c->pinned, r.rp.parents.data(), r.np * sizeof(Parent));
-			memcpy((char *)c->pinned + r.np * sizeof(Parent), r.rp.stripes.data(), r.ns * sizeof(Stripe));
+			// (with room for the plan of a next round that goes behind this one: at most kReadAhead parents, and about as many
+			// stripes as a round of all n keys has, one more per parent)
+			const size_t next_stripes = (size_t)std::max<uint64_t>((uint64_t)c->sm_count * MSD_STRIPE_WANT, n >> MSD_STRIPE_CAP_LOG) + 2 * kReadAhead + 64;
+			const size_t want = !ahead && c->early_plan && !job.single_pass() ? stage2_bytes(kReadAhead, next_stripes) : 0;
+			if ((rc = pinned_reserve(c, std::max({ kStagingBytes, r.np * sizeof(Parent) + r.ns * sizeof(Stripe), want })))) return rc;
+			char *stage = (char *)c->pinned + (ahead ? kStage2Off : 0);
+			if (!ahead) HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
+			memcpy(stage, r.rp.parents.data(), r.np * sizeof(Parent));
+			memcpy(stage + r.np * sizeof(Parent), r.rp.stripes.data(), r.ns * sizeof(Stripe));
 			void *staged = nullptr; // (pinned memory is mapped: an error here, never a guess at the address)
 			HIPCHK(c, hipHostGetDevicePointer(&staged, c->pinned, 0));
+			staged = (char *)staged + (stage - (char *)c->pinned);
 			const unsigned grid = (unsigned)std::min<uint64_t>(1024, (std::max({ plan_words, ntiles, parent_words, stripe_words }) + 255) / 256 + 1);
 			LAUNCH(c, round_init_kernel, grid, 256, 0, ctr, reinterpret_cast<uint32_t *>(r.rb.plans), plan_words, r.rb.scan_state, ntiles, r.rb.scan_ctr,
 			       static_cast<const uint32_t *>(staged), reinterpret_cast<uint32_t *>(r.rb.parents), parent_words,
-			       reinterpret_cast<uint32_t *>(r.rb.stripes), stripe_words);
+			       reinterpret_cast<uint32_t *>(r.rb.stripes), stripe_words, ahead ? park() : nullptr);
 		}
 		phase_mark(c, "plan+upload");
 		return MSD_OK;
@@ -1094,6 +1122,18 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		return MSD_OK;
 	}
 
+	// Is the average child of some parent too long for a leaf (and, 8-byte keys, for the register-resident pass)?  If not, the
+	// round is most likely the last general one and the early copy for the next round's plan would travel for nothing.
+	bool may_leave_parents(const Round &r) const
+	{
+		uint64_t leaf_max = small_max;
+		if constexpr (sizeof(K) == 8)
+			if (c->regpart) leaf_max = std::max<uint64_t>(leaf_max, kRpCap - 1);
+		for (const Parent &p : r.rp.parents)
+			if ((p.count >> p.width) > leaf_max) return true;
+		return false;
+	}
+
 	// ---- the children to the next round or the leaf lists (behind the child scan); a round that the leaves follow sends a
 	// copy of the counters to the host behind it -- the kernels behind the copy do not wait for the host
 	int collect(Round &r)
@@ -1112,6 +1152,15 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (r.leaves_follow) {
 			if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
 			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kEarlyOff, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+			HIPCHK(c, hipEventRecord(c->ev_early, c->stream));
+		} else if (c->early_plan && !sp && !r.hist_checks && !parked.open && c->pinned_bytes >= kStage2Off && may_leave_parents(r)) {
+			// a round that may leave parents (one that carries the check behind a sampled bit skip decides about a restart
+			// first; one parked round at a time): the counters and the first next parents travel now, so that the host can
+			// plan the next round while this one's fix-up runs
+			r.plan_ahead = std::min<size_t>(r.rp.round_keys / (small_max + 1) + 2, kReadAhead);
+			if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
+			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kPlanCtrOff, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kPlanSegOff, rb.next_parents, r.plan_ahead * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
 			HIPCHK(c, hipEventRecord(c->ev_early, c->stream));
 		}
 		return MSD_OK;
@@ -1146,6 +1195,69 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		set_stat(c, "excess_blocks", hc.nexcess);
 	}
 
+	// ---- the counters of a parked round have come with a readback (to kParkOff): its errors and statistics, under its own
+	// number and shape
+	int parked_summary()
+	{
+		if (!parked.open) return MSD_OK;
+		parked.open = false;
+		Counters pc;
+		memcpy(&pc, (char *)c->pinned + kParkOff, sizeof pc);
+		if (pc.errors) return round_errors(pc, parked.round, parked.np, parked.ns, parked_direct ? "used" : "not used");
+		round_stats(pc, parked.np, parked.ns, parked.nc, parked.nslots);
+		return MSD_OK;
+	}
+	ToHost parked_piece() const { return { kParkOff, park(), parked.open ? sizeof(Counters) : 0 }; }
+
+	// ---- a round that is not the last: the next round is planned from the early copy of the counters and the next parents
+	// (collect) and enqueued behind this round's cleanup while its fix-up still runs; this round's summary is parked.  The
+	// ordinary summary instead, with nothing enqueued ahead, if the round failed a check or left no parent or more than
+	// travelled, if its next parents stay on the device or take a register-resident pass, or if a buffer of the next round
+	// would have to grow (that synchronises).
+	int plan_next_early(Round &r)
+	{
+		HIPCHK(c, hipEventSynchronize(c->ev_early));
+		Counters hc;
+		memcpy(&hc, (char *)c->pinned + kPlanCtrOff, sizeof hc);
+		bool ok = !hc.errors && hc.next_parents != 0 && hc.next_parents <= r.plan_ahead;
+		std::vector<Segment> next;
+		if (ok) {
+			const Segment *sg = (const Segment *)((char *)c->pinned + kPlanSegOff);
+			next.assign(sg, sg + hc.next_parents);
+			sort_by_start(next);
+			if constexpr (sizeof(K) == 8) {
+				if (c->regpart) { // (rounds(): such parents take a register-resident pass, or their list stays on the device)
+					size_t fit = 0;
+					for (auto &s : next) fit += s.count + 1 <= kRpCap && s.count > small_max;
+					if (fit >= 64 || (fit && fit == next.size())) ok = false;
+				}
+			}
+		}
+		if (ok) {
+			RoundPlan rp;
+			RoundBufs rb;
+			plan_next(next, rp);
+			Bump sz(nullptr);
+			carve_round<K, V>(sz, rp, small_max, rb);
+			ok = sz.off + 4096 <= c->slab_bytes && (size_t)std::max(hc.nsmall, hc.ncount) + rp.nchildren + 16 <= c->lists_cap &&
+			     stage2_bytes(rp.parents.size(), rp.stripes.size()) <= c->pinned_bytes;
+		}
+		if (!ok) return round_summary(r);
+		prev_direct = r.tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
+		if (prev_direct) add_stat(c, "direct_rounds", 1);
+		nsmall_host = hc.nsmall;
+		ncount_host = hc.ncount;
+		nbig_host = hc.nbig;
+		parked = { true, round, r.np, r.ns, r.nc, r.rp.nslots };
+		parked_direct = prev_direct;
+		enqueue_ahead = true;
+		add_stat(c, "rounds_planned_early", 1);
+		cur = std::move(next);
+		phase_mark(c, "readback");
+		++round;
+		return MSD_OK;
+	}
+
 	// ---- the summary of a round that the leaves follow: the lists' lengths from the early copy of the counters, while the
 	// round's fix-up still runs; the rest of the summary (errors, holes, chain steps) comes with the leaves' counters
 	// (count_leaves).  If the round left a parent after all, or no counting leaf: the ordinary summary.
@@ -1176,8 +1288,9 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		Counters hc;
 		int rc = pinned_reserve(c, kStagingBytes);
 		if (rc || (rc = read_counters(c, ctr, hc, { { kSegOff, r.rb.next_parents, ahead * sizeof(Segment) },
-							    { kVresOff, vres, r.hist_checks ? 2 * sizeof(unsigned long long) : 0 } })))
+							    { kVresOff, vres, r.hist_checks ? 2 * sizeof(unsigned long long) : 0 }, parked_piece() })))
 			return rc;
+		if ((rc = parked_summary())) return rc;
 		if (hc.errors) return round_errors(hc, round, r.np, r.ns, r.tried_direct ? (hc.direct_uneven ? "declined" : "used") : "not tried");
 		if (r.hist_checks) {
 			const unsigned long long *h = (const unsigned long long *)((char *)c->pinned + kVresOff);
@@ -1239,7 +1352,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (top > 0 && (uint32_t)top > job.stop_bits) cur.push_back({ 0, n, (uint32_t)top, 0 });
 		nsmall_host = ncount_host = nbig_host = dev_np = 0;
 		round = 0;
-		pending.open = false;
+		pending.open = parked.open = enqueue_ahead = false;
 		prev_direct = unverified = false;
 		HIPCHK(c, hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
 		return MSD_OK;
@@ -1283,7 +1396,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			phase_mark(c, "count sort");
 			// byte-counter overflows of segments above the LDS-sort capacity joined the big list
 			Counters hc;
-			if ((rc = read_counters(c, ctr, hc))) return rc;
+			if ((rc = read_counters(c, ctr, hc, { parked_piece() })) || (rc = parked_summary())) return rc;
 			if (pending.open) { // the last round's summary travels with the leaves' counters (early_summary)
 				pending.open = false;
 				// (every check but count_walk_kernel's, site 7, is a round's; a scan tile's time-out leaves no site)
@@ -3096,6 +3209,8 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 		c->mid_leaf = value != 0;
 	} else if (!strcmp(name, "early_leaves")) {
 		c->early_leaves = value != 0;
+	} else if (!strcmp(name, "early_plan")) {
+		c->early_plan = value != 0;
 	} else if (!strcmp(name, "merge_leaf")) {
 		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "merge_leaf must be 0, 1 or 2");
 		c->merge_leaf = (int)value;
