@@ -799,6 +799,104 @@ class MsdContext:
                                           ptr["out"], ptr.get("out_values", null), ptr.get("out_origin", null)))
         return res[0] if len(res) == 1 else tuple(res)
 
+    # ---- set operations on two sorted arrays (include/msd_setops_hip.h)
+    SET_OPS = {"intersection": 0, "union": 1, "difference": 2, "symmetric_difference": 3}   # MSD_SET_* of include/msd_setops_hip.h
+
+    def set_sorted_limits(self, key_bytes: int) -> Tuple[int, int]:
+        """``(tile, scan_tile)`` of ``msd_set_sorted_limits``: the elements (of both inputs together) one workgroup takes
+        for that key width, and how many tile counts one workgroup of the tile-count scan takes at once."""
+        return self._limits2(self._L.msd_set_sorted_limits, key_bytes, "key_bytes")
+
+    @staticmethod
+    def _set_bound(op: str, n: int, m: int) -> int:
+        """the most results ``op`` can have on inputs of n and m elements"""
+        return min(n, m) if op == "intersection" else n if op == "difference" else n + m
+
+    def set_sorted(self, a, b, op: str, origin: bool = False, cap: Optional[int] = None, out=None, out_origin=None):
+        """A set operation on two sorted tensors: ``a`` and ``b`` are 1-D, contiguous, of the same dtype (float32, int32,
+        float64, int64, uint32 or uint64) and each ascending as :meth:`sort_typed` leaves it (trusted; duplicates are
+        allowed).  ``op`` is ``"intersection"`` (the values in both), ``"union"`` (in either), ``"difference"`` (in
+        ``a`` and not in ``b``) or ``"symmetric_difference"`` (in exactly one).  The result is a set: every value once,
+        ascending, bit-exact -- ``np.intersect1d`` / ``union1d`` / ``setdiff1d`` / ``setxor1d`` on sorted inputs, without
+        sorting or concatenating anything.
+
+        Values are told apart by their BITS and floats ordered by IEEE-754 totalOrder, as everywhere in this library:
+        -0.0 and +0.0 are two values (-0.0 below +0.0), so with -0.0 only in ``b`` and +0.0 only in ``a`` both are in the
+        union and neither is in the intersection; NaNs with equal bits are one value and intersect, NaNs of different
+        sign or payload do not.  numpy and torch compare floats by value: they merge the zeros and keep every NaN apart.
+
+        Returns ``(num, out)`` or, with ``origin=True`` (or ``out_origin``), ``(num, out, origin)``.  ``num`` is a
+        one-element int64 tensor on the device: the true number of results, also when it exceeds ``cap``.  ``out`` has
+        ``cap`` elements (default: the most the operation can give -- min(n, m), n + m, n, n + m in the order above), of
+        which the first min(num, cap) are written.  ``origin`` (int64, ``cap`` elements) names, per result, the index in
+        ``torch.cat([a, b])`` of the first occurrence of that value; a value that both sides hold is taken from ``a``.
+        ``out`` and ``out_origin`` (contiguous, shape ``(cap,)``) receive the results and must not overlap an input.
+        The inputs are not modified.  Nothing waits on the host."""
+        torch = _torch()
+        kt = self._key_type(a)
+        if b.dtype != a.dtype:
+            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
+        if a.dim() != 1 or b.dim() != 1:
+            raise MsdError("set_sorted takes 1-D tensors")
+        if not a.is_contiguous() or not b.is_contiguous():
+            raise MsdError("set_sorted takes contiguous tensors")
+        if op not in self.SET_OPS:
+            raise MsdError(f"op must be one of {sorted(self.SET_OPS)}, not {op!r}")
+        n, m = a.numel(), b.numel()
+        cap = self._set_bound(op, n, m) if cap is None else int(cap)
+        if cap < 0:
+            raise MsdError("cap must not be negative")
+        want_origin = origin or out_origin is not None
+        wanted = [("out", out, a.dtype)] + ([("out_origin", out_origin, torch.int64)] if want_origin else [])
+        for name, t, dt in wanted:
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (cap,) or not t.is_contiguous()):
+                raise MsdError(f"{name} must be a contiguous {dt} tensor of shape {(cap,)}")
+        self._on_gpu(a, b, out, out_origin)
+        num = torch.empty(1, dtype=torch.int64, device=a.device)
+        res = [t if t is not None else torch.empty(cap, dtype=dt, device=a.device) for _, t, dt in wanted]
+        self._ok(self._L.msd_set_sorted(self._h, self.SET_OPS[op], C.c_void_p(a.data_ptr()), n, C.c_void_p(b.data_ptr()), m, kt, cap,
+                                        C.c_void_p(res[0].data_ptr()), C.c_void_p(res[1].data_ptr() if want_origin else 0), C.c_void_p(num.data_ptr())))
+        return (num, *res)
+
+    def _set1d(self, a, b, op: str, name: str):
+        self._key_type(a)
+        if b.dtype != a.dtype:
+            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
+        if a.dim() != 1 or b.dim() != 1:
+            raise MsdError(f"{name} takes 1-D tensors")
+        self._on_gpu(a, b)
+        sa, sb = a.clone(), b.clone()   # (contiguous copies)
+        self.sort_typed(sa)
+        self.sort_typed(sb)
+        num, out = self.set_sorted(sa, sb, op)
+        return out[:int(num.item())]
+
+    def intersect1d(self, a, b):
+        """``np.intersect1d(a, b)`` for UNSORTED 1-D tensors of one dtype (float32, int32, float64, int64, uint32 or
+        uint64): the distinct values that both hold, in the dtype's order.  Copies of both are sorted
+        (:meth:`sort_typed`) and handed to :meth:`set_sorted`; the inputs are not modified.  Floats are told apart by
+        their BITS and ordered by totalOrder: where numpy says -0.0 == +0.0 and NaN != NaN, here -0.0 and +0.0 do not
+        intersect and NaNs with equal bits do.  One host wait beyond the sorts' own: the count sizes the result."""
+        return self._set1d(a, b, "intersection", "intersect1d")
+
+    def union1d(self, a, b):
+        """``np.union1d(a, b)`` for UNSORTED 1-D tensors, as :meth:`intersect1d`: the distinct values of both.  Floats by
+        their BITS: -0.0 and +0.0 are both in the result (-0.0 first) where numpy keeps one zero, and NaNs with equal
+        bits are one value, -NaNs in front of -inf and +NaNs behind +inf, where numpy collapses all NaNs into one at the end."""
+        return self._set1d(a, b, "union", "union1d")
+
+    def setdiff1d(self, a, b):
+        """``np.setdiff1d(a, b)`` for UNSORTED 1-D tensors, as :meth:`intersect1d`: the distinct values of ``a`` that
+        ``b`` does not hold.  Floats by their BITS: +0.0 in ``a`` survives a -0.0 in ``b`` where numpy removes it, and
+        a NaN in ``a`` is removed by a NaN with the same bits in ``b`` where numpy keeps it."""
+        return self._set1d(a, b, "difference", "setdiff1d")
+
+    def setxor1d(self, a, b):
+        """``np.setxor1d(a, b)`` for UNSORTED 1-D tensors, as :meth:`intersect1d`: the distinct values that exactly one
+        of the two holds.  Floats by their BITS: -0.0 in one and +0.0 in the other are both in the result where numpy
+        drops both, and NaNs with equal bits on both sides cancel where numpy keeps them."""
+        return self._set1d(a, b, "symmetric_difference", "setxor1d")
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))

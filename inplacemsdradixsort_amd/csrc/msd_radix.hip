@@ -12,6 +12,7 @@
 #include "msd_reduce.hpp"
 #include "msd_search.hpp"
 #include "msd_merge2.hpp"
+#include "msd_setops.hpp"
 #include "msd_args.hpp" // the argument rules, each stated once (host only)
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
@@ -20,6 +21,7 @@
 #include "../../include/msd_reduce_hip.h"
 #include "../../include/msd_search_hip.h"
 #include "../../include/msd_merge_hip.h"
+#include "../../include/msd_setops_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -3063,6 +3065,85 @@ int msd_merge_sorted(msd_ctx *c, const void *d_a, uint64_t n, const void *d_b, u
 													 (K *)d_out, d_out_vals, d_out_origin);
 			});
 		});
+	});
+}
+
+} // extern "C"
+
+// ---- set operations on two sorted arrays (msd_setops.hpp)
+
+// The splits, the count per tile, the scan of the counts, the write: five launches one behind the other on the stream; the
+// scratch -- one split per tile plus one, one count per tile, one sum per scan piece -- is the slab's, as for
+// msd_merge_sorted and msd_run_encode.  Nothing is read back.  n + m == 0 is one launch that writes 0 results.
+template <typename K>
+static int set_sorted_impl(msd_ctx *c, int op, const K *a, uint64_t n, const K *b, uint64_t m, int key_type, uint64_t cap, K *out, uint64_t *out_origin,
+			   uint64_t *num_out)
+{
+	const uint64_t total = n + m;
+	if (total == 0) {
+		phase_begin(c);
+		LAUNCH(c, set_empty_kernel, 1, 64, 0, num_out);
+		phase_mark(c, "set_sorted");
+		phase_end(c);
+		return MSD_OK;
+	}
+	const KeyCodec<K> cd = key_codec<K>(key_type);
+	const uint32_t keep = set_keep_mask(op);
+	const uint64_t tiles = (total + MergeCfg<K>::TILE - 1) / MergeCfg<K>::TILE; // (n + m < 2^37: at most 2^26)
+	const uint64_t pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile;
+	uint64_t *splits = nullptr, *tile_counts = nullptr, *piece_sums = nullptr;
+	if (int rc = slab_carve(c, [&](Bump &bump) {
+		    splits = bump.take<uint64_t>(tiles + 1);
+		    tile_counts = bump.take<uint64_t>(tiles);
+		    piece_sums = bump.take<uint64_t>(pieces);
+	    }))
+		return rc;
+	phase_begin(c);
+	LAUNCH(c, (merge_split_kernel<K>), (unsigned)((tiles + 1 + kMergeTh - 1) / kMergeTh), kMergeTh, 0, a, n, b, m, cd, tiles, splits);
+	LAUNCH(c, (set_count_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, keep, splits, tile_counts);
+	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
+	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_out);
+	if (cap && (out || out_origin)) // (cap == 0, or no output: the count alone)
+		LAUNCH(c, (set_write_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, keep, splits, tile_counts, piece_sums, num_out, cap, out, out_origin);
+	phase_mark(c, "set_sorted");
+	phase_end(c);
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_set_sorted_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile)
+{
+	if ((key_bytes != 4 && key_bytes != 8) || !tile || !scan_tile) return MSD_EINVAL;
+	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)MergeCfg<decltype(k0)>::TILE; });
+	*scan_tile = kRunsScanTile;
+	return MSD_OK;
+}
+
+int msd_set_sorted(msd_ctx *c, int op, const void *d_a, uint64_t n, const void *d_b, uint64_t m, int key_type, uint64_t cap, void *d_out, uint64_t *d_out_origin,
+		   uint64_t *d_num_out)
+{
+	if (!c) return MSD_EINVAL;
+	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key_type");
+	if (op != MSD_SET_INTERSECTION && op != MSD_SET_UNION && op != MSD_SET_DIFFERENCE && op != MSD_SET_SYMMETRIC_DIFFERENCE) return fail(c, MSD_EINVAL, "unknown op");
+	if (!d_num_out) return fail(c, MSD_EINVAL, "d_num_out is required");
+	if (n && !d_a) return fail(c, MSD_EINVAL, "null d_a pointer");
+	if (m && !d_b) return fail(c, MSD_EINVAL, "null d_b pointer");
+	// the extents: the inputs, then the outputs; at most min(cap, bound) results are stored (a count beyond 2^36 is refused behind the alignment rule; until then n + m saturates)
+	const uint32_t es = (uint32_t)key_type_bytes(key_type);
+	uint64_t total = 0;
+	if (__builtin_add_overflow(n, m, &total)) total = UINT64_MAX;
+	const uint64_t bound = op == MSD_SET_INTERSECTION ? std::min(n, m) : op == MSD_SET_DIFFERENCE ? n : total;
+	const uint64_t stored = std::min(cap, bound);
+	const Span buf[5] = { span_of(d_a, n, es), span_of(d_b, m, es), span_of(d_out, stored, es), span_of(d_out_origin, stored, 8), span_of(d_num_out, 1, 8) };
+	if (first_misaligned(buf) >= 0)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_a, d_b, d_out: the key's width; the others: 8)");
+	if (n >= kMaxElems || m >= kMaxElems) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^36 elements each");
+	if (outputs_overlap(buf, 2)) return fail(c, MSD_EINVAL, "d_out, d_out_origin and d_num_out must not overlap an input or each other (the operation is not in place)");
+	HIPCHK(c, hipSetDevice(c->device));
+	return with_width((int)es, [&](auto k0) {
+		typedef decltype(k0) K;
+		return set_sorted_impl<K>(c, op, (const K *)d_a, n, (const K *)d_b, m, key_type, cap, (K *)d_out, d_out_origin, d_num_out);
 	});
 }
 
