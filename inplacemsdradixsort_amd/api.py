@@ -897,6 +897,116 @@ class MsdContext:
         drops both, and NaNs with equal bits on both sides cancel where numpy keeps them."""
         return self._set1d(a, b, "symmetric_difference", "setxor1d")
 
+    # ---- sort-merge join of two sorted arrays (include/msd_join_hip.h)
+    def join_limits(self, key_bytes: int) -> Tuple[int, int, int]:
+        """``(tile, scan_tile, pair_tile)`` of ``msd_join_limits``: the elements (of both inputs together) one workgroup
+        of the groups call takes for that key width, the counts one workgroup of a scan takes, and the pair ranks one
+        workgroup of the expansion takes."""
+        t, s, p = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        if self._L.msd_join_limits(int(key_bytes), C.byref(t), C.byref(s), C.byref(p)) != 0:
+            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
+        return int(t.value), int(s.value), int(p.value)
+
+    def _join_inputs(self, a, b, name: str) -> int:
+        kt = self._key_type(a)
+        if b.dtype != a.dtype:
+            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
+        if a.dim() != 1 or b.dim() != 1:
+            raise MsdError(f"{name} takes 1-D tensors")
+        return kt
+
+    def join_groups(self, a, b, cap: Optional[int] = None, keys: bool = True):
+        """The matched groups of two sorted tensors: ``a`` and ``b`` are 1-D, contiguous, of the same dtype (float32,
+        int32, float64, int64, uint32 or uint64) and each ascending as :meth:`sort_typed` leaves it (trusted; duplicates
+        are allowed).  For every value that both hold, ascending: the key (bit-exact), the index of its first occurrence
+        in ``a`` and the length of its run there, and the same for ``b`` -- the sort-merge join in CSR form: group g
+        stands for ``a_count[g] * b_count[g]`` pairs, which :meth:`join_pairs` expands.
+
+        Values are told apart by their BITS and floats ordered by IEEE-754 totalOrder, as everywhere in this library:
+        -0.0 and +0.0 do not join, NaNs with equal bits do.  ``keys`` and ``a_first`` are what
+        :meth:`set_sorted` ``(a, b, "intersection", origin=True)`` gives.
+
+        Returns ``(num_groups, keys, a_first, a_count, b_first, b_count)``: ``num_groups`` is a one-element int64
+        tensor on the device, the true number of groups also when it exceeds ``cap``; the five arrays have ``cap``
+        elements (default: min(n, m), which holds every group), of which the first min(num_groups, cap) are written;
+        ``keys`` has the inputs' dtype (``None`` with ``keys=False``), the others are int64.  The inputs are not
+        modified.  Nothing waits on the host."""
+        torch = _torch()
+        kt = self._join_inputs(a, b, "join_groups")
+        if not a.is_contiguous() or not b.is_contiguous():
+            raise MsdError("join_groups takes contiguous tensors")
+        n, m = a.numel(), b.numel()
+        cap = min(n, m) if cap is None else int(cap)
+        if cap < 0:
+            raise MsdError("cap must not be negative")
+        self._on_gpu(a, b)
+        num = torch.empty(1, dtype=torch.int64, device=a.device)
+        k = torch.empty(cap, dtype=a.dtype, device=a.device) if keys else None
+        four = [torch.empty(cap, dtype=torch.int64, device=a.device) for _ in range(4)]
+        self._ok(self._L.msd_join_groups(self._h, C.c_void_p(a.data_ptr()), n, C.c_void_p(b.data_ptr()), m, kt, cap, C.c_void_p(k.data_ptr() if keys else 0),
+                                         *[C.c_void_p(t.data_ptr()) for t in four], C.c_void_p(num.data_ptr())))
+        return (num, k, *four)
+
+    def join_pairs(self, groups, n: int, m: int, cap: int, positions_a=None, positions_b=None, out_a=None, out_b=None):
+        """The index pairs of matched groups: ``groups`` is what :meth:`join_groups` returned (the keys are not looked
+        at), ``n`` and ``m`` the lengths of its inputs.  Pair r, in lexicographic order of (index in ``a``, index in
+        ``b``), lies in the group g that the running sum of ``a_count * b_count`` puts it in, at local rank t:
+        ``ia = a_first[g] + t // b_count[g]``, ``ib = b_first[g] + t % b_count[g]``.  If the groups were truncated by
+        their ``cap``, the pairs are those of the stored groups.
+
+        Returns ``(num_pairs, ia, ib)``: ``num_pairs`` is a one-element int64 tensor on the device, the true total also
+        when it exceeds ``cap``; ``ia`` and ``ib`` (int64, ``cap`` elements; ``out_a`` / ``out_b`` where given) hold the
+        first min(num_pairs, cap) pairs.  ``cap=0`` only counts.  ``positions_a`` (int64, ``n`` elements) stores
+        ``positions_a[ia]`` in place of ``ia``, ``positions_b`` likewise: the positions of a sort with positions, so
+        that the pairs index the unsorted tensors.  Nothing waits on the host."""
+        torch = _torch()
+        num_groups, _, a_first, a_count, b_first, b_count = groups
+        n, m, cap = int(n), int(m), int(cap)
+        if n < 0 or m < 0 or cap < 0:
+            raise MsdError("n, m and cap must not be negative")
+        four = (a_first, a_count, b_first, b_count)
+        gcap = a_first.numel()
+        if num_groups.dtype != torch.int64 or num_groups.numel() != 1:
+            raise MsdError("num_groups must be a one-element int64 tensor")
+        if any(t.dtype != torch.int64 or t.dim() != 1 or t.numel() != gcap or not t.is_contiguous() for t in four):
+            raise MsdError("the groups must be contiguous 1-D int64 tensors of one length")
+        for name, t, count in (("positions_a", positions_a, n), ("positions_b", positions_b, m)):
+            if t is not None and (t.dtype != torch.int64 or t.dim() != 1 or t.numel() != count or not t.is_contiguous()):
+                raise MsdError(f"{name} must be a contiguous 1-D int64 tensor of {count} elements")
+        for name, t in (("out_a", out_a), ("out_b", out_b)):
+            if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (cap,) or not t.is_contiguous()):
+                raise MsdError(f"{name} must be a contiguous int64 tensor of shape {(cap,)}")
+        self._on_gpu(num_groups, *four, positions_a, positions_b, out_a, out_b)
+        dev = num_groups.device
+        num = torch.empty(1, dtype=torch.int64, device=dev)
+        ia = out_a if out_a is not None else torch.empty(cap, dtype=torch.int64, device=dev)
+        ib = out_b if out_b is not None else torch.empty(cap, dtype=torch.int64, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._ok(self._L.msd_join_pairs(self._h, gcap, ptr(num_groups), ptr(a_first), ptr(a_count), ptr(b_first), ptr(b_count), n, m, ptr(positions_a),
+                                        ptr(positions_b), cap, ptr(ia), ptr(ib), ptr(num)))
+        return num, ia, ib
+
+    def join(self, a, b):
+        """The inner equi-join of two UNSORTED 1-D tensors of one dtype (float32, int32, float64, int64, uint32 or
+        uint64): ``(ia, ib)``, int64 indices into ``a`` and ``b`` with ``a[ia[r]]`` bit-equal to ``b[ib[r]]``, every such
+        pair exactly once.  The order is that of :meth:`join_pairs` on the sorted copies: ascending by key, and within
+        a key by the place in the sorted copy of ``a``, then of ``b``.  Values are told apart by their BITS: -0.0 and
+        +0.0 do not join, NaNs with equal bits do.  Both inputs are sorted with positions (copies; the inputs are not
+        modified), :meth:`join_groups` finds the groups and :meth:`join_pairs` expands them through both position
+        arrays.  One host wait beyond the sorts' own: the number of pairs sizes the result."""
+        self._join_inputs(a, b, "join")
+        self._on_gpu(a, b)
+        n, m = a.numel(), b.numel()
+        if n == 0 or m == 0:
+            none = _torch().empty(0, dtype=_torch().int64, device=a.device)
+            return none, none.clone()
+        sa, pa = self._sorted_with_positions(a.contiguous())
+        sb, pb = self._sorted_with_positions(b.contiguous())
+        groups = self.join_groups(sa, sb, keys=False)
+        total, _, _ = self.join_pairs(groups, n, m, 0)
+        _, ia, ib = self.join_pairs(groups, n, m, int(total.item()), positions_a=pa, positions_b=pb)
+        return ia, ib
+
     # ---- synthetic inputs (SURVEY.md section 8d)
     def gen_uniform_u32(self, keys, seed: int = 0x5EED0001, first: int = 0) -> None:
         self._ok(self._L.msd_gen_uniform_u32(self._h, self._ptr(keys, 4), keys.numel(), seed, first))

@@ -13,6 +13,7 @@
 #include "msd_search.hpp"
 #include "msd_merge2.hpp"
 #include "msd_setops.hpp"
+#include "msd_join.hpp"
 #include "msd_args.hpp" // the argument rules, each stated once (host only)
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
@@ -22,6 +23,7 @@
 #include "../../include/msd_search_hip.h"
 #include "../../include/msd_merge_hip.h"
 #include "../../include/msd_setops_hip.h"
+#include "../../include/msd_join_hip.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -3145,6 +3147,145 @@ int msd_set_sorted(msd_ctx *c, int op, const void *d_a, uint64_t n, const void *
 		typedef decltype(k0) K;
 		return set_sorted_impl<K>(c, op, (const K *)d_a, n, (const K *)d_b, m, key_type, cap, (K *)d_out, d_out_origin, d_num_out);
 	});
+}
+
+} // extern "C"
+
+// ---- sort-merge join of two sorted arrays (msd_join.hpp)
+
+// The groups: the five launches of msd_set_sorted with the intersection's mask and the join's own write kernel; the scratch is
+// that of msd_set_sorted.  Nothing is read back.  n + m == 0 is one launch that writes 0 groups.
+template <typename K>
+static int join_groups_impl(msd_ctx *c, const K *a, uint64_t n, const K *b, uint64_t m, int key_type, uint64_t cap, K *keys, uint64_t *a_first, uint64_t *a_count,
+			    uint64_t *b_first, uint64_t *b_count, uint64_t *num_groups)
+{
+	const uint64_t total = n + m;
+	if (total == 0) {
+		phase_begin(c);
+		LAUNCH(c, set_empty_kernel, 1, 64, 0, num_groups);
+		phase_mark(c, "join_groups");
+		phase_end(c);
+		return MSD_OK;
+	}
+	const KeyCodec<K> cd = key_codec<K>(key_type);
+	const uint64_t tiles = (total + MergeCfg<K>::TILE - 1) / MergeCfg<K>::TILE; // (n + m < 2^33: at most 2^22)
+	const uint64_t pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile;
+	uint64_t *splits = nullptr, *tile_counts = nullptr, *piece_sums = nullptr;
+	if (int rc = slab_carve(c, [&](Bump &bump) {
+		    splits = bump.take<uint64_t>(tiles + 1);
+		    tile_counts = bump.take<uint64_t>(tiles);
+		    piece_sums = bump.take<uint64_t>(pieces);
+	    }))
+		return rc;
+	phase_begin(c);
+	LAUNCH(c, (merge_split_kernel<K>), (unsigned)((tiles + 1 + kMergeTh - 1) / kMergeTh), kMergeTh, 0, a, n, b, m, cd, tiles, splits);
+	LAUNCH(c, (set_count_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, kSetKeepMatchedA, splits, tile_counts);
+	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
+	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_groups);
+	if (cap && (keys || a_first || a_count || b_first || b_count)) // (cap == 0, or no output: the count alone)
+		LAUNCH(c, (join_write_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, splits, tile_counts, piece_sums, num_groups, cap, keys, a_first, a_count, b_first,
+		       b_count);
+	phase_mark(c, "join_groups");
+	phase_end(c);
+	return MSD_OK;
+}
+
+// The pairs: the scan of the products, the expansion; the scratch -- one 8-byte offset per group of groups_cap, one 8-byte
+// sum per scan piece -- is the slab's.  Nothing is read back: the grid of the expansion is that of min(cap, n * m) ranks.
+static int join_pairs_impl(msd_ctx *c, uint64_t groups_cap, const uint64_t *num_groups, const uint64_t *a_first, const uint64_t *a_count, const uint64_t *b_first,
+			   const uint64_t *b_count, uint64_t n, uint64_t m, const uint64_t *pos_a, const uint64_t *pos_b, uint64_t stored, uint64_t cap, uint64_t *out_a,
+			   uint64_t *out_b, uint64_t *num_pairs)
+{
+	if (groups_cap == 0) {
+		phase_begin(c);
+		LAUNCH(c, set_empty_kernel, 1, 64, 0, num_pairs);
+		phase_mark(c, "join_pairs");
+		phase_end(c);
+		return MSD_OK;
+	}
+	const uint64_t pieces = (groups_cap + kRunsScanTile - 1) / kRunsScanTile;
+	uint64_t *offs = nullptr, *piece_sums = nullptr;
+	if (int rc = slab_carve(c, [&](Bump &bump) {
+		    offs = bump.take<uint64_t>(groups_cap);
+		    piece_sums = bump.take<uint64_t>(pieces);
+	    }))
+		return rc;
+	const uint64_t grid = (stored + kJoinPairTile - 1) / kJoinPairTile; // (stored < 2^40: at most 2^29)
+	phase_begin(c);
+	LAUNCH(c, join_offsets_kernel, (unsigned)pieces, kRunsScanTh, 0, groups_cap, num_groups, a_count, b_count, offs, piece_sums);
+	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_pairs);
+	if (grid && (out_a || out_b)) { // (cap == 0, an empty side or no output: the count alone)
+		int rc = with_flag(pos_a != nullptr, [&](auto pa) {
+			return with_flag(pos_b != nullptr, [&](auto pb) {
+				LAUNCH(c, (join_expand_kernel<decltype(pa)::value, decltype(pb)::value>), (unsigned)grid, kJoinPairTh, 0, groups_cap, num_groups, offs, piece_sums, num_pairs, a_first,
+				       b_first, b_count, n, m, pos_a, pos_b, cap, out_a, out_b);
+				return (int)MSD_OK;
+			});
+		});
+		if (rc) return rc;
+	}
+	phase_mark(c, "join_pairs");
+	phase_end(c);
+	return MSD_OK;
+}
+
+extern "C" {
+
+int msd_join_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile, uint64_t *pair_tile)
+{
+	if ((key_bytes != 4 && key_bytes != 8) || !tile || !scan_tile || !pair_tile) return MSD_EINVAL;
+	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)MergeCfg<decltype(k0)>::TILE; });
+	*scan_tile = kRunsScanTile;
+	*pair_tile = kJoinPairTile;
+	return MSD_OK;
+}
+
+int msd_join_groups(msd_ctx *c, const void *d_a, uint64_t n, const void *d_b, uint64_t m, int key_type, uint64_t cap, void *d_keys, uint64_t *d_a_first,
+		    uint64_t *d_a_count, uint64_t *d_b_first, uint64_t *d_b_count, uint64_t *d_num_groups)
+{
+	if (!c) return MSD_EINVAL;
+	if (!key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key_type");
+	if (!d_num_groups) return fail(c, MSD_EINVAL, "d_num_groups is required");
+	if (n && !d_a) return fail(c, MSD_EINVAL, "null d_a pointer");
+	if (m && !d_b) return fail(c, MSD_EINVAL, "null d_b pointer");
+	// the extents: the inputs, then the outputs; at most min(cap, n, m) groups are stored
+	const uint32_t es = (uint32_t)key_type_bytes(key_type);
+	const uint64_t stored = std::min(cap, std::min(n, m));
+	const Span buf[8] = { span_of(d_a, n, es),           span_of(d_b, m, es),           span_of(d_keys, stored, es),    span_of(d_a_first, stored, 8),
+			      span_of(d_a_count, stored, 8), span_of(d_b_first, stored, 8), span_of(d_b_count, stored, 8), span_of(d_num_groups, 1, 8) };
+	if (first_misaligned(buf) >= 0)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_a, d_b, d_keys: the key's width; the others: 8)");
+	if (n >= kJoinMaxElems || m >= kJoinMaxElems) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^32 elements each");
+	if (outputs_overlap(buf, 2)) return fail(c, MSD_EINVAL, "the outputs and d_num_groups must not overlap an input or each other");
+	HIPCHK(c, hipSetDevice(c->device));
+	return with_width((int)es, [&](auto k0) {
+		typedef decltype(k0) K;
+		return join_groups_impl<K>(c, (const K *)d_a, n, (const K *)d_b, m, key_type, cap, (K *)d_keys, d_a_first, d_a_count, d_b_first, d_b_count, d_num_groups);
+	});
+}
+
+int msd_join_pairs(msd_ctx *c, uint64_t groups_cap, const uint64_t *d_num_groups, const uint64_t *d_a_first, const uint64_t *d_a_count, const uint64_t *d_b_first,
+		   const uint64_t *d_b_count, uint64_t n, uint64_t m, const uint64_t *d_pos_a, const uint64_t *d_pos_b, uint64_t cap, uint64_t *d_out_a, uint64_t *d_out_b,
+		   uint64_t *d_num_pairs)
+{
+	if (!c) return MSD_EINVAL;
+	if (!d_num_pairs) return fail(c, MSD_EINVAL, "d_num_pairs is required");
+	if (groups_cap && !d_num_groups) return fail(c, MSD_EINVAL, "null d_num_groups pointer");
+	if (groups_cap && (!d_a_first || !d_a_count || !d_b_first || !d_b_count)) return fail(c, MSD_EINVAL, "null group array (d_a_first, d_a_count, d_b_first, d_b_count)");
+	// the extents: the inputs, then the outputs; at most min(cap, n * m) pairs are stored (n * m saturates until n and m are checked)
+	uint64_t all = 0;
+	if (__builtin_mul_overflow(n, m, &all)) all = UINT64_MAX;
+	const uint64_t stored = std::min(cap, all);
+	const Span buf[10] = { span_of(d_num_groups, 1, 8),        span_of(d_a_first, groups_cap, 8), span_of(d_a_count, groups_cap, 8), span_of(d_b_first, groups_cap, 8),
+			       span_of(d_b_count, groups_cap, 8), span_of(d_pos_a, n, 8),            span_of(d_pos_b, m, 8),            span_of(d_out_a, stored, 8),
+			       span_of(d_out_b, stored, 8),        span_of(d_num_pairs, 1, 8) };
+	if (first_misaligned(buf) >= 0) return fail(c, MSD_EINVAL, "every buffer must be aligned to 8 bytes");
+	if (n >= kJoinMaxElems || m >= kJoinMaxElems) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^32 elements each");
+	if (groups_cap >= kJoinMaxElems) return fail(c, MSD_EINVAL, "groups_cap too large: fewer than 2^32 groups");
+	if ((d_out_a || d_out_b) && stored >= kJoinMaxStored) return fail(c, MSD_EINVAL, "cap too large: fewer than 2^40 pairs are stored by one call");
+	if (outputs_overlap(buf, 7)) return fail(c, MSD_EINVAL, "d_out_a, d_out_b and d_num_pairs must not overlap an input or each other");
+	HIPCHK(c, hipSetDevice(c->device));
+	return join_pairs_impl(c, groups_cap, d_num_groups, d_a_first, d_a_count, d_b_first, d_b_count, n, m, d_pos_a, d_pos_b, stored, cap, d_out_a, d_out_b, d_num_pairs);
 }
 
 } // extern "C"
