@@ -670,6 +670,74 @@ class MsdContext:
         m = int(num.item())
         return distinct[:m], out[:m]
 
+    # ---- scan-by-key over runs: window functions on sorted keys (include/msd_scan_hip.h)
+    SCAN_OPS = {"sum": 0, "min": 1, "max": 2, "count": 3}   # MSD_SCAN_* of include/msd_scan_hip.h
+
+    def scan_runs_limits(self, key_bytes: int) -> Tuple[int, int]:
+        """``(tile, scan_tile)`` of ``msd_scan_runs_limits``: the geometry of :meth:`run_encode_limits`."""
+        return self._limits2(self._L.msd_scan_runs_limits, key_bytes, "key_bytes")
+
+    def scan_runs(self, keys, vals, op: str = "sum", exclusive: bool = False, positions=None, scatter: bool = False):
+        """One number per ELEMENT of ``keys``: the running ``"sum"``, ``"min"``, ``"max"`` or ``"count"`` inside its run --
+        ``OVER (PARTITION BY key ORDER BY the order of the elements)``.  The runs are those of :meth:`run_encode` and
+        :meth:`reduce_runs` (maximal stretches of equal BIT patterns; 4- or 8-byte elements).  The value of element i is
+        ``vals[i]``: the value column lies in the order of the keys (sorted along with them, or gathered with the
+        positions a sort left: ``vals[positions]``).  ``positions`` and ``scatter`` are reserved for reading the values
+        through positions and storing the results through them; they are NOT OFFERED YET and refused.  ``vals`` is float32, int32, float64, int64, uint32 or uint64, whatever the keys are, and may
+        be ``None`` for ``"count"`` only, which counts 1 per element.  All tensors are 1-D and contiguous.
+
+        Returns a tensor of ``keys.numel()`` elements: element i holds the op over its run's elements up to and
+        including i, with ``exclusive`` up to the one in front of i and the op's identity at the first element of a
+        run (0; for ``min`` the largest value of the dtype, for ``max`` the smallest: for floats the +NaN / -NaN with
+        all payload bits set).  ``"count"``
+        gives int64: the 1-based row number inside the run, 0-based with ``exclusive``.  A sum is int64 for integer
+        values (uint64 for unsigned ones where torch has that dtype), exact modulo 2^64, and float64 for float values:
+        every output is the sum of exactly its own prefix, summed in double without atomics and never formed by
+        subtraction, in an order that the sizes and addresses alone fix, so the same call gives the same bits every
+        time -- reproducible, but not the bits of a sequential sum or of ``torch.cumsum``.  ``min`` / ``max`` have the
+        values' dtype and are bit-exact, floats in IEEE-754 totalOrder as everywhere in this library: -0.0 is below
+        +0.0 and a NaN is an ordinary largest value (the smallest, if its sign bit is set), unlike ``torch.cummax`` /
+        ``torch.cummin``, which propagate any NaN.  Nothing waits on the host.
+
+        There is no convenience on UNSORTED keys: the library's sort is unstable, so the order of the elements inside a
+        group -- and with it every running value but the last -- would be unspecified.  For a defined order sort a
+        64-bit composite ``(key code << 32) | order column`` with positions, scan on the keys taken from its upper
+        half and the values gathered through the positions; ``"count"`` alone may accept the arbitrary order."""
+        torch = _torch()
+        if op not in self.SCAN_OPS:
+            raise MsdError(f"op must be one of {sorted(self.SCAN_OPS)}, not {op!r}")
+        if vals is None and op != "count":
+            raise MsdError(f"vals may be None for op 'count' only, not for {op!r}")
+        if keys.dim() != 1 or not keys.is_contiguous() or (vals is not None and (vals.dim() != 1 or not vals.is_contiguous())):
+            raise MsdError("scan_runs takes 1-D contiguous tensors")
+        ks = keys.element_size()
+        if ks not in (4, 8):
+            raise MsdError(f"scan_runs takes 4- or 8-byte keys, not {keys.dtype}")
+        vt = self._key_type(vals) if vals is not None else 0   # (a value dtype without an order is refused here)
+        n = keys.numel()
+        if vals is not None and vals.numel() != n:
+            raise MsdError("keys and vals differ in length")
+        self._check_positions(positions, n)
+        if scatter and positions is None:
+            raise MsdError("scatter without positions")
+        if positions is not None:
+            raise MsdError("positions (and with them scatter) are not offered yet: gather the values, vals[positions], and scatter the result")
+        self._on_gpu(keys, vals)
+        if op == "count":
+            odt, vals = torch.int64, None
+        elif op != "sum":
+            odt = vals.dtype
+        elif vt in (self.KEY_F32, self.KEY_F64):
+            odt = torch.float64
+        elif vt in (self.KEY_U32, self.KEY_U64) and hasattr(torch, "uint64"):
+            odt = torch.uint64
+        else:
+            odt = torch.int64
+        out = torch.empty(n, dtype=odt, device=keys.device)
+        self._ok(self._L.msd_scan_runs(self._h, C.c_void_p(keys.data_ptr()), ks, n, C.c_void_p(vals.data_ptr() if vals is not None else 0), vt,
+                                       C.c_void_p(0), self.SCAN_OPS[op], 1 if exclusive else 0, C.c_void_p(out.data_ptr())))
+        return out
+
     # ---- sorted search (include/msd_search_hip.h)
     def search_sorted_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, direct_tile)`` of ``msd_search_sorted_limits``: the elements (keys plus needles together) one

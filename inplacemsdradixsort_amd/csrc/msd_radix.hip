@@ -10,6 +10,7 @@
 #include "msd_sort_rows.hpp"
 #include "msd_runs.hpp"
 #include "msd_reduce.hpp"
+#include "msd_scan.hpp"
 #include "msd_search.hpp"
 #include "msd_merge2.hpp"
 #include "msd_setops.hpp"
@@ -20,6 +21,7 @@
 #include "../../include/msd_sort_rows_hip.h"
 #include "../../include/msd_runs_hip.h"
 #include "../../include/msd_reduce_hip.h"
+#include "../../include/msd_scan_hip.h"
 #include "../../include/msd_search_hip.h"
 #include "../../include/msd_merge_hip.h"
 #include "../../include/msd_setops_hip.h"
@@ -2935,6 +2937,88 @@ int msd_reduce_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, c
 	HIPCHK(c, hipSetDevice(c->device));
 	return with_width(key_bytes, [&](auto k0) {
 		return reduce_runs_typed(c, (const decltype(k0) *)d_keys, n, d_vals, val_type, d_positions, op, cap, d_out, d_num_runs);
+	});
+}
+
+} // extern "C"
+
+// ---- scan-by-key over runs (msd_scan.hpp)
+
+// Tail, carry (pieces, top), tile: four launches one behind the other on the stream, nothing read back.  The scratch -- per
+// tile and per scan piece one 8-byte tail and one 4-byte flag -- is the slab's, like a sort round's.
+template <typename E, typename P>
+static int scan_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *vals, int flags, void *out, KeyCodec<typename P::R::O> cd)
+{
+	typedef typename P::R R;
+	const uint64_t tiles = runs_tiles(keys, n), pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile; // (tiles <= 2^25 + 1)
+	ScanRecord rec{ nullptr, nullptr }, piece{ nullptr, nullptr };
+	if (int rc = slab_carve(c, [&](Bump &b) {
+		    rec.tail = b.take<uint64_t>(tiles);
+		    rec.flag = b.take<uint32_t>(tiles);
+		    piece.tail = b.take<uint64_t>(pieces);
+		    piece.flag = b.take<uint32_t>(pieces);
+	    }))
+		return rc;
+	phase_begin(c);
+	LAUNCH(c, (scan_tail_kernel<E, P>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, cd, rec);
+	LAUNCH(c, (scan_carry_pieces_kernel<R>), (unsigned)pieces, kRunsScanTh, 0, rec, tiles, cd, piece);
+	LAUNCH(c, (scan_carry_top_kernel<R>), 1, kRunsScanTh, 0, piece, pieces, cd);
+	LAUNCH(c, (scan_tile_kernel<E, P>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, cd, rec, piece, flags, out);
+	phase_mark(c, "scan_runs");
+	phase_end(c);
+	return MSD_OK;
+}
+
+template <typename E>
+static int scan_runs_typed(msd_ctx *c, const E *keys, uint64_t n, const void *vals, int val_type, int op, int flags, void *out)
+{
+	const KeyCodec<uint64_t> none{ 0, 0 };
+	if (op == MSD_SCAN_COUNT) return scan_runs_impl<E, CountOne>(c, keys, n, nullptr, flags, out, none);
+	if (op == MSD_SCAN_SUM) {
+		switch (val_type) {
+		case kKeyU32: return scan_runs_impl<E, SumU32>(c, keys, n, vals, flags, out, none);
+		case kKeyI32: return scan_runs_impl<E, SumI32>(c, keys, n, vals, flags, out, none);
+		case kKeyF32: return scan_runs_impl<E, SumF32>(c, keys, n, vals, flags, out, none);
+		case kKeyF64: return scan_runs_impl<E, SumF64>(c, keys, n, vals, flags, out, none);
+		default: return scan_runs_impl<E, SumX64>(c, keys, n, vals, flags, out, none); // (U64, I64: the same sum modulo 2^64)
+		}
+	}
+	// a maximum is the minimum of the complemented codes
+	const bool mx = op == MSD_SCAN_MAX;
+	if (key_type_bytes(val_type) == 4)
+		return scan_runs_impl<E, MinOf<uint32_t>>(c, keys, n, vals, flags, out, key_codec<uint32_t>(val_type).flipped(mx ? ~0u : 0u));
+	return scan_runs_impl<E, MinOf<uint64_t>>(c, keys, n, vals, flags, out, key_codec<uint64_t>(val_type).flipped(mx ? ~0ull : 0ull));
+}
+
+extern "C" {
+
+int msd_scan_runs_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile) { return msd_run_encode_limits(key_bytes, tile, scan_tile); }
+
+int msd_scan_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, const void *d_vals, int val_type, const uint64_t *d_positions, int op, int flags,
+		  void *d_out)
+{
+	if (!c) return MSD_EINVAL;
+	if (key_bytes != 4 && key_bytes != 8) return fail(c, MSD_EINVAL, "key_bytes must be 4 or 8");
+	if (op != MSD_SCAN_SUM && op != MSD_SCAN_MIN && op != MSD_SCAN_MAX && op != MSD_SCAN_COUNT) return fail(c, MSD_EINVAL, "unknown op");
+	const bool count = op == MSD_SCAN_COUNT;
+	if (!count && !key_type_ok(val_type)) return fail(c, MSD_EINVAL, "unknown val_type");
+	if (flags & ~(MSD_SCAN_EXCLUSIVE | MSD_SCAN_SCATTER)) return fail(c, MSD_EINVAL, "unknown flags");
+	if ((flags & MSD_SCAN_SCATTER) && !d_positions) return fail(c, MSD_EINVAL, "MSD_SCAN_SCATTER without d_positions");
+	if (d_positions) return fail(c, MSD_EINVAL, "d_positions is not offered yet: it must be null (and with it MSD_SCAN_SCATTER is not offered)");
+	if (n && !d_keys) return fail(c, MSD_EINVAL, "null keys pointer");
+	if (n && !count && !d_vals) return fail(c, MSD_EINVAL, "null values pointer");
+	if (n && !d_out) return fail(c, MSD_EINVAL, "null d_out pointer");
+	// the extents: inputs first, then the output; a sum and a count as 8 bytes, a count reads no values
+	const uint32_t ks = (uint32_t)key_bytes, vs = count ? 1 : (uint32_t)key_type_bytes(val_type), os = op == MSD_SCAN_SUM || count ? 8 : vs;
+	const Span buf[3] = { span_of(d_keys, n, ks), span_of(count ? nullptr : d_vals, n, vs), span_of(d_out, n, os) };
+	if (first_misaligned(buf) >= 0)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_keys: key_bytes; d_vals: the value's; d_out: 8 for a sum or a count, else the value's)");
+	if (n >= kMaxElems) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
+	if (outputs_overlap(buf, 2)) return fail(c, MSD_EINVAL, "d_out must not overlap the keys or the values (in place is not offered)");
+	if (n == 0) return MSD_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	return with_width(key_bytes, [&](auto k0) {
+		return scan_runs_typed(c, (const decltype(k0) *)d_keys, n, count ? nullptr : d_vals, val_type, op, flags, d_out);
 	});
 }
 
