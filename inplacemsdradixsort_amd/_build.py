@@ -24,7 +24,7 @@ DEPS = SOURCES + sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC
     os.path.join("..", "..", "include", "msd_runs_hip.h"), os.path.join("..", "..", "include", "msd_reduce_hip.h"),
     os.path.join("..", "..", "include", "msd_search_hip.h"), os.path.join("..", "..", "include", "msd_merge_hip.h"),
     os.path.join("..", "..", "include", "msd_setops_hip.h"), os.path.join("..", "..", "include", "msd_join_hip.h"),
-    os.path.join("..", "..", "include", "msd_scan_hip.h")]
+    os.path.join("..", "..", "include", "msd_scan_hip.h"), os.path.join("..", "..", "include", "msd_compact_hip.h")]
 # the multi-GPU entry points (include/msd_sharded_hip.h): a library of its own, linked against the one above and RCCL
 RCCL_LIB = os.path.join(HERE, "libinpmsdradix_hip_rccl.so")
 RCCL_SOURCES = ["msd_sharded.hip"]

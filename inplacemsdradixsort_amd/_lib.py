@@ -92,6 +92,13 @@ SCAN_EXPORTS = {
     "msd_scan_runs_limits": [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
 }
 
+# every symbol include/msd_compact_hip.h declares (the same library): name -> argtypes, set in load()
+COMPACT_EXPORTS = {
+    "msd_compact": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                    C.c_void_p, C.c_void_p],
+    "msd_compact_limits": [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+}
+
 # every symbol include/msd_sharded_hip.h declares (libinpmsdradix_hip_rccl.so)
 RCCL_EXPORTS = ["msd_shard_create", "msd_shard_destroy", "msd_shard_set_option", "msd_shard_rank", "msd_shard_world", "msd_shard_last_error",
                 "msd_sort_u32_sharded", "msd_sort_pairs_u64_sharded", "msd_sort_u32_multi"]
@@ -222,6 +229,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     for f, argtypes in JOIN_EXPORTS.items():
         getattr(L, f).argtypes = argtypes
     for f, argtypes in SCAN_EXPORTS.items():
+        getattr(L, f).argtypes = argtypes
+    for f, argtypes in COMPACT_EXPORTS.items():
         getattr(L, f).argtypes = argtypes
     # reference surface (include/msb_64.h)
     L.sort.argtypes = [C.POINTER(_u64p), C.POINTER(_u64p), _u64p, C.c_int, C.c_int, C.c_double,

@@ -738,6 +738,132 @@ class MsdContext:
                                        C.c_void_p(0), self.SCAN_OPS[op], 1 if exclusive else 0, C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- stream compaction and stable partition: the filter (include/msd_compact_hip.h)
+    COMPACT_RANGE, COMPACT_INVERT, COMPACT_REST = 1, 2, 4   # MSD_COMPACT_* of include/msd_compact_hip.h
+
+    def compact_limits(self, key_bytes: int) -> Tuple[int, int]:
+        """``(tile, scan_tile)`` of ``msd_compact_limits``: the geometry of :meth:`run_encode_limits`."""
+        return self._limits2(self._L.msd_compact_limits, key_bytes, "key_bytes")
+
+    def _bound_bits(self, keys, kt: int, bound, lowest: bool) -> int:
+        """The bit pattern of a range bound in the keys' dtype; ``None`` is the key with the lowest / highest code."""
+        width = 8 * keys.element_size()
+        if bound is None:
+            bits = C.c_uint64()
+            self._L.msd_key_decode(kt, 0 if lowest else (1 << width) - 1, C.byref(bits))
+            return int(bits.value)
+        nt = {self.KEY_U32: np.uint32, self.KEY_I32: np.int32, self.KEY_F32: np.float32, self.KEY_U64: np.uint64, self.KEY_I64: np.int64,
+              self.KEY_F64: np.float64}[kt]
+        is_float = kt in (self.KEY_F32, self.KEY_F64)
+        try:
+            if not is_float and (int(bound) != bound or not np.iinfo(nt).min <= int(bound) <= np.iinfo(nt).max):
+                raise ValueError("not an integer of that range")
+            with np.errstate(over="ignore"):
+                a = np.array([float(bound) if is_float else int(bound)], dtype=nt)
+        except (OverflowError, ValueError, TypeError) as e:
+            raise MsdError(f"the bound {bound!r} is not a value of {keys.dtype}: {e}")
+        return int(a.view(np.uint32 if width == 32 else np.uint64)[0])
+
+    def compact(self, keys=None, mask=None, lo=None, hi=None, invert: bool = False, rest: bool = False, values=None, indices: bool = False,
+                cap: Optional[int] = None, out=None, out_values=None, out_indices=None):
+        """The filter: the elements that a predicate keeps, in their original order (the call is stable) -- ``x[mask]``,
+        ``torch.masked_select``, ``torch.nonzero``, a ``WHERE lo <= key AND key <= hi``.  Element i is kept if
+        ``mask[i] != 0`` (where a ``mask`` is given: any one-byte dtype, ``torch.bool`` included) AND ``lo <= keys[i] <= hi``
+        (where ``lo`` or ``hi`` is given: Python numbers, converted to the keys' dtype, both inclusive, ``None`` the lowest
+        / highest key of the dtype); ``invert`` keeps exactly the others.  With neither a mask nor a bound everything is
+        kept.  ``keys`` is float32, int32, float64, int64, uint32 or uint64 and may be ``None`` for the mask-only form;
+        ``values`` is a column of 4- or 8-byte elements of any dtype, as long as the keys or the mask.  All tensors are
+        1-D and contiguous, and they are not modified.
+
+        The range is tested in the key order of this library: floats in IEEE-754 totalOrder on their bits.  -0.0 is below
+        +0.0, so ``lo=0.0`` drops the -0.0s that ``keys >= 0`` keeps in torch; a NaN is an ordinary key above +inf (below
+        -inf with the sign bit set), so ``hi=None`` keeps the +NaNs and ``hi=float("inf")`` does not, where every torch
+        comparison with a NaN is false.  ``lo > hi`` keeps nothing.
+
+        Returns ``(out_keys, out_values, out_indices, count)``; an output that was not asked for is ``None``: the kept keys
+        (whenever ``keys`` is given; bit-exact), the kept values (with ``values``) and the int64 positions of the kept
+        elements (with ``indices`` or ``out_indices``).  ``count`` is a one-element int64 tensor on the device: the true
+        number m of kept elements, also when m > ``cap`` (default: the number of elements).  The outputs are allocated at
+        ``cap`` elements, or are ``out`` / ``out_values`` / ``out_indices`` of at least that many; their first
+        min(m, cap) elements are written and nothing else.  With ``rest`` (a stable partitioning into kept and rejected)
+        the outputs hold all elements: the kept ones, then the rejected ones in their original order, ``count`` being the
+        split point and ``out_indices`` a permutation that :meth:`run_encode` and :meth:`reduce_runs` take as
+        ``positions``; ``cap`` must then be at least the number of elements.  Nothing waits on the host."""
+        torch = _torch()
+        if keys is None and mask is None:
+            raise MsdError("compact needs keys or a mask")
+        given = [t for t in (keys, mask, values) if t is not None]
+        if any(t.dim() != 1 or not t.is_contiguous() for t in given):
+            raise MsdError("compact takes 1-D contiguous tensors")
+        n = given[0].numel()
+        if any(t.numel() != n for t in given):
+            raise MsdError("keys, mask and values differ in length")
+        kt = self._key_type(keys) if keys is not None else 0   # (a dtype without a key order is refused here)
+        if mask is not None and mask.element_size() != 1:
+            raise MsdError(f"the mask has a one-byte dtype (torch.bool, uint8, int8), not {mask.dtype}")
+        if values is not None and values.element_size() not in (4, 8):
+            raise MsdError(f"compact takes values of 4- or 8-byte elements, not {values.dtype}")
+        want_range = lo is not None or hi is not None
+        if want_range and keys is None:
+            raise MsdError("lo / hi without keys")
+        if (out is not None and keys is None) or (out_values is not None and values is None):
+            raise MsdError("out without keys, or out_values without values")
+        cap = n if cap is None else int(cap)
+        if cap < 0:
+            raise MsdError("cap must not be negative")
+        if rest and cap < n:
+            raise MsdError("rest needs cap >= the number of elements")
+        want_idx = bool(indices) or out_indices is not None
+        for t, like, what in ((out, keys, "out"), (out_values, values, "out_values")):
+            if t is not None and (t.dtype != like.dtype or t.dim() != 1 or not t.is_contiguous() or t.numel() < cap):
+                raise MsdError(f"{what} must be a contiguous 1-D tensor of the input's dtype with at least cap elements")
+        if out_indices is not None and (out_indices.dtype != torch.int64 or out_indices.dim() != 1 or not out_indices.is_contiguous() or out_indices.numel() < cap):
+            raise MsdError("out_indices must be a contiguous 1-D int64 tensor with at least cap elements")
+        self._on_gpu(keys, mask, values, out, out_values, out_indices)
+        lo_bits = self._bound_bits(keys, kt, lo, True) if want_range else 0
+        hi_bits = self._bound_bits(keys, kt, hi, False) if want_range else 0
+        dev = given[0].device
+        if keys is not None and out is None:
+            out = torch.empty(cap, dtype=keys.dtype, device=dev)
+        if values is not None and out_values is None:
+            out_values = torch.empty(cap, dtype=values.dtype, device=dev)
+        if want_idx and out_indices is None:
+            out_indices = torch.empty(cap, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        flags = (self.COMPACT_RANGE if want_range and n else 0) | (self.COMPACT_INVERT if invert else 0) | (self.COMPACT_REST if rest else 0)
+        # (nothing to filter: only the count is written, and an empty tensor has no address to hand over)
+        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and (n or x is count) else 0)
+        mask8 = mask.view(torch.uint8) if mask is not None else None
+        self._ok(self._L.msd_compact(self._h, ptr(keys), kt, n, ptr(mask8), lo_bits, hi_bits, flags, ptr(values),
+                                     values.element_size() if values is not None else 0, cap, ptr(out), ptr(out_values), ptr(out_indices), ptr(count)))
+        return out, out_values, out_indices, count
+
+    def masked_select(self, t, mask):
+        """``torch.masked_select(t, mask)`` for contiguous tensors of one shape: the elements of ``t`` (float32, int32,
+        float64, int64, uint32 or uint64; bit-exact) where ``mask`` (a one-byte dtype) is non-zero, 1-D, in their order.
+        :meth:`compact` and ONE host wait: the count sizes the result."""
+        if tuple(t.shape) != tuple(mask.shape) or not t.is_contiguous() or not mask.is_contiguous():
+            raise MsdError("masked_select takes contiguous tensors of one shape")
+        out, _, _, count = self.compact(t.reshape(-1), mask=mask.reshape(-1))
+        return out[:int(count.item())]
+
+    def nonzero(self, mask):
+        """``torch.nonzero(mask).flatten()`` for a 1-D contiguous ``mask`` of a one-byte dtype: the int64 positions of its
+        non-zero bytes, ascending.  :meth:`compact` in its mask-only form and ONE host wait: the count sizes the result."""
+        _, _, idx, count = self.compact(mask=mask, indices=True)
+        return idx[:int(count.item())]
+
+    def filter_range(self, keys, lo, hi, values=None):
+        """The keys with ``lo <= key <= hi`` in their order -- and, with ``values``, ``(keys, values)``: the rows of the
+        value column beside them.  The range is tested as in :meth:`compact` (floats in totalOrder: -0.0 is below +0.0, a
+        NaN is an ordinary key), so it equals ``keys[(keys >= lo) & (keys <= hi)]`` on data without NaNs and negative
+        zeros.  :meth:`compact` and ONE host wait: the count sizes the result."""
+        if lo is None and hi is None:
+            raise MsdError("filter_range takes a bound")
+        out, out_values, _, count = self.compact(keys, lo=lo, hi=hi, values=values)
+        m = int(count.item())
+        return out[:m] if values is None else (out[:m], out_values[:m])
+
     # ---- sorted search (include/msd_search_hip.h)
     def search_sorted_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, direct_tile)`` of ``msd_search_sorted_limits``: the elements (keys plus needles together) one

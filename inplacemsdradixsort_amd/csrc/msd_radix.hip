@@ -11,6 +11,7 @@
 #include "msd_runs.hpp"
 #include "msd_reduce.hpp"
 #include "msd_scan.hpp"
+#include "msd_compact.hpp"
 #include "msd_search.hpp"
 #include "msd_merge2.hpp"
 #include "msd_setops.hpp"
@@ -22,6 +23,7 @@
 #include "../../include/msd_runs_hip.h"
 #include "../../include/msd_reduce_hip.h"
 #include "../../include/msd_scan_hip.h"
+#include "../../include/msd_compact_hip.h"
 #include "../../include/msd_search_hip.h"
 #include "../../include/msd_merge_hip.h"
 #include "../../include/msd_setops_hip.h"
@@ -3019,6 +3021,108 @@ int msd_scan_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, con
 	HIPCHK(c, hipSetDevice(c->device));
 	return with_width(key_bytes, [&](auto k0) {
 		return scan_runs_typed(c, (const decltype(k0) *)d_keys, n, count ? nullptr : d_vals, val_type, op, flags, d_out);
+	});
+}
+
+} // extern "C"
+
+// ---- stream compaction and stable partition (msd_compact.hpp)
+
+// Count, scan, write: four launches one behind the other on the stream, nothing read back.  The scratch -- one word per
+// tile and one per scan piece -- is the slab's, like msd_run_encode's.  in.keys is what the write pass reads (null where it
+// needs no keys); the count reads keys for the range test only.  n == 0 is one launch that writes a count of 0.
+template <typename E, bool RANGE, bool MASK, int VB, bool REST>
+static int compact_impl(msd_ctx *c, const CompactIn<E> &in, const void *vals, uint64_t cap, E *out_keys, void *out_vals, uint64_t *out_idx, uint64_t *count)
+{
+	if (in.n == 0) {
+		phase_begin(c);
+		LAUNCH(c, runs_empty_kernel, 1, 64, 0, count, (uint64_t *)nullptr);
+	} else {
+		const uint64_t tiles = (in.m + in.n + RunsCfg<E>::TILE - 1) / RunsCfg<E>::TILE; // (<= 2^25 + 1)
+		const uint64_t pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile;
+		uint64_t *tile_counts = nullptr, *piece_sums = nullptr;
+		if (int rc = slab_carve(c, [&](Bump &b) {
+			    tile_counts = b.take<uint64_t>(tiles);
+			    piece_sums = b.take<uint64_t>(pieces);
+		    }))
+			return rc;
+		CompactIn<E> cin = in;
+		if (!RANGE) cin.keys = nullptr;
+		phase_begin(c);
+		LAUNCH(c, (compact_count_kernel<E, RANGE, MASK>), (unsigned)tiles, kRunsTh, 0, cin, tile_counts);
+		LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
+		LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, count);
+		if (out_keys || out_vals || out_idx) // (none: the call only counts)
+			LAUNCH(c, (compact_write_kernel<E, RANGE, MASK, VB, REST>), (unsigned)tiles, kRunsTh, 0, in, vals, cap, tile_counts, piece_sums, count, out_keys, out_vals, out_idx);
+	}
+	phase_mark(c, "compact");
+	phase_end(c);
+	return MSD_OK;
+}
+
+// the values' width -> f(std::integral_constant<int, 0 | 4 | 8>())
+template <typename F> static int with_val_bytes(int vb, F &&f)
+{
+	if (vb == 4) return f(std::integral_constant<int, 4>());
+	if (vb == 8) return f(std::integral_constant<int, 8>());
+	return f(std::integral_constant<int, 0>());
+}
+
+template <typename E>
+static int compact_typed(msd_ctx *c, const CompactIn<E> &in, bool range, bool rest, const void *vals, int vb, uint64_t cap, void *out_keys, void *out_vals,
+			 uint64_t *out_idx, uint64_t *count)
+{
+	return with_flag(range, [&](auto rg) {
+		return with_flag(in.mask != nullptr, [&](auto mk) {
+			return with_flag(rest, [&](auto rs) {
+				return with_val_bytes(vb, [&](auto v) {
+					return compact_impl<E, decltype(rg)::value, decltype(mk)::value, decltype(v)::value, decltype(rs)::value>(c, in, vals, cap, (E *)out_keys, out_vals, out_idx,
+																		     count);
+				});
+			});
+		});
+	});
+}
+
+extern "C" {
+
+int msd_compact_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile) { return msd_run_encode_limits(key_bytes, tile, scan_tile); }
+
+int msd_compact(msd_ctx *c, const void *d_keys, int key_type, uint64_t n, const uint8_t *d_mask, uint64_t lo_bits, uint64_t hi_bits, int flags, const void *d_vals,
+		int val_bytes, uint64_t cap, void *d_out_keys, void *d_out_vals, uint64_t *d_out_idx, uint64_t *d_count)
+{
+	if (!c) return MSD_EINVAL;
+	if (d_keys && !key_type_ok(key_type)) return fail(c, MSD_EINVAL, "unknown key_type");
+	if (flags & ~(MSD_COMPACT_RANGE | MSD_COMPACT_INVERT | MSD_COMPACT_REST)) return fail(c, MSD_EINVAL, "unknown flags");
+	if (!d_count) return fail(c, MSD_EINVAL, "d_count is required");
+	const bool range = (flags & MSD_COMPACT_RANGE) != 0, rest = (flags & MSD_COMPACT_REST) != 0;
+	if ((range || d_out_keys) && !d_keys) return fail(c, MSD_EINVAL, "MSD_COMPACT_RANGE or d_out_keys without d_keys");
+	// without keys the grid is the mask's, with the 4-byte geometry (key_type is not looked at)
+	const uint32_t es = d_keys ? (uint32_t)key_type_bytes(key_type) : 4u;
+	if (range && es == 4 && ((lo_bits | hi_bits) >> 32)) return fail(c, MSD_EINVAL, "a bound of a 32-bit key type has bits above 2^32");
+	if ((d_vals != nullptr) != (d_out_vals != nullptr)) return fail(c, MSD_EINVAL, "d_vals and d_out_vals go together");
+	if (d_vals && val_bytes != 4 && val_bytes != 8) return fail(c, MSD_EINVAL, "val_bytes must be 4 or 8");
+	if (n && !d_keys && !d_mask && (d_out_keys || d_out_vals)) return fail(c, MSD_EINVAL, "neither d_keys nor d_mask: there is nothing to take elements from");
+	// the extents: inputs first, then the outputs; at most min(cap, n) elements are stored (REST: cap >= n), n at most 2^36 - 1 wherever an extent is looked at
+	const uint32_t vs = d_vals ? (uint32_t)val_bytes : 0u;
+	const uint64_t stored = std::min({ cap, n, kMaxElems });
+	const Span buf[7] = { span_of(d_keys, n, es),          span_of(d_mask, n, 1),           span_of(d_vals, n, vs ? vs : 1), span_of(d_out_keys, stored, es),
+			      span_of(d_out_vals, stored, vs ? vs : 1), span_of(d_out_idx, stored, 8), span_of(d_count, 1, 8) };
+	if (first_misaligned(buf) >= 0)
+		return fail(c, MSD_EINVAL, "every buffer must be aligned to its element size (d_keys, d_out_keys: the key's; d_vals, d_out_vals: val_bytes; d_out_idx, d_count: 8)");
+	if (n >= kMaxElems) return fail(c, MSD_EINVAL, "n too large: fewer than 2^36 elements");
+	if (rest && cap < n) return fail(c, MSD_EINVAL, "MSD_COMPACT_REST needs cap >= n");
+	if (outputs_overlap(buf, 3)) return fail(c, MSD_EINVAL, "the outputs must not overlap d_keys, d_mask, d_vals or each other (in-place operation is not offered)");
+	HIPCHK(c, hipSetDevice(c->device));
+	const bool read_keys = range || d_out_keys; // (the write pass; the count reads them for the range test only)
+	return with_width(read_keys ? (int)es : 4, [&](auto k0) {
+		typedef decltype(k0) E;
+		const KeyCodec<E> cd = range ? key_codec<E>(key_type) : KeyCodec<E>{ 0, 0 };
+		const void *grid = read_keys ? d_keys : d_mask ? (const void *)d_mask : nullptr; // whose 16-byte grid the tiles lie on
+		const uint32_t m = read_keys ? runs_misalign((const E *)d_keys) : (uint32_t)((uintptr_t)grid & 15u);
+		const CompactIn<E> in{ read_keys ? (const E *)d_keys : nullptr, d_mask, n, m, (flags & MSD_COMPACT_INVERT) ? 1u : 0u, cd,
+				       range ? cd.enc((E)lo_bits) : (E)0, range ? cd.enc((E)hi_bits) : (E)0 };
+		return compact_typed<E>(c, in, range, rest, d_vals, (int)vs, cap, d_out_keys, d_out_vals, d_out_idx, d_count);
 	});
 }
 
