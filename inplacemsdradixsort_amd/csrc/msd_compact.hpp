@@ -4,7 +4,7 @@
 // their order (stable), with REST the rejected ones follow them in theirs.  Three stream-ordered steps, and no workgroup
 // ever waits for another one (stream order is the only barrier between them):
 //   1. compact_count_kernel: one workgroup per tile evaluates keep per element and counts, one word per tile.
-//   2. runs_scan_pieces_kernel / runs_scan_top_kernel of msd_runs.hpp, unchanged: the tile counts scanned in place, the
+//   2. runs_scan_pieces_kernel / runs_scan_top_kernel of msd_runs.hpp: the tile counts scanned in place, the
 //      number of kept elements written to *d_count.
 //   3. compact_write_kernel: reads each tile again, evaluates keep again, ranks every kept element (REST: every element) in
 //      the tile, stages key and place in the LDS at that rank and stores from there in output order: coalesced stores
@@ -12,7 +12,8 @@
 //      sweep; nothing is gathered from global memory.
 //
 // The geometry is that of msd_runs.hpp (RunsCfg<E>, virtual indices on the 16-byte grid, the partial 16 bytes at either end
-// read element by element).  The grid is the keys' when keys are read, else the mask's with the 4-byte geometry.  The mask
+// read element by element: runs_load_keys), and so are the count word, the ranks and the tile's base (runs_store_count,
+// runs_rank, tile_out_base).  The grid is the keys' when keys are read, else the mask's with the 4-byte geometry.  The mask
 // and the values lie at any phase of that grid: a lane's V mask bytes (V values) are one load where their address is
 // aligned for it and lies inside the array, else one load per element; mask[-1] and mask[n] are never read.
 #pragma once
@@ -57,46 +58,29 @@ template <typename T, uint32_t V> __device__ __forceinline__ void compact_load_l
 	}
 }
 
-// This lane's keys of tile `tile` (x[k][e]: virtual index wave's first + (k * 64 + lane) * V + e; zeros without keys) and
-// the ballots of keep, one per (k, e)
+// This lane's keys of tile `tile` (runs_load_keys of msd_runs.hpp; zeros without keys) and the ballots of keep, one per (k, e)
 template <typename E, bool RANGE, bool MASK>
-__device__ __forceinline__ void compact_load_keep(const CompactIn<E> &in, uint64_t tile, E (&x)[kRunsVecs][RunsCfg<E>::V], uint64_t (&kb)[kRunsVecs][RunsCfg<E>::V])
+__device__ __forceinline__ void compact_load_keep(const CompactIn<E> &in, uint64_t tile, uint32_t w, uint32_t lane, E (&x)[kRunsVecs][RunsCfg<E>::V],
+	uint64_t (&kb)[kRunsVecs][RunsCfg<E>::V])
 {
-	typedef RunsCfg<E> C;
-	constexpr uint32_t V = C::V;
-	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	constexpr uint32_t V = RunsCfg<E>::V;
 	const uint64_t lo = in.m, hi = (uint64_t)in.m + in.n; // the array in virtual indices
-	const uint64_t wv0 = tile * C::TILE + w * C::WAVE;    // the wave's first virtual index
 	uint8_t mb[kRunsVecs][V];
+	if (in.keys) {
+		runs_load_keys<E>(in.keys - in.m, lo, hi, tile, w, lane, x);
+	} else {
 #pragma unroll
-	for (int k = 0; k < kRunsVecs; ++k) {
-		const uint64_t v0 = wv0 + (uint64_t)((k * 64 + lane) * V);
-		if (in.keys) {
-			const E *const vbase = in.keys - in.m; // (16-byte aligned; dereferenced inside [lo, hi) only)
-			if (v0 >= lo && v0 + V <= hi) {
-				const u32x4 q = *reinterpret_cast<const u32x4 *>(vbase + v0);
-				if constexpr (sizeof(E) == 4) {
-					x[k][0] = q.x;
-					x[k][1] = q.y;
-					x[k][2] = q.z;
-					x[k][3] = q.w;
-				} else {
-					x[k][0] = (E)q.x | ((E)q.y << 32);
-					x[k][1] = (E)q.z | ((E)q.w << 32);
-				}
-			} else {
-#pragma unroll
-				for (uint32_t e = 0; e < V; ++e) x[k][e] = (v0 + e >= lo && v0 + e < hi) ? vbase[v0 + e] : (E)0;
-			}
-		} else {
+		for (int k = 0; k < kRunsVecs; ++k)
 #pragma unroll
 			for (uint32_t e = 0; e < V; ++e) x[k][e] = 0;
-		}
-		if constexpr (MASK) compact_load_lane<uint8_t, V>(in.mask - in.m, v0, lo, hi, mb[k]);
+	}
+	if constexpr (MASK) {
+#pragma unroll
+		for (int k = 0; k < kRunsVecs; ++k) compact_load_lane<uint8_t, V>(in.mask - in.m, runs_vindex<E>(tile, w, lane, k), lo, hi, mb[k]);
 	}
 #pragma unroll
 	for (int k = 0; k < kRunsVecs; ++k) {
-		const uint64_t v0 = wv0 + (uint64_t)((k * 64 + lane) * V);
+		const uint64_t v0 = runs_vindex<E>(tile, w, lane, k);
 #pragma unroll
 		for (uint32_t e = 0; e < V; ++e) {
 			const uint64_t v = v0 + e;
@@ -116,18 +100,10 @@ template <typename E, bool RANGE, bool MASK>
 __global__ __launch_bounds__(kRunsTh) void compact_count_kernel(CompactIn<E> in, uint64_t *__restrict__ tile_counts)
 {
 	typedef RunsCfg<E> C;
-	__shared__ uint32_t wsum[kRunsTh / 64];
 	E x[kRunsVecs][C::V];
 	uint64_t kb[kRunsVecs][C::V];
-	compact_load_keep<E, RANGE, MASK>(in, blockIdx.x, x, kb);
-	uint32_t c = 0;
-#pragma unroll
-	for (int k = 0; k < kRunsVecs; ++k)
-#pragma unroll
-		for (uint32_t e = 0; e < C::V; ++e) c += (uint32_t)__popcll(kb[k][e]);
-	if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = c;
-	__syncthreads();
-	if (threadIdx.x == 0) tile_counts[blockIdx.x] = (uint64_t)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+	compact_load_keep<E, RANGE, MASK>(in, blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63u, x, kb);
+	runs_store_count<C::V>(kb, tile_counts);
 }
 
 // ---- step 3
@@ -135,16 +111,14 @@ __global__ __launch_bounds__(kRunsTh) void compact_count_kernel(CompactIn<E> in,
 // REST a rejected one behind the `kept` kept ones, at its rank among the rejected.  The elements of the array are the places
 // [pstart, pend) of the tile, so the rejected in front of place p are (p - pstart) minus the kept in front of it.
 template <typename E, bool REST, typename F>
-__device__ __forceinline__ void compact_for_slots(const uint64_t (&kb)[kRunsVecs][RunsCfg<E>::V], uint32_t wpre, const uint32_t (&before_k)[kRunsVecs], uint32_t kept,
-	uint32_t pstart, uint32_t pend, F &&f)
+__device__ __forceinline__ void compact_for_slots(const uint64_t (&kb)[kRunsVecs][RunsCfg<E>::V], const RunsRank &rk, uint32_t pstart, uint32_t pend, F &&f)
 {
-	typedef RunsCfg<E> C;
-	constexpr uint32_t V = C::V;
-	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	constexpr uint32_t V = RunsCfg<E>::V;
+	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, kept = rk.total;
 #pragma unroll
 	for (int k = 0; k < kRunsVecs; ++k) {
-		const uint32_t p0 = w * C::WAVE + (uint32_t)(k * 64 + lane) * V; // place in the tile
-		uint32_t r = wpre + before_k[k];                                  // kept elements of the tile in front of the element
+		const uint32_t p0 = runs_place<E>(w, lane, k);
+		uint32_t r = rk.wpre + rk.before_k[k]; // kept elements of the tile in front of the element
 #pragma unroll
 		for (uint32_t e = 0; e < V; ++e) r += popc_below_lane(kb[k][e]);
 #pragma unroll
@@ -180,35 +154,22 @@ __global__ __launch_bounds__(kRunsTh) void compact_write_kernel(CompactIn<E> in,
 	const uint64_t tile = blockIdx.x, t0 = tile * C::TILE, lo = in.m, hi = (uint64_t)in.m + in.n;
 	E x[kRunsVecs][V];
 	uint64_t kb[kRunsVecs][V];
-	compact_load_keep<E, RANGE, MASK>(in, tile, x, kb);
+	compact_load_keep<E, RANGE, MASK>(in, tile, w, lane, x, kb);
 	VT y[VB ? kRunsVecs : 1][V];
 	if constexpr (VB != 0) { // (in flight while the keys are staged)
 #pragma unroll
-		for (int k = 0; k < kRunsVecs; ++k)
-			compact_load_lane<VT, V>(static_cast<const VT *>(vals) - in.m, t0 + w * C::WAVE + (uint64_t)((k * 64 + lane) * V), lo, hi, y[k]);
+		for (int k = 0; k < kRunsVecs; ++k) compact_load_lane<VT, V>(static_cast<const VT *>(vals) - in.m, runs_vindex<E>(tile, w, lane, k), lo, hi, y[k]);
 	}
-	uint32_t before_k[kRunsVecs], c = 0; // kept elements of the wave in front of k (uniform)
-#pragma unroll
-	for (int k = 0; k < kRunsVecs; ++k) {
-		before_k[k] = c;
-#pragma unroll
-		for (uint32_t e = 0; e < V; ++e) c += (uint32_t)__popcll(kb[k][e]);
-	}
-	if (lane == 0) wsum[w] = c;
-	__syncthreads();
-	uint32_t wpre = 0;
-#pragma unroll
-	for (uint32_t ww = 0; ww < kRunsTh / 64 - 1; ++ww)
-		if (ww < w) wpre += wsum[ww];
-	const uint32_t kept = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+	const RunsRank rk = runs_rank<V>(kb, w, lane, wsum);
+	const uint32_t kept = rk.total;
 	const uint32_t pstart = lo > t0 ? (uint32_t)(lo - t0) : 0u, pend = hi - t0 < C::TILE ? (uint32_t)(hi - t0) : C::TILE; // (tile < tiles: hi > t0)
 	const uint32_t staged = REST ? pend - pstart : kept;
-	const uint64_t base = tile_base[tile] + piece_base[tile / kRunsScanTile]; // kept elements in front of the tile
+	const uint64_t base = tile_out_base(tile_base, piece_base, tile);         // kept elements in front of the tile
 	uint64_t rest_base = 0;                                                   // where slot `kept` goes
 	if constexpr (REST) rest_base = *total + ((t0 + pstart - lo) - base);
 	const auto dst_of = [&](uint32_t j) { return j < kept ? base + j : rest_base + (j - kept); };
 
-	compact_for_slots<E, REST>(kb, wpre, before_k, kept, pstart, pend, [&](int k, uint32_t e, uint32_t slot, uint32_t p) {
+	compact_for_slots<E, REST>(kb, rk, pstart, pend, [&](int k, uint32_t e, uint32_t slot, uint32_t p) {
 		if (out_keys) skey[slot] = x[k][e];
 		at[slot] = (uint16_t)p;
 	});
@@ -223,7 +184,7 @@ __global__ __launch_bounds__(kRunsTh) void compact_write_kernel(CompactIn<E> in,
 	}
 	if constexpr (VB != 0) {
 		__syncthreads(); // (the keys have left the buffer)
-		compact_for_slots<E, REST>(kb, wpre, before_k, kept, pstart, pend, [&](int k, uint32_t e, uint32_t slot, uint32_t) { sval[slot] = y[k][e]; });
+		compact_for_slots<E, REST>(kb, rk, pstart, pend, [&](int k, uint32_t e, uint32_t slot, uint32_t) { sval[slot] = y[k][e]; });
 		__syncthreads();
 		for (uint32_t j = threadIdx.x; j < staged; j += kRunsTh) {
 			const uint64_t dst = dst_of(j);

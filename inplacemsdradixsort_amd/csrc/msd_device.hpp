@@ -270,6 +270,19 @@ __device__ __forceinline__ uint64_t block_excl_scan256_64(uint64_t v, uint64_t *
 template <typename K> struct Vec16;
 template <> struct Vec16<uint32_t> { static constexpr int N = 4; };
 template <> struct Vec16<uint64_t> { static constexpr int N = 2; };
+// one aligned 16 bytes as its Vec16<K>::N elements
+template <typename K> __device__ __forceinline__ void vec16_unpack(const u32x4 q, K (&x)[Vec16<K>::N])
+{
+	if constexpr (sizeof(K) == 4) {
+		x[0] = q.x;
+		x[1] = q.y;
+		x[2] = q.z;
+		x[3] = q.w;
+	} else {
+		x[0] = (K)q.x | ((K)q.y << 32);
+		x[1] = (K)q.z | ((K)q.w << 32);
+	}
+}
 
 // ------------------------------------ A': classify with direct block placement
 

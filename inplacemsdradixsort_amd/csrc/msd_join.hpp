@@ -5,13 +5,13 @@
 // the key, the first index and the length of its run in a, and the same for b.  The groups are the join in CSR form.
 //
 // ---- msd_join_groups: the steps of msd_setops.hpp, no atomics, and no workgroup ever waits for another one:
-//   1. merge_split_kernel (msd_merge2.hpp, unchanged): the merge path's cut of the merged sequence into tiles.
-//   2. set_count_kernel (msd_setops.hpp, unchanged) with the mask of the intersection: the kept elements of a tile are the
+//   1. search_split_kernel (msd_search.hpp) with the RIGHT rule: the merge path's cut of the merged sequence into tiles.
+//   2. set_count_kernel (msd_setops.hpp) with the mask of the intersection: the kept elements of a tile are the
 //      matched heads of a -- one per group, at the tile that holds the first a of the group.
-//   3. runs_scan_pieces_kernel, runs_scan_top_kernel (msd_runs.hpp, unchanged): the tiles' bases and *d_num_groups.
-//   4. join_write_kernel: stages the tile, decides again (the A side of set_decide: head and matched), compacts the kept
-//      heads in the order of their local index -- ballots, wave by wave, as set_write_kernel does -- and works out, for
-//      the kept heads only, the four numbers of the group.
+//   3. runs_scan_pieces_kernel, runs_scan_top_kernel (msd_runs.hpp): the tiles' bases and *d_num_groups.
+//   4. join_write_kernel: stages the tile, decides again (set_decide_a: head and matched), compacts the kept heads in the
+//      order of their local index (ballot_compact of msd_merge2.hpp) and works out, for the kept heads only, the four
+//      numbers of the group.
 //
 // For a kept head with code v at local index e:  a_first = a_i + e, and b_first = b_i + |{ b in tile : b < v }|, which is
 // exact by the argument of msd_setops.hpp: every b in front of the tile is strictly smaller than v.
@@ -36,7 +36,7 @@
 //      runs_scan_pieces_kernel scans tile counts -- the product is formed where that kernel loads a word, so no array of
 //      products is written and read again -- into exclusive offsets, 8 bytes per group, and one sum per piece.  A piece
 //      behind the last group writes its sum of 0 and nothing else: groups_cap may be far above G at no cost in traffic.
-//   2. runs_scan_top_kernel (msd_runs.hpp, unchanged): the pieces' bases and *d_num_pairs.  off[g] = the group's word plus
+//   2. runs_scan_top_kernel (msd_runs.hpp): the pieces' bases and *d_num_pairs.  off[g] = the group's word plus
 //      its piece's base, for g < G; behind the last group off is the total.
 //   3. join_expand_kernel, OUTPUT-partitioned: workgroup j owns the ranks [j * PAIR_TILE, min((j + 1) * PAIR_TILE, total,
 //      cap)) and leaves before it loads anything else if that is empty.  Every group holds at least one pair, so the range
@@ -52,32 +52,16 @@
 
 #include "msd_device.hpp"
 #include "msd_keycodec.hpp"
-#include "msd_merge2.hpp" // MergeCfg, merge_split_kernel
-#include "msd_runs.hpp"   // kRunsScanTile: the scan of the tile counts and of the products
-#include "msd_search.hpp" // search_stage, search_counts
-#include "msd_setops.hpp" // set_tile, set_count_kernel, kSetNone
+#include "msd_merge2.hpp" // MergeCfg, tile_out_window, ballot_compact, kSetNone
+#include "msd_runs.hpp"   // runs_scan_piece, tile_out_base: the scan of the products
+#include "msd_search.hpp" // search_stage, lds_count
+#include "msd_setops.hpp" // set_tile, set_decide_a, set_count_kernel
 
 namespace msd {
 
 // Fewer than 2^32 elements per side: every product a_count * b_count and the number of pairs (at most n * m) fit 64 bits, and
 // an index into a or b fits the 32-bit words the expansion stages.  Fewer than 2^40 pairs are stored by one call (its grid).
 constexpr uint64_t kJoinMaxElems = (uint64_t)1 << 32, kJoinMaxStored = (uint64_t)1 << 40;
-
-// |{ k in codes[0, len) : k < x }| (RIGHT: <= x): the branch-free search of merge_rank, one element
-template <typename K> __device__ __forceinline__ uint32_t join_lds_count(const K *__restrict__ codes, uint32_t len, K x, bool right)
-{
-	uint32_t base = 0;
-	if (len) {
-		uint32_t l = len; // invariant: the count lies in [base, base + l], base + l <= len
-		while (l > 1) {
-			const uint32_t half = l >> 1;
-			base += search_counts(codes[base + half - 1], x, right) ? half : 0u;
-			l -= half;
-		}
-		base += search_counts(codes[base], x, right) ? 1u : 0u;
-	}
-	return base;
-}
 
 // |{ k in keys[lo, hi) : code(k) <= v }| + lo: where the run of v ends behind lo (lo <= hi <= the array's length; one lane)
 template <typename K> __device__ __forceinline__ uint64_t join_global_upper(const K *__restrict__ keys, uint64_t lo, uint64_t hi, K v, KeyCodec<K> cd)
@@ -91,7 +75,7 @@ template <typename K> __device__ __forceinline__ uint64_t join_global_upper(cons
 }
 
 // ---- msd_join_groups, step 4
-// The groups go to [base, lim) as in set_write_kernel.  LDS: the codes (16 KiB), per local a its b count or kSetNone, and the
+// The groups go to the tile's window [base, lim) (tile_out_window).  LDS: the codes (16 KiB), per local a its b count or kSetNone, and the
 // compacted local indices and b counts (3 x TILE x 2 bytes): 40 KiB for 4-byte keys, 28 KiB for 8-byte keys.
 template <typename K>
 __global__ __launch_bounds__(kMergeTh) void join_write_kernel(const K *__restrict__ a, uint64_t n, const K *__restrict__ b, uint64_t m, KeyCodec<K> cd,
@@ -104,10 +88,8 @@ __global__ __launch_bounds__(kMergeTh) void join_write_kernel(const K *__restric
 	__shared__ uint16_t below[TILE];  // per local a: |{ b in tile : b < a }| if it is a matched head, else kSetNone
 	__shared__ uint16_t kept_e[TILE]; // the kept heads' local indices, compacted
 	__shared__ uint16_t kept_lb[TILE]; // ... and their b counts
-	const uint64_t i = blockIdx.x;
-	const uint64_t base = tile_base[i] + piece_base[i / kRunsScanTile];
-	const uint64_t next = i + 1 < gridDim.x ? tile_base[i + 1] + piece_base[(i + 1) / kRunsScanTile] : *num_groups;
-	const uint64_t lim = next < cap ? next : cap;
+	const TileOutWindow win = tile_out_window(tile_base, piece_base, num_groups, cap);
+	const uint64_t base = win.base, lim = win.lim;
 	if (base >= lim) return; // (uniform: the barriers below are never reached by a part of the workgroup)
 	const SetTile<K> t = set_tile<K>(a, n, b, m, cd, splits);
 	if (t.na == 0) return; // (uniform) no a, no head
@@ -117,75 +99,21 @@ __global__ __launch_bounds__(kMergeTh) void join_write_kernel(const K *__restric
 	search_stage<K>(a + t.a0, t.na, cd, codes);
 	search_stage<K>(b + t.b0, t.nb, cd, codes + t.na);
 	__syncthreads();
-	// the decision of set_decide's A side with the intersection's mask: kMergePer searches side by side
-	{
-		const K *const other = codes + t.na;
-		const uint32_t len = t.nb;
-		for (uint32_t e0 = threadIdx.x; e0 < t.na; e0 += kMergeTh * kMergePer) {
-			K x[kMergePer];
-			uint32_t lb[kMergePer];
-#pragma unroll
-			for (int v = 0; v < kMergePer; ++v) {
-				const uint32_t e = e0 + (uint32_t)v * kMergeTh;
-				x[v] = codes[e < t.na ? e : t.na - 1];
-				lb[v] = 0;
-			}
-			if (len) { // (uniform)
-				uint32_t l = len;
-				while (l > 1) {
-					const uint32_t half = l >> 1;
-					K k[kMergePer];
-#pragma unroll
-					for (int v = 0; v < kMergePer; ++v) k[v] = other[lb[v] + half - 1];
-#pragma unroll
-					for (int v = 0; v < kMergePer; ++v) lb[v] += k[v] < x[v] ? half : 0u;
-					l -= half;
-				}
-#pragma unroll
-				for (int v = 0; v < kMergePer; ++v) lb[v] += other[lb[v]] < x[v] ? 1u : 0u;
-			}
-#pragma unroll
-			for (int v = 0; v < kMergePer; ++v) {
-				const uint32_t e = e0 + (uint32_t)v * kMergeTh;
-				if (e < t.na) {
-					const K prev = codes[e ? e - 1 : 0u];
-					const bool head = e ? prev != x[v] : !(t.has_a_before && t.a_before == x[v]);
-					const bool in_tile = lb[v] < len;
-					const K y = codes[in_tile ? t.na + lb[v] : 0u];
-					const bool matched = in_tile ? y == x[v] : (t.has_b_behind && t.b_behind == x[v]);
-					below[e] = head && matched ? (uint16_t)lb[v] : kSetNone; // (lb <= nb < TILE <= 4096)
-				}
-			}
-		}
-	}
+	// the A side's decision with the intersection's mask: a matched head keeps its b count
+	set_decide_a<K>(codes, t, true, false, [&](uint32_t e, K, uint32_t lb, bool kept) { below[e] = kept ? (uint16_t)lb : kSetNone; }); // (lb <= nb < TILE <= 4096)
 	__syncthreads();
-	// the compaction of set_write_kernel over the local indices of a
-	const uint32_t lane = threadIdx.x & 63u, first = (threadIdx.x >> 6) * PER; // the wave's first ballot
-	uint32_t before = 0; // kept heads in front of the ballot at hand (uniform)
-	for (uint32_t c = 0; c < first; ++c) {
-		const uint32_t e = c * 64u + lane;
-		before += (uint32_t)__popcll(__ballot(e < t.na && below[e] != kSetNone));
-	}
-#pragma unroll
-	for (uint32_t k = 0; k < PER; ++k) {
-		const uint32_t e = (first + k) * 64u + lane;
-		const uint16_t s = e < t.na ? below[e] : kSetNone;
-		const uint64_t bits = __ballot(s != kSetNone);
-		const uint32_t to = before + popc_below_lane(bits);
-		if (s != kSetNone && to < cnt) {
-			kept_e[to] = (uint16_t)e;
-			kept_lb[to] = s;
-		}
-		before += (uint32_t)__popcll(bits);
-	}
+	ballot_compact<PER, false>(below, t.na, cnt, [&](uint32_t e, uint32_t to, uint16_t lb) {
+		kept_e[to] = (uint16_t)e;
+		kept_lb[to] = lb;
+	});
 	__syncthreads();
 	for (uint32_t p = threadIdx.x; p < cnt; p += kMergeTh) {
 		const uint32_t e = kept_e[p] < t.na - 1 ? kept_e[p] : t.na - 1; // (the clamps: positions nothing was compacted to)
 		const uint32_t lb = kept_lb[p] < t.nb ? kept_lb[p] : t.nb;
 		const K v = codes[e];
 		const uint64_t af = t.a0 + e, bf = t.b0 + lb;
-		const uint32_t ua = join_lds_count<K>(codes, t.na, v, true);
-		const uint32_t ub = join_lds_count<K>(codes + t.na, t.nb, v, true);
+		const uint32_t ua = lds_count<K>(codes, t.na, v, true);
+		const uint32_t ub = lds_count<K>(codes + t.na, t.nb, v, true);
 		uint64_t a_end = t.a0 + (ua > e ? ua : e + 1), b_end = t.b0 + (ub > lb ? ub : lb);
 		if (ua >= t.na && has_a_behind && a_behind == v) a_end = join_global_upper<K>(a, t.a0 + t.na, n, v, cd);
 		if (ub >= t.nb && t.has_b_behind && t.b_behind == v) b_end = join_global_upper<K>(b, t.b0 + t.nb, m, v, cd);
@@ -201,7 +129,7 @@ __global__ __launch_bounds__(kMergeTh) void join_write_kernel(const K *__restric
 constexpr int kJoinPairTh = 256, kJoinPairPer = 8;
 constexpr uint32_t kJoinPairTile = kJoinPairTh * kJoinPairPer; // ranks of one workgroup of the expansion
 
-// step 1: runs_scan_pieces_kernel over the products of the first G groups
+// step 1: runs_scan_pieces_kernel over the products of the first G groups: runs_scan_piece with the product for its load
 __global__ __launch_bounds__(kRunsScanTh) void join_offsets_kernel(uint64_t groups_cap, const uint64_t *__restrict__ num_groups, const uint64_t *__restrict__ a_count,
 	const uint64_t *__restrict__ b_count, uint64_t *__restrict__ off_word, uint64_t *__restrict__ piece_sums)
 {
@@ -213,21 +141,7 @@ __global__ __launch_bounds__(kRunsScanTh) void join_offsets_kernel(uint64_t grou
 		return;
 	}
 	const uint32_t count = G - first < kRunsScanTile ? (uint32_t)(G - first) : kRunsScanTile;
-	uint64_t v[kRunsScanPer], sum = 0;
-#pragma unroll
-	for (int j = 0; j < kRunsScanPer; ++j) {
-		const uint32_t idx = threadIdx.x * kRunsScanPer + j;
-		v[j] = idx < count ? a_count[first + idx] * b_count[first + idx] : 0;
-		sum += v[j];
-	}
-	uint64_t total;
-	uint64_t ex = block_excl_scan256_64(sum, tmp, total);
-#pragma unroll
-	for (int j = 0; j < kRunsScanPer; ++j) {
-		const uint32_t idx = threadIdx.x * kRunsScanPer + j;
-		if (idx < count) off_word[first + idx] = ex;
-		ex += v[j];
-	}
+	const uint64_t total = runs_scan_piece(off_word + first, count, 0, tmp, [&](uint32_t idx) { return a_count[first + idx] * b_count[first + idx]; });
 	if (threadIdx.x == 0) piece_sums[blockIdx.x] = total;
 }
 
@@ -248,7 +162,7 @@ __global__ __launch_bounds__(kJoinPairTh) void join_expand_kernel(uint64_t group
 	const uint32_t cnt = stop - r0 < PT ? (uint32_t)(stop - r0) : PT;
 	const uint64_t G = *num_groups < groups_cap ? *num_groups : groups_cap;
 	if (G == 0) return; // (uniform; never with total > 0)
-	auto off = [&](uint64_t g) { return off_word[g] + off_piece[g / kRunsScanTile]; }; // (g < G)
+	auto off = [&](uint64_t g) { return tile_out_base(off_word, off_piece, g); }; // (g < G)
 	// The first group: the last g < G with off[g] <= r0 (off[0] = 0).  A 64-ary search,
 	// every wave for itself: the lanes probe 64 points of [lo, hi) at once and a ballot counts those that are not beyond r0,
 	// five steps for 2^28 groups where a binary search has 28 dependent loads.  [lo, hi) only ever shrinks, whatever off holds.
@@ -274,13 +188,7 @@ __global__ __launch_bounds__(kJoinPairTh) void join_expand_kernel(uint64_t group
 	const uint32_t x0 = threadIdx.x * kJoinPairPer;
 	if (x0 < cnt) {
 		// this lane's first group: the number of k in [1, PT) with rel[k] <= x0
-		uint32_t k = 0, l = PT - 1; // invariant: the count lies in [k, k + l]
-		while (l > 1) {
-			const uint32_t half = l >> 1;
-			k += rel[1 + k + half - 1] <= x0 ? half : 0u;
-			l -= half;
-		}
-		k += rel[1 + k] <= x0 ? 1u : 0u;
+		uint32_t k = lds_count<uint32_t>(rel + 1, PT - 1, x0, true);
 		uint64_t g = g0 + k < G ? g0 + k : G - 1;
 		uint64_t q = b_count[g] ? b_count[g] : 1;
 		const uint64_t t0 = r0 + x0 - off(g);

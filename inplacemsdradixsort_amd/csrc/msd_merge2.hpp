@@ -1,11 +1,13 @@
-// msd_merge2.hpp -- merge of two sorted arrays: msd_merge_sorted.
+// msd_merge2.hpp -- merge of two sorted arrays: msd_merge_sorted, and the pieces every tile kernel
+// of the merge path shares (msd_setops.hpp, msd_join.hpp): lds_count_per, merge_store, tile_out_window, ballot_compact.
 //
 // a (n keys) and b (m keys) are ascending by CODE (msd_keycodec.hpp); the output is the stable sort of the concatenation
 // [a; b] by code: among equal codes all of a's come before all of b's, and within one side equal keys keep their order.
 // Think of the merged sequence with the tie rule "b after every a that is not larger" -- the RIGHT rule of msd_search.hpp,
 // with b in the role of the needles.  Two kernels, no atomics, and no workgroup ever waits for another one:
-//   1. merge_split_kernel: one thread per diagonal d_i = min(i * TILE, n + m) finds by binary search (the merge path) how many
-//      elements of a (a_i) and of b (b_i = d_i - a_i) the first d_i elements of the merged sequence hold, and writes a_i.
+//   1. search_split_kernel (msd_search.hpp) with the RIGHT rule: one thread per diagonal d_i = min(i * TILE, n + m) finds by
+//      binary search (the merge path) how many elements of a (a_i) and of b (b_i = d_i - a_i) the first d_i elements of the
+//      merged sequence hold, and writes a_i.
 //   2. merge_tile_kernel: one workgroup per tile i loads a[a_i, a_{i+1}) and b[b_i, b_{i+1}) -- together at most TILE
 //      elements -- as codes into the LDS and RANKS every one of them inside the tile:
 //         local a element e goes to e + |{ b in tile : code(b) <  code(a_e) }|
@@ -15,13 +17,14 @@
 //      tile's slice out[d_i, d_{i+1}) is stored coalesced (whole aligned 16 bytes where the slice covers them: merge_store is
 //      the mirror of search_stage), and position p loads its 8-byte value from vals_a / vals_b through the local index --
 //      ascending per side -- and stores it and the origin coalesced.  Stream order is the only barrier between the launches.
-// Every extent is CLAMPED (see merge_tile_kernel): inputs that are not ascending give unspecified output VALUES, but every
-// load stays inside its input array and every store inside [0, n + m) of its output.
+// Every extent is CLAMPED (merge_tile_extent of msd_search.hpp, and merge_tile_kernel): inputs that are not ascending give
+// unspecified output VALUES, but every load stays inside its input array and every store inside [0, n + m) of its output.
 #pragma once
 
 #include "msd_device.hpp"
 #include "msd_keycodec.hpp"
-#include "msd_search.hpp" // search_stage, search_counts
+#include "msd_runs.hpp"   // tile_out_base: the scanned tile counts
+#include "msd_search.hpp" // search_split_kernel, merge_tile_extent, search_stage, search_counts
 
 namespace msd {
 
@@ -32,69 +35,63 @@ template <typename K> struct MergeCfg {
 	static constexpr uint32_t TILE = kMergeTh * 4u * V;   // elements of a plus b of one workgroup: 4096 (4-byte), 2048 (8-byte): 2 x 16 KiB of LDS for codes and keys
 };
 
-// ---- step 1
-// splits[i] = a_i for i = 0 .. tiles (tiles + 1 words): search_split_kernel with the RIGHT rule and the merge's own TILE.
-// b counts the elements of b among the first d of the merged sequence: b[mid] is among them iff it PRECEDES a[d - mid - 1],
-// i.e. is strictly smaller.  The search stays inside [max(0, d - n), min(d, m)] whatever the arrays hold: mid < m and
-// 0 <= d - mid - 1 < n for every probe, and 0 <= a_i <= n, 0 <= d - a_i <= m for every result.
+// lds_count (msd_search.hpp) for kMergePer elements side by side: base[v] = |{ k in other[0, len) : k counts for x[v] }|.
+// All reads of a step come first, so the dependent LDS reads of the kMergePer searches overlap.
 template <typename K>
-__global__ __launch_bounds__(kMergeTh) void merge_split_kernel(const K *__restrict__ a, uint64_t n, const K *__restrict__ b, uint64_t m, KeyCodec<K> cd, uint64_t tiles,
-	uint64_t *__restrict__ splits)
+__device__ __forceinline__ void lds_count_per(const K *__restrict__ other, uint32_t len, const K (&x)[kMergePer], bool right, uint32_t (&base)[kMergePer])
 {
-	const uint64_t i = (uint64_t)blockIdx.x * kMergeTh + threadIdx.x;
-	if (i > tiles) return;
-	const uint64_t total = n + m, d = i * MergeCfg<K>::TILE < total ? i * MergeCfg<K>::TILE : total;
-	uint64_t lo = d > n ? d - n : 0, hi = d < m ? d : m;
-	while (lo < hi) {
-		const uint64_t mid = lo + ((hi - lo) >> 1);
-		if (cd.enc(b[mid]) < cd.enc(a[d - mid - 1])) lo = mid + 1;
-		else hi = mid;
+#pragma unroll
+	for (int v = 0; v < kMergePer; ++v) base[v] = 0;
+	if (len) { // (uniform)
+		uint32_t l = len; // invariant: the count lies in [base, base + l], base + l <= len
+		while (l > 1) {
+			const uint32_t half = l >> 1;
+			K k[kMergePer];
+#pragma unroll
+			for (int v = 0; v < kMergePer; ++v) k[v] = other[base[v] + half - 1];
+#pragma unroll
+			for (int v = 0; v < kMergePer; ++v) base[v] += search_counts(k[v], x[v], right) ? half : 0u;
+			l -= half;
+		}
+#pragma unroll
+		for (int v = 0; v < kMergePer; ++v) base[v] += search_counts(other[base[v]], x[v], right) ? 1u : 0u; // (base < len)
 	}
-	splits[i] = d - lo;
 }
 
-// The `count` codes at codes[self0 ..] are ranked against the `len` codes at codes[other0 ..] (both ascending): element e goes
-// to e + the number of the others that count for it (RIGHT: <=, else <), clamped to `last`; its decoded key goes there in
-// outk, its local index self0 + e in src.  kMergePer branch-free searches per lane whose trip count depends on len only.
-// (Every thread of the workgroup calls it.)
-template <typename K, bool RIGHT, bool SRC>
-__device__ __forceinline__ void merge_rank(const K *__restrict__ codes, uint32_t self0, uint32_t count, uint32_t other0, uint32_t len, uint32_t last, KeyCodec<K> cd,
-	K *__restrict__ outk, uint16_t *__restrict__ src)
+// The `count` codes at codes[self0 ..] against the `len` codes at codes[other0 ..] (both ascending), kMergePer per lane:
+// f(e, x, base) for every element e < count, x its code and base the number of the others that count for it (RIGHT: <=,
+// else <).  What every tile kernel of the merge path decides, it decides in f.  (Every thread of the workgroup calls it.)
+template <typename K, bool RIGHT, typename F>
+__device__ __forceinline__ void merge_for_counts(const K *__restrict__ codes, uint32_t self0, uint32_t count, uint32_t other0, uint32_t len, F &&f)
 {
-	const K *const other = codes + other0;
 	for (uint32_t e0 = threadIdx.x; e0 < count; e0 += kMergeTh * kMergePer) {
 		K x[kMergePer];
 		uint32_t base[kMergePer];
 #pragma unroll
 		for (int v = 0; v < kMergePer; ++v) {
 			const uint32_t e = e0 + (uint32_t)v * kMergeTh;
-			x[v] = codes[self0 + (e < count ? e : count - 1)]; // (a lane beyond the end ranks the last element again and places nothing)
-			base[v] = 0;
+			x[v] = codes[self0 + (e < count ? e : count - 1)]; // (a lane beyond the end searches the last element again and f is not called)
 		}
-		if (len) { // (uniform)
-			uint32_t l = len; // invariant: the count lies in [base, base + l], base + l <= len
-			while (l > 1) {
-				const uint32_t half = l >> 1;
-				K k[kMergePer];
-#pragma unroll
-				for (int v = 0; v < kMergePer; ++v) k[v] = other[base[v] + half - 1]; // (all reads of the step first)
-#pragma unroll
-				for (int v = 0; v < kMergePer; ++v) base[v] += search_counts(k[v], x[v], RIGHT) ? half : 0u;
-				l -= half;
-			}
-#pragma unroll
-			for (int v = 0; v < kMergePer; ++v) base[v] += search_counts(other[base[v]], x[v], RIGHT) ? 1u : 0u; // (base < len)
-		}
+		lds_count_per<K>(codes + other0, len, x, RIGHT, base);
 #pragma unroll
 		for (int v = 0; v < kMergePer; ++v) {
 			const uint32_t e = e0 + (uint32_t)v * kMergeTh;
-			if (e < count) {
-				const uint32_t r = e + base[v] < last ? e + base[v] : last;
-				outk[r] = cd.dec(x[v]);
-				if constexpr (SRC) src[r] = (uint16_t)(self0 + e); // (< TILE <= 4096)
-			}
+			if (e < count) f(e, x[v], base[v]);
 		}
 	}
+}
+
+// Element e of merge_for_counts goes to e + base, clamped to `last`; its decoded key goes there in outk, its local index
+// self0 + e in src.
+template <typename K, bool RIGHT, bool SRC>
+__device__ __forceinline__ void merge_rank(const K *__restrict__ codes, uint32_t self0, uint32_t count, uint32_t other0, uint32_t len, uint32_t last, KeyCodec<K> cd,
+	K *__restrict__ outk, uint16_t *__restrict__ src)
+{
+	merge_for_counts<K, RIGHT>(codes, self0, count, other0, len, [&](uint32_t e, K x, uint32_t base) {
+		const uint32_t r = e + base < last ? e + base : last;
+		outk[r] = cd.dec(x);
+		if constexpr (SRC) src[r] = (uint16_t)(self0 + e); // (< TILE <= 4096)
+	});
 }
 
 // `count` elements from the LDS at from to dst (element alignment only): the mirror of search_stage.  Every 16 bytes that lie
@@ -124,13 +121,11 @@ template <typename K> __device__ __forceinline__ void merge_store(const K *__res
 }
 
 // ---- step 2
-// The clamps: na = the tile's elements of a, at most TILE and 0 if the splits are not ascending; nb = those of b, at most what
-// is left of TILE and 0 if b_{i+1} < b_i.  With 0 <= a_i <= n and na <= a_{i+1} - a_i the loads are a[a_i, a_i + na) inside
-// [0, n) and vals_a likewise; with 0 <= b_i <= m and nb <= b_{i+1} - b_i they are b[b_i, b_i + nb) inside [0, m).  cnt = the
-// positions stored, at most the tile's slice d_{i+1} - d_i, so every store is at d_i + p < d_{i+1} <= n + m.  Every rank is
-// clamped to na + nb - 1 before it indexes the LDS, and every staged local index on read, so a position that no element
-// was ranked to (inputs that are not ascending) stores whatever the LDS held -- but loads inside the inputs.  For ascending
-// inputs the clamps change nothing: na + nb = d_{i+1} - d_i <= TILE and the ranks are a bijection.
+// The clamps of merge_tile_extent (vals_a and vals_b are read where a and b are), and: cnt = the positions stored, at most
+// the tile's slice d_{i+1} - d_i, so every store is at d_i + p < d_{i+1} <= n + m.  Every rank is clamped to na + nb - 1
+// before it indexes the LDS, and every staged local index on read, so a position that no element was ranked to (inputs
+// that are not ascending) stores whatever the LDS held -- but loads inside the inputs.  For ascending inputs the clamps
+// change nothing: na + nb = d_{i+1} - d_i <= TILE and the ranks are a bijection.
 template <typename K, bool VALS, bool ORIGIN>
 __global__ __launch_bounds__(kMergeTh) void merge_tile_kernel(const K *__restrict__ a, uint64_t n, const K *__restrict__ b, uint64_t m, KeyCodec<K> cd,
 	const uint64_t *__restrict__ splits, const uint64_t *__restrict__ vals_a, const uint64_t *__restrict__ vals_b, K *__restrict__ out, uint64_t *__restrict__ out_vals,
@@ -141,12 +136,10 @@ __global__ __launch_bounds__(kMergeTh) void merge_tile_kernel(const K *__restric
 	__shared__ K codes[TILE];                // the tile's a as codes, the tile's b as codes behind them
 	__shared__ K outk[TILE];                 // the merged keys, decoded
 	__shared__ uint16_t src[SRC ? TILE : 1]; // per position the local index of its element: < na from a, else from b
-	const uint64_t i = blockIdx.x, total = n + m;
-	const uint64_t d0 = i * TILE < total ? i * TILE : total, d1 = (i + 1) * TILE < total ? (i + 1) * TILE : total;
-	const uint64_t a0 = splits[i], a1 = splits[i + 1], b0 = d0 - a0, b1 = d1 - a1;
-	const uint32_t na = a1 > a0 ? (uint32_t)(a1 - a0 < TILE ? a1 - a0 : TILE) : 0u;
-	const uint32_t nb = b1 > b0 ? (uint32_t)(b1 - b0 < TILE - na ? b1 - b0 : TILE - na) : 0u;
-	const uint32_t cnt = na + nb < d1 - d0 ? na + nb : (uint32_t)(d1 - d0);
+	const MergeTileExtent t = merge_tile_extent<TILE>(blockIdx.x, n, m, splits);
+	const uint64_t d0 = t.d0, a0 = t.a0, b0 = t.b0;
+	const uint32_t na = t.na, nb = t.nb;
+	const uint32_t cnt = na + nb < t.d1 - d0 ? na + nb : (uint32_t)(t.d1 - d0);
 	if (cnt == 0) return; // (uniform: the barriers below are never reached by a part of the workgroup)
 	const uint32_t last = na + nb - 1;
 	search_stage<K>(a + a0, na, cd, codes);
@@ -164,6 +157,56 @@ __global__ __launch_bounds__(kMergeTh) void merge_tile_kernel(const K *__restric
 			if constexpr (VALS) out_vals[d0 + p] = from_a ? vals_a[at] : vals_b[at];
 			if constexpr (ORIGIN) out_origin[d0 + p] = from_a ? at : n + at;
 		}
+	}
+}
+
+// ---- what the writers behind a count and a scan share (msd_setops.hpp, msd_join.hpp)
+
+// Tile blockIdx.x stores to [base, lim): base = its scanned count, lim = min(the next tile's base -- *total for the last
+// tile --, cap): at most the number the count kernel counted, whatever the writer decides.  base >= lim: nothing to store,
+// and the writer leaves before it loads anything (uniform).
+struct TileOutWindow {
+	uint64_t base, lim;
+};
+__device__ __forceinline__ TileOutWindow tile_out_window(const uint64_t *__restrict__ tile_base, const uint64_t *__restrict__ piece_base, const uint64_t *__restrict__ total,
+	uint64_t cap)
+{
+	const uint64_t i = blockIdx.x;
+	const uint64_t next = i + 1 < gridDim.x ? tile_out_base(tile_base, piece_base, i + 1) : *total;
+	return TileOutWindow{ tile_out_base(tile_base, piece_base, i), next < cap ? next : cap };
+}
+
+constexpr uint16_t kSetNone = 0xFFFFu; // in place of a 16-bit word of a tile (< TILE <= 4096): the place holds no kept element
+
+// The compaction: mark[r], r < count <= 64 * 4 * PER, is kSetNone or the word of a kept element.  Wave w owns the places
+// [w * 64 * PER, (w + 1) * 64 * PER), 64 at a time; the places that hold a kept element are one ballot, the kept ones in front
+// of a place are popcounts -- of the ballots of the places in front of the wave's, which the wave forms itself (no word of
+// LDS), of the wave's own earlier ballots, and of the lower lanes' bits.  place(r, to, mark[r]) for every kept element whose
+// rank `to` among the kept is below cnt.  INPLACE: place may overwrite mark -- all of it is read in front of a barrier.
+// (Every thread of the workgroup calls it.)
+template <uint32_t PER, bool INPLACE, typename F>
+__device__ __forceinline__ void ballot_compact(const uint16_t *mark, uint32_t count, uint32_t cnt, F &&place)
+{
+	const uint32_t lane = threadIdx.x & 63u, first = (threadIdx.x >> 6) * PER; // the wave's first ballot
+	uint32_t before = 0; // kept elements in front of the ballot at hand (uniform)
+	for (uint32_t c = 0; c < first; ++c) {
+		const uint32_t r = c * 64u + lane;
+		before += (uint32_t)__popcll(__ballot(r < count && mark[r] != kSetNone));
+	}
+	uint16_t s[PER];
+	uint64_t bits[PER];
+#pragma unroll
+	for (uint32_t k = 0; k < PER; ++k) {
+		const uint32_t r = (first + k) * 64u + lane;
+		s[k] = r < count ? mark[r] : kSetNone;
+		bits[k] = __ballot(s[k] != kSetNone);
+	}
+	if constexpr (INPLACE) __syncthreads();
+#pragma unroll
+	for (uint32_t k = 0; k < PER; ++k) {
+		const uint32_t r = (first + k) * 64u + lane, to = before + popc_below_lane(bits[k]);
+		if (s[k] != kSetNone && to < cnt) place(r, to, s[k]);
+		before += (uint32_t)__popcll(bits[k]);
 	}
 }
 

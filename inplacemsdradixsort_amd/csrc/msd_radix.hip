@@ -2776,30 +2776,60 @@ int msd_sort_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 
 // ---- run-length encode (msd_runs.hpp)
 
-// What msd_run_encode and msd_reduce_runs begin with: the runs counted per tile and the counts scanned, *num_runs written.
-// The scratch -- one word per tile, one per scan piece, then whatever `more` takes from the Bump -- is the slab's, like a
-// sort round's: the next call on the context overwrites it, in stream order.  The caller's phase begins here, behind the
-// carve; an empty array (tiles == 0 afterwards) is one launch that writes 0 runs, and starts[0] = 0 where starts is given.
-struct RunsScratch { uint64_t tiles = 0, pieces = 0, *tile_counts = nullptr, *piece_sums = nullptr; };
-template <typename E, typename F> static int runs_count_scan(msd_ctx *c, const E *data, uint64_t n, uint64_t *num_runs, uint64_t *starts, F &&more, RunsScratch &s)
+// What every entry point that counts per tile begins with (msd_run_encode, msd_reduce_runs, msd_compact, msd_set_sorted,
+// msd_join_groups; msd_join_pairs with groups in the place of tiles): `count` launches what writes one word per tile to
+// s.tile_counts, the words are scanned in place -- a tile's base is tile_out_base(s.tile_counts, s.piece_sums, t) -- and the
+// total goes to *d_total.  The scratch -- with_splits one split per tile plus one, one word per tile, one per scan piece,
+// then whatever `more` takes from the Bump -- is the slab's, like a sort round's: the next call on the context overwrites
+// it, in stream order.  The caller's phase begins here, behind the carve; the caller marks and ends it.  An empty input
+// (tiles == 0: s.tiles stays 0) is one launch that writes a total of 0, and starts[0] = 0 where starts is given.
+// scan_pieces false: `count` has scanned the pieces itself (join_offsets_kernel) and only the top level is left.
+struct RunsScratch { uint64_t tiles = 0, pieces = 0, *splits = nullptr, *tile_counts = nullptr, *piece_sums = nullptr; };
+template <typename F> static int runs_scratch_carve(msd_ctx *c, RunsScratch &s, uint64_t tiles, bool with_splits, F &&more)
 {
-	if (n == 0) {
+	s.tiles = tiles;
+	s.pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile;
+	return slab_carve(c, [&](Bump &b) {
+		if (with_splits) s.splits = b.take<uint64_t>(s.tiles + 1);
+		s.tile_counts = b.take<uint64_t>(s.tiles);
+		s.piece_sums = b.take<uint64_t>(s.pieces);
+		more(b);
+	});
+}
+static int runs_scan_counts(msd_ctx *c, const RunsScratch &s, uint64_t *d_total, bool scan_pieces)
+{
+	if (scan_pieces) LAUNCH(c, runs_scan_pieces_kernel, (unsigned)s.pieces, kRunsScanTh, 0, s.tile_counts, s.tiles, s.piece_sums);
+	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, s.piece_sums, s.pieces, d_total);
+	return MSD_OK;
+}
+template <typename CNT, typename F>
+static int runs_count_scan(msd_ctx *c, uint64_t tiles, bool with_splits, uint64_t *d_total, uint64_t *starts, CNT &&count, F &&more, RunsScratch &s, bool scan_pieces = true)
+{
+	if (tiles == 0) {
 		phase_begin(c);
-		LAUNCH(c, runs_empty_kernel, 1, 64, 0, num_runs, starts);
+		LAUNCH(c, runs_empty_kernel, 1, 64, 0, d_total, starts);
 		return MSD_OK;
 	}
-	s.tiles = runs_tiles(data, n); // (<= 2^25 + 1)
-	s.pieces = (s.tiles + kRunsScanTile - 1) / kRunsScanTile;
-	if (int rc = slab_carve(c, [&](Bump &b) {
-		    s.tile_counts = b.take<uint64_t>(s.tiles);
-		    s.piece_sums = b.take<uint64_t>(s.pieces);
-		    more(b);
-	    }))
-		return rc;
+	if (int rc = runs_scratch_carve(c, s, tiles, with_splits, more)) return rc;
 	phase_begin(c);
-	LAUNCH(c, (runs_count_kernel<E>), (unsigned)s.tiles, kRunsTh, 0, data, n, s.tile_counts);
-	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)s.pieces, kRunsScanTh, 0, s.tile_counts, s.tiles, s.piece_sums);
-	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, s.piece_sums, s.pieces, num_runs);
+	if (int rc = count()) return rc;
+	return runs_scan_counts(c, s, d_total, scan_pieces);
+}
+// (the runs of an array: msd_run_encode, msd_reduce_runs)
+template <typename E, typename F> static int runs_count_scan(msd_ctx *c, const E *data, uint64_t n, uint64_t *num_runs, uint64_t *starts, F &&more, RunsScratch &s)
+{
+	return runs_count_scan(c, n ? runs_tiles(data, n) : 0, false, num_runs, starts, // (tiles <= 2^25 + 1)
+			       [&] { return LAUNCH_RC(c, (runs_count_kernel<E>), (unsigned)s.tiles, kRunsTh, 0, data, n, s.tile_counts); }, more, s);
+}
+
+// The shared body of the *_limits exports: *tile = the TILE of Cfg at this width, then every further (pointer, value)
+template <template <typename> class Cfg> static int tile_limits(int key_bytes, uint64_t *tile, std::initializer_list<std::pair<uint64_t *, uint64_t>> more = {})
+{
+	if ((key_bytes != 4 && key_bytes != 8) || !tile) return MSD_EINVAL;
+	for (const auto &p : more)
+		if (!p.first) return MSD_EINVAL;
+	*tile = with_width(key_bytes, [](auto e) { return (uint64_t)Cfg<decltype(e)>::TILE; });
+	for (const auto &p : more) *p.first = p.second;
 	return MSD_OK;
 }
 
@@ -2827,13 +2857,7 @@ static int run_encode_impl(msd_ctx *c, const E *data, uint64_t n, uint64_t cap, 
 
 extern "C" {
 
-int msd_run_encode_limits(int elem_bytes, uint64_t *tile, uint64_t *scan_tile)
-{
-	if ((elem_bytes != 4 && elem_bytes != 8) || !tile || !scan_tile) return MSD_EINVAL;
-	*tile = with_width(elem_bytes, [](auto e) { return (uint64_t)RunsCfg<decltype(e)>::TILE; });
-	*scan_tile = kRunsScanTile;
-	return MSD_OK;
-}
+int msd_run_encode_limits(int elem_bytes, uint64_t *tile, uint64_t *scan_tile) { return tile_limits<RunsCfg>(elem_bytes, tile, { { scan_tile, kRunsScanTile } }); }
 
 int msd_run_encode(msd_ctx *c, const void *d_data, int elem_bytes, uint64_t n, uint64_t cap, void *d_values, uint64_t *d_starts, const uint64_t *d_positions,
 		   uint64_t *d_inverse, uint64_t *d_num_runs)
@@ -2872,12 +2896,12 @@ static int reduce_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *v
 {
 	typedef typename P::R R;
 	RunsScratch s;
-	ReduceRecord rec{ nullptr, nullptr }, piece{ nullptr, nullptr };
+	SegRecord rec{ nullptr, nullptr }, piece{ nullptr, nullptr };
 	const auto records = [&](Bump &b) {
-		rec.lead = b.take<uint64_t>(s.tiles);
-		rec.heads = b.take<uint32_t>(s.tiles);
-		piece.lead = b.take<uint64_t>(s.pieces);
-		piece.heads = b.take<uint32_t>(s.pieces);
+		rec.val = b.take<uint64_t>(s.tiles);
+		rec.flag = b.take<uint32_t>(s.tiles);
+		piece.val = b.take<uint64_t>(s.pieces);
+		piece.flag = b.take<uint32_t>(s.pieces);
 	};
 	if (int rc = runs_count_scan(c, keys, n, num_runs, nullptr, records, s)) return rc;
 	if (s.tiles && cap) { // (cap == 0 only counts)
@@ -2885,8 +2909,8 @@ static int reduce_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *v
 			return LAUNCH_RC(c, (reduce_tile_kernel<E, P, decltype(pos)::value>), (unsigned)s.tiles, kRunsTh, 0, keys, n, vals, positions, cap, s.tile_counts, s.piece_sums, cd, out, rec);
 		});
 		if (rc) return rc;
-		LAUNCH(c, (reduce_carry_pieces_kernel<R>), (unsigned)s.pieces, kRunsScanTh, 0, rec, s.tiles, cd, piece);
-		LAUNCH(c, (reduce_carry_top_kernel<R>), 1, kRunsScanTh, 0, piece, s.pieces, cd);
+		LAUNCH(c, (seg_carry_pieces_kernel<R, false>), (unsigned)s.pieces, kRunsScanTh, 0, rec, s.tiles, cd, piece);
+		LAUNCH(c, (seg_carry_top_kernel<R, false>), 1, kRunsScanTh, 0, piece, s.pieces, cd);
 		LAUNCH(c, (reduce_apply_kernel<R>), (unsigned)((s.tiles + 255) / 256), 256, 0, rec, piece, s.tiles, cap, s.tile_counts, s.piece_sums, cd, out);
 	}
 	phase_mark(c, "reduce_runs");
@@ -2894,25 +2918,31 @@ static int reduce_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *v
 	return MSD_OK;
 }
 
+// (op, val_type) -> f(the policy of msd_reduce.hpp, the codec of its results).  A maximum is the minimum of the complemented codes.
+enum class RedOp { Sum, Min, Max };
+template <typename F> static int with_reduction(RedOp op, int val_type, F &&f)
+{
+	if (op == RedOp::Sum) {
+		const KeyCodec<uint64_t> none{ 0, 0 };
+		switch (val_type) {
+		case kKeyU32: return f(SumU32(), none);
+		case kKeyI32: return f(SumI32(), none);
+		case kKeyF32: return f(SumF32(), none);
+		case kKeyF64: return f(SumF64(), none);
+		default: return f(SumX64(), none); // (U64, I64: the same sum modulo 2^64)
+		}
+	}
+	const bool mx = op == RedOp::Max;
+	if (key_type_bytes(val_type) == 4) return f(MinOf<uint32_t>(), key_codec<uint32_t>(val_type).flipped(mx ? ~0u : 0u));
+	return f(MinOf<uint64_t>(), key_codec<uint64_t>(val_type).flipped(mx ? ~0ull : 0ull));
+}
+
 template <typename E>
 static int reduce_runs_typed(msd_ctx *c, const E *keys, uint64_t n, const void *vals, int val_type, const uint64_t *positions, int op, uint64_t cap, void *out,
 			     uint64_t *num_runs)
 {
-	const KeyCodec<uint64_t> none{ 0, 0 };
-	if (op == MSD_REDUCE_SUM) {
-		switch (val_type) {
-		case kKeyU32: return reduce_runs_impl<E, SumU32>(c, keys, n, vals, positions, cap, out, num_runs, none);
-		case kKeyI32: return reduce_runs_impl<E, SumI32>(c, keys, n, vals, positions, cap, out, num_runs, none);
-		case kKeyF32: return reduce_runs_impl<E, SumF32>(c, keys, n, vals, positions, cap, out, num_runs, none);
-		case kKeyF64: return reduce_runs_impl<E, SumF64>(c, keys, n, vals, positions, cap, out, num_runs, none);
-		default: return reduce_runs_impl<E, SumX64>(c, keys, n, vals, positions, cap, out, num_runs, none); // (U64, I64: the same sum modulo 2^64)
-		}
-	}
-	// a maximum is the minimum of the complemented codes
-	const bool mx = op == MSD_REDUCE_MAX;
-	if (key_type_bytes(val_type) == 4)
-		return reduce_runs_impl<E, MinOf<uint32_t>>(c, keys, n, vals, positions, cap, out, num_runs, key_codec<uint32_t>(val_type).flipped(mx ? ~0u : 0u));
-	return reduce_runs_impl<E, MinOf<uint64_t>>(c, keys, n, vals, positions, cap, out, num_runs, key_codec<uint64_t>(val_type).flipped(mx ? ~0ull : 0ull));
+	const RedOp r = op == MSD_REDUCE_SUM ? RedOp::Sum : op == MSD_REDUCE_MIN ? RedOp::Min : RedOp::Max;
+	return with_reduction(r, val_type, [&](auto p, auto cd) { return reduce_runs_impl<E, decltype(p)>(c, keys, n, vals, positions, cap, out, num_runs, cd); });
 }
 
 extern "C" {
@@ -2953,18 +2983,18 @@ static int scan_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *val
 {
 	typedef typename P::R R;
 	const uint64_t tiles = runs_tiles(keys, n), pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile; // (tiles <= 2^25 + 1)
-	ScanRecord rec{ nullptr, nullptr }, piece{ nullptr, nullptr };
+	SegRecord rec{ nullptr, nullptr }, piece{ nullptr, nullptr };
 	if (int rc = slab_carve(c, [&](Bump &b) {
-		    rec.tail = b.take<uint64_t>(tiles);
+		    rec.val = b.take<uint64_t>(tiles);
 		    rec.flag = b.take<uint32_t>(tiles);
-		    piece.tail = b.take<uint64_t>(pieces);
+		    piece.val = b.take<uint64_t>(pieces);
 		    piece.flag = b.take<uint32_t>(pieces);
 	    }))
 		return rc;
 	phase_begin(c);
 	LAUNCH(c, (scan_tail_kernel<E, P>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, cd, rec);
-	LAUNCH(c, (scan_carry_pieces_kernel<R>), (unsigned)pieces, kRunsScanTh, 0, rec, tiles, cd, piece);
-	LAUNCH(c, (scan_carry_top_kernel<R>), 1, kRunsScanTh, 0, piece, pieces, cd);
+	LAUNCH(c, (seg_carry_pieces_kernel<R, true>), (unsigned)pieces, kRunsScanTh, 0, rec, tiles, cd, piece);
+	LAUNCH(c, (seg_carry_top_kernel<R, true>), 1, kRunsScanTh, 0, piece, pieces, cd);
 	LAUNCH(c, (scan_tile_kernel<E, P>), (unsigned)tiles, kRunsTh, 0, keys, n, vals, cd, rec, piece, flags, out);
 	phase_mark(c, "scan_runs");
 	phase_end(c);
@@ -2974,22 +3004,9 @@ static int scan_runs_impl(msd_ctx *c, const E *keys, uint64_t n, const void *val
 template <typename E>
 static int scan_runs_typed(msd_ctx *c, const E *keys, uint64_t n, const void *vals, int val_type, int op, int flags, void *out)
 {
-	const KeyCodec<uint64_t> none{ 0, 0 };
-	if (op == MSD_SCAN_COUNT) return scan_runs_impl<E, CountOne>(c, keys, n, nullptr, flags, out, none);
-	if (op == MSD_SCAN_SUM) {
-		switch (val_type) {
-		case kKeyU32: return scan_runs_impl<E, SumU32>(c, keys, n, vals, flags, out, none);
-		case kKeyI32: return scan_runs_impl<E, SumI32>(c, keys, n, vals, flags, out, none);
-		case kKeyF32: return scan_runs_impl<E, SumF32>(c, keys, n, vals, flags, out, none);
-		case kKeyF64: return scan_runs_impl<E, SumF64>(c, keys, n, vals, flags, out, none);
-		default: return scan_runs_impl<E, SumX64>(c, keys, n, vals, flags, out, none); // (U64, I64: the same sum modulo 2^64)
-		}
-	}
-	// a maximum is the minimum of the complemented codes
-	const bool mx = op == MSD_SCAN_MAX;
-	if (key_type_bytes(val_type) == 4)
-		return scan_runs_impl<E, MinOf<uint32_t>>(c, keys, n, vals, flags, out, key_codec<uint32_t>(val_type).flipped(mx ? ~0u : 0u));
-	return scan_runs_impl<E, MinOf<uint64_t>>(c, keys, n, vals, flags, out, key_codec<uint64_t>(val_type).flipped(mx ? ~0ull : 0ull));
+	if (op == MSD_SCAN_COUNT) return scan_runs_impl<E, CountOne>(c, keys, n, nullptr, flags, out, KeyCodec<uint64_t>{ 0, 0 });
+	const RedOp r = op == MSD_SCAN_SUM ? RedOp::Sum : op == MSD_SCAN_MIN ? RedOp::Min : RedOp::Max;
+	return with_reduction(r, val_type, [&](auto p, auto cd) { return scan_runs_impl<E, decltype(p)>(c, keys, n, vals, flags, out, cd); });
 }
 
 extern "C" {
@@ -3034,27 +3051,15 @@ int msd_scan_runs(msd_ctx *c, const void *d_keys, int key_bytes, uint64_t n, con
 template <typename E, bool RANGE, bool MASK, int VB, bool REST>
 static int compact_impl(msd_ctx *c, const CompactIn<E> &in, const void *vals, uint64_t cap, E *out_keys, void *out_vals, uint64_t *out_idx, uint64_t *count)
 {
-	if (in.n == 0) {
-		phase_begin(c);
-		LAUNCH(c, runs_empty_kernel, 1, 64, 0, count, (uint64_t *)nullptr);
-	} else {
-		const uint64_t tiles = (in.m + in.n + RunsCfg<E>::TILE - 1) / RunsCfg<E>::TILE; // (<= 2^25 + 1)
-		const uint64_t pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile;
-		uint64_t *tile_counts = nullptr, *piece_sums = nullptr;
-		if (int rc = slab_carve(c, [&](Bump &b) {
-			    tile_counts = b.take<uint64_t>(tiles);
-			    piece_sums = b.take<uint64_t>(pieces);
-		    }))
-			return rc;
-		CompactIn<E> cin = in;
-		if (!RANGE) cin.keys = nullptr;
-		phase_begin(c);
-		LAUNCH(c, (compact_count_kernel<E, RANGE, MASK>), (unsigned)tiles, kRunsTh, 0, cin, tile_counts);
-		LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
-		LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, count);
-		if (out_keys || out_vals || out_idx) // (none: the call only counts)
-			LAUNCH(c, (compact_write_kernel<E, RANGE, MASK, VB, REST>), (unsigned)tiles, kRunsTh, 0, in, vals, cap, tile_counts, piece_sums, count, out_keys, out_vals, out_idx);
-	}
+	CompactIn<E> cin = in;
+	if (!RANGE) cin.keys = nullptr;
+	RunsScratch s;
+	const uint64_t tiles = in.n ? (in.m + in.n + RunsCfg<E>::TILE - 1) / RunsCfg<E>::TILE : 0; // (<= 2^25 + 1)
+	if (int rc = runs_count_scan(c, tiles, false, count, nullptr,
+				     [&] { return LAUNCH_RC(c, (compact_count_kernel<E, RANGE, MASK>), (unsigned)s.tiles, kRunsTh, 0, cin, s.tile_counts); }, [](Bump &) {}, s))
+		return rc;
+	if (s.tiles && (out_keys || out_vals || out_idx)) // (none: the call only counts)
+		LAUNCH(c, (compact_write_kernel<E, RANGE, MASK, VB, REST>), (unsigned)s.tiles, kRunsTh, 0, in, vals, cap, s.tile_counts, s.piece_sums, count, out_keys, out_vals, out_idx);
 	phase_mark(c, "compact");
 	phase_end(c);
 	return MSD_OK;
@@ -3149,7 +3154,7 @@ static int search_sorted_impl(msd_ctx *c, const K *keys, int key_type, uint64_t 
 	uint64_t *splits = nullptr;
 	if (int rc = slab_carve(c, [&](Bump &b) { splits = b.take<uint64_t>(tiles + 1); })) return rc;
 	phase_begin(c);
-	LAUNCH(c, (search_split_kernel<K>), (unsigned)((tiles + 1 + kSearchTh - 1) / kSearchTh), kSearchTh, 0, keys, n, needles, m, right, cd, tiles, splits);
+	LAUNCH(c, (search_split_kernel<K, SearchCfg<K>::TILE>), (unsigned)((tiles + 1 + kSearchTh - 1) / kSearchTh), kSearchTh, 0, keys, n, needles, m, right, cd, tiles, splits);
 	LAUNCH(c, (search_tile_kernel<K, POS>), (unsigned)tiles, kSearchTh, 0, keys, n, needles, m, right, cd, splits, positions, out);
 	phase_mark(c, "search_sorted");
 	phase_end(c);
@@ -3158,13 +3163,7 @@ static int search_sorted_impl(msd_ctx *c, const K *keys, int key_type, uint64_t 
 
 extern "C" {
 
-int msd_search_sorted_limits(int key_bytes, uint64_t *tile, uint64_t *direct_tile)
-{
-	if ((key_bytes != 4 && key_bytes != 8) || !tile || !direct_tile) return MSD_EINVAL;
-	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)SearchCfg<decltype(k0)>::TILE; });
-	*direct_tile = kSearchDirectTile;
-	return MSD_OK;
-}
+int msd_search_sorted_limits(int key_bytes, uint64_t *tile, uint64_t *direct_tile) { return tile_limits<SearchCfg>(key_bytes, tile, { { direct_tile, kSearchDirectTile } }); }
 
 int msd_search_sorted(msd_ctx *c, const void *d_sorted, int key_type, uint64_t n, const void *d_needles, uint64_t m, int needles_sorted, int side,
 		      const uint64_t *d_positions, uint64_t *d_out)
@@ -3198,6 +3197,13 @@ int msd_search_sorted(msd_ctx *c, const void *d_sorted, int key_type, uint64_t n
 
 // ---- merge of two sorted arrays (msd_merge2.hpp)
 
+// The merge path's cut of [a; b] into tiles of MergeCfg: the split kernel of the sorted search with the RIGHT rule
+template <typename K> static int merge_split(msd_ctx *c, const K *a, uint64_t n, const K *b, uint64_t m, KeyCodec<K> cd, uint64_t tiles, uint64_t *splits)
+{
+	return LAUNCH_RC(c, (search_split_kernel<K, MergeCfg<K>::TILE>), (unsigned)((tiles + 1 + kMergeTh - 1) / kMergeTh), kMergeTh, 0, a, n, b, m, (uint32_t)MSD_SEARCH_RIGHT, cd, tiles,
+			 splits);
+}
+
 // The splits, then the tiles, one behind the other on the stream; the scratch -- one split per tile plus one -- is the
 // slab's, as for msd_search_sorted.  Nothing is read back.
 template <typename K, bool VALS, bool ORIGIN>
@@ -3209,7 +3215,7 @@ static int merge_sorted_impl(msd_ctx *c, const K *a, uint64_t n, const K *b, uin
 	uint64_t *splits = nullptr;
 	if (int rc = slab_carve(c, [&](Bump &bump) { splits = bump.take<uint64_t>(tiles + 1); })) return rc;
 	phase_begin(c);
-	LAUNCH(c, (merge_split_kernel<K>), (unsigned)((tiles + 1 + kMergeTh - 1) / kMergeTh), kMergeTh, 0, a, n, b, m, cd, tiles, splits);
+	if (int rc = merge_split(c, a, n, b, m, cd, tiles, splits)) return rc;
 	LAUNCH(c, (merge_tile_kernel<K, VALS, ORIGIN>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, splits, vals_a, vals_b, out, out_vals, out_origin);
 	phase_mark(c, "merge_sorted");
 	phase_end(c);
@@ -3218,12 +3224,7 @@ static int merge_sorted_impl(msd_ctx *c, const K *a, uint64_t n, const K *b, uin
 
 extern "C" {
 
-int msd_merge_sorted_limits(int key_bytes, uint64_t *tile)
-{
-	if ((key_bytes != 4 && key_bytes != 8) || !tile) return MSD_EINVAL;
-	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)MergeCfg<decltype(k0)>::TILE; });
-	return MSD_OK;
-}
+int msd_merge_sorted_limits(int key_bytes, uint64_t *tile) { return tile_limits<MergeCfg>(key_bytes, tile); }
 
 int msd_merge_sorted(msd_ctx *c, const void *d_a, uint64_t n, const void *d_b, uint64_t m, int key_type, const uint64_t *d_vals_a, const uint64_t *d_vals_b,
 		     void *d_out, uint64_t *d_out_vals, uint64_t *d_out_origin)
@@ -3262,39 +3263,32 @@ int msd_merge_sorted(msd_ctx *c, const void *d_a, uint64_t n, const void *d_b, u
 
 // ---- set operations on two sorted arrays (msd_setops.hpp)
 
-// The splits, the count per tile, the scan of the counts, the write: five launches one behind the other on the stream; the
-// scratch -- one split per tile plus one, one count per tile, one sum per scan piece -- is the slab's, as for
-// msd_merge_sorted and msd_run_encode.  Nothing is read back.  n + m == 0 is one launch that writes 0 results.
+// What msd_set_sorted and msd_join_groups begin with: the splits, the count per tile of the elements that `keep` keeps, the
+// scan of the counts -- four launches one behind the other on the stream; the scratch -- one split per tile plus one, one
+// count per tile, one sum per scan piece -- is the slab's (runs_count_scan).  n + m == 0 is one launch that writes a total
+// of 0 (s.tiles stays 0).  The caller launches its write kernel and marks and ends the phase.
+template <typename K>
+static int set_count_scan(msd_ctx *c, const K *a, uint64_t n, const K *b, uint64_t m, KeyCodec<K> cd, uint32_t keep, uint64_t *d_total, RunsScratch &s)
+{
+	const uint64_t tiles = (n + m + MergeCfg<K>::TILE - 1) / MergeCfg<K>::TILE; // (n + m < 2^37: at most 2^26)
+	const auto count = [&] {
+		if (int rc = merge_split(c, a, n, b, m, cd, s.tiles, s.splits)) return rc;
+		return LAUNCH_RC(c, (set_count_kernel<K>), (unsigned)s.tiles, kMergeTh, 0, a, n, b, m, cd, keep, s.splits, s.tile_counts);
+	};
+	return runs_count_scan(c, tiles, true, d_total, nullptr, count, [](Bump &) {}, s);
+}
+
+// Front, write: five launches, nothing read back.
 template <typename K>
 static int set_sorted_impl(msd_ctx *c, int op, const K *a, uint64_t n, const K *b, uint64_t m, int key_type, uint64_t cap, K *out, uint64_t *out_origin,
 			   uint64_t *num_out)
 {
-	const uint64_t total = n + m;
-	if (total == 0) {
-		phase_begin(c);
-		LAUNCH(c, set_empty_kernel, 1, 64, 0, num_out);
-		phase_mark(c, "set_sorted");
-		phase_end(c);
-		return MSD_OK;
-	}
 	const KeyCodec<K> cd = key_codec<K>(key_type);
 	const uint32_t keep = set_keep_mask(op);
-	const uint64_t tiles = (total + MergeCfg<K>::TILE - 1) / MergeCfg<K>::TILE; // (n + m < 2^37: at most 2^26)
-	const uint64_t pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile;
-	uint64_t *splits = nullptr, *tile_counts = nullptr, *piece_sums = nullptr;
-	if (int rc = slab_carve(c, [&](Bump &bump) {
-		    splits = bump.take<uint64_t>(tiles + 1);
-		    tile_counts = bump.take<uint64_t>(tiles);
-		    piece_sums = bump.take<uint64_t>(pieces);
-	    }))
-		return rc;
-	phase_begin(c);
-	LAUNCH(c, (merge_split_kernel<K>), (unsigned)((tiles + 1 + kMergeTh - 1) / kMergeTh), kMergeTh, 0, a, n, b, m, cd, tiles, splits);
-	LAUNCH(c, (set_count_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, keep, splits, tile_counts);
-	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
-	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_out);
-	if (cap && (out || out_origin)) // (cap == 0, or no output: the count alone)
-		LAUNCH(c, (set_write_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, keep, splits, tile_counts, piece_sums, num_out, cap, out, out_origin);
+	RunsScratch s;
+	if (int rc = set_count_scan(c, a, n, b, m, cd, keep, num_out, s)) return rc;
+	if (s.tiles && cap && (out || out_origin)) // (cap == 0, or no output: the count alone)
+		LAUNCH(c, (set_write_kernel<K>), (unsigned)s.tiles, kMergeTh, 0, a, n, b, m, cd, keep, s.splits, s.tile_counts, s.piece_sums, num_out, cap, out, out_origin);
 	phase_mark(c, "set_sorted");
 	phase_end(c);
 	return MSD_OK;
@@ -3302,13 +3296,7 @@ static int set_sorted_impl(msd_ctx *c, int op, const K *a, uint64_t n, const K *
 
 extern "C" {
 
-int msd_set_sorted_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile)
-{
-	if ((key_bytes != 4 && key_bytes != 8) || !tile || !scan_tile) return MSD_EINVAL;
-	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)MergeCfg<decltype(k0)>::TILE; });
-	*scan_tile = kRunsScanTile;
-	return MSD_OK;
-}
+int msd_set_sorted_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile) { return tile_limits<MergeCfg>(key_bytes, tile, { { scan_tile, kRunsScanTile } }); }
 
 int msd_set_sorted(msd_ctx *c, int op, const void *d_a, uint64_t n, const void *d_b, uint64_t m, int key_type, uint64_t cap, void *d_out, uint64_t *d_out_origin,
 		   uint64_t *d_num_out)
@@ -3341,37 +3329,16 @@ int msd_set_sorted(msd_ctx *c, int op, const void *d_a, uint64_t n, const void *
 
 // ---- sort-merge join of two sorted arrays (msd_join.hpp)
 
-// The groups: the five launches of msd_set_sorted with the intersection's mask and the join's own write kernel; the scratch is
-// that of msd_set_sorted.  Nothing is read back.  n + m == 0 is one launch that writes 0 groups.
+// The groups: the front of msd_set_sorted (set_count_scan) with the intersection's mask, and the join's own write kernel.
 template <typename K>
 static int join_groups_impl(msd_ctx *c, const K *a, uint64_t n, const K *b, uint64_t m, int key_type, uint64_t cap, K *keys, uint64_t *a_first, uint64_t *a_count,
 			    uint64_t *b_first, uint64_t *b_count, uint64_t *num_groups)
 {
-	const uint64_t total = n + m;
-	if (total == 0) {
-		phase_begin(c);
-		LAUNCH(c, set_empty_kernel, 1, 64, 0, num_groups);
-		phase_mark(c, "join_groups");
-		phase_end(c);
-		return MSD_OK;
-	}
 	const KeyCodec<K> cd = key_codec<K>(key_type);
-	const uint64_t tiles = (total + MergeCfg<K>::TILE - 1) / MergeCfg<K>::TILE; // (n + m < 2^33: at most 2^22)
-	const uint64_t pieces = (tiles + kRunsScanTile - 1) / kRunsScanTile;
-	uint64_t *splits = nullptr, *tile_counts = nullptr, *piece_sums = nullptr;
-	if (int rc = slab_carve(c, [&](Bump &bump) {
-		    splits = bump.take<uint64_t>(tiles + 1);
-		    tile_counts = bump.take<uint64_t>(tiles);
-		    piece_sums = bump.take<uint64_t>(pieces);
-	    }))
-		return rc;
-	phase_begin(c);
-	LAUNCH(c, (merge_split_kernel<K>), (unsigned)((tiles + 1 + kMergeTh - 1) / kMergeTh), kMergeTh, 0, a, n, b, m, cd, tiles, splits);
-	LAUNCH(c, (set_count_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, kSetKeepMatchedA, splits, tile_counts);
-	LAUNCH(c, runs_scan_pieces_kernel, (unsigned)pieces, kRunsScanTh, 0, tile_counts, tiles, piece_sums);
-	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_groups);
-	if (cap && (keys || a_first || a_count || b_first || b_count)) // (cap == 0, or no output: the count alone)
-		LAUNCH(c, (join_write_kernel<K>), (unsigned)tiles, kMergeTh, 0, a, n, b, m, cd, splits, tile_counts, piece_sums, num_groups, cap, keys, a_first, a_count, b_first,
+	RunsScratch s;
+	if (int rc = set_count_scan(c, a, n, b, m, cd, kSetKeepMatchedA, num_groups, s)) return rc;
+	if (s.tiles && cap && (keys || a_first || a_count || b_first || b_count)) // (cap == 0, or no output: the count alone)
+		LAUNCH(c, (join_write_kernel<K>), (unsigned)s.tiles, kMergeTh, 0, a, n, b, m, cd, s.splits, s.tile_counts, s.piece_sums, num_groups, cap, keys, a_first, a_count, b_first,
 		       b_count);
 	phase_mark(c, "join_groups");
 	phase_end(c);
@@ -3384,24 +3351,14 @@ static int join_pairs_impl(msd_ctx *c, uint64_t groups_cap, const uint64_t *num_
 			   const uint64_t *b_count, uint64_t n, uint64_t m, const uint64_t *pos_a, const uint64_t *pos_b, uint64_t stored, uint64_t cap, uint64_t *out_a,
 			   uint64_t *out_b, uint64_t *num_pairs)
 {
-	if (groups_cap == 0) {
-		phase_begin(c);
-		LAUNCH(c, set_empty_kernel, 1, 64, 0, num_pairs);
-		phase_mark(c, "join_pairs");
-		phase_end(c);
-		return MSD_OK;
-	}
-	const uint64_t pieces = (groups_cap + kRunsScanTile - 1) / kRunsScanTile;
-	uint64_t *offs = nullptr, *piece_sums = nullptr;
-	if (int rc = slab_carve(c, [&](Bump &bump) {
-		    offs = bump.take<uint64_t>(groups_cap);
-		    piece_sums = bump.take<uint64_t>(pieces);
-	    }))
+	// (runs_count_scan with a word per group in the place of the tile counts: the offsets; join_offsets_kernel scans the pieces itself)
+	RunsScratch s;
+	if (int rc = runs_count_scan(c, groups_cap, false, num_pairs, nullptr,
+				     [&] { return LAUNCH_RC(c, join_offsets_kernel, (unsigned)s.pieces, kRunsScanTh, 0, groups_cap, num_groups, a_count, b_count, s.tile_counts, s.piece_sums); },
+				     [](Bump &) {}, s, false))
 		return rc;
-	const uint64_t grid = (stored + kJoinPairTile - 1) / kJoinPairTile; // (stored < 2^40: at most 2^29)
-	phase_begin(c);
-	LAUNCH(c, join_offsets_kernel, (unsigned)pieces, kRunsScanTh, 0, groups_cap, num_groups, a_count, b_count, offs, piece_sums);
-	LAUNCH(c, runs_scan_top_kernel, 1, kRunsScanTh, 0, piece_sums, pieces, num_pairs);
+	uint64_t *const offs = s.tile_counts, *const piece_sums = s.piece_sums;
+	const uint64_t grid = s.tiles ? (stored + kJoinPairTile - 1) / kJoinPairTile : 0; // (stored < 2^40: at most 2^29)
 	if (grid && (out_a || out_b)) { // (cap == 0, an empty side or no output: the count alone)
 		int rc = with_flag(pos_a != nullptr, [&](auto pa) {
 			return with_flag(pos_b != nullptr, [&](auto pb) {
@@ -3421,11 +3378,7 @@ extern "C" {
 
 int msd_join_limits(int key_bytes, uint64_t *tile, uint64_t *scan_tile, uint64_t *pair_tile)
 {
-	if ((key_bytes != 4 && key_bytes != 8) || !tile || !scan_tile || !pair_tile) return MSD_EINVAL;
-	*tile = with_width(key_bytes, [](auto k0) { return (uint64_t)MergeCfg<decltype(k0)>::TILE; });
-	*scan_tile = kRunsScanTile;
-	*pair_tile = kJoinPairTile;
-	return MSD_OK;
+	return tile_limits<MergeCfg>(key_bytes, tile, { { scan_tile, kRunsScanTile }, { pair_tile, kJoinPairTile } });
 }
 
 int msd_join_groups(msd_ctx *c, const void *d_a, uint64_t n, const void *d_b, uint64_t m, int key_type, uint64_t cap, void *d_keys, uint64_t *d_a_first,

@@ -22,7 +22,10 @@
 // uniform words -- plus the count of the lower lanes' bits.
 #pragma once
 
+#include <type_traits>
+
 #include "msd_device.hpp"
+#include "msd_keycodec.hpp"
 
 namespace msd {
 
@@ -39,8 +42,114 @@ constexpr uint32_t kRunsScanTile = kRunsScanTh * kRunsScanPer; // tile counts on
 template <typename E> __host__ __device__ inline uint32_t runs_misalign(const E *data) { return (uint32_t)(((uintptr_t)data & 15u) / sizeof(E)); }
 template <typename E> inline uint64_t runs_tiles(const E *data, uint64_t n) { return (runs_misalign(data) + n + RunsCfg<E>::TILE - 1) / RunsCfg<E>::TILE; }
 
-// This lane's elements of tile `tile` (x[k][e]: virtual index wave's first + (k * 64 + lane) * V + e) and the ballots of
-// their head flags
+// ---- the run grid's shared pieces: every tile algorithm on this grid (msd_reduce.hpp, msd_scan.hpp, msd_compact.hpp) and
+// every reader of scanned tile counts (msd_setops.hpp, msd_join.hpp) takes them from here
+
+// the first place in its tile of lane `lane` of wave `w` in vector k, and its virtual index in tile `tile`
+template <typename E> __device__ __forceinline__ uint32_t runs_place(uint32_t w, uint32_t lane, int k)
+{
+	return w * RunsCfg<E>::WAVE + (uint32_t)(k * 64 + lane) * RunsCfg<E>::V;
+}
+template <typename E> __device__ __forceinline__ uint64_t runs_vindex(uint64_t tile, uint32_t w, uint32_t lane, int k)
+{
+	return tile * RunsCfg<E>::TILE + w * RunsCfg<E>::WAVE + (uint64_t)((k * 64 + lane) * RunsCfg<E>::V);
+}
+
+// This lane's elements of tile `tile` from the 16-byte-grid base vbase (the array's pointer minus its misalignment: 16-byte
+// aligned, dereferenced inside the virtual indices [lo, hi) only).  x[k][e]: virtual index runs_vindex(k) + e, 0 outside
+// [lo, hi).  The 16 bytes that lie inside are one aligned load, the partly covered ones are read element by element.
+template <typename E>
+__device__ __forceinline__ void runs_load_keys(const E *__restrict__ vbase, uint64_t lo, uint64_t hi, uint64_t tile, uint32_t w, uint32_t lane, E (&x)[kRunsVecs][RunsCfg<E>::V])
+{
+	constexpr uint32_t V = RunsCfg<E>::V;
+#pragma unroll
+	for (int k = 0; k < kRunsVecs; ++k) {
+		const uint64_t v0 = runs_vindex<E>(tile, w, lane, k);
+		if (v0 >= lo && v0 + V <= hi) {
+			vec16_unpack<E>(*reinterpret_cast<const u32x4 *>(vbase + v0), x[k]);
+		} else {
+#pragma unroll
+			for (uint32_t e = 0; e < V; ++e) x[k][e] = (v0 + e >= lo && v0 + e < hi) ? vbase[v0 + e] : (E)0;
+		}
+	}
+}
+
+// What the ballots of a tile's flags (heads, kept elements: one per (k, e)) say about ranks.  before_k[k]: the flags of the
+// wave in front of vector k (uniform); wpre: those of the lower waves; total: the tile's.
+struct RunsRank {
+	uint32_t before_k[kRunsVecs], wpre, total;
+};
+// The workgroup's half of it: r.wpre and r.total from c, the wave's flags.  (Every thread of the workgroup calls it: one
+// barrier.  wsum: kRunsTh / 64 words of LDS.)
+__device__ __forceinline__ void runs_rank_waves(RunsRank &r, uint32_t c, uint32_t w, uint32_t lane, uint32_t *wsum)
+{
+	if (lane == 0) wsum[w] = c;
+	__syncthreads();
+	r.wpre = 0;
+#pragma unroll
+	for (uint32_t ww = 0; ww < kRunsTh / 64 - 1; ++ww)
+		if (ww < w) r.wpre += wsum[ww];
+	r.total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// All of it.  (reduce_tile_kernel counts before_k inside its own loop over the ballots and calls runs_rank_waves.)
+template <uint32_t V> __device__ __forceinline__ RunsRank runs_rank(const uint64_t (&bb)[kRunsVecs][V], uint32_t w, uint32_t lane, uint32_t *wsum)
+{
+	RunsRank r;
+	uint32_t c = 0;
+#pragma unroll
+	for (int k = 0; k < kRunsVecs; ++k) {
+		r.before_k[k] = c;
+#pragma unroll
+		for (uint32_t e = 0; e < V; ++e) c += (uint32_t)__popcll(bb[k][e]);
+	}
+	runs_rank_waves(r, c, w, lane, wsum);
+	return r;
+}
+
+// step 1 of every algorithm that counts per tile: the tile's flags, one word per tile
+template <uint32_t V> __device__ __forceinline__ void runs_store_count(const uint64_t (&bb)[kRunsVecs][V], uint64_t *__restrict__ tile_counts)
+{
+	__shared__ uint32_t wsum[kRunsTh / 64];
+	const RunsRank r = runs_rank<V>(bb, threadIdx.x >> 6, threadIdx.x & 63u, wsum);
+	if (threadIdx.x == 0) tile_counts[blockIdx.x] = (uint64_t)r.total;
+}
+
+// where tile t's output begins: its scanned count plus its piece's
+__device__ __forceinline__ uint64_t tile_out_base(const uint64_t *__restrict__ tile_base, const uint64_t *__restrict__ piece_base, uint64_t t)
+{
+	return tile_base[t] + piece_base[t / kRunsScanTile];
+}
+
+// The values of this lane's elements of tile `tile` as accumulators of the policy P (msd_reduce.hpp), once, directly or
+// (POS) through the positions: what lies outside the array counts as the identity.  A policy whose conv looks at no value
+// says so by specialising ReadsValue, and no value is loaded for it.
+template <typename P> struct ReadsValue : std::true_type {};
+template <typename E, typename P, bool POS>
+__device__ __forceinline__ void runs_load_values(uint64_t n, uint32_t m, uint64_t tile, const typename P::V *__restrict__ vals,
+	const uint64_t *__restrict__ positions, KeyCodec<typename P::R::O> cd, typename P::R::A (&a)[kRunsVecs][RunsCfg<E>::V])
+{
+	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6; // (worked out here again: handing them in costs the scan kernels registers)
+	const uint64_t lo = m, hi = (uint64_t)m + n;
+	const typename P::R::A ident = P::R::id(cd);
+#pragma unroll
+	for (int k = 0; k < kRunsVecs; ++k) {
+		const uint64_t v0 = runs_vindex<E>(tile, w, lane, k);
+#pragma unroll
+		for (uint32_t e = 0; e < RunsCfg<E>::V; ++e) {
+			const uint64_t v = v0 + e;
+			a[k][e] = ident;
+			if (v >= lo && v < hi) {
+				const uint64_t i = v - lo;
+				if constexpr (ReadsValue<P>::value)
+					a[k][e] = P::conv(vals[POS ? positions[i] : i], cd);
+				else
+					a[k][e] = P::conv(typename P::V(), cd);
+			}
+		}
+	}
+}
+
+// This lane's elements of tile `tile` (runs_load_keys) and the ballots of their head flags
 template <typename E>
 __device__ __forceinline__ void runs_load_heads(const E *__restrict__ data, uint64_t n, uint32_t m, uint64_t tile, E (&x)[kRunsVecs][RunsCfg<E>::V],
 	uint64_t (&hb)[kRunsVecs][RunsCfg<E>::V])
@@ -53,28 +162,10 @@ __device__ __forceinline__ void runs_load_heads(const E *__restrict__ data, uint
 	const E *const vbase = data - m;                       // (16-byte aligned; dereferenced inside [lo, hi) only)
 	E before = 0;
 	if (lane == 0 && wv0 > lo && wv0 <= hi) before = vbase[wv0 - 1];
+	runs_load_keys<E>(vbase, lo, hi, tile, w, lane, x);
 #pragma unroll
 	for (int k = 0; k < kRunsVecs; ++k) {
-		const uint64_t v0 = wv0 + (uint64_t)((k * 64 + lane) * V);
-		if (v0 >= lo && v0 + V <= hi) {
-			const u32x4 q = *reinterpret_cast<const u32x4 *>(vbase + v0);
-			if constexpr (sizeof(E) == 4) {
-				x[k][0] = q.x;
-				x[k][1] = q.y;
-				x[k][2] = q.z;
-				x[k][3] = q.w;
-			} else {
-				x[k][0] = (E)q.x | ((E)q.y << 32);
-				x[k][1] = (E)q.z | ((E)q.w << 32);
-			}
-		} else {
-#pragma unroll
-			for (uint32_t e = 0; e < V; ++e) x[k][e] = (v0 + e >= lo && v0 + e < hi) ? vbase[v0 + e] : (E)0;
-		}
-	}
-#pragma unroll
-	for (int k = 0; k < kRunsVecs; ++k) {
-		const uint64_t v0 = wv0 + (uint64_t)((k * 64 + lane) * V);
+		const uint64_t v0 = runs_vindex<E>(tile, w, lane, k);
 		E prev = __shfl_up(x[k][V - 1], 1);
 		const E edge = k == 0 ? before : __shfl(x[k == 0 ? 0 : k - 1][V - 1], 63);
 		if (lane == 0) prev = edge;
@@ -91,30 +182,22 @@ __device__ __forceinline__ void runs_load_heads(const E *__restrict__ data, uint
 template <typename E> __global__ __launch_bounds__(kRunsTh) void runs_count_kernel(const E *__restrict__ data, uint64_t n, uint64_t *__restrict__ tile_counts)
 {
 	typedef RunsCfg<E> C;
-	__shared__ uint32_t wsum[kRunsTh / 64];
 	E x[kRunsVecs][C::V];
 	uint64_t hb[kRunsVecs][C::V];
 	runs_load_heads<E>(data, n, runs_misalign(data), blockIdx.x, x, hb);
-	uint32_t c = 0;
-#pragma unroll
-	for (int k = 0; k < kRunsVecs; ++k)
-#pragma unroll
-		for (uint32_t e = 0; e < C::V; ++e) c += (uint32_t)__popcll(hb[k][e]);
-	if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = c;
-	__syncthreads();
-	if (threadIdx.x == 0) tile_counts[blockIdx.x] = (uint64_t)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+	runs_store_count<C::V>(hb, tile_counts);
 }
 
 // ---- step 2
-// Exclusive scan, in place, of the `count` <= kRunsScanTile words at w, on top of `carry`; returns their sum.
+// Exclusive scan of the `count` <= kRunsScanTile words load(0 .. count - 1), on top of `carry`, to w; returns their sum.
 // (Every thread of the workgroup calls it: barriers.  tmp: 4 words of LDS.)
-__device__ __forceinline__ uint64_t runs_scan_piece(uint64_t *__restrict__ w, uint32_t count, uint64_t carry, uint64_t *tmp)
+template <typename L> __device__ __forceinline__ uint64_t runs_scan_piece(uint64_t *__restrict__ w, uint32_t count, uint64_t carry, uint64_t *tmp, L &&load)
 {
 	uint64_t v[kRunsScanPer], sum = 0;
 #pragma unroll
 	for (int j = 0; j < kRunsScanPer; ++j) {
 		const uint32_t idx = threadIdx.x * kRunsScanPer + j;
-		v[j] = idx < count ? w[idx] : 0;
+		v[j] = idx < count ? load(idx) : 0;
 		sum += v[j];
 	}
 	uint64_t total;
@@ -126,6 +209,11 @@ __device__ __forceinline__ uint64_t runs_scan_piece(uint64_t *__restrict__ w, ui
 		ex += v[j];
 	}
 	return total;
+}
+// (in place)
+__device__ __forceinline__ uint64_t runs_scan_piece(uint64_t *__restrict__ w, uint32_t count, uint64_t carry, uint64_t *tmp)
+{
+	return runs_scan_piece(w, count, carry, tmp, [&](uint32_t idx) { return w[idx]; });
 }
 
 __global__ __launch_bounds__(kRunsScanTh) void runs_scan_pieces_kernel(uint64_t *__restrict__ tile_counts, uint64_t tiles, uint64_t *__restrict__ piece_sums)
@@ -146,7 +234,7 @@ __global__ __launch_bounds__(kRunsScanTh) void runs_scan_top_kernel(uint64_t *__
 	if (threadIdx.x == 0) *num_runs = carry;
 }
 
-// n == 0: no run, and the terminator of no run
+// An empty input, of every entry point that counts: a count of zero, and with starts the terminator of no run
 __global__ __launch_bounds__(64) void runs_empty_kernel(uint64_t *__restrict__ num_runs, uint64_t *__restrict__ starts)
 {
 	if (threadIdx.x != 0) return;
@@ -176,25 +264,13 @@ __global__ __launch_bounds__(kRunsTh) void runs_write_kernel(const E *__restrict
 	E x[kRunsVecs][V];
 	uint64_t hb[kRunsVecs][V];
 	runs_load_heads<E>(data, n, m, tile, x, hb);
-	uint32_t before_k[kRunsVecs], c = 0; // heads of the wave in front of k (uniform)
+	const RunsRank rk = runs_rank<V>(hb, w, lane, wsum);
+	const uint64_t base = tile_out_base(tile_base, piece_base, tile); // heads in front of the tile
 #pragma unroll
 	for (int k = 0; k < kRunsVecs; ++k) {
-		before_k[k] = c;
-#pragma unroll
-		for (uint32_t e = 0; e < V; ++e) c += (uint32_t)__popcll(hb[k][e]);
-	}
-	if (lane == 0) wsum[w] = c;
-	__syncthreads();
-	uint32_t wpre = 0;
-#pragma unroll
-	for (uint32_t ww = 0; ww < kRunsTh / 64 - 1; ++ww)
-		if (ww < w) wpre += wsum[ww];
-	const uint64_t base = tile_base[tile] + piece_base[tile / kRunsScanTile]; // heads in front of the tile
-#pragma unroll
-	for (int k = 0; k < kRunsVecs; ++k) {
-		const uint32_t p0 = w * C::WAVE + (uint32_t)(k * 64 + lane) * V; // place in the tile
+		const uint32_t p0 = runs_place<E>(w, lane, k);
 		const uint64_t v0 = tile * C::TILE + p0;
-		uint32_t incl = wpre + before_k[k];
+		uint32_t incl = rk.wpre + rk.before_k[k];
 #pragma unroll
 		for (uint32_t e = 0; e < V; ++e) incl += popc_below_lane(hb[k][e]);
 #pragma unroll
@@ -213,8 +289,7 @@ __global__ __launch_bounds__(kRunsTh) void runs_write_kernel(const E *__restrict
 	}
 	__syncthreads();
 	if (out) { // the heads in the order of their runs: coalesced stores; run == cap is the terminator of a full output
-		const uint32_t heads = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-		for (uint32_t j = threadIdx.x; j < heads; j += kRunsTh) {
+		for (uint32_t j = threadIdx.x; j < rk.total; j += kRunsTh) {
 			const uint64_t run = base + j;
 			if (run > cap) break;
 			if (starts) starts[run] = tile * C::TILE + head_at[j] - lo;

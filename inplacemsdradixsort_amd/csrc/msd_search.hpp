@@ -16,7 +16,7 @@
 //      2. search_tile_kernel: one workgroup per tile i loads key[a_i, a_{i+1}) and needle[b_i, b_{i+1}) -- together at most
 //         TILE elements -- as codes into the LDS; every needle of the tile binary-searches the tile's keys there and stores
 //         a_i + local.  Stream order is the only barrier between the two launches.
-//      Every extent is CLAMPED (see search_tile_kernel): needles that are not ascending give unspecified results, but every load
+//      Every extent is CLAMPED (see merge_tile_extent): needles that are not ascending give unspecified results, but every load
 //      stays inside the two arrays and every store inside d_out[0, m).
 #pragma once
 
@@ -35,6 +35,23 @@ template <typename K> struct SearchCfg {
 
 // does a key with code k count for a needle with code x?
 template <typename K> __device__ __forceinline__ bool search_counts(K k, K x, bool right) { return (k < x) | (right & (k == x)); }
+
+// |{ k in codes[0, len) : k counts for x }| over ascending codes in the LDS: the branch-free search of the direct kernel,
+// whose trip count depends on len only.  (The kMergePer searches side by side: lds_count_per of msd_merge2.hpp.)
+template <typename K> __device__ __forceinline__ uint32_t lds_count(const K *__restrict__ codes, uint32_t len, K x, bool right)
+{
+	uint32_t base = 0;
+	if (len) {
+		uint32_t l = len; // invariant: the count lies in [base, base + l], base + l <= len
+		while (l > 1) {
+			const uint32_t half = l >> 1;
+			base += search_counts(codes[base + half - 1], x, right) ? half : 0u;
+			l -= half;
+		}
+		base += search_counts(codes[base], x, right) ? 1u : 0u; // (base < len)
+	}
+	return base;
+}
 
 // ---- direct
 template <typename K, bool POS>
@@ -74,18 +91,19 @@ __global__ __launch_bounds__(kSearchTh) void search_direct_kernel(const K *__res
 	}
 }
 
-// ---- merge, step 1
+// ---- merge, step 1 (and step 1 of msd_merge2.hpp, msd_setops.hpp and msd_join.hpp: the RIGHT rule, b in the role of the
+// needles -- "b[mid] precedes a[d - mid - 1] iff it is strictly smaller" is the RIGHT case below, code for code)
 // splits[i] = a_i for i = 0 .. tiles (tiles + 1 words).  b counts the needles among the first d elements of the merged
 // sequence: needle b is among them iff it PRECEDES key[d - b - 1] (<= for LEFT, < for RIGHT), which is monotone in b for
 // ascending needles.  The search stays inside [max(0, d - n), min(d, m)] whatever the needles hold: mid < m and
 // 0 <= d - mid - 1 < n for every probe, and 0 <= a_i <= n, 0 <= d - a_i <= m for every result.
-template <typename K>
+template <typename K, uint32_t TILE>
 __global__ __launch_bounds__(kSearchTh) void search_split_kernel(const K *__restrict__ keys, uint64_t n, const K *__restrict__ needles, uint64_t m, uint32_t right,
 	KeyCodec<K> cd, uint64_t tiles, uint64_t *__restrict__ splits)
 {
 	const uint64_t i = (uint64_t)blockIdx.x * kSearchTh + threadIdx.x;
 	if (i > tiles) return;
-	const uint64_t total = n + m, d = i * SearchCfg<K>::TILE < total ? i * SearchCfg<K>::TILE : total;
+	const uint64_t total = n + m, d = i * TILE < total ? i * TILE : total;
 	uint64_t lo = d > n ? d - n : 0, hi = d < m ? d : m;
 	while (lo < hi) {
 		const uint64_t mid = lo + ((hi - lo) >> 1);
@@ -107,17 +125,11 @@ template <typename K> __device__ __forceinline__ void search_stage(const K *__re
 	const K *const vbase = src - mis;                                      // (16-byte aligned; dereferenced inside the range only)
 	for (uint32_t v0 = threadIdx.x * V; v0 < mis + count; v0 += kSearchTh * V) { // virtual index: element e has v = e + mis
 		if (v0 >= mis && v0 + V <= mis + count) {
-			const u32x4 q = *reinterpret_cast<const u32x4 *>(vbase + v0);
+			K x[V];
+			vec16_unpack<K>(*reinterpret_cast<const u32x4 *>(vbase + v0), x);
 			K *const to = dst + (v0 - mis);
-			if constexpr (sizeof(K) == 4) {
-				to[0] = cd.enc(q.x);
-				to[1] = cd.enc(q.y);
-				to[2] = cd.enc(q.z);
-				to[3] = cd.enc(q.w);
-			} else {
-				to[0] = cd.enc((K)q.x | ((K)q.y << 32));
-				to[1] = cd.enc((K)q.z | ((K)q.w << 32));
-			}
+#pragma unroll
+			for (uint32_t e = 0; e < V; ++e) to[e] = cd.enc(x[e]);
 		} else {
 #pragma unroll
 			for (uint32_t e = 0; e < V; ++e)
@@ -127,29 +139,48 @@ template <typename K> __device__ __forceinline__ void search_stage(const K *__re
 }
 
 // ---- merge, step 2
-// The clamps: na = the tile's keys, at most TILE and 0 if the splits are not ascending; nb = its needles, at most what is left
-// of TILE and 0 if b_{i+1} < b_i.  With 0 <= a_i <= a_{i+1} <= n the loads are keys[a_i, a_i + na) inside [0, n); with
-// 0 <= b_i <= b_{i+1} <= m the loads and stores are at [b_i, b_i + nb) inside [0, m).  For ascending needles the clamps change
-// nothing: na + nb = d_{i+1} - d_i <= TILE.
+// Tile i of the merged sequence of a (n elements: the keys) and b (m elements: the needles), as the splits cut it, for every
+// tile kernel of the merge path.  The clamps: na = the tile's a, at most TILE and 0 if the splits are not ascending; nb = its
+// b, at most what is left of TILE and 0 if b_{i+1} < b_i.  With 0 <= a_i <= a_{i+1} <= n the loads are a[a0, a0 + na)
+// inside [0, n); with 0 <= b_i <= b_{i+1} <= m the loads and stores are at [b0, b0 + nb) inside [0, m).  For ascending inputs
+// the clamps change nothing: na + nb = d1 - d0 <= TILE.  (All uniform.)
+struct MergeTileExtent {
+	uint64_t d0, d1, a0, b0;
+	uint32_t na, nb;
+};
+template <uint32_t TILE> __device__ __forceinline__ MergeTileExtent merge_tile_extent(uint64_t i, uint64_t n, uint64_t m, const uint64_t *__restrict__ splits)
+{
+	MergeTileExtent t;
+	const uint64_t total = n + m;
+	t.d0 = i * TILE < total ? i * TILE : total;
+	t.d1 = (i + 1) * TILE < total ? (i + 1) * TILE : total;
+	const uint64_t a1 = splits[i + 1], b1 = t.d1 - a1;
+	t.a0 = splits[i];
+	t.b0 = t.d0 - t.a0;
+	t.na = a1 > t.a0 ? (uint32_t)(a1 - t.a0 < TILE ? a1 - t.a0 : TILE) : 0u;
+	t.nb = b1 > t.b0 ? (uint32_t)(b1 - t.b0 < TILE - t.na ? b1 - t.b0 : TILE - t.na) : 0u;
+	return t;
+}
+
 template <typename K, bool POS>
 __global__ __launch_bounds__(kSearchTh) void search_tile_kernel(const K *__restrict__ keys, uint64_t n, const K *__restrict__ needles, uint64_t m, uint32_t right,
 	KeyCodec<K> cd, const uint64_t *__restrict__ splits, const uint64_t *__restrict__ positions, uint64_t *__restrict__ out)
 {
 	constexpr uint32_t TILE = SearchCfg<K>::TILE;
 	__shared__ K lds[TILE]; // the tile's keys as codes, the tile's needles as codes behind them
-	const uint64_t i = blockIdx.x, total = n + m;
-	const uint64_t d0 = i * TILE < total ? i * TILE : total, d1 = (i + 1) * TILE < total ? (i + 1) * TILE : total;
-	const uint64_t a0 = splits[i], a1 = splits[i + 1], b0 = d0 - a0, b1 = d1 - a1;
-	const uint32_t na = a1 > a0 ? (uint32_t)(a1 - a0 < TILE ? a1 - a0 : TILE) : 0u;
-	const uint32_t nb = b1 > b0 ? (uint32_t)(b1 - b0 < TILE - na ? b1 - b0 : TILE - na) : 0u;
+	const MergeTileExtent t = merge_tile_extent<TILE>(blockIdx.x, n, m, splits);
+	const uint64_t a0 = t.a0, b0 = t.b0;
+	const uint32_t na = t.na, nb = t.nb;
 	if (nb == 0) return; // a tile of keys only: nothing to store (uniform: the barrier below is never reached by a part of the workgroup)
 	search_stage<K>(keys + a0, na, cd, lds);
 	search_stage<K>(needles + b0, nb, cd, lds + na);
 	__syncthreads();
 	for (uint32_t j = threadIdx.x; j < nb; j += kSearchTh) {
+		// lds_count(lds, na, x, right), spelled out: the one exception to "one definition" (DESIGN.md 1.1).  Called as a
+		// function the same search compiles to other tests around the loop, and the call was measured 2.5 % slower.
 		const K x = lds[na + j];
 		uint32_t base = 0;
-		if (na) { // (uniform) the branch-free search of the direct kernel, over the tile's keys
+		if (na) { // (uniform)
 			uint32_t len = na;
 			while (len > 1) {
 				const uint32_t half = len >> 1;

@@ -198,6 +198,15 @@ def test_the_scan_with_more_than_one_piece(ctx):
     Pairs(gr.want, n, total - n, gr.count, what="two pieces").run(ctx, gr.count)
 
 
+def test_the_offsets_with_one_group_behind_the_first_piece(ctx):
+    """scan + 1 groups of one pair each: the offsets' second piece holds a single group, and every offset is its index"""
+    _, scan, _ = limits(ctx, 4)
+    G = scan + 1
+    idx, one = np.arange(G, dtype=np.uint64), np.ones(G, np.uint64)
+    Pairs((idx, one, idx, one), G, G, G, what="one pair each").run(ctx, G)
+    Pairs((idx, one, idx, one), G, G, G, gcap=G + scan + 7, what="one pair each, pieces behind the last group").run(ctx, scan)
+
+
 # ---- alignment
 
 @pytest.mark.parametrize("kt", [E.U32, E.I64], ids=["u32", "i64"])
