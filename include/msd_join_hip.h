@@ -55,7 +55,8 @@ extern "C" {
  * cap == 0 is legal and only counts, as does a call with none of the five arrays.
  *
  * Inputs that are NOT ascending give unspecified values and counts -- but every extent in the kernels is clamped:
- * every load stays inside its input array and every store inside [0, min(count, cap)) of its output.
+ * every load stays inside its input array and every store inside [0, min(count, cap)) of its output, and every
+ * stored group lies inside the arrays: a_count >= 1, a_first + a_count <= n and b_first + b_count <= m.
  *
  * Asynchronous: the launches go to the context's stream, nothing is read back and the host does not wait.  No
  * atomics, and no workgroup waits for another one.  Scratch, in the context's workspace like the sort's

@@ -64,7 +64,7 @@ namespace msd {
 constexpr uint64_t kJoinMaxElems = (uint64_t)1 << 32, kJoinMaxStored = (uint64_t)1 << 40;
 
 // |{ k in keys[lo, hi) : code(k) <= v }| + lo: where the run of v ends behind lo (lo <= hi <= the array's length; one lane)
-template <typename K> __device__ __forceinline__ uint64_t join_global_upper(const K *__restrict__ keys, uint64_t lo, uint64_t hi, K v, KeyCodec<K> cd)
+template <typename K> __host__ __device__ __forceinline__ uint64_t join_global_upper(const K *__restrict__ keys, uint64_t lo, uint64_t hi, K v, KeyCodec<K> cd)
 {
 	while (lo < hi) {
 		const uint64_t mid = lo + ((hi - lo) >> 1);

@@ -33,12 +33,14 @@ template <typename K> struct SearchCfg {
 	static constexpr uint32_t TILE = kSearchTh * 4u * V;   // merge: keys plus needles of one workgroup: 4096 (4-byte), 2048 (8-byte); 16 KiB of LDS
 };
 
+// (search_counts, lds_count and merge_tile_extent -- and join_global_upper of msd_join.hpp -- are __host__ as well for one
+// caller: tests/clamp_main.hip runs these index functions on the host, on inputs that are not ascending.)
 // does a key with code k count for a needle with code x?
-template <typename K> __device__ __forceinline__ bool search_counts(K k, K x, bool right) { return (k < x) | (right & (k == x)); }
+template <typename K> __host__ __device__ __forceinline__ bool search_counts(K k, K x, bool right) { return (k < x) | (right & (k == x)); }
 
 // |{ k in codes[0, len) : k counts for x }| over ascending codes in the LDS: the branch-free search of the direct kernel,
 // whose trip count depends on len only.  (The kMergePer searches side by side: lds_count_per of msd_merge2.hpp.)
-template <typename K> __device__ __forceinline__ uint32_t lds_count(const K *__restrict__ codes, uint32_t len, K x, bool right)
+template <typename K> __host__ __device__ __forceinline__ uint32_t lds_count(const K *__restrict__ codes, uint32_t len, K x, bool right)
 {
 	uint32_t base = 0;
 	if (len) {
@@ -148,7 +150,7 @@ struct MergeTileExtent {
 	uint64_t d0, d1, a0, b0;
 	uint32_t na, nb;
 };
-template <uint32_t TILE> __device__ __forceinline__ MergeTileExtent merge_tile_extent(uint64_t i, uint64_t n, uint64_t m, const uint64_t *__restrict__ splits)
+template <uint32_t TILE> __host__ __device__ __forceinline__ MergeTileExtent merge_tile_extent(uint64_t i, uint64_t n, uint64_t m, const uint64_t *__restrict__ splits)
 {
 	MergeTileExtent t;
 	const uint64_t total = n + m;

@@ -52,3 +52,58 @@ def tiles(a_codes, b_codes, tile):
             merged[d0 + r], origin[d0 + r] = x, src
     assert (origin >= 0).all(), "a position no tile wrote"
     return merged, origin.astype(np.uint64)
+
+
+def tiles_clamped(a_codes, b_codes, tile, junk=S.NONE16, first=False, stats=None):
+    """The clamped model of merge_tile_kernel with values and origin, for inputs in ANY order (the pieces: search_expect).
+    ``junk``: what an LDS cell that nothing wrote holds (S.JUNKS); ``first``: of two elements ranked to one place the first
+    stays (else the last).  Returns ``(S.Clamped(out, vals, origin), junk_reads, collisions)``: out holds codes, vals the index
+    in [A; B] of the value loaded, origin what the kernel stores."""
+    a_codes, b_codes = np.asarray(a_codes), np.asarray(b_codes)
+    n, m = len(a_codes), len(b_codes)
+    A, B = S.Checked(a_codes, "a"), S.Checked(b_codes, "b")
+    VA, VB = S.Checked(range(n), "vals_a"), S.Checked(range(n, n + m), "vals_b")
+    sa, _ = S.split_points(A.x, B.x, tile, True)
+    splits = S.Checked(sa, "splits")
+    out, vals, origin = S.Stores("d_out"), S.Stores("d_out_vals"), S.Stores("d_out_origin")
+    junk_reads = collisions = 0
+    for i in range(len(sa) - 1):
+        t = S.Extent(i, n, m, splits, tile, stats)
+        na, nb = t.na, t.nb
+        cnt = min(na + nb, t.d1 - t.d0)
+        if cnt == 0:
+            continue
+        last = na + nb - 1
+        assert last >= 0
+        j = last if junk == "last" else junk
+        codes, outk, src = S.Lds(tile, j, first, "codes"), S.Lds(tile, j, first, "outk"), S.Lds(tile, j, first, "src")
+        S.stage(A, t.a0, na, codes, 0)
+        S.stage(B, t.b0, nb, codes, na)
+        codes.barrier()
+
+        def rank(self0):
+            def f(e, x, base):
+                r = e + base if e + base < last else last
+                outk[r] = x
+                src[r] = self0 + e
+            return f
+        S.merge_for_counts(codes, 0, na, na, nb, False, rank(0))       # (no barrier between the two sides)
+        S.merge_for_counts(codes, na, nb, 0, na, True, rank(na))
+        if stats is not None:
+            stats.hit("collision", src.collisions)
+            stats.hit("hole", sum(1 for p in range(cnt) if p not in src.cells))
+        outk.barrier()
+        src.barrier()
+        for p in range(cnt):
+            assert t.d0 + p < t.d1 <= n + m
+            out[t.d0 + p] = outk[p]
+            s = src[p] if src[p] < last else last
+            from_a = s < na
+            at = t.a0 + s if from_a else t.b0 + (s - na)
+            vals[t.d0 + p] = VA[at] if from_a else VB[at]
+            assert at < (n if from_a else m)
+            origin[t.d0 + p] = at if from_a else n + at
+        assert codes.junk_reads == 0                                    # (every code that is read was staged)
+        junk_reads += outk.junk_reads + src.junk_reads
+        collisions += src.collisions
+    return S.Clamped(out=out, vals=vals, origin=origin), junk_reads, collisions

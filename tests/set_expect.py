@@ -99,3 +99,170 @@ def tiles(a_codes, b_codes, tile, op):
         codes += [x for _, x, _ in ranked]
         origin += [s for _, _, s in ranked]
     return np.array(codes, a_codes.dtype), np.array(origin, np.uint64)
+
+
+# ---- the clamped model: inputs in ANY order (the pieces: search_expect)
+
+KEEP_MASK = {INTERSECTION: 1, UNION: 7, DIFFERENCE: 2, SYMMETRIC_DIFFERENCE: 6}    # set_keep_mask: matched A, unmatched A, unmatched B
+
+
+class ClampedTile:
+    """set_tile: the extent and the halo of tile i (A, B: Checked arrays)"""
+
+    def __init__(self, i, A, B, splits, tile, stats=None):
+        n, m = len(A), len(B)
+        x = S.Extent(i, n, m, splits, tile, stats)
+        self.a0, self.b0, self.na, self.nb = x.a0, x.b0, x.na, x.nb
+        self.has_a_before = self.a0 > 0 and self.a0 <= n
+        self.has_b_before = self.b0 > 0 and self.b0 <= m
+        self.has_b_behind = self.b0 + self.nb < m
+        self.a_before = A[self.a0 - 1] if self.has_a_before else 0
+        self.b_before = B[self.b0 - 1] if self.has_b_before else 0
+        self.b_behind = B[self.b0 + self.nb] if self.has_b_behind else 0
+
+
+def decide(codes, self0, count, other0, length, has_before, before, has_edge, edge, keep_matched, keep_unmatched, bside, store):
+    """set_decide: the number of kept elements; store(e, x, base, keep) for every element"""
+    kept = [0]
+
+    def f(e, x, base):
+        prev = codes[self0 + (e - 1 if e else 0)]
+        head = prev != x if e else not (has_before and before == x)
+        in_tile = base > 0 if bside else base < length
+        y = codes[other0 + (base - 1 if bside else base) if in_tile else 0]
+        matched = y == x if in_tile else (has_edge and edge == x)
+        keep = head and (keep_matched if matched else keep_unmatched)
+        kept[0] += 1 if keep else 0
+        store(e, x, base, keep)
+    S.merge_for_counts(codes, self0, count, other0, length, bside, f)
+    return kept[0]
+
+
+def decide_a(codes, t, keep_matched, keep_unmatched, store):
+    """set_decide_a"""
+    return decide(codes, 0, t.na, t.na, t.nb, t.has_a_before, t.a_before, t.has_b_behind, t.b_behind, keep_matched, keep_unmatched, False, store)
+
+
+def decide_tile(codes, t, keep, outk, src):
+    """set_decide_tile (outk is None: the count kernel's, which writes nothing)"""
+    last = t.na + t.nb - 1
+    self0 = [0]
+
+    def store(e, x, base, kept):
+        if outk is not None:
+            r = e + base if e + base < last else last
+            src[r] = self0[0] + e if kept else S.NONE16
+            if kept:
+                outk[r] = x
+    kept = decide_a(codes, t, keep & 1 != 0, keep & 2 != 0, store)
+    self0[0] = t.na
+    kept += decide(codes, t.na, t.nb, 0, t.na, t.has_b_before, t.b_before, t.has_a_before, t.a_before, False, keep & 4 != 0, True, store)
+    return kept
+
+
+def count_clamped(A, B, splits, tile, keep):
+    """set_count_kernel for every tile: the tile counts (no race, no junk: every cell that is read was staged)"""
+    n, m = len(A), len(B)
+    tile_counts = []
+    for i in range(len(splits) - 1):
+        t = ClampedTile(i, A, B, splits, tile)
+        if t.na + t.nb == 0:
+            tile_counts.append(0)
+            continue
+        codes = S.Lds(tile, None, False, "codes")
+        S.stage(A, t.a0, t.na, codes, 0)
+        S.stage(B, t.b0, t.nb, codes, t.na)
+        codes.barrier()
+        tile_counts.append(decide_tile(codes, t, keep, None, None))
+        assert codes.junk_reads == 0 and tile_counts[-1] <= t.na + t.nb
+    return tile_counts
+
+
+def tiles_clamped(a_codes, b_codes, tile, op, cap=None, junk=S.NONE16, first=False, stats=None, counted=None):
+    """The clamped model of msd_set_sorted (the split, set_count_kernel, the scan, set_write_kernel with keys and origin) for
+    inputs in ANY order.  ``cap`` None: no cap.  ``junk``, ``first``: see merge_expect.tiles_clamped.  ``counted``: the
+    ``tile_counts`` an earlier run on these inputs returned (they depend on nothing else).  Returns
+    ``(Clamped(count, out, origin), junk_reads, collisions)``: count is what *d_num_out receives, out holds codes."""
+    a_codes, b_codes = np.asarray(a_codes), np.asarray(b_codes)
+    n, m = len(a_codes), len(b_codes)
+    A, B = S.Checked(a_codes, "a"), S.Checked(b_codes, "b")
+    sa, _ = S.split_points(A.x, B.x, tile, True)
+    splits = S.Checked(sa, "splits")
+    keep = KEEP_MASK[op]
+    tile_counts = count_clamped(A, B, splits, tile, keep) if counted is None else counted
+    count = sum(tile_counts)
+    windows = S.out_windows(tile_counts, count, count if cap is None else cap)
+    out, origin = S.Stores("d_out"), S.Stores("d_out_origin")
+    junk_reads = collisions = 0
+    for i, (base, lim) in enumerate(windows):
+        if base >= lim:
+            continue
+        t = ClampedTile(i, A, B, splits, tile, stats)
+        ranks = t.na + t.nb
+        if ranks == 0:
+            continue
+        cnt = min(lim - base, ranks)
+        last = ranks - 1
+        j = last if junk == "last" else junk
+        codes, outk, src = S.Lds(tile, j, first, "codes"), S.Lds(tile, j, first, "outk"), S.Lds(tile, j, first, "src")
+        S.stage(A, t.a0, t.na, codes, 0)
+        S.stage(B, t.b0, t.nb, codes, t.na)
+        codes.barrier()
+        decide_tile(codes, t, keep, outk, src)
+        collisions += src.collisions
+        if stats is not None:
+            stats.hit("collision", src.collisions)
+        for lds in (codes, outk, src):
+            lds.barrier()
+
+        def place(r, to, e):
+            codes[to] = outk[r]
+            src[to] = e
+        marks = S.ballot_compact(src, ranks, cnt, tile, place)
+        if stats is not None and min(marks, cnt) < cnt:
+            stats.hit("unplaced")                                       # positions nothing was compacted to are stored
+        codes.barrier()
+        src.barrier()
+        for p in range(cnt):
+            assert base + p < lim
+            out[base + p] = codes[p]
+            e = src[p] if src[p] < last else last
+            from_a = e < t.na
+            at = t.a0 + e if from_a else t.b0 + (e - t.na)
+            assert at < (n if from_a else m)
+            origin[base + p] = at if from_a else n + at
+        junk_reads += codes.junk_reads + outk.junk_reads + src.junk_reads
+    return S.Clamped(count=count, tile_counts=tile_counts, out=out, origin=origin), junk_reads, collisions
+
+
+def decide_np(codes, self0, count, other0, length, has_before, before, has_edge, edge, keep_matched, keep_unmatched, bside):
+    """decide, vectorised over the `count` elements: ``(keep, base)``"""
+    if count == 0:
+        return np.zeros(0, bool), np.zeros(0, np.int64)
+    e = np.arange(count)
+    x = codes[self0 + e]
+    base = S.lds_count_np(codes, other0, length, x, bside)
+    prev = codes[self0 + np.maximum(e - 1, 0)]
+    head = np.where(e > 0, prev != x, not (has_before and before == x[0]))
+    in_tile = base > 0 if bside else base < length
+    y = codes[np.where(in_tile, other0 + (base - 1 if bside else base), 0)]
+    matched = np.where(in_tile, y == x, bool(has_edge) & (x == edge))
+    return head & np.where(matched, keep_matched, keep_unmatched), base
+
+
+def count_np(a_codes, b_codes, tile, op):
+    """count_clamped, vectorised, at any tile: what *d_num_out (INTERSECTION: *d_num_groups) receives for inputs in any order"""
+    A, B = np.asarray(a_codes), np.asarray(b_codes)          # (the index checks are count_clamped's)
+    a_codes, b_codes = A, B
+    sa, _ = S.split_points(A, B, tile, True)
+    splits = S.Checked(sa, "splits")
+    keep, tile_counts = KEEP_MASK[op], []
+    for i in range(len(sa) - 1):
+        t = ClampedTile(i, A, B, splits, tile)
+        kept = 0
+        if t.na + t.nb:
+            codes = S.stage_np(a_codes, b_codes, t)
+            kept += int(decide_np(codes, 0, t.na, t.na, t.nb, t.has_a_before, t.a_before, t.has_b_behind, t.b_behind, keep & 1 != 0, keep & 2 != 0, False)[0].sum())
+            kept += int(decide_np(codes, t.na, t.nb, 0, t.na, t.has_b_before, t.b_before, t.has_a_before, t.a_before, False, keep & 4 != 0, True)[0].sum())
+        tile_counts.append(kept)
+    return tile_counts

@@ -7,8 +7,8 @@ with a known pattern: a case checks the count word, the min(count, cap) results,
 are what was uploaded, that the payload in front of an offset buffer is what it was, that no output word beyond min(count,
 cap) changed and that an output that was not given did not change.  The shapes are the smallest at which a kernel can go
 wrong, taken from msd_join_limits (T = the tile of the groups call, P = the pair ranks of one workgroup of the expansion).
-The buffers, the input kinds and the special values come from test_gpu_set_sorted.py and test_gpu_merge_sorted.py.  No test
-hands unsorted inputs to the calls.  The Python wrappers have a test of their own at the end."""
+The buffers, the input kinds and the special values come from test_gpu_set_sorted.py and test_gpu_merge_sorted.py.  Unsorted
+inputs and made-up groups: test_gpu_untrusted_order.py.  The Python wrappers have a test of their own at the end."""
 import ctypes as C
 
 import numpy as np

@@ -7,7 +7,7 @@ on integer tensors that carry the bit patterns, with EVERY buffer -- both key ar
 -- inside a guardband.Arena whose payload is pre-filled with a known pattern: a case checks the n + m outputs, that no guard
 was touched, that the inputs are what was uploaded, that the payload in front of an offset buffer is what it was and that no
 output word beyond n + m changed (every output buffer is TAIL elements longer than n + m).  The shapes are the smallest at
-which a kernel can go wrong, taken from msd_merge_sorted_limits (T = the tile).  No test hands unsorted inputs to the call.
+which a kernel can go wrong, taken from msd_merge_sorted_limits (T = the tile).  Unsorted inputs: test_gpu_untrusted_order.py.
 The Python wrapper has tests of its own at the end."""
 import ctypes as C
 

@@ -6,8 +6,8 @@ The expected result is defined in tests/search_expect.py and every result is com
 on integer tensors that carry the bit patterns, with EVERY buffer -- keys, needles, positions, d_out -- inside a
 guardband.Arena whose payload is pre-filled with a known pattern: a case checks the m outputs, that no guard was touched, that
 the inputs are what was uploaded and that the payload in front of an offset buffer is what it was.  The shapes are the smallest
-at which a kernel can go wrong, taken from msd_search_sorted_limits (T = the merge tile, D = the direct tile).  No test hands
-unsorted needles to the merge path.  The Python wrappers have tests of their own at the end."""
+at which a kernel can go wrong, taken from msd_search_sorted_limits (T = the merge tile, D = the direct tile).  Unsorted
+needles under the merge path: test_gpu_untrusted_order.py.  The Python wrappers have tests of their own at the end."""
 import ctypes as C
 
 import numpy as np

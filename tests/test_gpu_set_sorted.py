@@ -8,8 +8,8 @@ own, d_num_out -- inside a guardband.Arena whose payload is pre-filled with a kn
 min(count, cap) results, that no guard was touched, that the inputs are what was uploaded, that the payload in front of an
 offset buffer is what it was, that no output word beyond min(count, cap) changed and that an output that was not given did
 not change.  The shapes are the smallest at which a kernel can go wrong, taken from msd_set_sorted_limits (T = the tile).
-The buffers, the six kinds of input of the merge and the special values come from test_gpu_merge_sorted.py.  No test hands
-unsorted inputs to the call.  The Python wrappers have tests of their own at the end."""
+The buffers, the six kinds of input of the merge and the special values come from test_gpu_merge_sorted.py.  Unsorted
+inputs: test_gpu_untrusted_order.py.  The Python wrappers have tests of their own at the end."""
 import ctypes as C
 
 import numpy as np
