@@ -5,7 +5,8 @@ gets; everything around it is known memory, filled with a pseudo-random function
 could not show a shifted copy of itself, and a constant key input could equal it).  ``check()`` regenerates that pattern
 and compares.  The front guard ends on a 4 KiB boundary, so ``lead_bytes`` (a multiple of 16: the library refuses
 buffers that are not aligned to 16 bytes) says exactly where the payload starts relative to the 256-byte block grid and
-the page grid.
+the page grid.  A :class:`Buf` is a window into an Arena's payload that knows what the payload was filled with: the
+buffers of the tests that call the C ABI.
 
 Plain module, no fixture: ``import guardband`` (tests/ is on sys.path under pytest's default import mode).  It works on
 ``device="cpu"`` too, which is how tests/test_guardband.py tests it without a GPU.
@@ -18,6 +19,8 @@ MIN_GUARD_BYTES = 64 << 10
 
 _INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 _NP_INT = {1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}
+_NP_UINT = {1: np.uint8, 4: np.uint32, 8: np.uint64}
+BUF_PATTERN_FIRST = 12345                         # where a Buf's fill starts in the pattern; the value means nothing
 
 
 def guard_elems(elem_bytes, *unit_elems):
@@ -123,3 +126,43 @@ class Arena:
                 f"(payload of {self.n} elements at 4 KiB + {(self.front - self.guard) * self.es} bytes; "
                 f"first changed cell holds {int(got[first]) & ((1 << 8 * self.es) - 1):#x}, "
                 f"was {int(exp[first]) & ((1 << 8 * self.es) - 1):#x})")
+
+
+class Buf:
+    """``Buf(es, count, off=0, lead_bytes=0, a=None, device="cuda")``: `count` elements of es (1, 4 or 8) bytes that start
+    `off` elements into the payload of an Arena whose payload starts `lead_bytes` behind a page boundary.  The whole payload
+    holds a known pattern, or, behind `off`, the array `a`; ``fill`` is that content as unsigned words, ``ptr`` the address
+    of element `off`."""
+
+    def __init__(self, es, count, off=0, lead_bytes=0, a=None, device="cuda"):
+        self.es, self.count, self.off = es, count, off
+        self.arena = Arena(_INT[es], count + off, lead_bytes=lead_bytes, device=device)
+        self.fill = pattern(BUF_PATTERN_FIRST, count + off, es).numpy().view(_NP_UINT[es]).copy()
+        if a is not None:
+            self.fill[off:] = a
+        self.arena.fill(self.fill)
+        self.ptr = self.arena.ptr + off * es
+
+    def reset(self):
+        self.arena.fill(self.fill)
+
+    def host(self):
+        """the `count` elements; what lies in front of them in the payload must be what it was"""
+        h = self.arena.host(_NP_UINT[self.es])
+        assert (h[:self.off] == self.fill[:self.off]).all(), "payload in front of the buffer changed"
+        return h[self.off:]
+
+    def untouched_from(self, k):
+        return (self.host()[k:] == self.fill[self.off + k:]).all()
+
+    def unchanged(self):
+        return self.untouched_from(0)
+
+    def written(self, count):
+        """the first `count` elements; the rest of the buffer must be what it was"""
+        h = self.host()
+        assert (h[count:] == self.fill[self.off + count:]).all(), "an element beyond the first %d changed" % count
+        return h[:count]
+
+    def check(self, what):
+        self.arena.check(what)

@@ -1,8 +1,10 @@
-"""What msd_sort_rows has to produce, and the rows its tests feed it (a helper module like guardband.py, not a test).
+"""What msd_sort_rows has to produce, and the rows its tests feed it (a helper module like guardband.py, not a test); and
+the numpy side of what the tests of every family share: the key types, the tables by key type and by width, the key codec
+and the flat inputs.  The torch side is gpu_support.py.
 
 The expectation is defined HERE: the keys' bit patterns become order-preserving unsigned codes with the numpy expressions of
-this file (the ones of tests/test_gpu_topk_rows.py), np.sort orders the codes along axis 1, the inverse map gives the sorted
-bit patterns, and descending is that reversed along axis 1.  Floats are therefore in IEEE-754 totalOrder.
+this file, np.sort orders the codes along axis 1, the inverse map gives the sorted bit patterns, and descending is that
+reversed along axis 1.  Floats are therefore in IEEE-754 totalOrder.
 
 Plain module, no fixture: ``import sort_rows_expect`` (tests/ is on sys.path under pytest's default import mode)."""
 import numpy as np
@@ -10,6 +12,13 @@ import numpy as np
 U32, I32, F32, U64, I64, F64 = range(6)
 UT = {U32: np.uint32, I32: np.uint32, F32: np.uint32, U64: np.uint64, I64: np.uint64, F64: np.uint64}
 NAMES = {U32: "u32", I32: "i32", F32: "f32", U64: "u64", I64: "i64", F64: "f64"}
+# key type -> (unsigned view, typed view)
+VIEWS = {U32: (np.uint32, np.uint32), I32: (np.uint32, np.int32), F32: (np.uint32, np.float32),
+         U64: (np.uint64, np.uint64), I64: (np.uint64, np.int64), F64: (np.uint64, np.float64)}
+# by element width in bytes
+WIDTHS = (4, 8)
+UW = {1: np.uint8, 4: np.uint32, 8: np.uint64}
+UKT = {4: U32, 8: U64}              # the unsigned key type of a width: code == bits
 
 
 def np_encode(bits, kt):
@@ -135,6 +144,75 @@ def seed_of(*xs):
     for x in xs:
         s = (s * 1000003 + int(x)) % (1 << 31)
     return s
+
+
+# ---- flat inputs, as codes of an unsigned type (code == bits)
+
+def top(kb):
+    return (1 << (8 * kb)) - 1
+
+
+def uniform(rng, count, kb, lo=0, hi=None):
+    return rng.integers(lo, top(kb) if hi is None else hi, count, dtype=UW[kb], endpoint=True)
+
+
+def special_bits(kt):
+    ut = UT[kt]
+    W = 8 * np.dtype(ut).itemsize
+    if kt % 3 != 2:                                                 # integers: min, -1, 0, 1, max (as signed; as unsigned the same bits matter)
+        return np.array([1 << (W - 1), (1 << W) - 1, 0, 1, (1 << (W - 1)) - 1], ut)
+    if W == 32:
+        sign, inf, q, s, den = 0x80000000, 0x7F800000, 0x7FC00000, 0x7F800001, 0x007FFFFF
+    else:
+        sign, inf, q, s, den = 1 << 63, 0x7FF << 52, 0x7FF8 << 48, (0x7FF << 52) | 1, (1 << 52) - 1
+    pos = [0, 1, den, inf, q, q | 0x1234, s, s | 0x4320]           # zero, denormals, inf, quiet and signalling NaNs with two payloads each
+    return np.array(pos + [p | sign for p in pos], ut)
+
+
+# ---- flat typed inputs
+
+def make_float(n, kind, tt, seed):
+    rng = np.random.default_rng(seed)
+    ut = np.uint32 if tt == np.float32 else np.uint64
+    normal = lambda: rng.standard_normal(n).astype(tt)  # noqa: E731
+    if kind == "normal":
+        return normal()
+    if kind == "bits":
+        return rng.integers(0, np.iinfo(ut).max, n, dtype=ut, endpoint=True).view(tt)
+    if kind == "specials":
+        sp = np.repeat(float_specials(tt), 5)  # (a small n takes a random subset of them)
+        a = np.concatenate([sp, rng.standard_normal(max(n - len(sp), 0)).astype(tt)])
+        return np.ascontiguousarray(rng.permutation(a)[:n])
+    if kind == "const":
+        return np.full(n, -1.5, tt)
+    if kind == "negative":
+        return -(np.abs(normal()) + tt(1e-3))
+    if kind == "sorted":
+        return np.sort(normal())
+    if kind == "reverse":
+        return np.sort(normal())[::-1].copy()
+    if kind == "coarse":
+        return (np.round(normal() * 16) / 16).astype(tt)
+    raise ValueError(kind)
+
+
+def make_int(n, kind, tt, seed):
+    rng = np.random.default_rng(seed)
+    i = np.iinfo(tt)
+    bits = lambda: rng.integers(i.min, i.max, n, dtype=tt, endpoint=True)  # noqa: E731
+    if kind == "bits":
+        return bits()
+    if kind == "small":
+        return rng.integers(-2048, 2048, n, dtype=tt)
+    if kind == "const":
+        return np.full(n, -123456789, tt)
+    if kind == "extremes":
+        return rng.choice(np.array([i.min, i.max, -1, 0], dtype=tt), n)
+    if kind == "sorted":
+        return np.sort(bits())
+    if kind == "reverse":
+        return np.sort(bits())[::-1].copy()
+    raise ValueError(kind)
 
 
 def check_positions(bits, values, positions):

@@ -4,16 +4,15 @@ argument lists and the three flags, the library exports them, the binding lists 
 context is refused first, the limits call answers on the host, the Python wrapper refuses what never needs a device to be
 refused, and the numpy expectation of tests/compact_expect.py is what its docstring says."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import compact_expect as X
 import sort_rows_expect as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_compact": ["msd_ctx *ctx", "const void *d_keys", "int key_type", "uint64_t n", "const uint8_t *d_mask", "uint64_t lo_bits", "uint64_t hi_bits",
                     "int flags", "const void *d_vals", "int val_bytes", "uint64_t cap", "void *d_out_keys", "void *d_out_vals", "uint64_t *d_out_idx",
@@ -22,20 +21,10 @@ SIGNATURES = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_compact_hip.h")).read()
-    return text, re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_two_functions_and_the_flags():
-    text, flat = _header()
+    text, flat = A.header("msd_compact_hip.h")
     assert '#include "msd_radix_hip.h"' in flat and flat.count("#include") == 1
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
     assert re.search(r"enum \{ MSD_COMPACT_RANGE = 1, MSD_COMPACT_INVERT = 2, MSD_COMPACT_REST = 4 \};", flat)
     assert (X.RANGE, X.INVERT, X.REST) == (1, 2, 4)
     for word in ("stable", "totalOrder", "-0.0", "NaN", "checked in this order", "true count", "torch"):
@@ -46,25 +35,11 @@ def test_header_declares_the_two_functions_and_the_flags():
 
 
 def test_the_other_headers_declare_none_of_it():
-    for h in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if h != "msd_compact_hip.h":
-            assert "msd_compact" not in open(os.path.join(ROOT, "include", h)).read(), h
+    A.check_no_other_header_has("msd_compact_hip.h", "msd_compact")
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.COMPACT_EXPORTS) == sorted(SIGNATURES)
-    others = [_lib.EXPORTS, _lib.RCCL_EXPORTS] + [getattr(_lib, t) for t in dir(_lib) if t.endswith("_EXPORTS") and t not in ("COMPACT_EXPORTS", "RCCL_EXPORTS")]
-    assert len(others) >= 11
-    for table in others:
-        assert not any(f in _lib.COMPACT_EXPORTS for f in table)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        assert list(getattr(L, f).argtypes) == list(_lib.COMPACT_EXPORTS[f]), f
-        assert len(_lib.COMPACT_EXPORTS[f]) == len(SIGNATURES[f]), f
-    assert any(d.endswith("msd_compact_hip.h") for d in _build.DEPS)
-    assert "msd_compact.hpp" in _build.DEPS
+    A.check_exports("COMPACT_EXPORTS", SIGNATURES, "msd_compact_hip.h", "msd_compact.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -86,25 +61,12 @@ def test_limits_are_those_of_run_encode():
         assert L.msd_compact_limits(kb, C.byref(tile), C.byref(scan_tile)) == 0
         assert L.msd_run_encode_limits(kb, C.byref(t2), C.byref(s2)) == 0
         assert (tile.value, scan_tile.value) == (t2.value, s2.value) and tile.value >= 64 and scan_tile.value >= 64
-    a, b = C.c_uint64(77), C.c_uint64(78)
-    for kb in (0, 2, 16, -4, 5):
-        assert L.msd_compact_limits(kb, C.byref(a), C.byref(b)) == -1 and (a.value, b.value) == (77, 78)
-    for kb in (4, 8):
-        assert L.msd_compact_limits(kb, None, C.byref(b)) == -1 and b.value == 78
-        assert L.msd_compact_limits(kb, C.byref(a), None) == -1 and a.value == 77
-        assert L.msd_compact_limits(kb, None, None) == -1
-
-
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
+    A.check_limits_refusals(L.msd_compact_limits, 2, bad_widths=(0, 2, 16, -4, 5))
 
 
 def test_limits_wrapper_and_flags():
     from inplacemsdradixsort_amd import MsdContext, MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     for kb in (4, 8):
         assert ctx.compact_limits(kb) == ctx.run_encode_limits(kb)
@@ -117,7 +79,7 @@ def test_limits_wrapper_and_flags():
 def test_compact_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()                                                    # (no _L, no _h: touching the library would raise AttributeError)
+    ctx = A.bare_ctx()                                             # (no _L, no _h: touching the library would raise AttributeError)
     m8 = torch.ones(8, dtype=torch.bool)
     for kdt in (torch.float32, torch.int32, torch.float64, torch.int64):
         k = torch.zeros(8, dtype=kdt)
@@ -192,7 +154,7 @@ def test_compact_refuses_before_the_library_is_touched():
 def test_bounds_become_bit_patterns_of_the_keys_dtype():
     import torch
     from inplacemsdradixsort_amd import MsdContext, MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     f32, f64, i32, i64 = (torch.zeros(1, dtype=d) for d in (torch.float32, torch.float64, torch.int32, torch.int64))
     K = MsdContext

@@ -49,6 +49,7 @@ import torch
 import guardband
 from guardband import Arena
 from oracle import oracle as O
+from sort_rows_expect import np_encode
 
 pytestmark = pytest.mark.gpu
 
@@ -1005,17 +1006,6 @@ def test_generators_mt19937_64(ctx, n):
 
 U32, I32, F32, U64, I64, F64 = range(6)
 KT_BYTES = {U32: 4, I32: 4, F32: 4, U64: 8, I64: 8, F64: 8}
-
-
-def np_encode(bits, kt):
-    """the order-preserving unsigned code of a key's bit pattern (unsigned: itself; signed: sign bit flipped; float:
-    totalOrder) -- the expectation of tests/test_gpu_topk_typed.py"""
-    top = bits.dtype.type(1 << (bits.itemsize * 8 - 1))
-    if kt % 3 == 0:
-        return bits.copy()
-    if kt % 3 == 1:
-        return bits + top
-    return np.where(bits & top, ~bits, bits | top)
 
 
 def topk_input(kt, kind, n, rng):

@@ -17,12 +17,11 @@ import compact_expect as X
 import guardband
 import runs_expect as R
 import sort_rows_expect as E
+from guardband import Buf
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (4, 8)
-UT = {1: np.uint8, 4: np.uint32, 8: np.uint64}
-UKT = {4: E.U32, 8: E.U64}
+WIDTHS, UKT = E.WIDTHS, E.UKT
 KEY_TYPES = [E.U32, E.I32, E.F32, E.U64, E.I64, E.F64]
 PAGE = guardband.PAGE
 
@@ -31,40 +30,6 @@ def limits(ctx, es):
     tile, scan_tile = C.c_uint64(), C.c_uint64()
     assert ctx._L.msd_compact_limits(es, C.byref(tile), C.byref(scan_tile)) == 0
     return int(tile.value), int(scan_tile.value)
-
-
-def int_dtype(es):
-    import torch
-    return {1: torch.uint8, 4: torch.int32, 8: torch.int64}[es]
-
-
-class Buf:
-    """`count` elements of es bytes that start `off` elements into the payload of an Arena whose payload starts `lead_bytes`
-    behind a page boundary; the whole payload holds a known pattern (or, behind `off`, the array `a`)."""
-
-    def __init__(self, es, count, off=0, lead_bytes=0, a=None):
-        self.es, self.count, self.off = es, count, off
-        self.arena = guardband.Arena(int_dtype(es), count + off, lead_bytes=lead_bytes)
-        self.fill = guardband.pattern(12345, count + off, es).numpy().view(UT[es]).copy()
-        if a is not None:
-            self.fill[off:] = a
-        self.arena.fill(self.fill)
-        self.ptr = self.arena.ptr + off * es
-
-    def host(self):
-        """the `count` elements; what lies in front of them in the payload must be what it was"""
-        h = self.arena.host(UT[self.es])
-        assert (h[:self.off] == self.fill[:self.off]).all(), "payload in front of the buffer changed"
-        return h[self.off:]
-
-    def untouched_from(self, k):
-        return (self.host()[k:] == self.fill[self.off + k:]).all()
-
-    def unchanged(self):
-        return self.untouched_from(0)
-
-    def check(self, what):
-        self.arena.check(what)
 
 
 def at_page_start(es, n):
@@ -116,7 +81,7 @@ def run_case(ctx, n, keys=None, kt=0, mask=None, lo=None, hi=None, invert=False,
         if b is None:
             continue
         h = b.host()
-        e = e.view(UT[e.itemsize])
+        e = e.view(E.UW[e.itemsize])
         assert (h[:w] == e).all(), (what, name + " differ", int(np.argmax(h[:w] != e)))
         assert b.untouched_from(w), (what, name + " written beyond what the call may write")
         out[i] = h[:w]

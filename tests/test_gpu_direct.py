@@ -9,20 +9,9 @@ The reference has no counterpart; the oracle is numpy's sort of the same keys (b
 import numpy as np
 import pytest
 
-from oracle import oracle as O
+from gpu_support import dev_bits as dev, host_bits as host, shapes
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int64)).cuda()
-
-
-def host(t):
-    a = t.cpu().numpy()
-    return a.view(np.uint32) if a.dtype == np.int32 else a.view(np.uint64)
 
 
 @pytest.fixture()
@@ -34,34 +23,6 @@ def dctx(ctx):
     ctx.set_option("direct_min", 1 << 26)
     ctx.set_option("direct_min_parent", 1 << 17)
     ctx.set_option("direct_mode", 1)
-
-
-def shapes(rng, n, kind, bits):
-    full = (1 << bits) - 1
-    dt = np.uint32 if bits == 32 else np.uint64
-    if kind == "uniform":
-        k = rng.integers(0, full, n, dtype=np.uint64, endpoint=True)
-    elif kind == "sorted":
-        k = np.sort(rng.integers(0, full, n, dtype=np.uint64, endpoint=True))
-    elif kind == "reversed":
-        k = np.sort(rng.integers(0, full, n, dtype=np.uint64, endpoint=True))[::-1].copy()
-    elif kind == "stride":      # top digit cycles with the position: every stripe sees one bucket at a time
-        k = (np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15 & full)) & np.uint64(full)
-    elif kind == "runs":        # long runs of one top digit each (a piece is read long before it can be written)
-        top = (np.arange(n, dtype=np.uint64) // np.uint64(4096)) % np.uint64(256)
-        k = (top << np.uint64(bits - 8)) | rng.integers(0, (1 << (bits - 8)) - 1, n, dtype=np.uint64)
-    elif kind == "lowbits":     # uniform top digit, everything below it constant
-        k = rng.integers(0, 255, n, dtype=np.uint64, endpoint=True) << np.uint64(bits - 8)
-    elif kind == "zipf":
-        k = O.gen_zipf_u32(n, seed=int(rng.integers(1, 1 << 30))).astype(np.uint64)
-        if bits == 64:
-            k = k << np.uint64(32) | k
-    elif kind == "heavy":       # one value takes a third of the input
-        k = rng.integers(0, full, n, dtype=np.uint64, endpoint=True)
-        k[rng.random(n) < 0.33] = np.uint64(0x5A5A5A5A5A5A5A5A & full)
-    else:
-        raise ValueError(kind)
-    return (k & np.uint64(full)).astype(dt)
 
 
 KINDS_EVEN = ["uniform", "sorted", "reversed", "stride", "runs", "lowbits"]

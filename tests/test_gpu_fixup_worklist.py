@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import guardband
-from test_gpu_direct import shapes
+from gpu_support import shapes
 
 pytestmark = pytest.mark.gpu
 

@@ -5,19 +5,9 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from gpu_support import dev_bits as dev, host_bits as host
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int64)).cuda()
-
-
-def host(t):
-    a = t.cpu().numpy()
-    return a.view(np.uint32) if a.dtype == np.int32 else a.view(np.uint64)
 
 
 def random_keys(rng, n, bits):

@@ -7,19 +7,22 @@ with a known pattern: a case checks the count word, the min(count, cap) results,
 are what was uploaded, that the payload in front of an offset buffer is what it was, that no output word beyond min(count,
 cap) changed and that an output that was not given did not change.  The shapes are the smallest at which a kernel can go
 wrong, taken from msd_join_limits (T = the tile of the groups call, P = the pair ranks of one workgroup of the expansion).
-The buffers, the input kinds and the special values come from test_gpu_set_sorted.py and test_gpu_merge_sorted.py.  Unsorted
-inputs and made-up groups: test_gpu_untrusted_order.py.  The Python wrappers have a test of their own at the end."""
+The buffers are guardband.Buf, the special values those of sort_rows_expect.py and the input kinds come from
+test_gpu_set_sorted.py.  Unsorted inputs and made-up groups: test_gpu_untrusted_order.py.  The Python wrappers have a test of their own at the end."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import gpu_support as D
 import join_expect as J
 import search_expect as S
 import set_expect as X
 import sort_rows_expect as E
-from test_gpu_merge_sorted import TAIL, UKT, UT, WIDTHS, _bits, _to_gpu, special_bits, uniform
-from test_gpu_set_sorted import KINDS, Buf, inputs
+from gpu_support import TAIL
+from guardband import Buf
+from sort_rows_expect import UKT, WIDTHS, special_bits, uniform
+from test_gpu_set_sorted import KINDS, inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +57,7 @@ class Groups:
         self.a, self.b, self.kt = a, b, kt
         self.kb, self.n, self.m = a.itemsize, a.size, b.size
         self.bound = min(self.n, self.m)
-        self.da, self.db = Buf(self.kb, self.n, off, a), Buf(self.kb, self.m, off, b)
+        self.da, self.db = Buf(self.kb, self.n, off, a=a), Buf(self.kb, self.m, off, a=b)
         self.outs = [Buf(self.kb, self.bound + TAIL, off)] + [Buf(8, self.bound + TAIL, off) for _ in range(4)]
         self.dnum = Buf(8, 1, off)
         self.want = J.groups(a, b, kt)
@@ -107,8 +110,8 @@ class Pairs:
         G = four[0].size
         self.stated, self.gcap = G if stated is None else stated, G if gcap is None else gcap
         pad = np.full(max(self.gcap - G, 0), JUNK, np.uint64)
-        self.dng = Buf(8, 1, off, np.array([self.stated], np.uint64))
-        self.dg = [Buf(8, x.size + pad.size, off, np.r_[x, pad]) for x in four]
+        self.dng = Buf(8, 1, off, a=np.array([self.stated], np.uint64))
+        self.dg = [Buf(8, x.size + pad.size, off, a=np.r_[x, pad]) for x in four]
         used = min(self.stated, self.gcap, G)
         self.g = (None,) + tuple(x[:used] for x in four)
         self.total = J.total(self.g)
@@ -116,8 +119,8 @@ class Pairs:
         rng = np.random.default_rng(n + 3 * m)
         self.pa = rng.permutation(n).astype(np.uint64) if pos else None
         self.pb = rng.permutation(m).astype(np.uint64) if pos else None
-        self.dpa = Buf(8, n, off, self.pa) if pos else None
-        self.dpb = Buf(8, m, off, self.pb) if pos else None
+        self.dpa = Buf(8, n, off, a=self.pa) if pos else None
+        self.dpb = Buf(8, m, off, a=self.pb) if pos else None
         self.oa, self.ob = Buf(8, room + TAIL, off), Buf(8, room + TAIL, off)
         self.dnum = Buf(8, 1, off)
         self.what = (what, G, self.stated, self.gcap, n, m, off, pos)
@@ -248,7 +251,7 @@ def _straddling(T, ut):
 @pytest.mark.parametrize("kb", WIDTHS)
 def test_runs_that_straddle_tiles(ctx, kb):
     T, _, P = limits(ctx, kb)
-    for what, (a, b) in _straddling(T, UT[kb]).items():
+    for what, (a, b) in _straddling(T, E.UW[kb]).items():
         gr = Groups(a, b, UKT[kb], what=what)
         model = J.tiles(a, b, T)                                     # the model of the kernel agrees with the expectation on these
         assert all((x == y).all() for x, y in zip(model, gr.want)), what
@@ -506,7 +509,7 @@ def test_join_of_unsorted_tensors(ctx):
         a, b = torch.from_numpy(av).cuda(), torch.from_numpy(bv).cuda()
         ia, ib = ctx.join(a, b)
         assert ia.dtype == ib.dtype == torch.int64 and ia.shape == ib.shape and ia.dim() == 1
-        abits, bbits = av.view(UT[kb]), bv.view(UT[kb])
+        abits, bbits = av.view(E.UW[kb]), bv.view(E.UW[kb])
         wi, wj = np.nonzero(abits[:, None] == bbits[None, :])       # the brute-force join on the bits
         got = np.stack([ia.cpu().numpy(), ib.cpu().numpy()], 1)
         assert got.shape[0] == wi.size > 10000
@@ -517,12 +520,12 @@ def test_join_of_unsorted_tensors(ctx):
         # the wrappers of the two calls on the sorted copies
         sa, sb = np.sort(av), np.sort(bv)
         kt = {torch.int32: E.I32, torch.float32: E.F32, torch.int64: E.I64}[dt]
-        want = J.groups(sa.view(UT[kb]), sb.view(UT[kb]), kt)
-        ga, gb = _to_gpu(sa.view(UT[kb]), dt), _to_gpu(sb.view(UT[kb]), dt)
+        want = J.groups(sa.view(E.UW[kb]), sb.view(E.UW[kb]), kt)
+        ga, gb = D.to_gpu(sa.view(E.UW[kb]), dt), D.to_gpu(sb.view(E.UW[kb]), dt)
         groups = ctx.join_groups(ga, gb)
         G = int(groups[0].item())
         assert G == want[0].size and groups[1].dtype == dt and all(t.dtype == torch.int64 and t.shape == (4000,) for t in groups[2:])
-        assert (_bits(groups[1][:G]) == want[0]).all() and all((t[:G].cpu().numpy() == w.astype(np.int64)).all() for t, w in zip(groups[2:], want[1:]))
+        assert (D.bits(groups[1][:G]) == want[0]).all() and all((t[:G].cpu().numpy() == w.astype(np.int64)).all() for t, w in zip(groups[2:], want[1:]))
         assert ctx.join_groups(ga[:0], gb)[0].item() == 0 and ctx.join_groups(ga, gb, keys=False)[1] is None
         num, _, _ = ctx.join_pairs(groups, 5000, 4000, 0)
         assert int(num.item()) == wi.size

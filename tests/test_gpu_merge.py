@@ -6,16 +6,11 @@ import sys
 
 import numpy as np
 import pytest
+from gpu_support import dev_bits as dev
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int64)).cuda()
 
 
 def host(t, dt):

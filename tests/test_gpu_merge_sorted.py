@@ -14,17 +14,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import guardband
+import gpu_support as D
 import merge_expect as M
 import search_expect as S
 import sort_rows_expect as E
+from guardband import Buf
+from gpu_support import TAIL
+from sort_rows_expect import UKT, WIDTHS, special_bits, top, uniform
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (4, 8)
-UT = {4: np.uint32, 8: np.uint64}
-UKT = {4: E.U32, 8: E.U64}          # the unsigned key type of a width: code == bits
-TAIL = 64                           # elements of every output buffer behind the n + m that are written
 VARIANTS = ((False, False), (True, False), (False, True), (True, True))   # (values, origin)
 
 
@@ -32,46 +31,6 @@ def limits(ctx, kb):
     tile = C.c_uint64()
     assert ctx._L.msd_merge_sorted_limits(kb, C.byref(tile)) == 0
     return int(tile.value)
-
-
-def int_dtype(es):
-    import torch
-    return torch.int32 if es == 4 else torch.int64
-
-
-class Buf:
-    """`count` elements of es bytes that start `off` elements into the payload of an Arena; the whole payload holds a known
-    pattern (or, behind `off`, the array `a`)."""
-
-    def __init__(self, es, count, off=0, a=None):
-        self.es, self.count, self.off = es, count, off
-        self.arena = guardband.Arena(int_dtype(es), count + off)
-        self.fill = guardband.pattern(4321, count + off, es).numpy().view(UT[es]).copy()
-        if a is not None:
-            self.fill[off:] = a
-        self.arena.fill(self.fill)
-        self.ptr = self.arena.ptr + off * es
-
-    def reset(self):
-        self.arena.fill(self.fill)
-
-    def host(self):
-        """the `count` elements; what lies in front of them in the payload must be what it was"""
-        h = self.arena.host(UT[self.es])
-        assert (h[:self.off] == self.fill[:self.off]).all(), "payload in front of the buffer changed"
-        return h[self.off:]
-
-    def unchanged(self):
-        return (self.host() == self.fill[self.off:]).all()
-
-    def written(self, count):
-        """the first `count` elements; the rest of the buffer must be what it was"""
-        h = self.host()
-        assert (h[count:] == self.fill[self.off + count:]).all(), "an output element beyond n + m changed"
-        return h[:count]
-
-    def check(self, what):
-        self.arena.check(what)
 
 
 def raw_call(ctx, a, n, b, m, kt, va, vb, out, ov, oo):
@@ -92,8 +51,8 @@ class Case:
         self.kb, self.n, self.m = a.itemsize, a.size, b.size
         self.total = self.n + self.m
         self.va, self.vb = values_for(self.n, 11), values_for(self.m, 12)
-        self.da, self.db = Buf(self.kb, self.n, offs[0], a), Buf(self.kb, self.m, offs[1], b)
-        self.dva, self.dvb = Buf(8, self.n, offs[2], self.va), Buf(8, self.m, offs[3], self.vb)
+        self.da, self.db = Buf(self.kb, self.n, offs[0], a=a), Buf(self.kb, self.m, offs[1], a=b)
+        self.dva, self.dvb = Buf(8, self.n, offs[2], a=self.va), Buf(8, self.m, offs[3], a=self.vb)
         self.dout = Buf(self.kb, self.total + TAIL, offs[4])
         self.dov, self.doo = Buf(8, self.total + TAIL, offs[5]), Buf(8, self.total + TAIL, offs[6])
         self.want, self.origin = M.expected(a, b, kt)
@@ -144,21 +103,13 @@ class Case:
 
 # ---- inputs, as codes of an unsigned type (code == bits)
 
-def top(kb):
-    return (1 << (8 * kb)) - 1
-
-
-def uniform(rng, count, kb, lo=0, hi=None):
-    return rng.integers(lo, top(kb) if hi is None else hi, count, dtype=UT[kb], endpoint=True)
-
-
 KINDS = ["distinct", "five", "all_equal", "a_below", "a_above", "a_equal_in_distinct_b"]
 
 
 def inputs(kind, n, m, kb, seed):
     """A and B, both ascending"""
     rng = np.random.default_rng(E.seed_of(n, m, kb, seed, 8))
-    ut = UT[kb]
+    ut = E.UW[kb]
     half = top(kb) >> 1
     five = np.array([0, 1 << 9, 77777, half, top(kb)], ut)
     if kind == "distinct":                                          # distinct keys, interleaved at random
@@ -228,19 +179,6 @@ def test_a_larger_case(ctx, kb):
 
 
 # ---- all six key types
-
-def special_bits(kt):
-    ut = E.UT[kt]
-    W = 8 * np.dtype(ut).itemsize
-    if kt % 3 != 2:                                                 # integers: min, -1, 0, 1, max (as signed; as unsigned the same bits matter)
-        return np.array([1 << (W - 1), (1 << W) - 1, 0, 1, (1 << (W - 1)) - 1], ut)
-    if W == 32:
-        sign, inf, q, s, den = 0x80000000, 0x7F800000, 0x7FC00000, 0x7F800001, 0x007FFFFF
-    else:
-        sign, inf, q, s, den = 1 << 63, 0x7FF << 52, 0x7FF8 << 48, (0x7FF << 52) | 1, (1 << 52) - 1
-    pos = [0, 1, den, inf, q, q | 0x1234, s, s | 0x4320]           # zero, denormals, inf, quiet and signalling NaNs with two payloads each
-    return np.array(pos + [p | sign for p in pos], ut)
-
 
 @pytest.mark.parametrize("kt", M.KEY_TYPES, ids=[E.NAMES[k] for k in M.KEY_TYPES])
 def test_every_key_type_with_special_values(ctx, kt):
@@ -467,27 +405,9 @@ def test_the_phase_is_named(ctx):
 
 # ---- the Python wrapper
 
-def _dtypes():
-    import torch
-    dts = [(torch.int32, E.I32), (torch.float32, E.F32), (torch.int64, E.I64), (torch.float64, E.F64)]
-    for name, kt in (("uint32", E.U32), ("uint64", E.U64)):        # (not in every torch)
-        if hasattr(torch, name):
-            dts.append((getattr(torch, name), kt))
-    return dts
-
-
-def _to_gpu(bits, dt):
-    import torch
-    return torch.from_numpy(bits.view(np.int32 if bits.itemsize == 4 else np.int64)).cuda().view(dt)
-
-
-def _bits(t):
-    return t.view(int_dtype(t.element_size())).cpu().numpy().view(UT[t.element_size()])
-
-
 def test_merge_sorted_wrapper_for_every_dtype(ctx):
     import torch
-    dts = _dtypes()
+    dts = D.dtypes()
     assert len(dts) == 6
     for dt, kt in dts:
         kb = np.dtype(E.UT[kt]).itemsize
@@ -498,24 +418,24 @@ def test_merge_sorted_wrapper_for_every_dtype(ctx):
         n, m = T + 7, 2 * T - 3
         a_bits, b_bits = [S.sort_by_code(np.r_[sp, uniform(rng, c - sp.size, kb, 0, 1 << 12), ], kt) for c in (n, m)]
         want, want_origin = M.expected(a_bits, b_bits, kt)
-        a, b = _to_gpu(a_bits, dt), _to_gpu(b_bits, dt)
+        a, b = D.to_gpu(a_bits, dt), D.to_gpu(b_bits, dt)
         va, vb = torch.arange(n, dtype=torch.float64, device="cuda"), -torch.arange(m, dtype=torch.float64, device="cuda")
-        before = [x.view(int_dtype(x.element_size())).clone() for x in (a, b, va, vb)]
+        before = [x.view(D.int_dtype(x.element_size())).clone() for x in (a, b, va, vb)]
         merged = ctx.merge_sorted(a, b)
-        assert merged.dtype == dt and merged.shape == (n + m,) and (_bits(merged) == want).all()
+        assert merged.dtype == dt and merged.shape == (n + m,) and (D.bits(merged) == want).all()
         merged, origin = ctx.merge_sorted(a, b, origin=True)
-        assert origin.dtype == torch.int64 and (_bits(merged) == want).all() and (origin.cpu().numpy() == want_origin.astype(np.int64)).all()
+        assert origin.dtype == torch.int64 and (D.bits(merged) == want).all() and (origin.cpu().numpy() == want_origin.astype(np.int64)).all()
         merged, vals = ctx.merge_sorted(a, b, values_a=va, values_b=vb)
-        assert vals.dtype == torch.float64 and torch.equal(vals, torch.cat([va, vb])[origin]) and (_bits(merged) == want).all()
+        assert vals.dtype == torch.float64 and torch.equal(vals, torch.cat([va, vb])[origin]) and (D.bits(merged) == want).all()
         out = torch.empty(n + m, dtype=dt, device="cuda")
         ov, oo = torch.empty(n + m, dtype=torch.float64, device="cuda"), torch.empty(n + m, dtype=torch.int64, device="cuda")
         r = ctx.merge_sorted(a, b, values_a=va, values_b=vb, out=out, out_values=ov, out_origin=oo)
         assert r[0] is out and r[1] is ov and r[2] is oo and len(r) == 3
-        assert (_bits(out) == want).all() and torch.equal(ov, vals) and torch.equal(oo, origin)
+        assert (D.bits(out) == want).all() and torch.equal(ov, vals) and torch.equal(oo, origin)
         for x, y in zip((a, b, va, vb), before):                    # the inputs are what they were
-            assert torch.equal(x.view(int_dtype(x.element_size())), y)
+            assert torch.equal(x.view(D.int_dtype(x.element_size())), y)
         # empty sides
-        assert (_bits(ctx.merge_sorted(a[:0], b)) == b_bits).all() and (_bits(ctx.merge_sorted(a, b[:0])) == a_bits).all()
+        assert (D.bits(ctx.merge_sorted(a[:0], b)) == b_bits).all() and (D.bits(ctx.merge_sorted(a, b[:0])) == a_bits).all()
         e, eo = ctx.merge_sorted(a[:0], b[:0], origin=True)
         assert e.shape == (0,) and eo.shape == (0,) and e.dtype == dt
 

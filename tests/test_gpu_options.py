@@ -10,6 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle as O  # noqa: E402
+from gpu_support import dev_bits as dev, host_bits as host
 
 pytestmark = pytest.mark.gpu
 
@@ -20,17 +21,6 @@ def ctx():
     c = MsdContext(0)
     yield c
     c.close()
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int64)).cuda()
-
-
-def host(t):
-    a = t.cpu().numpy()
-    return a.view(np.uint32) if a.dtype == np.int32 else a.view(np.uint64)
 
 
 @pytest.mark.parametrize("count16", [0, 1, 2])

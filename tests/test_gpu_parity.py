@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from gpu_support import host_bits as host
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -22,11 +23,6 @@ def dev(a):
         return torch.from_numpy(a.view(np.int32)).cuda()
     assert a.dtype == np.uint64
     return torch.from_numpy(a.view(np.int64)).cuda()
-
-
-def host(t):
-    a = t.cpu().numpy()
-    return a.view(np.uint32) if a.dtype == np.int32 else a.view(np.uint64)
 
 
 def make_u32(n, kind, seed=1):

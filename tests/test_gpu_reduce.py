@@ -15,14 +15,16 @@ import math
 import numpy as np
 import pytest
 
+import gpu_support as D
 import guardband
 import reduce_expect as X
 import runs_expect as R
 import sort_rows_expect as E
+from guardband import Buf
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (4, 8)
+WIDTHS = E.WIDTHS
 OPS = ("sum", "min", "max")
 VT_IDS = [E.NAMES[v] for v in X.VAL_TYPES]
 
@@ -33,46 +35,12 @@ def limits(ctx, kb):
     return int(tile.value), int(scan_tile.value)
 
 
-def int_dtype(es):
-    import torch
-    return torch.int32 if es == 4 else torch.int64
-
-
 def vbytes(vt):
     return 4 if vt < E.U64 else 8
 
 
 def obytes(vt, op):
     return 8 if op == "sum" else vbytes(vt)
-
-
-class Buf:
-    """`count` elements of es bytes that start `off` elements into the payload of an Arena whose payload starts `lead_bytes`
-    behind a page boundary; the whole payload holds a known pattern (or, behind `off`, the array `a`)."""
-
-    def __init__(self, es, count, off=0, lead_bytes=0, a=None):
-        self.es, self.count, self.off = es, count, off
-        self.arena = guardband.Arena(int_dtype(es), count + off, lead_bytes=lead_bytes)
-        self.fill = guardband.pattern(12345, count + off, es).numpy().view(R.UT[es]).copy()
-        if a is not None:
-            self.fill[off:] = a
-        self.arena.fill(self.fill)
-        self.ptr = self.arena.ptr + off * es
-
-    def host(self):
-        """the `count` elements; what lies in front of them in the payload must be what it was"""
-        h = self.arena.host(R.UT[self.es])
-        assert (h[:self.off] == self.fill[:self.off]).all(), "payload in front of the buffer changed"
-        return h[self.off:]
-
-    def untouched_from(self, k):
-        return (self.host()[k:] == self.fill[self.off + k:]).all()
-
-    def unchanged(self):
-        return self.untouched_from(0)
-
-    def check(self, what):
-        self.arena.check(what)
 
 
 def raw_call(ctx, keys_ptr, kb, n, vals_ptr, vt, positions_ptr, op, cap, out_ptr, num_ptr):
@@ -656,7 +624,7 @@ def test_group_reduce(ctx, kt, n, op):
         red = np.full(codes.size, 0 if op == "max" else np.iinfo(vc.dtype).max, vc.dtype)
         (np.maximum if op == "max" else np.minimum).at(red, inv, vc)
         want = E.np_decode(red, vt)
-    host = lambda x: x.view(int_dtype(x.element_size())).cpu().numpy().view(R.UT[x.element_size()])
+    host = D.bits
     gk, ga = ctx.group_reduce(tk, tv, op=op)
     assert gk.dtype == tk.dtype and gk.numel() == codes.size and (host(gk) == want_keys).all()
     assert ga.numel() == codes.size and ga.dtype == (tv.dtype if op != "sum" else

@@ -13,53 +13,21 @@ import itertools
 import numpy as np
 import pytest
 
+import gpu_support as D
 import guardband
 import runs_expect as R
 import sort_rows_expect as E
+from guardband import Buf
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (4, 8)
+WIDTHS = E.WIDTHS
 
 
 def limits(ctx, es):
     tile, scan_tile = C.c_uint64(), C.c_uint64()
     assert ctx._L.msd_run_encode_limits(es, C.byref(tile), C.byref(scan_tile)) == 0
     return int(tile.value), int(scan_tile.value)
-
-
-def int_dtype(es):
-    import torch
-    return torch.int32 if es == 4 else torch.int64
-
-
-class Buf:
-    """`count` elements of es bytes that start `off` elements into the payload of an Arena whose payload starts `lead_bytes`
-    behind a page boundary; the whole payload holds a known pattern (or, behind `off`, the array `a`)."""
-
-    def __init__(self, es, count, off=0, lead_bytes=0, a=None):
-        self.es, self.count, self.off = es, count, off
-        self.arena = guardband.Arena(int_dtype(es), count + off, lead_bytes=lead_bytes)
-        self.fill = guardband.pattern(12345, count + off, es).numpy().view(R.UT[es]).copy()
-        if a is not None:
-            self.fill[off:] = a
-        self.arena.fill(self.fill)
-        self.ptr = self.arena.ptr + off * es
-
-    def host(self):
-        """the `count` elements; what lies in front of them in the payload must be what it was"""
-        h = self.arena.host(R.UT[self.es])
-        assert (h[:self.off] == self.fill[:self.off]).all(), "payload in front of the buffer changed"
-        return h[self.off:]
-
-    def untouched_from(self, k):
-        return (self.host()[k:] == self.fill[self.off + k:]).all()
-
-    def unchanged(self):
-        return self.untouched_from(0)
-
-    def check(self, what):
-        self.arena.check(what)
 
 
 def raw_call(ctx, data_ptr, es, n, cap, values_ptr, starts_ptr, positions_ptr, inverse_ptr, num_ptr):
@@ -391,7 +359,7 @@ def test_unique(ctx, kt, n, kind):
     t = t.view(dt)
     codes, inv, counts = np.unique(E.np_encode(bits, kt), return_inverse=True, return_counts=True)
     want = E.np_decode(codes, kt)
-    host = lambda x: x.view(int_dtype(es)).cpu().numpy().view(ut)
+    host = D.bits
     v = ctx.unique(t)
     assert v.dtype == dt and (host(v) == want).all() and host(v).size == want.size
     v, c = ctx.unique(t, return_counts=True)

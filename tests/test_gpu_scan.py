@@ -8,24 +8,26 @@ every minimum and maximum are compared exactly -- min / max BITWISE --, float su
 float64 cumsum within the bound that holds for every order of summation.  The calls go through the C ABI on integer tensors
 that carry the bit patterns, with EVERY buffer -- keys, values, d_out -- inside a guardband.Arena whose payload is
 pre-filled with a known pattern and is larger than the buffer: a case checks the n results, that the payload in front of
-and behind them is what it was, that no guard was touched and that the inputs are what was uploaded.  The buffers, the key
-patterns and the value columns are those of tests/test_gpu_reduce.py.  The Python wrapper has tests of its own at the end."""
+and behind them is what it was, that no guard was touched and that the inputs are what was uploaded.  The buffers are
+guardband.Buf; the key patterns and the value columns are those of tests/test_gpu_reduce.py.  The Python wrapper has tests of its own at the end."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+import gpu_support as D
 import guardband
 import reduce_expect as X
 import runs_expect as R
 import scan_expect as S
 import sort_rows_expect as E
-import test_gpu_reduce as G                                         # (Buf, Inputs, make_keys, make_values, specials: helpers, no fixtures)
+import test_gpu_reduce as G                                         # (Inputs, make_keys, make_values, specials: the family's helpers, no fixtures)
+from guardband import Buf
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (4, 8)
+WIDTHS = E.WIDTHS
 OPS = ("sum", "min", "max", "count")
 VT_IDS = [E.NAMES[v] for v in X.VAL_TYPES]
 BIG_PATTERNS = ["equal", "distinct", "geo5000"] + G.CARRY_PATTERNS
@@ -68,8 +70,8 @@ def scan_case(ctx, inp, vbits, vt, op, flags=0, val_off=0, val_lead=0, out_off=0
     count = op == "count"
     ob = obytes(vt, op)
     what = (what, inp.where, "count" if count else E.NAMES[vt], op, flags, val_off, val_lead, out_off, out_lead)
-    dval = None if count else G.Buf(G.vbytes(vt), n, val_off, val_lead, vbits)
-    dout = G.Buf(ob, n + EXTRA, out_off, out_lead)
+    dval = None if count else Buf(G.vbytes(vt), n, val_off, val_lead, vbits)
+    dout = Buf(ob, n + EXTRA, out_off, out_lead)
     ctx._ok(raw_call(ctx, inp.dkeys.ptr, inp.kb, n, dval and dval.ptr, JUNK_VT if count else vt, inp.dpos and inp.dpos.ptr, S.OPS[op], flags, dout.ptr))
     got = dout.host()[:n]
     if exact:
@@ -114,7 +116,7 @@ def test_the_geometry_cases_are_what_the_list_says():
 
 def refused_case(ctx, inp, vt, op, flags, message):
     """the call is refused with `message`, and neither d_out nor an input is touched"""
-    dout = G.Buf(obytes(vt, op), inp.n + EXTRA)
+    dout = Buf(obytes(vt, op), inp.n + EXTRA)
     rc = raw_call(ctx, inp.dkeys.ptr, inp.kb, inp.n, 0, JUNK_VT if op == "count" else vt, inp.dpos and inp.dpos.ptr, S.OPS[op], flags, dout.ptr)
     err = ctx._L.msd_last_error(ctx._h).decode()
     assert rc == -1 and message in err, (rc, err)
@@ -223,7 +225,7 @@ def test_float_sums_of_infinities_and_nans(ctx, kb, vt):
 def test_relations(ctx, kb):
     import torch
     tile, scan_tile = limits(ctx, kb)
-    host = lambda x: x.view(G.int_dtype(x.element_size())).cpu().numpy().view(R.UT[x.element_size()])
+    host = D.bits
     for n, pattern in ((3 * tile - 1, "geo40"), ((scan_tile + 1) * tile + 5, "geo5000"), (2 * tile + 1, "tile_runs_half")):
         keys = G.make_keys(pattern, n, kb, tile, seed=12)
         t = torch.from_numpy(keys.view(R.IT[kb])).cuda()
@@ -345,8 +347,8 @@ def test_refusals_in_order_touch_nothing(ctx):
             vb, ob = G.vbytes(vt), 8 if op in (0, 3) else G.vbytes(vt)
             keys = R.make("geo1.5", n, kb, 64, seed=2)
             vbits = G.make_values(vt, OPS[op], keys, 3) if op != 3 else G.make_values(vt, "sum", keys, 3)
-            din, dval, dout = G.Buf(kb, n, a=keys), G.Buf(vb, n, a=vbits), G.Buf(ob, n + EXTRA)
-            dpos = G.Buf(8, n, a=np.arange(n, dtype=np.uint64))
+            din, dval, dout = Buf(kb, n, a=keys), Buf(vb, n, a=vbits), Buf(ob, n + EXTRA)
+            dpos = Buf(8, n, a=np.arange(n, dtype=np.uint64))
             bufs = (din, dval, dout, dpos)
             count = op == 3
             good = dict(keys=din.ptr, kb=kb, n=n, vals=dval.ptr, vt=vt, positions=0, op=op, flags=(kb // 4 + op) % 2, out=dout.ptr)

@@ -13,15 +13,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import guardband
 import search_expect as S
 import sort_rows_expect as E
+from guardband import Buf
+from sort_rows_expect import UKT, WIDTHS, special_bits, top, uniform
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = (4, 8)
-UT = {4: np.uint32, 8: np.uint64}
-UKT = {4: E.U32, 8: E.U64}          # the unsigned key type of a width: code == bits
 DIRECT, MERGE = 1, 2                # values of the option search_mode
 
 
@@ -29,40 +27,6 @@ def limits(ctx, kb):
     tile, direct = C.c_uint64(), C.c_uint64()
     assert ctx._L.msd_search_sorted_limits(kb, C.byref(tile), C.byref(direct)) == 0
     return int(tile.value), int(direct.value)
-
-
-def int_dtype(es):
-    import torch
-    return torch.int32 if es == 4 else torch.int64
-
-
-class Buf:
-    """`count` elements of es bytes that start `off` elements into the payload of an Arena; the whole payload holds a known
-    pattern (or, behind `off`, the array `a`)."""
-
-    def __init__(self, es, count, off=0, a=None):
-        self.es, self.count, self.off = es, count, off
-        self.arena = guardband.Arena(int_dtype(es), count + off)
-        self.fill = guardband.pattern(4321, count + off, es).numpy().view(UT[es]).copy()
-        if a is not None:
-            self.fill[off:] = a
-        self.arena.fill(self.fill)
-        self.ptr = self.arena.ptr + off * es
-
-    def reset(self):
-        self.arena.fill(self.fill)
-
-    def host(self):
-        """the `count` elements; what lies in front of them in the payload must be what it was"""
-        h = self.arena.host(UT[self.es])
-        assert (h[:self.off] == self.fill[:self.off]).all(), "payload in front of the buffer changed"
-        return h[self.off:]
-
-    def unchanged(self):
-        return (self.host() == self.fill[self.off:]).all()
-
-    def check(self, what):
-        self.arena.check(what)
 
 
 def raw_call(ctx, sorted_ptr, kt, n, needles_ptr, m, needles_sorted, side, positions_ptr, out_ptr):
@@ -89,9 +53,9 @@ class Case:
     def __init__(self, keys, needles, kt, positions=None, offs=(0, 0, 0, 0), what=""):
         self.keys, self.needles, self.kt, self.positions = keys, needles, kt, positions
         self.kb, self.n, self.m = keys.itemsize, keys.size, needles.size
-        self.dkeys = Buf(self.kb, self.n, offs[0], keys)
-        self.dneedles = Buf(self.kb, self.m, offs[1], needles)
-        self.dpos = Buf(8, self.m, offs[2], positions.astype(np.uint64)) if positions is not None else None
+        self.dkeys = Buf(self.kb, self.n, offs[0], a=keys)
+        self.dneedles = Buf(self.kb, self.m, offs[1], a=needles)
+        self.dpos = Buf(8, self.m, offs[2], a=positions.astype(np.uint64)) if positions is not None else None
         self.dout = Buf(8, self.m, offs[3])
         self.want = {right: S.expected(keys, needles, kt, right) for right in (False, True)}
         self.what = (what, E.NAMES[kt], self.n, self.m, offs, positions is not None)
@@ -121,18 +85,10 @@ class Case:
 
 # ---- inputs, as codes of an unsigned type (code == bits)
 
-def top(kb):
-    return (1 << (8 * kb)) - 1
-
-
-def uniform(rng, count, kb, lo=0, hi=None):
-    return rng.integers(lo, top(kb) if hi is None else hi, count, dtype=UT[kb], endpoint=True)
-
-
 def direct_inputs(kind, n, m, kb, seed):
     """keys (ascending) and UNSORTED needles: below the first key, above the last one, code 0 and code all-ones among them"""
     rng = np.random.default_rng(E.seed_of(n, m, kb, seed))
-    ut = UT[kb]
+    ut = E.UW[kb]
     if kind == "distinct":
         keys = np.unique(uniform(rng, n + 64, kb, 1 << 8, top(kb) - (1 << 8)))[:n]
         assert keys.size == n
@@ -153,7 +109,7 @@ MERGE_KINDS = ["distinct", "five", "needles_equal", "above", "below", "keys_equa
 def merge_inputs(kind, n, m, kb, seed):
     """keys and needles, both ascending"""
     rng = np.random.default_rng(E.seed_of(n, m, kb, seed, 7))
-    ut = UT[kb]
+    ut = E.UW[kb]
     half = top(kb) >> 1
     five = np.array([0, 1 << 9, 77777, half, top(kb)], ut)
     if kind == "distinct":
@@ -273,19 +229,6 @@ def test_buffers_off_the_16_byte_grid(ctx, kb):
 
 # ---- all six key types
 
-def special_bits(kt):
-    ut = E.UT[kt]
-    W = 8 * np.dtype(ut).itemsize
-    if kt % 3 != 2:                                                 # integers: min, -1, 0, 1, max (as signed; as unsigned the same bits matter)
-        return np.array([1 << (W - 1), (1 << W) - 1, 0, 1, (1 << (W - 1)) - 1], ut)
-    if W == 32:
-        sign, inf, q, s, den = 0x80000000, 0x7F800000, 0x7FC00000, 0x7F800001, 0x007FFFFF
-    else:
-        sign, inf, q, s, den = 1 << 63, 0x7FF << 52, 0x7FF8 << 48, (0x7FF << 52) | 1, (1 << 52) - 1
-    pos = [0, 1, den, inf, q, q | 0x1234, s, s | 0x4320]           # zero, denormals, inf, quiet and signalling NaNs with two payloads each
-    return np.array(pos + [p | sign for p in pos], ut)
-
-
 @pytest.mark.parametrize("kt", S.KEY_TYPES, ids=[E.NAMES[k] for k in S.KEY_TYPES])
 def test_every_key_type_with_special_values(ctx, kt):
     ut = E.UT[kt]
@@ -376,13 +319,13 @@ def test_the_phase_is_named(ctx):
 def test_no_keys_and_no_needles(ctx):
     for kb in WIDTHS:
         for mode in (DIRECT, MERGE):
-            empty = Case(np.zeros(0, UT[kb]), np.sort(uniform(np.random.default_rng(1), 1000, kb)), UKT[kb], what="n = 0")
+            empty = Case(np.zeros(0, E.UW[kb]), np.sort(uniform(np.random.default_rng(1), 1000, kb)), UKT[kb], what="n = 0")
             for right in (False, True):
                 assert (empty.run(ctx, mode, right) == 0).all()
-            none = Case(np.arange(100, dtype=UT[kb]), np.zeros(0, UT[kb]), UKT[kb], what="m = 0")
+            none = Case(np.arange(100, dtype=E.UW[kb]), np.zeros(0, E.UW[kb]), UKT[kb], what="m = 0")
             none.run(ctx, mode, False)
         # null pointers where nothing is read or written
-        dn, dout = Buf(kb, 5, a=np.arange(5, dtype=UT[kb])), Buf(8, 5)
+        dn, dout = Buf(kb, 5, a=np.arange(5, dtype=E.UW[kb])), Buf(8, 5)
         ctx._ok(raw_call(ctx, 0, UKT[kb], 0, dn.ptr, 5, 1, 0, 0, dout.ptr))
         assert (dout.host() == 0).all()
         dout.reset()

@@ -5,6 +5,7 @@ import sys
 
 import numpy as np
 import pytest
+from gpu_support import dev_bits as dev
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -17,12 +18,6 @@ def ctx():
     c = MsdContext(0)
     yield c
     c.close()
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int64)).cuda()
 
 
 def host(t, dt):

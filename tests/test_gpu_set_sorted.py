@@ -8,17 +8,20 @@ own, d_num_out -- inside a guardband.Arena whose payload is pre-filled with a kn
 min(count, cap) results, that no guard was touched, that the inputs are what was uploaded, that the payload in front of an
 offset buffer is what it was, that no output word beyond min(count, cap) changed and that an output that was not given did
 not change.  The shapes are the smallest at which a kernel can go wrong, taken from msd_set_sorted_limits (T = the tile).
-The buffers, the six kinds of input of the merge and the special values come from test_gpu_merge_sorted.py.  Unsorted
-inputs: test_gpu_untrusted_order.py.  The Python wrappers have tests of their own at the end."""
+The buffers are guardband.Buf, the special values those of sort_rows_expect.py and the six kinds of input of the merge come
+from test_gpu_merge_sorted.py.  Unsorted inputs: test_gpu_untrusted_order.py.  The Python wrappers have tests of their own at the end."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import gpu_support as D
 import search_expect as S
 import set_expect as X
 import sort_rows_expect as E
-from test_gpu_merge_sorted import TAIL, UKT, UT, WIDTHS, Buf, _bits, _dtypes, _to_gpu, int_dtype, special_bits, top, uniform
+from gpu_support import TAIL
+from guardband import Buf
+from sort_rows_expect import UKT, WIDTHS, special_bits, top, uniform
 from test_gpu_merge_sorted import KINDS as MERGE_KINDS
 from test_gpu_merge_sorted import inputs as merge_inputs
 
@@ -42,7 +45,7 @@ def raw_call(ctx, op, a, n, b, m, kt, cap, out, oo, num):
 def distinct_pool(rng, count, kb):
     """`count` distinct values, ascending"""
     step = max(1, min(top(kb) // (count + 1), 1 << 20))
-    return np.cumsum(rng.integers(1, step, count, dtype=np.uint64, endpoint=True)).astype(UT[kb])
+    return np.cumsum(rng.integers(1, step, count, dtype=np.uint64, endpoint=True)).astype(E.UW[kb])
 
 
 def inputs(kind, n, m, kb, seed):
@@ -62,7 +65,7 @@ class Case:
     def __init__(self, a, b, kt, offs=(0,) * 4, what=""):
         self.a, self.b, self.kt = a, b, kt
         self.kb, self.n, self.m = a.itemsize, a.size, b.size
-        self.da, self.db = Buf(self.kb, self.n, offs[0], a), Buf(self.kb, self.m, offs[1], b)
+        self.da, self.db = Buf(self.kb, self.n, offs[0], a=a), Buf(self.kb, self.m, offs[1], a=b)
         self.dout, self.doo = Buf(self.kb, self.n + self.m + TAIL, offs[2]), Buf(8, self.n + self.m + TAIL, offs[3])
         self.dnum = Buf(8, 1)
         self._want = {}
@@ -438,7 +441,7 @@ def test_the_phase_is_named(ctx):
 @gpu
 def test_set_sorted_wrapper_for_every_dtype(ctx):
     import torch
-    dts = _dtypes()
+    dts = D.dtypes()
     assert len(dts) == 6
     for dt, kt in dts:
         kb = np.dtype(E.UT[kt]).itemsize
@@ -448,27 +451,27 @@ def test_set_sorted_wrapper_for_every_dtype(ctx):
         sp = special_bits(kt)
         n, m = T + 7, 2 * T - 3
         a_bits, b_bits = [S.sort_by_code(np.r_[sp, uniform(rng, c - sp.size, kb, 0, 1 << 12), ], kt) for c in (n, m)]
-        a, b = _to_gpu(a_bits, dt), _to_gpu(b_bits, dt)
-        before = [x.view(int_dtype(kb)).clone() for x in (a, b)]
+        a, b = D.to_gpu(a_bits, dt), D.to_gpu(b_bits, dt)
+        before = [x.view(D.int_dtype(kb)).clone() for x in (a, b)]
         for op in X.OPS:
             name = X.OP_NAMES[op]
             want, want_origin = X.expected(a_bits, b_bits, kt, op)
             bound = X.bound(op, n, m)
             num, out = ctx.set_sorted(a, b, name)
             assert num.dtype == torch.int64 and num.shape == (1,) and num.is_cuda and int(num.item()) == want.size
-            assert out.dtype == dt and out.shape == (bound,) and (_bits(out[:want.size]) == want).all()
+            assert out.dtype == dt and out.shape == (bound,) and (D.bits(out[:want.size]) == want).all()
             num, out, origin = ctx.set_sorted(a, b, name, origin=True)
             assert origin.dtype == torch.int64 and origin.shape == (bound,) and int(num.item()) == want.size
-            assert (_bits(out[:want.size]) == want).all() and (origin[:want.size].cpu().numpy() == want_origin.astype(np.int64)).all()
+            assert (D.bits(out[:want.size]) == want).all() and (origin[:want.size].cpu().numpy() == want_origin.astype(np.int64)).all()
             cap = want.size // 2
             o, oo = torch.zeros(cap, dtype=dt, device="cuda"), torch.zeros(cap, dtype=torch.int64, device="cuda")
             r = ctx.set_sorted(a, b, name, cap=cap, out=o, out_origin=oo)
             assert len(r) == 3 and r[1] is o and r[2] is oo and int(r[0].item()) == want.size
-            assert (_bits(o) == want[:cap]).all() and (oo.cpu().numpy() == want_origin[:cap].astype(np.int64)).all()
+            assert (D.bits(o) == want[:cap]).all() and (oo.cpu().numpy() == want_origin[:cap].astype(np.int64)).all()
             num, none = ctx.set_sorted(a, b, name, cap=0)
             assert none.shape == (0,) and int(num.item()) == want.size
         for x, y in zip((a, b), before):                            # the inputs are what they were
-            assert torch.equal(x.view(int_dtype(kb)), y)
+            assert torch.equal(x.view(D.int_dtype(kb)), y)
         # empty sides
         distinct = np.unique(E.np_encode(b_bits, kt)).size
         assert int(ctx.set_sorted(a[:0], b, "union")[0].item()) == distinct and int(ctx.set_sorted(a[:0], b, "intersection")[0].item()) == 0

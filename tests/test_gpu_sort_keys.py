@@ -1,8 +1,8 @@
 """GPU tests of the typed, two-way sort (msd_sort_keys, msd_sort_pairs_keys, msd_reverse of include/msd_sort_keys_hip.h;
 MsdContext.sort_typed / reverse).
 
-The expected order is defined HERE with numpy: bit patterns -> order-preserving unsigned codes (np_encode, the scheme of
-tests/test_gpu_topk_typed.py), np.sort, decode; descending is that array reversed.  Results are compared BITWISE through
+The expected order is defined HERE with numpy: bit patterns -> order-preserving unsigned codes (np_encode of
+tests/sort_rows_expect.py), np.sort, decode; descending is that array reversed.  Results are compared BITWISE through
 integer views; inputs without NaN and -0 are also compared with np.sort of the typed array.  The two counters are compared
 with the table of the header, computed here from the input's sign bits alone."""
 import ctypes as C
@@ -12,13 +12,13 @@ import numpy as np
 import pytest
 
 import guardband
-from test_gpu_topk_typed import VIEWS, dev, float_specials, make_float, make_int, np_decode, np_encode
+from gpu_support import dev
+from sort_rows_expect import NAMES, VIEWS, float_specials, make_float, make_int, np_decode, np_encode
 
 pytestmark = pytest.mark.gpu
 
 U32, I32, F32, U64, I64, F64 = range(6)
 KEY_TYPES = [U32, I32, F32, U64, I64, F64]
-NAMES = {U32: "u32", I32: "i32", F32: "f32", U64: "u64", I64: "i64", F64: "f64"}
 TILE = {4: 4092, 8: 2046}   # elements a workgroup of reverse_ranges_kernel takes from each end (RevCfg<E>::TILE)
 EINVAL = -1
 

@@ -16,6 +16,7 @@ import pytest
 
 import guardband
 import sort_rows_expect as E
+from gpu_support import int_dtype_of_key as int_dtype
 from sort_rows_expect import F32, F64, I32, I64, NAMES, U32, U64, UT, make_rows, seed_of
 
 pytestmark = pytest.mark.gpu
@@ -30,11 +31,6 @@ def limit(ctx, kt, with_idx):
     v = C.c_uint64()
     assert ctx._L.msd_sort_rows_limits(kt, int(with_idx), C.byref(v)) == 0
     return int(v.value)
-
-
-def int_dtype(kt):
-    import torch
-    return torch.int32 if UT[kt] == np.uint32 else torch.int64
 
 
 def np_int(kt):

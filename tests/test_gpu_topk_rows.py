@@ -3,11 +3,11 @@ for all six key types, with and without the positions of the keys, through the o
 over msd_topk_keys.
 
 The expected result is defined HERE, as in tests/test_gpu_topk_typed.py: the keys' bit patterns are turned into
-order-preserving unsigned codes with numpy expressions of this file, np.sort orders the codes along axis 1, and the
-inverse map gives the sorted bit patterns.  Values are compared BITWISE, all rows and all k elements.  Indices are never
-compared with expected indices (ties make them unspecified), only checked: in [0, row_len), pointing at a key of their own
-row that is bit-equal to the value beside them, no position twice within a row.  After every case the input is compared
-with what was uploaded.
+order-preserving unsigned codes with the numpy expressions of tests/sort_rows_expect.py, np.sort orders the codes along
+axis 1, and the inverse map gives the sorted bit patterns.  Values are compared BITWISE, all rows and all k elements.
+Indices are never compared with expected indices (ties make them unspecified), only checked: in [0, row_len), pointing at a
+key of their own row that is bit-equal to the value beside them, no position twice within a row.  After every case the
+input is compared with what was uploaded.
 
 The calls go through the C ABI on integer tensors that carry the bit patterns (so that the unsigned key types, padded rows
 and arbitrary alignment need nothing of torch); the Python wrapper has tests of its own at the end."""
@@ -17,12 +17,11 @@ import numpy as np
 import pytest
 
 import guardband
+from gpu_support import int_dtype_of_key as int_dtype
+from sort_rows_expect import F32, F64, I32, I64, NAMES, U32, U64, UT, float_specials, np_decode, np_encode, row_bits, row_normal
 
 pytestmark = pytest.mark.gpu
 
-U32, I32, F32, U64, I64, F64 = range(6)
-UT = {U32: np.uint32, I32: np.uint32, F32: np.uint32, U64: np.uint64, I64: np.uint64, F64: np.uint64}
-NAMES = {U32: "u32", I32: "i32", F32: "f32", U64: "u64", I64: "i64", F64: "f64"}
 
 SHAPES_IN = [(1, 1), (1, 70001), (3, 64), (1000, 65), (4096, 128), (100000, 8), (257, 4097), (64, 131072), (300, 50257), (3, 1 << 20)]
 SHAPES_BEYOND = [(5, (1 << 20) + 77), (2, 1 << 22)]
@@ -31,26 +30,6 @@ SMALL_ROWS = 300   # "small" shapes: the loop is affordable, and k = row_len is 
 
 
 # ---- the expectation
-
-def np_encode(bits, kt):
-    ut = bits.dtype.type
-    top = ut(1 << (bits.itemsize * 8 - 1))
-    if kt % 3 == 0:
-        return bits.copy()
-    if kt % 3 == 1:
-        return bits + top
-    return np.where(bits & top, ~bits, bits | top)
-
-
-def np_decode(codes, kt):
-    ut = codes.dtype.type
-    top = ut(1 << (codes.itemsize * 8 - 1))
-    if kt % 3 == 0:
-        return codes.copy()
-    if kt % 3 == 1:
-        return codes - top
-    return np.where(codes & top, codes ^ top, ~codes)
-
 
 def sorted_rows(bits, kt):
     """every row of the bit patterns (rows x row_len) in the ascending order of key type kt"""
@@ -70,45 +49,6 @@ def test_the_expectation_orders_like_numpy_where_numpy_has_an_order():
 
 
 # ---- inputs: row r is a function of (seed + r, column) and of a scale of its own
-
-def _splitmix(x):
-    x = (x + np.uint64(0x9E3779B97F4A7C15))
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
-
-
-def row_bits(rows, n, seed):
-    """rows x n uint64: row r is the stream of the generator seeded with splitmix(seed + r)"""
-    with np.errstate(over="ignore"):
-        s = _splitmix(np.arange(rows, dtype=np.uint64) + np.uint64(seed))
-        return _splitmix(s[:, None] + np.arange(n, dtype=np.uint64)[None, :])
-
-
-def row_normal(rows, n, seed, tt):
-    """N(0, scale_r^2): Box-Muller on the two halves of the row's bits, scale_r = 2^(r % 9 - 4)"""
-    b = row_bits(rows, n, seed)
-    u1 = ((b >> np.uint64(32)).astype(np.float64) + 1.0) / 4294967296.0
-    u2 = (b & np.uint64(0xFFFFFFFF)).astype(np.float64) / 4294967296.0
-    z = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
-    scale = np.exp2((np.arange(rows) % 9) - 4.0)[:, None]
-    return (z * scale).astype(tt)
-
-
-def float_specials(tt):
-    i = np.finfo(tt)
-    ut = np.uint32 if tt == np.float32 else np.uint64
-    if tt == np.float32:
-        nan_bits = [0x7FC00000, 0x7FC05555, 0x7F800001, 0x7F801234, 0x7FFFFFFF]
-        sign = 0x80000000
-    else:
-        nan_bits = [0x7FF8 << 48, (0x7FF8 << 48) | 0x5555, (0x7FF << 52) | 1, (0x7FF << 52) | 0x1234, (1 << 63) - 1]
-        sign = 1 << 63
-    nans = np.array(nan_bits + [b | sign for b in nan_bits], dtype=ut).view(tt)
-    den_min, den_max = np.array([1], ut).view(tt)[0], np.nextafter(i.tiny, tt(0), dtype=tt)
-    vals = np.array([0.0, -0.0, np.inf, -np.inf, den_min, -den_min, den_max, -den_max, i.tiny, -i.tiny, i.max, -i.max], dtype=tt)
-    return np.concatenate([nans, vals])
-
 
 FLOAT_KINDS = ["normal", "bits", "specials", "const", "coarse", "sorted", "reverse", "rotated"]
 INT_KINDS = ["bits", "small", "const", "extremes", "sorted", "reverse", "rotated"]
@@ -194,11 +134,6 @@ def k_list(rows, row_len, max_k):
 def raw_call(ctx, in_ptr, kt, rows, row_len, stride, k, largest, out_ptr, idx_ptr):
     return ctx._L.msd_topk_rows(ctx._h, C.c_void_p(in_ptr), kt, rows, row_len, stride, k, 1 if largest else 0, C.c_void_p(out_ptr),
                                 C.c_void_p(idx_ptr) if idx_ptr else None)
-
-
-def int_dtype(kt):
-    import torch
-    return torch.int32 if UT[kt] == np.uint32 else torch.int64
 
 
 class Uploaded:

@@ -1,47 +1,26 @@
 """GPU tests of typed top-k / select (msd_topk_keys, msd_select_key; MsdContext.topk_typed / select_typed): signed and
 float keys in their own order, with and without the positions of the keys.
 
-The expected result is defined HERE: the keys' bit patterns are turned into order-preserving unsigned codes with numpy
-expressions of this file (unsigned: the pattern; signed: value + 2^(W-1); float: positive -> sign bit set, negative -> all
-bits inverted, i.e. IEEE-754 totalOrder), np.sort orders the codes, and the inverse map gives the sorted bit patterns.
-Inputs without NaN and without -0 are also compared with np.sort of the typed array itself.  Values are compared BITWISE
-(integer views).  Indices are never compared with expected indices (ties make them unspecified), only checked: in range,
-pointing at a key bit-equal to the value, no position twice."""
+The expected result is defined HERE: the keys' bit patterns are turned into order-preserving unsigned codes with the numpy
+expressions of tests/sort_rows_expect.py (unsigned: the pattern; signed: value + 2^(W-1); float: positive -> sign bit set,
+negative -> all bits inverted, i.e. IEEE-754 totalOrder), np.sort orders the codes, and the inverse map gives the sorted
+bit patterns.  Inputs without NaN and without -0 are also compared with np.sort of the typed array itself.  Values are
+compared BITWISE (integer views).  Indices are never compared with expected indices (ties make them unspecified), only
+checked: in range, pointing at a key bit-equal to the value, no position twice."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from gpu_support import dev
+from sort_rows_expect import F32, F64, I32, I64, U32, U64, VIEWS, make_float, make_int, np_decode, np_encode
+
 pytestmark = pytest.mark.gpu
 
 DEFAULT_CAP = 1 << 20  # the library's default "select_cap" (include/msd_radix_hip.h)
-U32, I32, F32, U64, I64, F64 = range(6)
-# key type -> (unsigned view, typed view)
-VIEWS = {U32: (np.uint32, np.uint32), I32: (np.uint32, np.int32), F32: (np.uint32, np.float32),
-         U64: (np.uint64, np.uint64), I64: (np.uint64, np.int64), F64: (np.uint64, np.float64)}
 
 
 # ---- the expectation
-
-def np_encode(bits, kt):
-    ut = bits.dtype.type
-    top = ut(1 << (bits.itemsize * 8 - 1))
-    if kt % 3 == 0:
-        return bits.copy()
-    if kt % 3 == 1:
-        return bits + top
-    return np.where(bits & top, ~bits, bits | top)
-
-
-def np_decode(codes, kt):
-    ut = codes.dtype.type
-    top = ut(1 << (codes.itemsize * 8 - 1))
-    if kt % 3 == 0:
-        return codes.copy()
-    if kt % 3 == 1:
-        return codes - top
-    return np.where(codes & top, codes ^ top, ~codes)
-
 
 def sorted_bits(a, kt):
     """the bit patterns of the typed array a in the ascending order of key type kt"""
@@ -57,73 +36,7 @@ def k_list(n):  # (as tests/test_gpu_topk.py)
     return sorted({k for k in (0, 1, 2, n // 1000 + 1, n // 2, n - 1, n) if 0 <= k <= n})
 
 
-# ---- inputs
-
-def float_specials(tt):
-    i = np.finfo(tt)
-    ut = np.uint32 if tt == np.float32 else np.uint64
-    if tt == np.float32:
-        nan_bits = [0x7FC00000, 0x7FC05555, 0x7F800001, 0x7F801234, 0x7FFFFFFF]       # quiet, quiet + payload, signalling x 2, all ones
-        sign = 0x80000000
-    else:
-        nan_bits = [0x7FF8 << 48, (0x7FF8 << 48) | 0x5555, (0x7FF << 52) | 1, (0x7FF << 52) | 0x1234, (1 << 63) - 1]
-        sign = 1 << 63
-    nans = np.array(nan_bits + [b | sign for b in nan_bits], dtype=ut).view(tt)
-    den_min, den_max = np.array([1], ut).view(tt)[0], np.nextafter(i.tiny, tt(0), dtype=tt)
-    vals = np.array([0.0, -0.0, np.inf, -np.inf, den_min, -den_min, den_max, -den_max, i.tiny, -i.tiny, i.max, -i.max], dtype=tt)
-    return np.concatenate([nans, vals])
-
-
-def make_float(n, kind, tt, seed):
-    rng = np.random.default_rng(seed)
-    ut = np.uint32 if tt == np.float32 else np.uint64
-    normal = lambda: rng.standard_normal(n).astype(tt)  # noqa: E731
-    if kind == "normal":
-        return normal()
-    if kind == "bits":
-        return rng.integers(0, np.iinfo(ut).max, n, dtype=ut, endpoint=True).view(tt)
-    if kind == "specials":
-        sp = np.repeat(float_specials(tt), 5)  # (a small n takes a random subset of them)
-        a = np.concatenate([sp, rng.standard_normal(max(n - len(sp), 0)).astype(tt)])
-        return np.ascontiguousarray(rng.permutation(a)[:n])
-    if kind == "const":
-        return np.full(n, -1.5, tt)
-    if kind == "negative":
-        return -(np.abs(normal()) + tt(1e-3))
-    if kind == "sorted":
-        return np.sort(normal())
-    if kind == "reverse":
-        return np.sort(normal())[::-1].copy()
-    if kind == "coarse":
-        return (np.round(normal() * 16) / 16).astype(tt)
-    raise ValueError(kind)
-
-
-def make_int(n, kind, tt, seed):
-    rng = np.random.default_rng(seed)
-    i = np.iinfo(tt)
-    bits = lambda: rng.integers(i.min, i.max, n, dtype=tt, endpoint=True)  # noqa: E731
-    if kind == "bits":
-        return bits()
-    if kind == "small":
-        return rng.integers(-2048, 2048, n, dtype=tt)
-    if kind == "const":
-        return np.full(n, -123456789, tt)
-    if kind == "extremes":
-        return rng.choice(np.array([i.min, i.max, -1, 0], dtype=tt), n)
-    if kind == "sorted":
-        return np.sort(bits())
-    if kind == "reverse":
-        return np.sort(bits())[::-1].copy()
-    raise ValueError(kind)
-
-
 # ---- the check
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
 
 def host_bits(t, kt):
     return t.cpu().numpy().view(VIEWS[kt][0])

@@ -10,48 +10,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import guardband
+import sort_rows_expect as E
+from guardband import Buf
 
 pytestmark = pytest.mark.gpu
 
 U32, I32, F32, U64, I64, F64 = range(6)      # MSD_KEY_*
-UKT = {4: U32, 8: U64}                        # the unsigned key type of a width: the order of the bit patterns
-UT = {4: np.uint32, 8: np.uint64}
+UKT = E.UKT                                   # the unsigned key type of a width: the order of the bit patterns
 N = 65
 ROWS, LEN, STRIDE = 3, 65, 80
 EXTENT = (ROWS - 1) * STRIDE + LEN            # elements of a strided input: the padding behind the last row is not part of it
 
 
-def int_dtype(es):
-    import torch
-    return torch.int32 if es == 4 else torch.int64
-
-
-class Buf:
-    """`count` elements of es bytes in the payload of an Arena, filled with the array `a` or a known pattern"""
-
-    def __init__(self, es, count, a=None):
-        self.es, self.count = es, count
-        self.arena = guardband.Arena(int_dtype(es), count)
-        self.fill = guardband.pattern(1234, count, es).numpy().view(UT[es]).copy() if a is None else np.asarray(a, dtype=UT[es]).copy()
-        self.arena.fill(self.fill)
-        self.ptr = self.arena.ptr
-
-    def reset(self):
-        self.arena.fill(self.fill)
-
-    def host(self):
-        return self.arena.host(UT[self.es])
-
-    def unchanged(self):
-        return (self.host() == self.fill).all()
-
-    def check(self, what):
-        self.arena.check(what)
-
-
 def keys_for(es, count, seed):
-    return np.random.default_rng(seed).integers(0, 1 << (8 * es - 1), count, dtype=np.uint64).astype(UT[es])
+    return np.random.default_rng(seed).integers(0, 1 << (8 * es - 1), count, dtype=np.uint64).astype(E.UW[es])
 
 
 def refuser(ctx, fn, order, good, bufs):
@@ -80,7 +52,7 @@ def off_grid(es):
 @pytest.mark.parametrize("es", (4, 8))
 def test_sort_keys_refusals_in_order_touch_nothing(ctx, es):
     a = keys_for(es, N, 1)
-    dk = Buf(es, N, a)
+    dk = Buf(es, N, a=a)
     order = ("keys", "kt", "n", "order")
     good = dict(keys=dk.ptr, kt=UKT[es], n=N, order=0)
     refused = refuser(ctx, ctx._L.msd_sort_keys, order, good, (dk,))
@@ -111,7 +83,7 @@ def test_sort_keys_refusals_in_order_touch_nothing(ctx, es):
 
 def test_sort_pairs_keys_refusals_in_order_touch_nothing(ctx):
     a = keys_for(8, N, 2)
-    dk, dr = Buf(8, N, a), Buf(8, N, np.arange(N))
+    dk, dr = Buf(8, N, a=a), Buf(8, N, a=np.arange(N))
     order = ("keys", "kt", "rids", "n", "order")
     good = dict(keys=dk.ptr, kt=U64, rids=dr.ptr, n=N, order=0)
     refused = refuser(ctx, ctx._L.msd_sort_pairs_keys, order, good, (dk, dr))
@@ -143,7 +115,7 @@ def test_sort_pairs_keys_refusals_in_order_touch_nothing(ctx):
     ctx._ok(ctx._L.msd_sort_pairs_keys(ctx._h, 0, F64, 0, 0, 1))
     ctx._ok(ctx._L.msd_sort_pairs_keys(ctx._h, dk.ptr, U64, dk.ptr, 0, 0))
     assert dk.unchanged() and dr.unchanged()
-    both = Buf(8, 64, np.concatenate([keys_for(8, 32, 3), np.arange(32, dtype=np.uint64)]))
+    both = Buf(8, 64, a=np.concatenate([keys_for(8, 32, 3), np.arange(32, dtype=np.uint64)]))
     ctx._ok(ctx._L.msd_sort_pairs_keys(ctx._h, both.ptr, U64, both.ptr + 8 * 32, 32, 0))
     h = both.host()
     assert (h[:32] == np.sort(both.fill[:32])).all() and (both.fill[:32][h[32:]] == h[:32]).all()
@@ -200,7 +172,7 @@ def strided(es, seed):
 def test_topk_rows_refusals_in_order_touch_nothing(ctx, es):
     K = 5
     flat, rows = strided(es, 4)
-    di, do, dx = Buf(es, ROWS * STRIDE, flat), Buf(es, ROWS * K), Buf(8, ROWS * K)
+    di, do, dx = Buf(es, ROWS * STRIDE, a=flat), Buf(es, ROWS * K), Buf(8, ROWS * K)
     order = ("inp", "kt", "rows", "len", "stride", "k", "which", "out", "idx")
     good = dict(inp=di.ptr, kt=UKT[es], rows=ROWS, len=LEN, stride=STRIDE, k=K, which=0, out=do.ptr, idx=dx.ptr)
     fn = ctx._L.msd_topk_rows
@@ -271,7 +243,7 @@ def test_topk_rows_refusals_in_order_touch_nothing(ctx, es):
 @pytest.mark.parametrize("es", (4, 8))
 def test_sort_rows_refusals_in_order_touch_nothing(ctx, es):
     flat, rows = strided(es, 5)
-    di, do, dx = Buf(es, ROWS * STRIDE, flat), Buf(es, ROWS * LEN), Buf(8, ROWS * LEN)
+    di, do, dx = Buf(es, ROWS * STRIDE, a=flat), Buf(es, ROWS * LEN), Buf(8, ROWS * LEN)
     order = ("inp", "kt", "rows", "len", "stride", "order", "out", "idx")
     good = dict(inp=di.ptr, kt=UKT[es], rows=ROWS, len=LEN, stride=STRIDE, order=0, out=do.ptr, idx=dx.ptr)
     fn = ctx._L.msd_sort_rows
@@ -332,7 +304,7 @@ def test_sort_rows_refusals_in_order_touch_nothing(ctx, es):
         assert b.unchanged()
         b.check("nothing to do")
     # accepted: in place, d_out_keys == d_keys with row_stride == row_len, with positions elsewhere
-    dense = Buf(es, ROWS * LEN, np.ascontiguousarray(rows).reshape(-1))
+    dense = Buf(es, ROWS * LEN, a=np.ascontiguousarray(rows).reshape(-1))
     ctx._ok(fn(ctx._h, dense.ptr, UKT[es], ROWS, LEN, LEN, 0, dense.ptr, dx.ptr))
     got, pos = dense.host().reshape(ROWS, LEN), dx.host().reshape(ROWS, LEN).astype(np.int64)
     assert (got == np.sort(rows, axis=1)).all() and (np.take_along_axis(rows, pos, 1) == got).all()

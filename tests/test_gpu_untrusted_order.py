@@ -25,7 +25,9 @@ import test_gpu_join as GJ
 import test_gpu_merge_sorted as GM
 import test_gpu_search as GS
 import test_gpu_set_sorted as GX
-from test_gpu_merge_sorted import TAIL, UKT, UT, WIDTHS, Buf, top
+from gpu_support import TAIL
+from guardband import Buf
+from sort_rows_expect import UKT, WIDTHS, top
 
 gpu = pytest.mark.gpu                                               # (test_the_inputs_are_what_they_say needs none)
 
@@ -73,18 +75,18 @@ def torch_sort_order(rng, count, kb):
     x = np.sort(rng.integers(-6, 7, count).astype(ft) / 2)
     zeros = np.flatnonzero(x == 0)
     x[zeros[1::2]] = -0.0
-    bits = x.view(UT[kb]).copy()
-    sign = UT[kb](1 << (8 * kb - 1))
-    nan = UT[kb](0x7FC00000 if kb == 4 else 0x7FF8 << 48)
+    bits = x.view(E.UW[kb]).copy()
+    sign = E.UW[kb](1 << (8 * kb - 1))
+    nan = E.UW[kb](0x7FC00000 if kb == 4 else 0x7FF8 << 48)
     k = min(count, 5)
-    bits[count - k:] = np.array([nan, nan | sign, nan | UT[kb](5), nan | sign | UT[kb](5), nan], UT[kb])[:k]
+    bits[count - k:] = np.array([nan, nan | sign, nan | E.UW[kb](5), nan | sign | E.UW[kb](5), nan], E.UW[kb])[:k]
     return bits
 
 
 def inputs(kind, n, m, kb, T):
     """``(a_bits, b_bits, key_type)``: A and B, NOT ascending in the order of the type (a side of 0 or 1 elements is)"""
     rng = np.random.default_rng([n, m, kb, KINDS.index(kind)])
-    ut, kt = UT[kb], UKT[kb]
+    ut, kt = E.UW[kb], UKT[kb]
     span = max((n + m) // 2, 2)                                     # few enough values that the two sides share many
     draw = lambda count: rng.integers(0, span, count).astype(ut)
     up = np.sort
@@ -141,7 +143,7 @@ def test_the_inputs_are_what_they_say():
             a, b, kt = inputs(kind, n, m, kb, T)
             for x in (a, b):
                 f = x.view(np.float32 if kb == 4 else np.float64)
-                sign = x >> UT[kb](8 * kb - 1)
+                sign = x >> E.UW[kb](8 * kb - 1)
                 finite = f[~np.isnan(f)]
                 assert (finite[1:] >= finite[:-1]).all() and np.isnan(f[finite.size:]).all()       # torch.sort's order
                 zeros = np.flatnonzero(f == 0)
@@ -194,7 +196,7 @@ def test_search_with_unsorted_needles_keys_and_both(ctx, kb, kind):
             needles = b if vary != "keys" else S.sort_by_code(b, kt)
             ck, cn = codes_of(keys, needles, kt)
             perm = np.random.default_rng(m).permutation(m).astype(np.uint64)
-            dkeys, dneedles, dpos, dout = Buf(kb, n, 0, keys), Buf(kb, m, 0, needles), Buf(8, m, 0, perm), Buf(8, m + TAIL)
+            dkeys, dneedles, dpos, dout = Buf(kb, n, a=keys), Buf(kb, m, a=needles), Buf(8, m, a=perm), Buf(8, m + TAIL)
             bufs = (("d_sorted", dkeys), ("d_needles", dneedles), ("d_positions", dpos), ("d_out", dout))
             for right, positions in ((False, False), (True, True)) if turn % 2 else ((True, False), (False, True)):
                 what = (kind, E.NAMES[kt], n, m, vary, "right" if right else "left", positions)
@@ -234,7 +236,7 @@ def test_merge_of_unsorted_inputs(ctx, kb, kind):
         a, b, kt = inputs(kind, n, m, kb, T)
         total = n + m
         va, vb = TAG + np.arange(n, dtype=np.uint64), TAG + n + np.arange(m, dtype=np.uint64)
-        da, db, dva, dvb = Buf(kb, n, 0, a), Buf(kb, m, 0, b), Buf(8, n, 0, va), Buf(8, m, 0, vb)
+        da, db, dva, dvb = Buf(kb, n, a=a), Buf(kb, m, a=b), Buf(8, n, a=va), Buf(8, m, a=vb)
         dout, dov, doo = Buf(kb, total + TAIL), Buf(8, total + TAIL), Buf(8, total + TAIL)
         bufs = (("d_a", da), ("d_b", db), ("d_vals_a", dva), ("d_vals_b", dvb), ("d_out", dout), ("d_out_vals", dov), ("d_out_origin", doo))
         assert_no_tags(*[x for _, x in bufs])
@@ -269,7 +271,7 @@ def set_case(ctx, a, b, kt, T, ops, what, all_caps=True):
     ca, cb = codes_of(a, b, kt)
     counts = {op: sum(X.count_np(ca, cb, T, op)) for op in ops}
     room = max(counts.values()) + TAIL
-    da, db, dout, doo, dnum = Buf(kb, n, 0, a), Buf(kb, m, 0, b), Buf(kb, room), Buf(8, room), Buf(8, 1)
+    da, db, dout, doo, dnum = Buf(kb, n, a=a), Buf(kb, m, a=b), Buf(kb, room), Buf(8, room), Buf(8, 1)
     bufs = (("d_a", da), ("d_b", db), ("d_out", dout), ("d_out_origin", doo), ("d_num_out", dnum))
     for op in ops:
         count = counts[op]
@@ -312,7 +314,7 @@ def reversed_over_a_scan_piece(kb):
     total = (scan + 1) * T + 5
     n = total * 3 // 5
     rng = np.random.default_rng(kb)
-    draw = lambda count: np.sort(rng.integers(0, total // 2, count).astype(UT[kb]))[::-1].copy()
+    draw = lambda count: np.sort(rng.integers(0, total // 2, count).astype(E.UW[kb]))[::-1].copy()
     return draw(n), draw(total - n), T
 
 
@@ -331,10 +333,10 @@ def pairs_case(ctx, g, stated, gcap, n, m, caps, positions, what):
     P = PAIR_TH * PAIR_PER
     cols = [np.asarray(x, np.uint64) for x in g]
     room = max(caps)
-    dng = Buf(8, 1, 0, np.array([stated], np.uint64))
-    dg = [Buf(8, gcap, 0, x) for x in cols]
+    dng = Buf(8, 1, a=np.array([stated], np.uint64))
+    dg = [Buf(8, gcap, a=x) for x in cols]
     pa, pb = TAG + np.arange(n, dtype=np.uint64), TAG + (1 << 31) + np.arange(m, dtype=np.uint64)
-    dpa, dpb = Buf(8, n, 0, pa), Buf(8, m, 0, pb)
+    dpa, dpb = Buf(8, n, a=pa), Buf(8, m, a=pb)
     oa, ob, dnum = Buf(8, room + TAIL), Buf(8, room + TAIL), Buf(8, 1)
     ins = [("d_num_groups", dng)] + list(zip(GJ.NAMES5[1:], dg)) + [("d_pos_a", dpa), ("d_pos_b", dpb)]
     bufs = ins + [("d_out_a", oa), ("d_out_b", ob), ("d_num_pairs", dnum)]
@@ -373,7 +375,7 @@ def groups_case(ctx, a, b, kt, T, what, all_caps=True, pairs=True):
     ca, cb = codes_of(a, b, kt)
     count = sum(X.count_np(ca, cb, T, X.INTERSECTION))
     room = count + TAIL
-    da, db = Buf(kb, n, 0, a), Buf(kb, m, 0, b)
+    da, db = Buf(kb, n, a=a), Buf(kb, m, a=b)
     outs = [Buf(kb, room)] + [Buf(8, room) for _ in range(4)]
     dnum = Buf(8, 1)
     bufs = [("d_a", da), ("d_b", db)] + list(zip(GJ.NAMES5, outs)) + [("d_num_groups", dnum)]

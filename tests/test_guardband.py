@@ -195,3 +195,70 @@ def test_fill_checks_size_and_host_returns_the_bits():
     e = Arena(torch.int32, 0, lead_bytes=16, device="cpu")       # an empty payload: the guards touch
     e.fill(np.zeros(0, np.uint32))
     e.check()
+
+
+# ---- Buf: a window into an Arena that knows what it was filled with
+
+BUF_CASES = [(1, 0, 0), (4, 3, 48), (8, 1, 272)]      # (element bytes, off, lead_bytes)
+
+
+def _buf(es, off, lead, count=7, given=True):
+    a = np.arange(101, 101 + count).astype(NP_U[es]) if given else None
+    return guardband.Buf(es, count, off, lead, a, device="cpu"), a
+
+
+@pytest.mark.parametrize("es,off,lead", BUF_CASES)
+def test_buf_address_and_contents(es, off, lead):
+    b, a = _buf(es, off, lead)
+    assert b.ptr % 4096 == lead + off * es and b.ptr == b.arena.ptr + off * es and b.arena.n == 7 + off
+    assert (b.host() == a).all() and b.host().dtype == NP_U[es] and (b.written(7) == a).all()
+    assert (b.fill[off:] == a).all() and (b.fill[:off] == guardband.pattern(guardband.BUF_PATTERN_FIRST, off, es).numpy().view(NP_U[es])).all()
+    assert b.unchanged() and b.untouched_from(0) and b.untouched_from(7)
+    b.check("untouched")
+    p, _ = _buf(es, off, lead, given=False)               # without an array the pattern goes on behind `off`
+    assert (p.host() == guardband.pattern(guardband.BUF_PATTERN_FIRST + off, 7, es).numpy().view(NP_U[es])).all() and p.unchanged()
+
+
+@pytest.mark.parametrize("es,off,lead", BUF_CASES[1:])
+def test_buf_catches_a_changed_cell_in_front_of_off(es, off, lead):
+    b, _ = _buf(es, off, lead)
+    _cells(b.arena)[b.arena.front + off - 1] ^= 1
+    for call in (b.host, b.unchanged, lambda: b.untouched_from(7), lambda: b.written(7)):
+        with pytest.raises(AssertionError, match="in front of the buffer"):
+            call()
+    b.check("the guards are what they were")
+    b.reset()
+    assert b.unchanged()
+
+
+@pytest.mark.parametrize("es,off,lead", BUF_CASES)
+def test_buf_catches_a_changed_cell_at_or_beyond_count(es, off, lead):
+    for at in (3, 6):
+        b, a = _buf(es, off, lead)
+        _cells(b.arena)[b.arena.front + off + at] ^= 1
+        with pytest.raises(AssertionError, match="beyond the first 3 changed"):
+            b.written(3)
+        assert not b.untouched_from(3) and not b.untouched_from(at) and b.untouched_from(at + 1) and not b.unchanged()
+        assert (b.written(at + 1)[:at] == a[:at]).all() and b.written(at + 1)[at] == a[at] ^ 1
+        b.check("the guards are what they were")
+        b.reset()
+        assert b.unchanged() and (b.written(3) == a[:3]).all()
+
+
+@pytest.mark.parametrize("es,off,lead", BUF_CASES)
+def test_buf_catches_a_changed_cell_below_count(es, off, lead):
+    b, a = _buf(es, off, lead)
+    _cells(b.arena)[b.arena.front + off] ^= 1
+    assert not b.unchanged() and b.untouched_from(1) and b.host()[0] == a[0] ^ 1 and (b.written(1) == a[:1] ^ 1).all()
+    b.reset()
+    assert b.unchanged() and (b.host() == a).all()
+
+
+@pytest.mark.parametrize("es,off,lead", BUF_CASES)
+def test_buf_check_catches_a_changed_guard_cell_on_either_side(es, off, lead):
+    for at, side in ((-1, "front"), (7 + off, "back")):
+        b, _ = _buf(es, off, lead)
+        _cells(b.arena)[b.arena.front + at] ^= 1
+        with pytest.raises(AssertionError, match="case: %s guard touched: 1 cell" % side):
+            b.check("case")
+        assert b.unchanged()                              # (the payload is what it was: only check() looks at the guards)

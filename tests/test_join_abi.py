@@ -5,16 +5,15 @@ other surfaces, a null context is refused first, the limits call answers on the 
 needs a device to be refused, and the numpy expectation and the model of the write kernel in tests/join_expect.py are what
 their docstrings say."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import join_expect as J
 import sort_rows_expect as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_join_groups": ["msd_ctx *ctx", "const void *d_a", "uint64_t n", "const void *d_b", "uint64_t m", "int key_type", "uint64_t cap", "void *d_keys",
                         "uint64_t *d_a_first", "uint64_t *d_a_count", "uint64_t *d_b_first", "uint64_t *d_b_count", "uint64_t *d_num_groups"],
@@ -25,20 +24,10 @@ SIGNATURES = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_join_hip.h")).read()
-    return text, re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_three_functions():
-    text, flat = _header()
+    text, flat = A.header("msd_join_hip.h")
     assert '#include "msd_radix_hip.h"' in flat
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
     # the header says what is promised about equality and floats, what is taken on trust, the order of the pairs, what a
     # truncated groups call means, and the order of the refusals
     for word in ("TRUSTED", "totalOrder", "-0.0", "NaN", "first occurrence", "lexicographic", "TRUNCATED", "checked in this order", "2^32", "join_groups", "join_pairs"):
@@ -49,24 +38,11 @@ def test_header_declares_the_three_functions():
 
 
 def test_the_other_headers_declare_none_of_it():
-    for h in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if h != "msd_join_hip.h":
-            assert "msd_join" not in open(os.path.join(ROOT, "include", h)).read(), h
+    A.check_no_other_header_has("msd_join_hip.h", "msd_join")
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.JOIN_EXPORTS) == sorted(SIGNATURES)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        for other in (_lib.EXPORTS, _lib.SORT_KEYS_EXPORTS, _lib.SORT_ROWS_EXPORTS, _lib.RUNS_EXPORTS, _lib.REDUCE_EXPORTS, _lib.SEARCH_EXPORTS,
-                      _lib.MERGE_EXPORTS, _lib.SETOPS_EXPORTS, _lib.RCCL_EXPORTS):
-            assert f not in other, f
-        assert list(getattr(L, f).argtypes) == list(_lib.JOIN_EXPORTS[f]), f
-        assert len(_lib.JOIN_EXPORTS[f]) == len(SIGNATURES[f]), f
-    assert any(d.endswith("msd_join_hip.h") for d in _build.DEPS)
-    assert "msd_join.hpp" in _build.DEPS
+    A.check_exports("JOIN_EXPORTS", SIGNATURES, "msd_join_hip.h", "msd_join.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -93,26 +69,12 @@ def test_limits_answer_on_the_host():
         assert scan.value >= 64 and pair.value >= 64
         assert L.msd_set_sorted_limits(kb, C.byref(set_tile), C.byref(set_scan)) == 0
         assert (set_tile.value, set_scan.value) == (tile.value, scan.value)   # the tiles and the scan of the set operations
-    a, b, c = C.c_uint64(77), C.c_uint64(78), C.c_uint64(79)
-    for kb in (0, 2, 5, 16, -4):
-        assert L.msd_join_limits(kb, C.byref(a), C.byref(b), C.byref(c)) == -1 and (a.value, b.value, c.value) == (77, 78, 79)
-    for kb in (4, 8):
-        assert L.msd_join_limits(kb, None, C.byref(b), C.byref(c)) == -1 and (b.value, c.value) == (78, 79)
-        assert L.msd_join_limits(kb, C.byref(a), None, C.byref(c)) == -1 and (a.value, c.value) == (77, 79)
-        assert L.msd_join_limits(kb, C.byref(a), C.byref(b), None) == -1 and (a.value, b.value) == (77, 78)
-        assert L.msd_join_limits(kb, None, None, None) == -1
-
-
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
+    A.check_limits_refusals(L.msd_join_limits, 3)
 
 
 def test_limits_wrapper():
     from inplacemsdradixsort_amd import MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     for kb in (4, 8):
         t, s, p = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -126,7 +88,7 @@ def test_limits_wrapper():
 def test_the_wrappers_refuse_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()                                                    # (no _L, no _h: touching the library would raise AttributeError)
+    ctx = A.bare_ctx()                                             # (no _L, no _h: touching the library would raise AttributeError)
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         a, b = torch.zeros(5, dtype=dt), torch.zeros(3, dtype=dt)
         for kw in ({}, {"cap": 2}, {"cap": 0}, {"keys": False}):

@@ -4,16 +4,14 @@ exports them, the binding lists them apart from the other surfaces, a null conte
 on the host, the Python wrapper refuses what never needs a device to be refused, and the numpy expectation and the model of
 the two kernels in tests/merge_expect.py are what their docstrings say."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import merge_expect as M
 import sort_rows_expect as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_merge_sorted": ["msd_ctx *ctx", "const void *d_a", "uint64_t n", "const void *d_b", "uint64_t m", "int key_type",
                          "const uint64_t *d_vals_a", "const uint64_t *d_vals_b", "void *d_out", "uint64_t *d_out_vals", "uint64_t *d_out_origin"],
@@ -21,44 +19,21 @@ SIGNATURES = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_merge_hip.h")).read()
-    return text, re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_two_functions():
-    text, flat = _header()
+    text, flat = A.header("msd_merge_hip.h")
     assert '#include "msd_radix_hip.h"' in flat
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
     # the header says what is promised about ties and floats, and what is taken on trust
     for word in ("stable", "TRUSTED", "totalOrder", "-0.0", "NaN"):
         assert word in text, word
 
 
 def test_the_other_headers_declare_none_of_it():
-    for h in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if h != "msd_merge_hip.h":
-            assert "msd_merge_sorted" not in open(os.path.join(ROOT, "include", h)).read(), h
+    A.check_no_other_header_has("msd_merge_hip.h", "msd_merge_sorted")
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.MERGE_EXPORTS) == sorted(SIGNATURES)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        for other in (_lib.EXPORTS, _lib.SORT_KEYS_EXPORTS, _lib.SORT_ROWS_EXPORTS, _lib.RUNS_EXPORTS, _lib.REDUCE_EXPORTS, _lib.SEARCH_EXPORTS,
-                      _lib.RCCL_EXPORTS):
-            assert f not in other, f
-        assert list(getattr(L, f).argtypes) == list(_lib.MERGE_EXPORTS[f]), f
-        assert len(_lib.MERGE_EXPORTS[f]) == len(SIGNATURES[f]), f
-    assert any(d.endswith("msd_merge_hip.h") for d in _build.DEPS)
-    assert "msd_merge2.hpp" in _build.DEPS
+    A.check_exports("MERGE_EXPORTS", SIGNATURES, "msd_merge_hip.h", "msd_merge2.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -80,23 +55,12 @@ def test_limits_answer_on_the_host():
         tile = C.c_uint64(0)
         assert L.msd_merge_sorted_limits(kb, C.byref(tile)) == 0
         assert 64 <= tile.value <= 1 << 16                          # (the kernels keep a local index in 16 bits)
-    a = C.c_uint64(77)
-    for kb in (0, 2, 16, -4, 5):
-        assert L.msd_merge_sorted_limits(kb, C.byref(a)) == -1 and a.value == 77
-    for kb in (4, 8):
-        assert L.msd_merge_sorted_limits(kb, None) == -1
-
-
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
+    A.check_limits_refusals(L.msd_merge_sorted_limits, 1)
 
 
 def test_limits_wrapper():
     from inplacemsdradixsort_amd import MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     for kb in (4, 8):
         tile = C.c_uint64(0)
@@ -110,7 +74,7 @@ def test_limits_wrapper():
 def test_merge_sorted_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()                                                    # (no _L, no _h: touching the library would raise AttributeError)
+    ctx = A.bare_ctx()                                             # (no _L, no _h: touching the library would raise AttributeError)
     v5, v3 = torch.zeros(5, dtype=torch.int64), torch.zeros(3, dtype=torch.int64)
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         a, b = torch.zeros(5, dtype=dt), torch.zeros(3, dtype=dt)

@@ -4,15 +4,13 @@ binding lists them apart from the other surfaces, a null context is refused firs
 Python wrappers refuse what never needs a device to be refused, and the numpy expectation of tests/runs_expect.py is what
 its docstring says."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import runs_expect as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_run_encode": ["msd_ctx *ctx", "const void *d_data", "int elem_bytes", "uint64_t n", "uint64_t cap", "void *d_values",
                        "uint64_t *d_starts", "const uint64_t *d_positions", "uint64_t *d_inverse", "uint64_t *d_num_runs"],
@@ -20,34 +18,15 @@ SIGNATURES = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_runs_hip.h")).read()
-    return text, re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_two_functions():
-    text, flat = _header()
+    text, flat = A.header("msd_runs_hip.h")
     assert '#include "msd_radix_hip.h"' in flat
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
     assert "torch.unique" in text and "NaN" in text and "-0.0" in text   # the header says where bitwise equality differs
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.RUNS_EXPORTS) == sorted(SIGNATURES)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        assert f not in _lib.EXPORTS and f not in _lib.SORT_KEYS_EXPORTS and f not in _lib.SORT_ROWS_EXPORTS, f
-        assert list(getattr(L, f).argtypes) == list(_lib.RUNS_EXPORTS[f]), f
-        assert len(_lib.RUNS_EXPORTS[f]) == len(SIGNATURES[f]), f
-    assert any(d.endswith("msd_runs_hip.h") for d in _build.DEPS)
-    assert "msd_runs.hpp" in _build.DEPS
+    A.check_exports("RUNS_EXPORTS", SIGNATURES, "msd_runs_hip.h", "msd_runs.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -69,25 +48,12 @@ def test_limits():
         tile, scan_tile = C.c_uint64(0), C.c_uint64(0)
         assert L.msd_run_encode_limits(es, C.byref(tile), C.byref(scan_tile)) == 0
         assert tile.value >= 64 and scan_tile.value >= 64, (es, tile.value, scan_tile.value)
-    a, b = C.c_uint64(77), C.c_uint64(78)
-    for es in (0, 2, 16, -4, 5):
-        assert L.msd_run_encode_limits(es, C.byref(a), C.byref(b)) == -1 and (a.value, b.value) == (77, 78)
-    for es in (4, 8):
-        assert L.msd_run_encode_limits(es, None, C.byref(b)) == -1 and b.value == 78
-        assert L.msd_run_encode_limits(es, C.byref(a), None) == -1 and a.value == 77
-        assert L.msd_run_encode_limits(es, None, None) == -1
-
-
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
+    A.check_limits_refusals(L.msd_run_encode_limits, 2, bad_widths=(0, 2, 16, -4, 5))
 
 
 def test_limits_wrapper():
     from inplacemsdradixsort_amd import MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     for es in (4, 8):
         tile, scan_tile = ctx.run_encode_limits(es)
@@ -100,7 +66,7 @@ def test_limits_wrapper():
 def test_run_encode_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()                                                    # (no _L, no _h: touching the library would raise AttributeError)
+    ctx = A.bare_ctx()                                             # (no _L, no _h: touching the library would raise AttributeError)
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         for kw in ({}, {"cap": 3}, {"inverse": True}, {"values": False, "starts": False}):
             with pytest.raises(MsdError, match="GPU"):              # a CPU tensor
@@ -128,7 +94,7 @@ def test_run_encode_refuses_before_the_library_is_touched():
 def test_unique_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         for kw in ({}, {"return_inverse": True}, {"return_counts": True}):
             with pytest.raises(MsdError, match="GPU"):

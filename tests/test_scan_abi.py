@@ -4,18 +4,17 @@ two flags, the library exports them, the binding lists them apart from the other
 the limits call answers on the host, the Python wrapper refuses what never needs a device to be refused, and the numpy
 expectation of tests/scan_expect.py is what its docstring says."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import reduce_expect as X
 import runs_expect as R
 import scan_expect as S
 import sort_rows_expect as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_scan_runs": ["msd_ctx *ctx", "const void *d_keys", "int key_bytes", "uint64_t n", "const void *d_vals", "int val_type",
                       "const uint64_t *d_positions", "int op", "int flags", "void *d_out"],
@@ -23,20 +22,10 @@ SIGNATURES = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_scan_hip.h")).read()
-    return text, re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_two_functions_the_ops_and_the_flags():
-    text, flat = _header()
+    text, flat = A.header("msd_scan_hip.h")
     assert '#include "msd_radix_hip.h"' in flat
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
     assert re.search(r"enum \{ MSD_SCAN_SUM = 0, MSD_SCAN_MIN = 1, MSD_SCAN_MAX = 2, MSD_SCAN_COUNT = 3 \};", flat)
     assert re.search(r"enum \{ MSD_SCAN_EXCLUSIVE = 1, MSD_SCAN_SCATTER = 2 \};", flat)
     # the header says where the float order differs from torch, that sums are reproducible but not sequential and never
@@ -50,31 +39,18 @@ def test_header_declares_the_two_functions_the_ops_and_the_flags():
 
 
 def test_the_scan_ops_are_the_reduce_ops():
-    reduce_h = open(os.path.join(ROOT, "include", "msd_reduce_hip.h")).read()
+    reduce_h, _ = A.header("msd_reduce_hip.h")
     for name, value in (("SUM", 0), ("MIN", 1), ("MAX", 2)):
         assert "MSD_REDUCE_%s = %d" % (name, value) in reduce_h and S.OPS[name.lower()] == X.OPS[name.lower()] == value
     assert S.OPS["count"] == 3 and (S.EXCLUSIVE, S.SCATTER) == (1, 2)
 
 
 def test_the_other_headers_declare_none_of_it():
-    for h in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if h != "msd_scan_hip.h":
-            assert "msd_scan" not in open(os.path.join(ROOT, "include", h)).read(), h
+    A.check_no_other_header_has("msd_scan_hip.h", "msd_scan")
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.SCAN_EXPORTS) == sorted(SIGNATURES)
-    others = [_lib.EXPORTS, _lib.RCCL_EXPORTS] + [getattr(_lib, t) for t in dir(_lib) if t.endswith("_EXPORTS") and t not in ("SCAN_EXPORTS", "RCCL_EXPORTS")]
-    assert len(others) >= 10
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        assert not any(f in table for table in others), f
-        assert list(getattr(L, f).argtypes) == list(_lib.SCAN_EXPORTS[f]), f
-        assert len(_lib.SCAN_EXPORTS[f]) == len(SIGNATURES[f]), f
-    assert any(d.endswith("msd_scan_hip.h") for d in _build.DEPS)
-    assert "msd_scan.hpp" in _build.DEPS
+    A.check_exports("SCAN_EXPORTS", SIGNATURES, "msd_scan_hip.h", "msd_scan.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -97,25 +73,12 @@ def test_limits_are_those_of_run_encode():
         assert L.msd_scan_runs_limits(kb, C.byref(tile), C.byref(scan_tile)) == 0
         assert L.msd_run_encode_limits(kb, C.byref(t2), C.byref(s2)) == 0
         assert (tile.value, scan_tile.value) == (t2.value, s2.value) and tile.value >= 64 and scan_tile.value >= 64
-    a, b = C.c_uint64(77), C.c_uint64(78)
-    for kb in (0, 2, 16, -4, 5):
-        assert L.msd_scan_runs_limits(kb, C.byref(a), C.byref(b)) == -1 and (a.value, b.value) == (77, 78)
-    for kb in (4, 8):
-        assert L.msd_scan_runs_limits(kb, None, C.byref(b)) == -1 and b.value == 78
-        assert L.msd_scan_runs_limits(kb, C.byref(a), None) == -1 and a.value == 77
-        assert L.msd_scan_runs_limits(kb, None, None) == -1
-
-
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
+    A.check_limits_refusals(L.msd_scan_runs_limits, 2, bad_widths=(0, 2, 16, -4, 5))
 
 
 def test_limits_wrapper_and_ops_table():
     from inplacemsdradixsort_amd import MsdContext, MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     for kb in (4, 8):
         assert ctx.scan_runs_limits(kb) == ctx.run_encode_limits(kb)
@@ -129,7 +92,7 @@ def test_limits_wrapper_and_ops_table():
 def test_scan_runs_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()                                                    # (no _L, no _h: touching the library would raise AttributeError)
+    ctx = A.bare_ctx()                                             # (no _L, no _h: touching the library would raise AttributeError)
     for kdt in (torch.float32, torch.int32, torch.float64, torch.int64):
         for vdt in (torch.float32, torch.int64):
             for kw in ({}, {"op": "min"}, {"op": "max", "exclusive": True}, {"op": "count"}):

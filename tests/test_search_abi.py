@@ -4,16 +4,15 @@ the library exports them, the binding lists them apart from the other surfaces, 
 call answers on the host, the Python wrappers refuse what never needs a device to be refused, and the numpy expectation and
 the model of the merge path's decomposition in tests/search_expect.py are what their docstrings say."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import search_expect as S
 import sort_rows_expect as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_search_sorted": ["msd_ctx *ctx", "const void *d_sorted", "int key_type", "uint64_t n", "const void *d_needles", "uint64_t m",
                           "int needles_sorted", "int side", "const uint64_t *d_positions", "uint64_t *d_out"],
@@ -21,20 +20,10 @@ SIGNATURES = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_search_hip.h")).read()
-    return text, re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_two_functions_and_the_sides():
-    text, flat = _header()
+    text, flat = A.header("msd_search_hip.h")
     assert '#include "msd_radix_hip.h"' in flat
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
     assert re.search(r"enum \{ MSD_SEARCH_LEFT = 0, MSD_SEARCH_RIGHT = 1 \};", flat)
     # the header says where the order differs from torch, and what is taken on trust
     for word in ("torch.searchsorted", "-0.0", "NaN", "totalOrder", "TRUSTED"):
@@ -42,22 +31,11 @@ def test_header_declares_the_two_functions_and_the_sides():
 
 
 def test_the_other_headers_declare_none_of_it():
-    for h in ("msd_radix_hip.h", "msd_runs_hip.h", "msd_reduce_hip.h"):
-        assert "msd_search" not in open(os.path.join(ROOT, "include", h)).read(), h
+    A.check_no_other_header_has("msd_search_hip.h", "msd_search", headers=("msd_radix_hip.h", "msd_runs_hip.h", "msd_reduce_hip.h"))
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.SEARCH_EXPORTS) == sorted(SIGNATURES)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        for other in (_lib.EXPORTS, _lib.SORT_KEYS_EXPORTS, _lib.SORT_ROWS_EXPORTS, _lib.RUNS_EXPORTS, _lib.REDUCE_EXPORTS, _lib.RCCL_EXPORTS):
-            assert f not in other, f
-        assert list(getattr(L, f).argtypes) == list(_lib.SEARCH_EXPORTS[f]), f
-        assert len(_lib.SEARCH_EXPORTS[f]) == len(SIGNATURES[f]), f
-    assert any(d.endswith("msd_search_hip.h") for d in _build.DEPS)
-    assert "msd_search.hpp" in _build.DEPS
+    A.check_exports("SEARCH_EXPORTS", SIGNATURES, "msd_search_hip.h", "msd_search.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -79,25 +57,12 @@ def test_limits_answer_on_the_host():
         tile, direct = C.c_uint64(0), C.c_uint64(0)
         assert L.msd_search_sorted_limits(kb, C.byref(tile), C.byref(direct)) == 0
         assert tile.value >= 64 and direct.value >= 64
-    a, b = C.c_uint64(77), C.c_uint64(78)
-    for kb in (0, 2, 16, -4, 5):
-        assert L.msd_search_sorted_limits(kb, C.byref(a), C.byref(b)) == -1 and (a.value, b.value) == (77, 78)
-    for kb in (4, 8):
-        assert L.msd_search_sorted_limits(kb, None, C.byref(b)) == -1 and b.value == 78
-        assert L.msd_search_sorted_limits(kb, C.byref(a), None) == -1 and a.value == 77
-        assert L.msd_search_sorted_limits(kb, None, None) == -1
-
-
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
+    A.check_limits_refusals(L.msd_search_sorted_limits, 2, bad_widths=(0, 2, 16, -4, 5))
 
 
 def test_limits_wrapper():
     from inplacemsdradixsort_amd import MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     for kb in (4, 8):
         tile, direct = C.c_uint64(0), C.c_uint64(0)
@@ -111,7 +76,7 @@ def test_limits_wrapper():
 def test_searchsorted_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()                                                    # (no _L, no _h: touching the library would raise AttributeError)
+    ctx = A.bare_ctx()                                             # (no _L, no _h: touching the library would raise AttributeError)
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         for kw in ({}, {"right": True}, {"needles_sorted": True}, {"sort_needles": True}, {"positions": torch.arange(6)},
                    {"out": torch.zeros(2, 3, dtype=torch.int64)}):

@@ -4,16 +4,15 @@ the agreed argument lists, the library exports them, the binding lists them apar
 refused first, the limits call answers on the host, the Python wrapper refuses what never needs a device to be refused, and
 the numpy expectation and the model of the kernels in tests/set_expect.py are what their docstrings say."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import set_expect as X
 import sort_rows_expect as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_set_sorted": ["msd_ctx *ctx", "int op", "const void *d_a", "uint64_t n", "const void *d_b", "uint64_t m", "int key_type", "uint64_t cap", "void *d_out",
                        "uint64_t *d_out_origin", "uint64_t *d_num_out"],
@@ -22,20 +21,10 @@ SIGNATURES = {
 OPS = ("intersection", "union", "difference", "symmetric_difference")
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_setops_hip.h")).read()
-    return text, re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_two_functions():
-    text, flat = _header()
+    text, flat = A.header("msd_setops_hip.h")
     assert '#include "msd_radix_hip.h"' in flat
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
     for name, value in (("MSD_SET_INTERSECTION", 0), ("MSD_SET_UNION", 1), ("MSD_SET_DIFFERENCE", 2), ("MSD_SET_SYMMETRIC_DIFFERENCE", 3)):
         assert re.search(r"#define %s %d\b" % (name, value), flat), name
         assert getattr(X, name[len("MSD_SET_"):]) == value
@@ -48,24 +37,11 @@ def test_header_declares_the_two_functions():
 
 
 def test_the_other_headers_declare_none_of_it():
-    for h in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if h != "msd_setops_hip.h":
-            assert "msd_set_sorted" not in open(os.path.join(ROOT, "include", h)).read(), h
+    A.check_no_other_header_has("msd_setops_hip.h", "msd_set_sorted")
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.SETOPS_EXPORTS) == sorted(SIGNATURES)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        for other in (_lib.EXPORTS, _lib.SORT_KEYS_EXPORTS, _lib.SORT_ROWS_EXPORTS, _lib.RUNS_EXPORTS, _lib.REDUCE_EXPORTS, _lib.SEARCH_EXPORTS,
-                      _lib.MERGE_EXPORTS, _lib.RCCL_EXPORTS):
-            assert f not in other, f
-        assert list(getattr(L, f).argtypes) == list(_lib.SETOPS_EXPORTS[f]), f
-        assert len(_lib.SETOPS_EXPORTS[f]) == len(SIGNATURES[f]), f
-    assert any(d.endswith("msd_setops_hip.h") for d in _build.DEPS)
-    assert "msd_setops.hpp" in _build.DEPS
+    A.check_exports("SETOPS_EXPORTS", SIGNATURES, "msd_setops_hip.h", "msd_setops.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -89,25 +65,12 @@ def test_limits_answer_on_the_host():
         assert 64 <= tile.value < 0xFFFF                            # (the kernels keep a local index in 16 bits, all ones apart)
         assert scan.value >= 64
         assert L.msd_merge_sorted_limits(kb, C.byref(merge_tile)) == 0 and merge_tile.value == tile.value   # the merge's splits
-    a, b = C.c_uint64(77), C.c_uint64(78)
-    for kb in (0, 2, 5, 16, -4):
-        assert L.msd_set_sorted_limits(kb, C.byref(a), C.byref(b)) == -1 and (a.value, b.value) == (77, 78)
-    for kb in (4, 8):
-        assert L.msd_set_sorted_limits(kb, None, C.byref(b)) == -1 and b.value == 78
-        assert L.msd_set_sorted_limits(kb, C.byref(a), None) == -1 and a.value == 77
-        assert L.msd_set_sorted_limits(kb, None, None) == -1
-
-
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
+    A.check_limits_refusals(L.msd_set_sorted_limits, 2, bad_widths=(0, 2, 5, 16, -4))
 
 
 def test_limits_wrapper():
     from inplacemsdradixsort_amd import MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     for kb in (4, 8):
         tile, scan = C.c_uint64(0), C.c_uint64(0)
@@ -121,7 +84,7 @@ def test_limits_wrapper():
 def test_set_sorted_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()                                                    # (no _L, no _h: touching the library would raise AttributeError)
+    ctx = A.bare_ctx()                                             # (no _L, no _h: touching the library would raise AttributeError)
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         a, b = torch.zeros(5, dtype=dt), torch.zeros(3, dtype=dt)
         for op in OPS:

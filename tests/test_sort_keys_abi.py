@@ -4,12 +4,12 @@ them, the binding lists them apart from the surface of msd_radix_hip.h, a null c
 wrapper refuses what never needs a device to be refused."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_support as A
+
 SIGNATURES = {
     "msd_sort_keys": ["msd_ctx *ctx", "void *d_keys", "int key_type", "uint64_t n", "int order"],
     "msd_sort_pairs_keys": ["msd_ctx *ctx", "void *d_keys", "int key_type", "uint64_t *d_rids", "uint64_t n", "int order"],
@@ -17,35 +17,16 @@ SIGNATURES = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_sort_keys_hip.h")).read()
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_three_functions():
-    flat = _header()
+    _, flat = A.header("msd_sort_keys_hip.h")
     assert '#include "msd_radix_hip.h"' in flat
     for name, value in (("MSD_ASCENDING", 0), ("MSD_DESCENDING", 1)):
         assert re.search(r"\b%s\s*=\s*%d\b" % (name, value), flat), name
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.SORT_KEYS_EXPORTS) == sorted(SIGNATURES)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        assert f not in _lib.EXPORTS, f
-        assert getattr(L, f).argtypes is not None and len(getattr(L, f).argtypes) == len(SIGNATURES[f]), f
-        assert list(getattr(L, f).argtypes) == list(_lib.SORT_KEYS_EXPORTS[f]), f
-    assert any(d.endswith("msd_sort_keys_hip.h") for d in _build.DEPS)
-    assert "msd_reverse.hpp" in _build.DEPS
+    A.check_exports("SORT_KEYS_EXPORTS", SIGNATURES, "msd_sort_keys_hip.h", "msd_reverse.hpp")
 
 
 def test_null_context_is_refused_with_every_other_argument_zero():
@@ -69,15 +50,10 @@ def test_stat_names_are_unknown_to_a_null_context():
         assert L.msd_stat(None, name, C.byref(v)) == -1 and v.value == 77
 
 
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    return MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-
-
 def test_sort_typed_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         with pytest.raises(MsdError):                   # a CPU tensor
             ctx.sort_typed(torch.zeros(8, dtype=dt))
@@ -101,7 +77,7 @@ def test_sort_typed_refuses_before_the_library_is_touched():
 def test_reverse_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     for t, args in ((torch.zeros(8), ()),                                       # a CPU tensor
                     (torch.zeros(8, dtype=torch.int16), ()), (torch.zeros(4, 2), ()),
                     (torch.zeros(8), (5, 4)), (torch.zeros(8), (-1, 2)), (torch.zeros(8), (9,))):

@@ -4,15 +4,13 @@ lists them apart from the other surfaces, a null context is refused first, the l
 Python wrapper refuses what never needs a device to be refused."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_support as A
 import sort_rows_expect as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGNATURES = {
     "msd_sort_rows": ["msd_ctx *ctx", "const void *d_keys", "int key_type", "uint64_t rows", "uint64_t row_len", "uint64_t row_stride",
                       "int order", "void *d_out_keys", "uint64_t *d_out_idx"],
@@ -22,33 +20,14 @@ SIGNATURES = {
 FLOORS = {(4, False): 24576, (8, False): 17408, (4, True): 16384, (8, True): 8192}
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_sort_rows_hip.h")).read()
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_two_functions():
-    flat = _header()
+    _, flat = A.header("msd_sort_rows_hip.h")
     assert '#include "msd_sort_keys_hip.h"' in flat
-    declared = re.findall(r"\bint (msd_\w+)\s*\(", flat)
-    assert sorted(declared) == sorted(SIGNATURES), declared
-    for f, want in SIGNATURES.items():
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, flat)
-        assert m, f
-        assert [a.strip() for a in m.group(1).split(",")] == want, f
+    A.check_signatures(flat, SIGNATURES)
 
 
 def test_library_exports_and_binding_lists_them_apart():
-    from inplacemsdradixsort_amd import _build, _lib
-    L = _lib.load()
-    assert sorted(_lib.SORT_ROWS_EXPORTS) == sorted(SIGNATURES)
-    for f in SIGNATURES:
-        assert hasattr(L, f), f
-        assert f not in _lib.EXPORTS and f not in _lib.SORT_KEYS_EXPORTS, f
-        assert getattr(L, f).argtypes is not None and len(getattr(L, f).argtypes) == len(SIGNATURES[f]), f
-        assert list(getattr(L, f).argtypes) == list(_lib.SORT_ROWS_EXPORTS[f]), f
-    assert any(d.endswith("msd_sort_rows_hip.h") for d in _build.DEPS)
-    assert "msd_sort_rows.hpp" in _build.DEPS
+    A.check_exports("SORT_ROWS_EXPORTS", SIGNATURES, "msd_sort_rows_hip.h", "msd_sort_rows.hpp")
 
 
 def test_null_context_is_refused_whatever_the_other_arguments_are():
@@ -87,17 +66,10 @@ def test_stat_names_are_unknown_to_a_null_context():
         assert L.msd_stat(None, name, C.byref(v)) == -1 and v.value == 77
 
 
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    c = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-    c.device = 0
-    return c
-
-
 def test_sort_rows_refuses_before_the_library_is_touched():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     for dt in (torch.float32, torch.int32, torch.float64, torch.int64):
         for kw in ({}, {"descending": True}, {"indices": True}):
             with pytest.raises(MsdError):                       # a CPU tensor
@@ -128,7 +100,7 @@ def test_sort_rows_refuses_before_the_library_is_touched():
 
 def test_limits_wrapper_and_stats_names():
     from inplacemsdradixsort_amd import MsdContext, MsdError, _lib
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     ctx._L = _lib.load()
     assert ctx.sort_rows_limits(MsdContext.KEY_F32) >= FLOORS[(4, False)]
     assert ctx.sort_rows_limits(MsdContext.KEY_I64, indices=True) >= FLOORS[(8, True)]

@@ -1,19 +1,14 @@
 """Radix select / top-k at the ABI level (no GPU): include/msd_radix_hip.h declares the five entry points and the
 MSD_SMALLEST / MSD_LARGEST enum, the built library exports the symbols, the Python binding lists them."""
-import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_support as A
+
 SYMBOLS = ["msd_topk_u32", "msd_topk_u64", "msd_topk_pairs_u64", "msd_select_u32", "msd_select_u64"]
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_radix_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 def test_header_declares_topk_and_select():
-    h = _header()
+    _, h = A.header("msd_radix_hip.h")
     for s in SYMBOLS:
         assert re.search(r"\bint\s+%s\s*\(\s*msd_ctx\s*\*" % s, h), s
     # inputs are const: the calls do not modify the caller's arrays
@@ -23,7 +18,7 @@ def test_header_declares_topk_and_select():
 
 
 def test_enum_values():
-    m = re.search(r"enum\s*\{([^}]*MSD_SMALLEST[^}]*)\}", _header())
+    m = re.search(r"enum\s*\{([^}]*MSD_SMALLEST[^}]*)\}", A.header("msd_radix_hip.h")[1])
     assert m, "enum with MSD_SMALLEST not found"
     vals = dict((k, int(v)) for k, v in re.findall(r"(MSD_\w+)\s*=\s*(-?\d+)", m.group(1)))
     assert vals == {"MSD_SMALLEST": 0, "MSD_LARGEST": 1}

@@ -3,12 +3,11 @@ functions with the agreed argument lists, the library exports them and the bindi
 before anything touches a device, the envelope is reported, and the layout rule of the Python wrapper -- which needs no
 device -- accepts and refuses what it should on CPU tensors."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_support as A
+
 NEW = ["msd_topk_rows", "msd_topk_rows_limits"]
 ARGS = {
     "msd_topk_rows": ["msd_ctx *ctx", "const void *d_keys", "int key_type", "uint64_t rows", "uint64_t row_len", "uint64_t row_stride",
@@ -17,16 +16,9 @@ ARGS = {
 }
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_radix_hip.h")).read()
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 @pytest.mark.parametrize("f", NEW)
 def test_header_declares_the_function_with_its_argument_list(f):
-    m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % f, _header())
-    assert m, f
-    assert [a.strip() for a in m.group(1).split(",")] == ARGS[f]
+    A.check_signatures(A.header("msd_radix_hip.h")[1], {f: ARGS[f]}, exactly=False)
 
 
 def test_library_exports_and_binding_lists_them():
@@ -71,14 +63,9 @@ def test_limits_refuses_bad_arguments_and_leaves_the_outputs():
 
 # ---- the layout rule of MsdContext.topk_rows: no device needed
 
-def _ctx():
-    from inplacemsdradixsort_amd import MsdContext
-    return MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
-
-
 def test_layouts_that_are_taken():
     import torch
-    lay = _ctx()._rows_layout
+    lay = A.bare_ctx()._rows_layout
     assert lay(torch.empty(50257)) == (1, 50257, 50257)                       # 1-D: one row
     assert lay(torch.empty(7, 131)) == (7, 131, 131)
     assert lay(torch.empty(3, 5, 131)) == (15, 131, 131)                      # contiguous: the leading dimensions collapse
@@ -99,7 +86,7 @@ def test_layouts_that_are_taken():
 def test_layouts_that_are_refused():
     import torch
     from inplacemsdradixsort_amd import MsdError
-    lay = _ctx()._rows_layout
+    lay = A.bare_ctx()._rows_layout
     x = torch.empty(64, 48)
     for bad in (x.t(),                                  # a transposed matrix: the last dimension has stride 48
                 x[:, ::2],                              # every other column
@@ -114,7 +101,7 @@ def test_layouts_that_are_refused():
 def test_dtype_without_a_key_order_is_refused_before_the_layout():
     import torch
     from inplacemsdradixsort_amd import MsdContext, MsdError
-    ctx = _ctx()
+    ctx = A.bare_ctx()
     for dt in (torch.float16, torch.bfloat16, torch.int16, torch.uint8, torch.bool):
         with pytest.raises(MsdError):
             ctx.topk_rows(torch.zeros(4, 8).to(dt), 2)

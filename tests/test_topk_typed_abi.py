@@ -3,28 +3,20 @@ them with the agreed enum values, the library exports them, arguments are refuse
 the key codec -- through the two host-only C functions alone -- is a bijection whose unsigned order is the order of the
 key type.  Every expectation is computed here with numpy, never with the library."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_support as A
+from sort_rows_expect import VIEWS
+
 KEY_TYPES = {"MSD_KEY_U32": 0, "MSD_KEY_I32": 1, "MSD_KEY_F32": 2, "MSD_KEY_U64": 3, "MSD_KEY_I64": 4, "MSD_KEY_F64": 5}
 NEW = ["msd_topk_keys", "msd_select_key", "msd_key_encode", "msd_key_decode"]
-# key type -> (unsigned view, typed view)
-VIEWS = {0: (np.uint32, np.uint32), 1: (np.uint32, np.int32), 2: (np.uint32, np.float32),
-         3: (np.uint64, np.uint64), 4: (np.uint64, np.int64), 5: (np.uint64, np.float64)}
-
-
-def _header():
-    text = open(os.path.join(ROOT, "include", "msd_radix_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
 
 
 def test_header_declares_the_functions_and_the_enum():
-    text = _header()
-    flat = re.sub(r"\s+", " ", text)
+    _, flat = A.header("msd_radix_hip.h")
     for name, value in KEY_TYPES.items():
         assert re.search(r"\b%s\s*=\s*%d\b" % (name, value), flat), name
     for f in NEW:
@@ -179,7 +171,7 @@ def test_python_dispatch_refuses_unknown_dtypes():
     """MsdContext._key_type needs no device: the dtype table and its error."""
     import torch
     from inplacemsdradixsort_amd import MsdContext, MsdError
-    ctx = MsdContext.__new__(MsdContext)  # (no msd_create: there may be no GPU)
+    ctx = A.bare_ctx()
     want = {torch.float32: 2, torch.int32: 1, torch.float64: 5, torch.int64: 4}
     if hasattr(torch, "uint32"):
         want[torch.uint32] = 0
