@@ -371,6 +371,15 @@ int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, 
  *   if it left no parent or more than travelled, if its next parents stay on the device or take a register-resident
  *   pass, if it carries the check behind a sampled bit skip, or if a buffer of the next round would have to grow;
  *   0 = always (A/B comparisons).  msd_stat "rounds_planned_early" counts the rounds planned this way.
+ * "front_count": u32 keys, a whole-array sort whose plan is two direct 8-bit rounds: 1 (default) = the top 16 key bits are
+ *   counted once before the first round (csrc/msd_front16.hpp) and ONE readback tells the host what the bit-skip sample,
+ *   the first round's sample and the second round's exact count used to tell it in three; both rounds are placed from
+ *   exact counts and enqueued without waiting for each other.  The sort takes the usual path, on untouched keys, if a
+ *   whole leading digit is constant, if either round's children are uneven or its keys come in runs, if a 16-bit counter
+ *   overflowed, or if some child of the second round is no counting leaf; 0 = never (A/B comparisons).  msd_stat
+ *   "front_count_sorts" / "front_count_declined" count the sorts that took the path / counted and then declined it.
+ * "front_min": smallest sort (elements) the front pass is tried on (default 2^29: at 2^28 keys it loses 0.7 %, the second
+ *   round no longer starts behind a read that left a quarter of the array in the memory-side cache; tests lower it).
  * "merge_leaf": msd_merge_buckets_u32: 0 (default) = by bucket size, 1 = the register-resident leaf, 2 = the 16-bit-counter leaf.
  * "regpart": u64 keys / tuples: 1 (default) = segments of <= 17408 elements take the register-resident
  *   partition pass (csrc/msd_regpart.hpp) instead of a general round, 0 = never.

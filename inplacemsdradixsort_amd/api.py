@@ -1241,7 +1241,7 @@ class MsdContext:
         out = {}
         for name in ("rounds", "parents", "stripes", "children", "slots", "holes", "chain_steps",
                      "small_segments", "count_segments", "big_count_segments", "direct_rounds", "regpart_rounds", "skipped_bits", "bit_skip_restarts", "bit_skip_checked_by_histogram",
-                     "leaves_behind_round", "rounds_planned_early", "excess_blocks", "child_scan_split_rounds", "count16_rejected", "count_slow_segments",
+                     "leaves_behind_round", "rounds_planned_early", "front_count_sorts", "front_count_declined", "excess_blocks", "child_scan_split_rounds", "count16_rejected", "count_slow_segments",
                      "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes",
                      "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below",
                      "topk_rows_kernel_rows", "topk_rows_looped_rows",

@@ -423,8 +423,20 @@ __global__ __launch_bounds__(1024) void direct_hist_kernel(const K *__restrict__
 	}
 }
 
+// Direct placement declines a parent whose biggest child has more than 1.25 x the keys of its smallest one, or whose
+// keys come in runs.  One rule for direct_plan_kernel and for the front pass (msd_front16.hpp).
+#ifndef MSD_UNEVEN_PCT // (overridable for experiments)
+#define MSD_UNEVEN_PCT 125
+#endif
+__device__ __forceinline__ bool direct_declines(uint32_t mn, uint32_t mx, uint32_t adj_same, uint32_t adj_seen)
+{
+	// (equal neighbours: 1/256 of the pairs on random keys; an eighth of them means runs)
+	const bool runs = (uint64_t)adj_same * 8u > adj_seen;
+	return runs || !(mn > 0 && (double)mx * 100.0 <= (double)MSD_UNEVEN_PCT * (double)mn);
+}
+
 // One workgroup per parent: counts (sampled or exact) -> child boundaries on the slot grid; a parent
-// whose biggest child has more than 1.25 x the keys of its smallest one is reported as uneven.
+// that direct_declines is reported as uneven.
 template <int B>
 __global__ __launch_bounds__(256) void direct_plan_kernel(const Parent *__restrict__ parents, DirectPlan *__restrict__ plans,
 	Counters *__restrict__ ctr)
@@ -450,12 +462,7 @@ __global__ __launch_bounds__(256) void direct_plan_kernel(const Parent *__restri
 		atomicMax(&s_mx, (uint32_t)c);
 	}
 	__syncthreads();
-	// (equal neighbours: 1/256 of the pairs on random keys; an eighth of them means runs)
-	const bool runs = (uint64_t)plan->adj_same * 8u > plan->adj_seen;
-#ifndef MSD_UNEVEN_PCT // (overridable for experiments)
-#define MSD_UNEVEN_PCT 125
-#endif
-	if (d == 0 && (runs || !(s_mn > 0 && (double)s_mx * 100.0 <= (double)MSD_UNEVEN_PCT * (double)s_mn))) atomicAdd(&ctr->direct_uneven, 1u);
+	if (d == 0 && direct_declines(s_mn, s_mx, plan->adj_same, plan->adj_seen)) atomicAdd(&ctr->direct_uneven, 1u);
 }
 
 // The `need` lanes with the smallest 10-bit value among the eligible ones (ties: lower lane first).
@@ -1428,6 +1435,7 @@ __global__ __launch_bounds__(256) void collect_kernel(const Parent *__restrict__
 }
 
 } // namespace msd
+#include "msd_front16.hpp"
 #include "msd_regpart.hpp"
 namespace msd {
 

@@ -80,6 +80,8 @@ struct msd_ctx {
 	int mid_leaf = 1;      // u32 keys: merge_count_kernel (list mode) in front of count_walk_kernel (0: A/B comparisons)
 	int early_leaves = 1;  // keys only: the counting leaves go behind a last round without waiting for its end (0: A/B comparisons)
 	int early_plan = 1;    // a round that is not the last: the next round is planned and enqueued while its fix-up runs (0: A/B comparisons)
+	int front_count = 1;   // u32 keys, two direct 8-bit rounds: the top 16 bits are counted once up front and both rounds placed from that (msd_front16.hpp; 0: A/B comparisons)
+	uint64_t front_min = 1ull << 29; // smallest sort the front pass is tried on (tools/size_sweep.py: 0.7 % slower at 2^28 keys, 1 % faster at 2^29, 1.5 % at 2^30)
 	const uint32_t *order_keys = nullptr; // msd_order_low16_counts_u32 has run on these keys and its tables are still in the slab
 	uint64_t order_n = 0;
 	int merge_leaf = 0;    // msd_merge_buckets_u32: 0 = by bucket size, 1 = merge_place16_kernel, 2 = merge_count_kernel (tests)
@@ -756,6 +758,85 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		return MSD_OK;
 	}
 
+	// ---- the front pass (msd_front16.hpp): a whole-array sort of u32 keys whose plan is two direct 8-bit rounds counts the
+	// top 16 key bits once, before round 0.  ONE readback then tells the host what it used to learn in three instalments
+	// (the bit-skip sample, round 0's sample, round 1's exact count): the exact OR / AND of the keys, round 0's children =
+	// round 1's parents, both rounds' verdicts on direct placement, and that every child of round 1 is a counting leaf.
+	// Both rounds are placed from exact counts (front_apply_kernel where direct_sample_kernel / direct_hist_kernel ran), and
+	// the host enqueues round 0, round 1 and the leaves without waiting in between (plan_next_early, early_summary).
+	// Declined -- the sort goes on as it always did, the keys are untouched -- if a whole leading digit is constant, if
+	// either round is uneven or has runs, if a counter overflowed, or if some child is no counting leaf.  Inputs that a
+	// sample of 2^15 keys shows to be hopeless (front_probe_kernel: Zipf keys, small key ranges, sorted input) are declined
+	// without the read: the counting kernel returns at once, the same readback says so.
+	bool front = false; // this sort takes the front path
+	FrontSummary fsum;  // the summary as read back
+	// (device) the 2^16 counts and the summary live in the second quarter of the leaf lists, which nothing uses before the
+	// leaves run; the per-workgroup partials in the round slab, which is free before round 0
+	uint32_t *front_hist() const { return reinterpret_cast<uint32_t *>(c->lists + c->lists_cap); }
+	FrontSummary *front_sum() const { return reinterpret_cast<FrontSummary *>(front_hist() + (size_t)kP * kP); }
+	int front_count()
+	{
+		if constexpr (!HV && sizeof(K) == 4) {
+			if (!c->front_count || job.kind != SortJob<K>::kWhole || job.stop_bits || end_bit != 32 || cur.size() != 1 || c->direct_mode == 0 ||
+			    n < c->direct_min || n < c->front_min || n < ((uint64_t)1 << 20) || n >= ((uint64_t)1 << 32))
+				return MSD_OK;
+			{ // would today's plan run two direct 8-bit rounds on evenly spread keys?  (Round 1's parents an eighth below and
+			  // above the mean must still get 8-bit digits: near the size where the planner changes its mind -- 2^27 -- half
+			  // of them do not, and the count would be paid for nothing.)
+				const uint64_t mean = n / kP;
+				if (pick_width(n, 32, small_max, count_bits) != 8 || mean - mean / 8 < c->direct_min_parent ||
+				    pick_width(mean - mean / 8, 24, small_max, count_bits) != 8 || pick_width(mean + mean / 8, 24, small_max, count_bits) != 8)
+					return MSD_OK;
+			}
+			// (the slab as round 0 reserves it, the lists as round 1 does: nothing grows because of this pass, and the
+			// lists do not move between here and round 1)
+			int rc = slab_reserve(c, round_bytes_estimate<K, V>(n, c->sm_count), true);
+			if (!rc) rc = lists_reserve(c, (size_t)kP * kP + 16, 0, 0);
+			if (rc) return rc;
+			static_assert(((size_t)kP * kP + 16) * sizeof(Segment) >= (size_t)kP * kP * 4 + sizeof(FrontSummary), "the counts and the summary fit a quarter of the lists");
+			const unsigned grid = (unsigned)std::min<uint64_t>({ (uint64_t)c->sm_count, std::max<uint64_t>(1, n >> 18), c->slab_bytes / (kF16Words * sizeof(uint32_t)) });
+			if (!grid) return MSD_OK;
+			uint32_t *partials = reinterpret_cast<uint32_t *>(c->slab);
+			LAUNCH(c, (front_probe_kernel<K>), 1, 1024, 0, keys, n, 16u, front_sum()); // (clears the summary first)
+			LAUNCH(c, (front_count16_kernel<K>), grid, kF16Th, kF16Lds, keys, n, 16u, partials, front_sum());
+			LAUNCH(c, front_plan_kernel, kP, 256, 0, partials, grid, front_hist(), front_sum(), 16u, job.stop_bits, count_bits, small_max,
+			       std::max<uint64_t>(small_max, kCountMedMax));
+			LAUNCH(c, front_top_kernel, 1, 256, 0, front_sum());
+			HIPCHK(c, hipMemcpyAsync(c->pinned, front_sum(), sizeof(FrontSummary), hipMemcpyDeviceToHost, c->stream));
+			HIPCHK(c, hipStreamSynchronize(c->stream));
+			memcpy(&fsum, c->pinned, sizeof fsum);
+			phase_mark(c, "front count");
+			const uint64_t vary = (fsum.v_or ^ fsum.v_and) & low_mask;
+			const int top = vary ? 64 - __builtin_clzll(vary) : 0;
+			if (fsum.hopeless) { // front_probe_kernel: skewed or in runs by a sample, nothing was counted
+				add_stat(c, "front_count_declined", 1);
+				return MSD_OK;
+			}
+			bool ok = !fsum.overflow && top + 8 > end_bit && !fsum.uneven[0] && !fsum.uneven[1] && fsum.nroute[kRouteCount + 1] == (uint32_t)kP * kP;
+			std::vector<Segment> next = front_parents();
+			uint64_t total = 0;
+			for (const Segment &sg : next) { // round 1 as the host will plan it: every parent big enough, with an 8-bit digit
+				ok = ok && sg.count >= c->direct_min_parent && pick_width(sg.count, sg.bits, small_max, count_bits) == 8;
+				total += sg.count;
+			}
+			if (!fsum.overflow && total != n) return fail(c, MSD_EINTERNAL, "front count: the counts add up to %llu of %llu keys", (unsigned long long)total, (unsigned long long)n);
+			add_stat(c, ok ? "front_count_sorts" : "front_count_declined", 1);
+			front = ok;
+		}
+		return MSD_OK;
+	}
+	// round 0's children, which are round 1's parents, from the front pass's summary
+	std::vector<Segment> front_parents() const
+	{
+		std::vector<Segment> v;
+		uint64_t at = 0;
+		for (int d = 0; d < kP; ++d) {
+			v.push_back({ at, fsum.top[d], (uint32_t)end_bit - 8u, 0 });
+			at += fsum.top[d];
+		}
+		return v;
+	}
+
 	// ---- segments that need no partition round go to the leaf lists at once
 	int route_to_leaves()
 	{
@@ -1041,9 +1122,18 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		uint64_t max_piece = 0; // a piece is at most one stripe's share of its parent's slots; the kernel counts it in 16 bits
 		for (size_t i = 0; i < np && try_direct; ++i)
 			max_piece = std::max<uint64_t>(max_piece, rp.parents[i].count / B / (rp.parents[i].stripe_hi - rp.parents[i].stripe_lo) + 2);
-		if (!try_direct || max_piece >= 65535) return MSD_OK;
+		// (the front path stands on both rounds being direct and shaped as planned: otherwise the sort goes on from here
+		// with the usual readbacks)
+		if (front && (round > 1 || np != (round == 0 ? 1u : (uint32_t)kP))) front = false;
+		if (!try_direct || max_piece >= 65535) {
+			front = false;
+			return MSD_OK;
+		}
 		const RoundBufs &rb = r.rb;
-		if (np == 1) {
+		if (front) {
+			// exact counts from the front pass: round 0's are the row sums, round 1's parent d has row d
+			LAUNCH(c, front_apply_kernel, np, 256, 0, rb.plans, front_hist(), front_sum(), (uint32_t)round);
+		} else if (np == 1) {
 			// sample about 2^22 keys or more, as runs of 256 spread evenly over the parent
 			const uint64_t nruns = rp.parents[0].count / 256;
 			const uint32_t every = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, nruns / 16384));
@@ -1059,7 +1149,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			LAUNCH(c, (direct_hist_kernel<K>), ns, 1024, 0, keys, rb.stripes, rb.parents, rb.plans, r.hist_checks ? vres : nullptr);
 		}
 		LAUNCH(c, (direct_plan_kernel<B>), np, 256, 0, rb.parents, rb.plans, ctr);
-		phase_mark(c, np == 1 ? "A sample" : "A histogram");
+		phase_mark(c, front ? "A front counts" : np == 1 ? "A sample" : "A histogram");
 		// The plan's verdict (Counters::direct_uneven: some parent's children are too unequal, or its keys come in
 		// runs) stays on the device: the direct kernel returns at once if it is non-zero, the streaming kernel
 		// launched behind it if it is zero.  The host learns it with the round's summary.
@@ -1158,6 +1248,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		       rb.next_parents, small(), small_count(), (HV || sp) ? nullptr : big, big_cap, ctr,
 		       (sp && job.counts) ? job.counts : nullptr, job.splitters ? job.nsplit + 1u : nc, job.stop_bits);
 		if (r.leaves_follow) {
+			if (front && round == 1) return MSD_OK; // (the lists' lengths are known: front_plan_kernel has counted the children by route)
 			if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
 			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kEarlyOff, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
 			HIPCHK(c, hipEventRecord(c->ev_early, c->stream));
@@ -1166,6 +1257,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// first; one parked round at a time): the counters and the first next parents travel now, so that the host can
 			// plan the next round while this one's fix-up runs
 			r.plan_ahead = std::min<size_t>(r.rp.round_keys / (small_max + 1) + 2, kReadAhead);
+			if (front && round == 0) return MSD_OK; // (the next parents are known: the front pass's row sums)
 			if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
 			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kPlanCtrOff, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
 			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kPlanSegOff, rb.next_parents, r.plan_ahead * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
@@ -1224,14 +1316,25 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	// would have to grow (that synchronises).
 	int plan_next_early(Round &r)
 	{
-		HIPCHK(c, hipEventSynchronize(c->ev_early));
-		Counters hc;
-		memcpy(&hc, (char *)c->pinned + kPlanCtrOff, sizeof hc);
+		// (the front path, round 0: nothing travelled and nothing is waited for -- the next parents are the front pass's row
+		// sums, no child went to a leaf list, and the round's errors come with its parked counters like everything else)
+		const bool known = front && round == 0;
+		Counters hc = {};
+		if (known)
+			hc.next_parents = kP;
+		else {
+			HIPCHK(c, hipEventSynchronize(c->ev_early));
+			memcpy(&hc, (char *)c->pinned + kPlanCtrOff, sizeof hc);
+		}
 		bool ok = !hc.errors && hc.next_parents != 0 && hc.next_parents <= r.plan_ahead;
 		std::vector<Segment> next;
 		if (ok) {
-			const Segment *sg = (const Segment *)((char *)c->pinned + kPlanSegOff);
-			next.assign(sg, sg + hc.next_parents);
+			if (known)
+				next = front_parents();
+			else {
+				const Segment *sg = (const Segment *)((char *)c->pinned + kPlanSegOff);
+				next.assign(sg, sg + hc.next_parents);
+			}
 			sort_by_start(next);
 			if constexpr (sizeof(K) == 8) {
 				if (c->regpart) { // (rounds(): such parents take a register-resident pass, or their list stays on the device)
@@ -1271,9 +1374,13 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	// (count_leaves).  If the round left a parent after all, or no counting leaf: the ordinary summary.
 	int early_summary(Round &r)
 	{
-		HIPCHK(c, hipEventSynchronize(c->ev_early));
-		Counters hc;
-		memcpy(&hc, (char *)c->pinned + kEarlyOff, sizeof hc);
+		Counters hc = {};
+		if (front && round == 1) // (nothing travelled: every child is a counting leaf, as front_plan_kernel has counted them)
+			hc.ncount = fsum.nroute[kRouteCount + 1];
+		else {
+			HIPCHK(c, hipEventSynchronize(c->ev_early));
+			memcpy(&hc, (char *)c->pinned + kEarlyOff, sizeof hc);
+		}
 		if (hc.next_parents || hc.ncount == 0 || hc.errors) return round_summary(r);
 		prev_direct = r.tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
 		if (prev_direct) add_stat(c, "direct_rounds", 1);
@@ -1361,7 +1468,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		nsmall_host = ncount_host = nbig_host = dev_np = 0;
 		round = 0;
 		pending.open = parked.open = enqueue_ahead = false;
-		prev_direct = unverified = false;
+		prev_direct = unverified = front = false;
 		HIPCHK(c, hipMemsetAsync(ctr, 0, sizeof(Counters), c->stream));
 		return MSD_OK;
 	}
@@ -1534,7 +1641,8 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 	SortRun<K, V> s(c, keys, vals, n, end_bit, job);
 	int rc = s.initial_segments();
 	if (!rc) rc = s.reserve_keep();
-	if (!rc) rc = s.skip_leading_bits();
+	if (!rc) rc = s.front_count();
+	if (!rc && !s.front) rc = s.skip_leading_bits(); // (the front pass has the exact OR / AND: no whole leading digit is constant)
 	if (!rc) rc = s.route_to_leaves();
 	// the partition rounds; if the exact check behind a sampled leading-bit skip fails -- on a round's histogram pass or on
 	// a pass of its own behind the rounds -- they start over on the bits that really vary (the data is the same multiset)
@@ -1650,6 +1758,7 @@ template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
 	HIPCHK(c, max_lds(&leaf_count_sort_kernel<K, V>, LeafCountLds<K, V>::bytes));
 	if constexpr (!has_val<V>::value) {
 		if constexpr (sizeof(K) == 4) {
+			HIPCHK(c, max_lds(&front_count16_kernel<K>, kF16Lds));
 			HIPCHK(c, max_lds(&count_place16_kernel, kC16Lds));
 			HIPCHK(c, max_lds(&merge_place16_kernel<2>, kC16Lds));
 			HIPCHK(c, max_lds(&merge_place16_kernel<4>, kC16Lds));
@@ -3574,6 +3683,11 @@ int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 		c->early_leaves = value != 0;
 	} else if (!strcmp(name, "early_plan")) {
 		c->early_plan = value != 0;
+	} else if (!strcmp(name, "front_count")) {
+		c->front_count = value != 0;
+	} else if (!strcmp(name, "front_min")) {
+		if (value < 1) return fail(c, MSD_EINVAL, "front_min must be positive");
+		c->front_min = (uint64_t)value;
 	} else if (!strcmp(name, "merge_leaf")) {
 		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "merge_leaf must be 0, 1 or 2");
 		c->merge_leaf = (int)value;

@@ -3,8 +3,9 @@
 
     python tools/fixup_gaps.py <..._kernel_trace.csv> [--skip W] > profiles/fixup_gaps_<tag>.txt
 
-A sort is the run of kernels from one bit-skip sample (vary_kernel) to the last kernel before the next one, or before
-the first kernel that is not the library's sort (input generation, checks).  The first W sorts (bench.py's warm-up)
+A sort is the run of kernels from one bit-skip sample (vary_kernel) or one front pass (front_probe_kernel, where the sort
+tries that path: csrc/msd_front16.hpp; a declined one goes on with the bit-skip sample) to the last kernel before the next one, or before the first kernel that is not the
+library's sort (input generation, checks).  The first W sorts (bench.py's warm-up)
 are dropped; the rest are averaged position by position, so they must all launch the same kernels -- they do for the
 seeded inputs of one config.  Printed: the big four, every other kernel with its duration, every interval of at least
 --gap microseconds in which no kernel runs with the kernels on either side and the host call it sits behind, and the
@@ -13,12 +14,13 @@ import argparse
 import csv
 import re
 
-BIG = ("classify_direct2_kernel", "count_place16_kernel", "direct_hist_kernel")
+BIG = ("classify_direct2_kernel", "count_place16_kernel", "direct_hist_kernel", "front_count16_kernel")
 # the host synchronisation behind which the GPU waits, by the kernel that ran last before it
 # (a round ends with collect_kernel, or with cleanup_kernel where collect_kernel runs behind the child scan)
-HOST_CALL = {"vary_kernel": "run_vary (skip_leading_bits)", "cleanup_kernel": "round_summary",
+HOST_CALL = {"vary_kernel": "run_vary (skip_leading_bits)", "front_top_kernel": "the front pass's readback (front_count)", "cleanup_kernel": "round_summary",
              "collect_kernel": "round_summary, or (collect_kernel behind the child scan) the early copy of the counters",
              "count_walk_kernel": "read_counters (count_leaves)"}
+STARTS = ("vary_kernel", "front_probe_kernel")
 OUTSIDE = ("gen_", "check_", "at::", "elementwise")
 FILLS = "__amd_rocclr"  # the runtime's own fills and copies (hipMemsetAsync, hipMemcpyAsync of a few words): left out, their time counts as idle
 
@@ -49,7 +51,8 @@ def main():
         if nm.startswith(FILLS):
             continue
         inside = not nm.startswith(OUTSIDE)
-        if nm.startswith("vary_kernel") and (cur is None or not cur[-1][2].startswith("vary_kernel")):
+        declined = bool(cur) and nm.startswith("vary_kernel") and all(k[2].startswith("front_") for k in cur)
+        if nm.startswith(STARTS) and not declined and (cur is None or not cur or not cur[-1][2].startswith("vary_kernel")):
             if cur:
                 sorts.append(cur)
             cur = []
