@@ -15,16 +15,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
-
-
-class MsdError(RuntimeError):
-    pass
-
-
-def _torch():
-    import torch
-    return torch
+from . import _args, _lib
+from ._args import MsdError, _torch, ptr   # (the argument rules, their error and the null-or-address of a tensor live in _args.py)
 
 
 class MsdContext:
@@ -65,23 +57,30 @@ class MsdContext:
         self._on_gpu(t)
         if not t.is_contiguous() or t.element_size() != dtype_size:
             raise MsdError("tensor must be contiguous with the expected element size")
-        return C.c_void_p(t.data_ptr())
+        return ptr(t)
 
-    @staticmethod
-    def _check_positions(positions, n: int, what: str = "elements") -> None:
-        """Refuses ``positions`` (``None``: absent) that are not ``n`` contiguous int64 in one dimension."""
-        if positions is not None and (positions.dtype != _torch().int64 or positions.dim() != 1 or positions.numel() != n or not positions.is_contiguous()):
-            raise MsdError(f"positions must be a contiguous 1-D int64 tensor, as many as the {what}")
+    _check_positions = staticmethod(_args.positions)
+
+    def _layout(self, stem: str, keys, rids=None):
+        """``(export, pointers)`` for the key layout: the export named ``stem`` with ``_u32``, ``_u64`` or -- with ``rids`` --
+        ``_pairs_u64`` in place of its ``{}``, and the checked pointers its arguments open with, the keys' and the rids'."""
+        if rids is not None:
+            layout, ptrs = "_pairs_u64", (self._ptr(keys, 8), self._ptr(rids, 8))
+        elif keys.element_size() == 4:
+            layout, ptrs = "_u32", (self._ptr(keys, 4),)
+        else:
+            layout, ptrs = "_u64", (self._ptr(keys, 8),)
+        return getattr(self._L, stem.format(layout)), ptrs
 
     def _value_index_outputs(self, shape, keys, out, out_indices, want_idx: bool, exact: bool = True):
         """``(out, out_indices)``: the values (the keys' dtype) and, with ``want_idx``, the int64 positions, allocated with
         ``shape`` where not given.  ``exact``: contiguous tensors of exactly that shape on the context's GPU; otherwise 1-D
-        tensors of at least ``shape[0]`` elements (:meth:`_ptr` looks at the rest)."""
+        tensors of at least ``shape[0]`` elements (:meth:`_ptr` looks at the rest).  Both dtypes are looked at before
+        either shape, so the checks stand here for the pair and :func:`_args.output` only allocates."""
         torch = _torch()
-        if out is None:
-            out = torch.empty(shape, dtype=keys.dtype, device=keys.device)
-        if want_idx and out_indices is None:
-            out_indices = torch.empty(shape, dtype=torch.int64, device=keys.device)
+        out = _args.output(out, keys.dtype, shape, None, keys.device)
+        if want_idx:
+            out_indices = _args.output(out_indices, torch.int64, shape, None, keys.device)
         outs = (out, out_indices) if want_idx else (out,)
         if out.dtype != keys.dtype or (want_idx and out_indices.dtype != torch.int64):
             raise MsdError("the values have the keys' dtype, the indices are int64")
@@ -103,13 +102,17 @@ class MsdContext:
         self.sort_typed(s, rids=positions)
         return s, positions
 
-    @staticmethod
-    def _limits2(fn, arg: int, what: str) -> Tuple[int, int]:
-        """The two words of a ``*_limits`` call that takes an element width."""
-        a, b = C.c_uint64(), C.c_uint64()
-        if fn(int(arg), C.byref(a), C.byref(b)) != 0:
-            raise MsdError(f"error -1: {what} must be 4 or 8, not {arg}")
-        return int(a.value), int(b.value)
+    def _limits(self, export: str, words: int, arg, what: Optional[str] = None, indices: bool = False):
+        """The ``words`` numbers the ``*_limits`` call ``export`` answers with (one: the number, else a tuple).  ``arg`` is an
+        element width that the message calls ``what``, or -- without ``what`` -- a key type or a tensor that has one, asked
+        about with or without ``indices``."""
+        if what is None and not isinstance(arg, int):
+            arg = self._key_type(arg)
+        cells = [C.c_uint64() for _ in range(words)]
+        asked = (int(arg),) if what else (arg, int(indices))
+        if getattr(self._L, export)(*asked, *[C.byref(c) for c in cells]) != 0:
+            raise MsdError(f"error -1: {what} must be 4 or 8, not {arg}" if what else f"error -1: unknown key type {arg}")
+        return tuple(int(c.value) for c in cells) if words > 1 else int(cells[0].value)
 
     def use_torch_stream(self) -> None:
         torch = _torch()
@@ -145,8 +148,7 @@ class MsdContext:
         torch = _torch()
         kt = self._key_type(keys)
         es = keys.element_size()
-        if keys.dim() != 1 or (rids is not None and rids.dim() != 1):
-            raise MsdError("sort_typed takes 1-D tensors")
+        _args.one_dim("sort_typed", keys, rids)
         order = 1 if descending else 0
         if rids is not None and es != 8:
             raise MsdError("tuples have 64-bit keys: float64, int64 or uint64")
@@ -174,20 +176,16 @@ class MsdContext:
     def sort_top(self, keys, begin_bit: int, end_bit: Optional[int] = None, rids=None) -> None:
         """Orders ``keys`` by ``key >> begin_bit`` only (keys that agree above ``begin_bit`` end up adjacent, in any order)."""
         eb = keys.element_size() * 8 if end_bit is None else end_bit
-        if rids is not None:
-            self._ok(self._L.msd_sort_pairs_u64_top(self._h, self._ptr(keys, 8), self._ptr(rids, 8), keys.numel(), eb, begin_bit))
-        elif keys.element_size() == 4:
-            self._ok(self._L.msd_sort_u32_top(self._h, self._ptr(keys, 4), keys.numel(), eb, begin_bit))
-        else:
-            self._ok(self._L.msd_sort_u64_top(self._h, self._ptr(keys, 8), keys.numel(), eb, begin_bit))
+        f, ptrs = self._layout("msd_sort{}_top", keys, rids)
+        self._ok(f(self._h, *ptrs, keys.numel(), eb, begin_bit))
 
     def bucket_bounds(self, keys, shift: int, nbuckets: int, first: int = 0):
         """int64[nbuckets + 1] on the device: bounds[b] = first index whose ``key >> shift`` is >= first + b
         (``keys`` ordered by ``key >> shift``)."""
         torch = _torch()
         out = torch.empty(nbuckets + 1, dtype=torch.int64, device=keys.device)
-        f = self._L.msd_bucket_bounds_u32 if keys.element_size() == 4 else self._L.msd_bucket_bounds_u64
-        self._ok(f(self._h, self._ptr(keys, keys.element_size()), keys.numel(), shift, first, nbuckets, C.c_void_p(out.data_ptr())))
+        f, ptrs = self._layout("msd_bucket_bounds{}", keys)
+        self._ok(f(self._h, *ptrs, keys.numel(), shift, first, nbuckets, ptr(out)))
         return out
 
     def merge_buckets(self, src, counts, src_base, open_bits: int, first_prefix: int, dst, n_expected: int) -> None:
@@ -225,14 +223,14 @@ class MsdContext:
             raise MsdError("hist2_pack: u32 keys or their low halves, a uint8 buffer of one record per bucket")
         flag = torch.zeros(1, dtype=torch.int32, device=keys.device)
         f = self._L.msd_hist2_pack_u32 if es == 4 else self._L.msd_hist2_pack_u32_low16
-        self._ok(f(self._h, self._ptr(keys, es), keys.numel(), self._ptr(bounds, 8), nb, self._ptr(rec, 1), rec.numel(), C.c_void_p(flag.data_ptr())))
+        self._ok(f(self._h, self._ptr(keys, es), keys.numel(), self._ptr(bounds, 8), nb, self._ptr(rec, 1), rec.numel(), ptr(flag)))
         return flag
 
     def bounds_from_counts16(self, counts):
         """int64[65537] on the device: the prefix sums of 65536 bucket sizes."""
         torch = _torch()
         out = torch.empty(65537, dtype=torch.int64, device=counts.device)
-        self._ok(self._L.msd_bounds_from_counts16(self._h, self._ptr(counts, 8), C.c_void_p(out.data_ptr())))
+        self._ok(self._L.msd_bounds_from_counts16(self._h, self._ptr(counts, 8), ptr(out)))
         return out
 
     def order_low16(self, keys, out):
@@ -243,7 +241,7 @@ class MsdContext:
         if keys.element_size() != 4 or out.element_size() != 2 or out.numel() < keys.numel():
             raise MsdError("order_low16: u32 keys, an int16 buffer at least as long")
         counts = torch.empty(65536, dtype=torch.int64, device=keys.device)
-        self._ok(self._L.msd_order_low16_u32(self._h, self._ptr(keys, 4), keys.numel(), self._ptr(out, 2), C.c_void_p(counts.data_ptr())))
+        self._ok(self._L.msd_order_low16_u32(self._h, self._ptr(keys, 4), keys.numel(), self._ptr(out, 2), ptr(counts)))
         return counts
 
     def order_low16_counts(self, keys):
@@ -251,7 +249,7 @@ class MsdContext:
         be this context's next call."""
         torch = _torch()
         counts = torch.empty(65536, dtype=torch.int64, device=keys.device)
-        self._ok(self._L.msd_order_low16_counts_u32(self._h, self._ptr(keys, 4), keys.numel(), C.c_void_p(counts.data_ptr())))
+        self._ok(self._L.msd_order_low16_counts_u32(self._h, self._ptr(keys, 4), keys.numel(), ptr(counts)))
         return counts
 
     def order_low16_scatter(self, keys, out) -> None:
@@ -269,27 +267,22 @@ class MsdContext:
     def histogram(self, keys, shift: int, radix_bits: int):
         torch = _torch()
         out = torch.empty(1 << radix_bits, dtype=torch.int64, device=keys.device)
-        f = self._L.msd_histogram_u32 if keys.element_size() == 4 else self._L.msd_histogram_u64
-        self._ok(f(self._h, self._ptr(keys, keys.element_size()), keys.numel(), shift, radix_bits, C.c_void_p(out.data_ptr())))
+        f, ptrs = self._layout("msd_histogram{}", keys)
+        self._ok(f(self._h, *ptrs, keys.numel(), shift, radix_bits, ptr(out)))
         return out
 
     def exclusive_scan(self, x):
         torch = _torch()
         out = torch.empty_like(x)
-        self._ok(self._L.msd_exclusive_scan_u64(self._h, self._ptr(x, 8), C.c_void_p(out.data_ptr()), x.numel()))
+        self._ok(self._L.msd_exclusive_scan_u64(self._h, self._ptr(x, 8), ptr(out), x.numel()))
         return out
 
     def partition(self, keys, shift: int, radix_bits: int, rids=None):
         """One in-place digit pass; returns the bucket sizes (int64 tensor)."""
         torch = _torch()
         cnt = torch.zeros(1 << radix_bits, dtype=torch.int64, device=keys.device)
-        if rids is not None:
-            self._ok(self._L.msd_partition_pairs_u64(self._h, self._ptr(keys, 8), self._ptr(rids, 8), keys.numel(),
-                                                      shift, radix_bits, C.c_void_p(cnt.data_ptr())))
-        elif keys.element_size() == 4:
-            self._ok(self._L.msd_partition_u32(self._h, self._ptr(keys, 4), keys.numel(), shift, radix_bits, C.c_void_p(cnt.data_ptr())))
-        else:
-            self._ok(self._L.msd_partition_u64(self._h, self._ptr(keys, 8), keys.numel(), shift, radix_bits, C.c_void_p(cnt.data_ptr())))
+        f, ptrs = self._layout("msd_partition{}", keys, rids)
+        self._ok(f(self._h, *ptrs, keys.numel(), shift, radix_bits, ptr(cnt)))
         return cnt
 
     # ---- a rank of the multi-GPU sort after its exchange (reference: local sorting of whole key ranges, src/msb_64.c:2200-2255)
@@ -308,12 +301,8 @@ class MsdContext:
         if nseg <= 0:
             return
         off = self._u64arr(seg_off)
-        if rids is not None:
-            self._ok(self._L.msd_sort_pairs_u64_segments(self._h, self._ptr(keys, 8), self._ptr(rids, 8), keys.numel(), off, nseg, end_bit))
-        elif keys.element_size() == 4:
-            self._ok(self._L.msd_sort_u32_segments(self._h, self._ptr(keys, 4), keys.numel(), off, nseg, end_bit))
-        else:
-            self._ok(self._L.msd_sort_u64_segments(self._h, self._ptr(keys, 8), keys.numel(), off, nseg, end_bit))
+        f, ptrs = self._layout("msd_sort{}_segments", keys, rids)
+        self._ok(f(self._h, *ptrs, keys.numel(), off, nseg, end_bit))
 
     def gather_runs(self, dst, src, src_off, dst_off, lens) -> None:
         """Copies run i (``lens[i]`` elements) from ``src[src_off[i]:]`` to ``dst[dst_off[i]:]``, all runs in one launch."""
@@ -321,28 +310,26 @@ class MsdContext:
             raise MsdError("gather_runs: the three lists differ in length")
         if dst.element_size() != src.element_size():
             raise MsdError("gather_runs: element sizes differ")
-        f = self._L.msd_gather_runs_u32 if src.element_size() == 4 else self._L.msd_gather_runs_u64
-        self._ok(f(self._h, self._ptr(dst, dst.element_size()), self._ptr(src, src.element_size()),
-                   self._u64arr(src_off), self._u64arr(dst_off), self._u64arr(lens), len(lens)))
+        dp = self._ptr(dst, dst.element_size())
+        f, ptrs = self._layout("msd_gather_runs{}", src)
+        self._ok(f(self._h, dp, *ptrs, self._u64arr(src_off), self._u64arr(dst_off), self._u64arr(lens), len(lens)))
 
     # ---- splitter service (reference: src/msb_64.c:1511-1521, :1304-1322, :188-204)
     def sample(self, keys, m: int, seed: int = 0x5EED0007):
         """m keys drawn from the (unsorted) tensor at pseudo-random positions mulhi(splitmix64(seed + i), n);
         u32 (int32 tensor) or u64 (int64 tensor) keys."""
         torch = _torch()
-        es = keys.element_size()
         out = torch.empty(m, dtype=keys.dtype, device=keys.device)
-        f = self._L.msd_sample_u32 if es == 4 else self._L.msd_sample_u64
-        self._ok(f(self._h, self._ptr(keys, es), keys.numel(), m, seed, C.c_void_p(out.data_ptr())))
+        f, ptrs = self._layout("msd_sample{}", keys)
+        self._ok(f(self._h, *ptrs, keys.numel(), m, seed, ptr(out)))
         return out
 
     def splitters(self, sorted_sample, parts: int):
         """parts-1 equi-depth delimiters (bit patterns in a tensor of the sample's dtype) with the reference's duplicate rule."""
         torch = _torch()
-        es = sorted_sample.element_size()
         out = torch.empty(max(parts - 1, 0), dtype=sorted_sample.dtype, device=sorted_sample.device)
-        f = self._L.msd_splitters_u32 if es == 4 else self._L.msd_splitters_u64
-        self._ok(f(self._h, self._ptr(sorted_sample, es), sorted_sample.numel(), parts, C.c_void_p(out.data_ptr())))
+        f, ptrs = self._layout("msd_splitters{}", sorted_sample)
+        self._ok(f(self._h, *ptrs, sorted_sample.numel(), parts, ptr(out)))
         return out
 
     sample_u32 = sample          # (round 2's names)
@@ -352,25 +339,19 @@ class MsdContext:
         """One in-place pass: range p = keys in (delims[p-1], delims[p]] (rids move with their keys); returns the range
         sizes (int64 tensor)."""
         torch = _torch()
-        es = keys.element_size()
         cnt = torch.zeros(parts, dtype=torch.int64, device=keys.device)
-        dp = self._ptr(delims, es) if parts > 1 else C.c_void_p(0)
-        if rids is not None:
-            self._ok(self._L.msd_partition_by_splitters_pairs_u64(self._h, self._ptr(keys, 8), self._ptr(rids, 8), keys.numel(), dp, parts,
-                                                                  C.c_void_p(cnt.data_ptr())))
-        else:
-            f = self._L.msd_partition_by_splitters_u32 if es == 4 else self._L.msd_partition_by_splitters_u64
-            self._ok(f(self._h, self._ptr(keys, es), keys.numel(), dp, parts, C.c_void_p(cnt.data_ptr())))
+        dp = self._ptr(delims, keys.element_size()) if parts > 1 else ptr(None)
+        f, ptrs = self._layout("msd_partition_by_splitters{}", keys, rids)
+        self._ok(f(self._h, *ptrs, keys.numel(), dp, parts, ptr(cnt)))
         return cnt
 
     def check(self, keys, rids=None) -> Tuple[int, int, int]:
         """(violations, sum, xor): device form of the reference's check()."""
         v, s, x = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        if keys.element_size() == 4:
-            self._ok(self._L.msd_check_u32(self._h, self._ptr(keys, 4), keys.numel(), C.byref(v), C.byref(s), C.byref(x)))
-        else:
-            rp = self._ptr(rids, 8) if rids is not None else C.c_void_p(0)
-            self._ok(self._L.msd_check_u64(self._h, self._ptr(keys, 8), rp, keys.numel(), C.byref(v), C.byref(s), C.byref(x)))
+        f, ptrs = self._layout("msd_check{}", keys)
+        if keys.element_size() != 4:   # (the 64-bit export takes the rids, or null, behind the keys)
+            ptrs += (self._ptr(rids, 8) if rids is not None else ptr(None),)
+        self._ok(f(self._h, *ptrs, keys.numel(), C.byref(v), C.byref(s), C.byref(x)))
         return int(v.value), int(s.value), int(x.value)
 
     # ---- radix select and top-k (read-only on ``keys``)
@@ -389,36 +370,22 @@ class MsdContext:
             out_rids = torch.empty(max(int(k), 0), dtype=rids.dtype, device=rids.device)
         if out.numel() < k or (rids is not None and out_rids.numel() < k):
             raise MsdError("output tensor shorter than k")
-        if rids is not None:
-            self._ok(self._L.msd_topk_pairs_u64(self._h, self._ptr(keys, 8), self._ptr(rids, 8), keys.numel(), k, which,
-                                                self._ptr(out, 8), self._ptr(out_rids, 8)))
-            return out, out_rids
-        f = self._L.msd_topk_u32 if es == 4 else self._L.msd_topk_u64
-        self._ok(f(self._h, self._ptr(keys, es), keys.numel(), k, which, self._ptr(out, es)))
-        return out
+        f, ptrs = self._layout("msd_topk{}", keys, rids)
+        outs = (out,) if rids is None else (out, out_rids)
+        self._ok(f(self._h, *ptrs, keys.numel(), k, which, *[self._ptr(t, es) for t in outs]))
+        return out if rids is None else outs
 
     def select(self, keys, k: int, largest: bool = False) -> int:
         """The key of rank ``k`` (0-based) from the small end, or from the large end with ``largest``; ``keys`` is not modified."""
-        if keys.element_size() == 4:
-            v = C.c_uint32()
-            self._ok(self._L.msd_select_u32(self._h, self._ptr(keys, 4), keys.numel(), k, 1 if largest else 0, C.byref(v)))
-        else:
-            v = C.c_uint64()
-            self._ok(self._L.msd_select_u64(self._h, self._ptr(keys, 8), keys.numel(), k, 1 if largest else 0, C.byref(v)))
+        f, ptrs = self._layout("msd_select{}", keys)
+        v = (C.c_uint32 if keys.element_size() == 4 else C.c_uint64)()
+        self._ok(f(self._h, *ptrs, keys.numel(), k, 1 if largest else 0, C.byref(v)))
         return int(v.value)
 
     # ---- top-k with indices, signed and float keys: the tensor's dtype says how its bit patterns are ordered
-    KEY_U32, KEY_I32, KEY_F32, KEY_U64, KEY_I64, KEY_F64 = range(6)   # MSD_KEY_* of include/msd_radix_hip.h
-
-    def _key_type(self, keys) -> int:
-        torch = _torch()
-        table = {torch.int32: self.KEY_I32, torch.float32: self.KEY_F32, torch.int64: self.KEY_I64, torch.float64: self.KEY_F64}
-        for name, kt in (("uint32", self.KEY_U32), ("uint64", self.KEY_U64)):   # (not in every torch)
-            if hasattr(torch, name):
-                table[getattr(torch, name)] = kt
-        if keys.dtype not in table:
-            raise MsdError(f"no key order for dtype {keys.dtype}: float32, int32, float64, int64, uint32 or uint64")
-        return table[keys.dtype]
+    KEY_U32, KEY_I32, KEY_F32, KEY_U64, KEY_I64, KEY_F64 = (_args.KEY_U32, _args.KEY_I32, _args.KEY_F32, _args.KEY_U64, _args.KEY_I64,
+                                                            _args.KEY_F64)   # MSD_KEY_* of include/msd_radix_hip.h
+    _key_type = staticmethod(_args.key_type)
 
     def topk_typed(self, keys, k: int, largest: bool = False, indices: bool = False, out=None, out_indices=None):
         """The ``k`` smallest (``largest``: largest) keys of ``keys`` in the order of its dtype, ascending in both cases: a
@@ -432,7 +399,7 @@ class MsdContext:
         want_idx = indices or out_indices is not None
         out, out_indices = self._value_index_outputs((max(int(k), 0),), keys, out, out_indices, want_idx, exact=False)
         self._ok(self._L.msd_topk_keys(self._h, self._ptr(keys, es), kt, keys.numel(), k, 1 if largest else 0, self._ptr(out, es),
-                                       self._ptr(out_indices, 8) if want_idx else C.c_void_p(0)))
+                                       self._ptr(out_indices, 8) if want_idx else ptr(None)))
         return (out, out_indices) if want_idx else out
 
     def select_typed(self, keys, k: int, largest: bool = False):
@@ -478,11 +445,7 @@ class MsdContext:
 
     def topk_rows_limits(self, keys_or_key_type, indices: bool = False) -> Tuple[int, int]:
         """``(max_row_len, max_k)``: the envelope of the one-launch row kernel (``msd_topk_rows_limits``)."""
-        kt = keys_or_key_type if isinstance(keys_or_key_type, int) else self._key_type(keys_or_key_type)
-        a, b = C.c_uint64(), C.c_uint64()
-        if self._L.msd_topk_rows_limits(kt, int(indices), C.byref(a), C.byref(b)) != 0:
-            raise MsdError(f"error -1: unknown key type {kt}")
-        return int(a.value), int(b.value)
+        return self._limits("msd_topk_rows_limits", 2, keys_or_key_type, indices=indices)
 
     def topk_rows(self, keys, k: int, largest: bool = False, indices: bool = False, out=None, out_indices=None):
         """Top-k along the LAST dimension: for every row the ``k`` smallest (``largest``: largest) keys in the order of the
@@ -496,19 +459,15 @@ class MsdContext:
         k = int(k)
         want_idx = indices or out_indices is not None
         out, out_indices = self._value_index_outputs(tuple(keys.shape[:-1]) + (max(k, 0),), keys, out, out_indices, want_idx)
-        self._ok(self._L.msd_topk_rows(self._h, C.c_void_p(keys.data_ptr()), kt, rows, row_len, row_stride, k, 1 if largest else 0,
-                                       C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
+        self._ok(self._L.msd_topk_rows(self._h, ptr(keys), kt, rows, row_len, row_stride, k, 1 if largest else 0,
+                                       ptr(out), ptr(out_indices if want_idx else None)))
         return (out, out_indices) if want_idx else out
 
     # ---- per-row (batched) sort: torch.sort(x, dim=-1)
     def sort_rows_limits(self, keys_or_key_type, indices: bool = False) -> int:
         """``max_row_len``: the longest row the one-launch row kernel takes (``msd_sort_rows_limits``); longer rows go
         through the segment sort."""
-        kt = keys_or_key_type if isinstance(keys_or_key_type, int) else self._key_type(keys_or_key_type)
-        a = C.c_uint64()
-        if self._L.msd_sort_rows_limits(kt, int(indices), C.byref(a)) != 0:
-            raise MsdError(f"error -1: unknown key type {kt}")
-        return int(a.value)
+        return self._limits("msd_sort_rows_limits", 1, keys_or_key_type, indices=indices)
 
     def sort_rows(self, keys, descending: bool = False, indices: bool = False, out=None, out_indices=None):
         """Sorts along the LAST dimension: every row in the order of the dtype (floats in IEEE-754 totalOrder, as
@@ -522,15 +481,15 @@ class MsdContext:
         rows, row_len, row_stride = self._rows_layout(keys)
         want_idx = indices or out_indices is not None
         out, out_indices = self._value_index_outputs(tuple(keys.shape), keys, out, out_indices, want_idx)
-        self._ok(self._L.msd_sort_rows(self._h, C.c_void_p(keys.data_ptr()), kt, rows, row_len, row_stride, 1 if descending else 0,
-                                       C.c_void_p(out.data_ptr()), C.c_void_p(out_indices.data_ptr()) if want_idx else C.c_void_p(0)))
+        self._ok(self._L.msd_sort_rows(self._h, ptr(keys), kt, rows, row_len, row_stride, 1 if descending else 0,
+                                       ptr(out), ptr(out_indices if want_idx else None)))
         return (out, out_indices) if want_idx else out
 
     # ---- run-length encode and unique (include/msd_runs_hip.h)
     def run_encode_limits(self, elem_bytes: int) -> Tuple[int, int]:
         """``(tile, scan_tile)``: the elements one workgroup takes per tile for that element width, and how many tile
         counts one workgroup of the tile-count scan takes at once (``msd_run_encode_limits``)."""
-        return self._limits2(self._L.msd_run_encode_limits, elem_bytes, "elem_bytes")
+        return self._limits("msd_run_encode_limits", 2, elem_bytes, "elem_bytes")
 
     def run_encode(self, t, cap: Optional[int] = None, values: bool = True, starts: bool = True, inverse: bool = False, positions=None):
         """Run-length encodes the 1-D contiguous tensor ``t`` of 4- or 8-byte elements (``torch.unique_consecutive``; on a
@@ -547,25 +506,19 @@ class MsdContext:
         permutation of the indices as :meth:`sort_rows` or :meth:`sort_typed` with rids produce it)
         ``inverse[positions[i]]`` is the run of element i.  Nothing waits on the host."""
         torch = _torch()
-        if t.dim() != 1 or not t.is_contiguous():
-            raise MsdError("run_encode takes a 1-D contiguous tensor")
-        es = t.element_size()
-        if es not in (4, 8):
-            raise MsdError(f"run_encode takes 4- or 8-byte elements, not {t.dtype}")
+        _args.flat("run_encode", t, what="a 1-D contiguous tensor")
+        es = _args.elem_4_or_8("run_encode", t)
         n = t.numel()
-        self._check_positions(positions, n)
+        _args.positions(positions, n)
         if positions is not None and not inverse:
             raise MsdError("positions without inverse")
-        cap = n if cap is None else int(cap)
-        if cap < 0:
-            raise MsdError("cap must not be negative")
+        cap = _args.cap_or(cap, n)
         self._on_gpu(t, positions)
-        num = torch.empty(1, dtype=torch.int64, device=t.device)
+        num = _args.count_cell(t.device)
         vals = torch.empty(cap, dtype=t.dtype, device=t.device) if values else None
         st = torch.empty(cap + 1, dtype=torch.int64, device=t.device) if starts else None
         inv = torch.empty(n, dtype=torch.int64, device=t.device) if inverse else None
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
-        self._ok(self._L.msd_run_encode(self._h, C.c_void_p(t.data_ptr()), es, n, cap, ptr(vals), ptr(st), ptr(positions), ptr(inv), ptr(num)))
+        self._ok(self._L.msd_run_encode(self._h, ptr(t), es, n, cap, ptr(vals), ptr(st), ptr(positions), ptr(inv), ptr(num)))
         return num, vals, st, inv
 
     def unique(self, keys, return_inverse: bool = False, return_counts: bool = False):
@@ -576,8 +529,7 @@ class MsdContext:
         with equal bits are one, where ``torch.unique`` merges the zeros and keeps every NaN apart.  ``keys`` is not
         modified.  One host wait beyond the sort's own: the number of distinct values sizes the results."""
         self._key_type(keys)   # (a dtype without a key order is refused here)
-        if keys.dim() != 1 or not keys.is_contiguous():
-            raise MsdError("unique takes a 1-D contiguous tensor")
+        _args.flat("unique", keys, what="a 1-D contiguous tensor")
         self._on_gpu(keys)
         if return_inverse:
             s, positions = self._sorted_with_positions(keys)
@@ -598,7 +550,7 @@ class MsdContext:
 
     def reduce_runs_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, scan_tile)`` of ``msd_reduce_runs_limits``: the geometry of :meth:`run_encode_limits`."""
-        return self._limits2(self._L.msd_reduce_runs_limits, key_bytes, "key_bytes")
+        return self._limits("msd_reduce_runs_limits", 2, key_bytes, "key_bytes")
 
     def reduce_runs(self, keys, vals, op: str = "sum", positions=None, cap: Optional[int] = None):
         """One number per run of ``keys``: the ``"sum"``, ``"min"`` or ``"max"`` of the values of its elements.  The runs
@@ -617,35 +569,18 @@ class MsdContext:
         as everywhere in this library: -0.0 is below +0.0, a NaN is the maximum of its run (the minimum, if its sign
         bit is set), unlike ``torch.amax`` / ``torch.amin``, which propagate any NaN.  Nothing waits on the host."""
         torch = _torch()
-        if op not in self.REDUCE_OPS:
-            raise MsdError(f"op must be one of {sorted(self.REDUCE_OPS)}, not {op!r}")
-        if keys.dim() != 1 or vals.dim() != 1 or not keys.is_contiguous() or not vals.is_contiguous():
-            raise MsdError("reduce_runs takes 1-D contiguous tensors")
-        ks = keys.element_size()
-        if ks not in (4, 8):
-            raise MsdError(f"reduce_runs takes 4- or 8-byte keys, not {keys.dtype}")
+        code = _args.op_code(self.REDUCE_OPS, op)
+        _args.flat("reduce_runs", keys, vals)
+        ks = _args.elem_4_or_8("reduce_runs", keys, "4- or 8-byte keys")
         vt = self._key_type(vals)   # (a value dtype without an order is refused here)
         n = keys.numel()
-        if vals.numel() != n:
-            raise MsdError("keys and vals differ in length")
-        self._check_positions(positions, n)
-        cap = n if cap is None else int(cap)
-        if cap < 0:
-            raise MsdError("cap must not be negative")
+        _args.same_length("keys and vals", keys, vals)
+        _args.positions(positions, n)
+        cap = _args.cap_or(cap, n)
         self._on_gpu(keys, vals, positions)
-        if op != "sum":
-            odt = vals.dtype
-        elif vt in (self.KEY_F32, self.KEY_F64):
-            odt = torch.float64
-        elif vt in (self.KEY_U32, self.KEY_U64) and hasattr(torch, "uint64"):
-            odt = torch.uint64
-        else:
-            odt = torch.int64
-        num = torch.empty(1, dtype=torch.int64, device=keys.device)
-        out = torch.empty(cap, dtype=odt, device=keys.device)
-        self._ok(self._L.msd_reduce_runs(self._h, C.c_void_p(keys.data_ptr()), ks, n, C.c_void_p(vals.data_ptr()), vt,
-                                         C.c_void_p(positions.data_ptr() if positions is not None else 0), self.REDUCE_OPS[op], cap,
-                                         C.c_void_p(out.data_ptr()), C.c_void_p(num.data_ptr())))
+        num = _args.count_cell(keys.device)
+        out = torch.empty(cap, dtype=_args.result_dtype(op, vals, vt), device=keys.device)
+        self._ok(self._L.msd_reduce_runs(self._h, ptr(keys), ks, n, ptr(vals), vt, ptr(positions), code, cap, ptr(out), ptr(num)))
         return num, out
 
     def group_reduce(self, keys, vals, op: str = "sum"):
@@ -655,14 +590,11 @@ class MsdContext:
         the dtypes and the rules of :meth:`reduce_runs`.  The keys are sorted with positions, the value column is read
         through them where it lies.  ``keys`` and ``vals`` are not modified.  One host wait beyond the sort's own: the
         number of distinct keys sizes the results."""
-        if op not in self.REDUCE_OPS:
-            raise MsdError(f"op must be one of {sorted(self.REDUCE_OPS)}, not {op!r}")
+        _args.op_code(self.REDUCE_OPS, op)
         self._key_type(keys)
         self._key_type(vals)
-        if keys.dim() != 1 or vals.dim() != 1 or not keys.is_contiguous() or not vals.is_contiguous():
-            raise MsdError("group_reduce takes 1-D contiguous tensors")
-        if vals.numel() != keys.numel():
-            raise MsdError("keys and vals differ in length")
+        _args.flat("group_reduce", keys, vals)
+        _args.same_length("keys and vals", keys, vals)
         self._on_gpu(keys, vals)
         s, positions = self._sorted_with_positions(keys)
         _, distinct, _, _ = self.run_encode(s, starts=False)
@@ -675,7 +607,7 @@ class MsdContext:
 
     def scan_runs_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, scan_tile)`` of ``msd_scan_runs_limits``: the geometry of :meth:`run_encode_limits`."""
-        return self._limits2(self._L.msd_scan_runs_limits, key_bytes, "key_bytes")
+        return self._limits("msd_scan_runs_limits", 2, key_bytes, "key_bytes")
 
     def scan_runs(self, keys, vals, op: str = "sum", exclusive: bool = False, positions=None, scatter: bool = False):
         """One number per ELEMENT of ``keys``: the running ``"sum"``, ``"min"``, ``"max"`` or ``"count"`` inside its run --
@@ -704,38 +636,23 @@ class MsdContext:
         64-bit composite ``(key code << 32) | order column`` with positions, scan on the keys taken from its upper
         half and the values gathered through the positions; ``"count"`` alone may accept the arbitrary order."""
         torch = _torch()
-        if op not in self.SCAN_OPS:
-            raise MsdError(f"op must be one of {sorted(self.SCAN_OPS)}, not {op!r}")
+        code = _args.op_code(self.SCAN_OPS, op)
         if vals is None and op != "count":
             raise MsdError(f"vals may be None for op 'count' only, not for {op!r}")
-        if keys.dim() != 1 or not keys.is_contiguous() or (vals is not None and (vals.dim() != 1 or not vals.is_contiguous())):
-            raise MsdError("scan_runs takes 1-D contiguous tensors")
-        ks = keys.element_size()
-        if ks not in (4, 8):
-            raise MsdError(f"scan_runs takes 4- or 8-byte keys, not {keys.dtype}")
+        _args.flat("scan_runs", keys, vals)
+        ks = _args.elem_4_or_8("scan_runs", keys, "4- or 8-byte keys")
         vt = self._key_type(vals) if vals is not None else 0   # (a value dtype without an order is refused here)
         n = keys.numel()
-        if vals is not None and vals.numel() != n:
-            raise MsdError("keys and vals differ in length")
-        self._check_positions(positions, n)
+        _args.same_length("keys and vals", keys, vals)
+        _args.positions(positions, n)
         if scatter and positions is None:
             raise MsdError("scatter without positions")
         if positions is not None:
             raise MsdError("positions (and with them scatter) are not offered yet: gather the values, vals[positions], and scatter the result")
         self._on_gpu(keys, vals)
-        if op == "count":
-            odt, vals = torch.int64, None
-        elif op != "sum":
-            odt = vals.dtype
-        elif vt in (self.KEY_F32, self.KEY_F64):
-            odt = torch.float64
-        elif vt in (self.KEY_U32, self.KEY_U64) and hasattr(torch, "uint64"):
-            odt = torch.uint64
-        else:
-            odt = torch.int64
-        out = torch.empty(n, dtype=odt, device=keys.device)
-        self._ok(self._L.msd_scan_runs(self._h, C.c_void_p(keys.data_ptr()), ks, n, C.c_void_p(vals.data_ptr() if vals is not None else 0), vt,
-                                       C.c_void_p(0), self.SCAN_OPS[op], 1 if exclusive else 0, C.c_void_p(out.data_ptr())))
+        out = torch.empty(n, dtype=_args.result_dtype(op, vals, vt), device=keys.device)
+        self._ok(self._L.msd_scan_runs(self._h, ptr(keys), ks, n, ptr(vals if op != "count" else None), vt, ptr(None), code,
+                                       1 if exclusive else 0, ptr(out)))   # (a count reads no values)
         return out
 
     # ---- stream compaction and stable partition: the filter (include/msd_compact_hip.h)
@@ -743,7 +660,7 @@ class MsdContext:
 
     def compact_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, scan_tile)`` of ``msd_compact_limits``: the geometry of :meth:`run_encode_limits`."""
-        return self._limits2(self._L.msd_compact_limits, key_bytes, "key_bytes")
+        return self._limits("msd_compact_limits", 2, key_bytes, "key_bytes")
 
     def _bound_bits(self, keys, kt: int, bound, lowest: bool) -> int:
         """The bit pattern of a range bound in the keys' dtype; ``None`` is the key with the lowest / highest code."""
@@ -792,50 +709,42 @@ class MsdContext:
         torch = _torch()
         if keys is None and mask is None:
             raise MsdError("compact needs keys or a mask")
-        given = [t for t in (keys, mask, values) if t is not None]
-        if any(t.dim() != 1 or not t.is_contiguous() for t in given):
-            raise MsdError("compact takes 1-D contiguous tensors")
-        n = given[0].numel()
-        if any(t.numel() != n for t in given):
-            raise MsdError("keys, mask and values differ in length")
+        first = keys if keys is not None else mask
+        _args.flat("compact", keys, mask, values)
+        n = first.numel()
+        _args.same_length("keys, mask and values", keys, mask, values)
         kt = self._key_type(keys) if keys is not None else 0   # (a dtype without a key order is refused here)
         if mask is not None and mask.element_size() != 1:
             raise MsdError(f"the mask has a one-byte dtype (torch.bool, uint8, int8), not {mask.dtype}")
-        if values is not None and values.element_size() not in (4, 8):
-            raise MsdError(f"compact takes values of 4- or 8-byte elements, not {values.dtype}")
+        if values is not None:
+            _args.elem_4_or_8("compact", values, "values of 4- or 8-byte elements")
         want_range = lo is not None or hi is not None
         if want_range and keys is None:
             raise MsdError("lo / hi without keys")
         if (out is not None and keys is None) or (out_values is not None and values is None):
             raise MsdError("out without keys, or out_values without values")
-        cap = n if cap is None else int(cap)
-        if cap < 0:
-            raise MsdError("cap must not be negative")
+        cap = _args.cap_or(cap, n)
         if rest and cap < n:
             raise MsdError("rest needs cap >= the number of elements")
         want_idx = bool(indices) or out_indices is not None
-        for t, like, what in ((out, keys, "out"), (out_values, values, "out_values")):
-            if t is not None and (t.dtype != like.dtype or t.dim() != 1 or not t.is_contiguous() or t.numel() < cap):
-                raise MsdError(f"{what} must be a contiguous 1-D tensor of the input's dtype with at least cap elements")
-        if out_indices is not None and (out_indices.dtype != torch.int64 or out_indices.dim() != 1 or not out_indices.is_contiguous() or out_indices.numel() < cap):
-            raise MsdError("out_indices must be a contiguous 1-D int64 tensor with at least cap elements")
+        # (the outputs: name, the tensor given, its dtype -- None: not asked for --, and what refuses a given one)
+        like = "must be a contiguous 1-D tensor of the input's dtype with at least cap elements"
+        outs = [("out", out, keys.dtype if keys is not None else None, like),
+                ("out_values", out_values, values.dtype if values is not None else None, like),
+                ("out_indices", out_indices, torch.int64 if want_idx else None, "must be a contiguous 1-D int64 tensor with at least cap elements")]
+        for name, t, dt, must in outs:
+            _args.output(t, dt, (cap,), name + " " + must, at_least=True)
         self._on_gpu(keys, mask, values, out, out_values, out_indices)
         lo_bits = self._bound_bits(keys, kt, lo, True) if want_range else 0
         hi_bits = self._bound_bits(keys, kt, hi, False) if want_range else 0
-        dev = given[0].device
-        if keys is not None and out is None:
-            out = torch.empty(cap, dtype=keys.dtype, device=dev)
-        if values is not None and out_values is None:
-            out_values = torch.empty(cap, dtype=values.dtype, device=dev)
-        if want_idx and out_indices is None:
-            out_indices = torch.empty(cap, dtype=torch.int64, device=dev)
-        count = torch.empty(1, dtype=torch.int64, device=dev)
+        out, out_values, out_indices = [_args.output(t, dt, (cap,), None, first.device) for _, t, dt, _ in outs]
+        count = _args.count_cell(first.device)
         flags = (self.COMPACT_RANGE if want_range and n else 0) | (self.COMPACT_INVERT if invert else 0) | (self.COMPACT_REST if rest else 0)
-        # (nothing to filter: only the count is written, and an empty tensor has no address to hand over)
-        ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and (n or x is count) else 0)
         mask8 = mask.view(torch.uint8) if mask is not None else None
-        self._ok(self._L.msd_compact(self._h, ptr(keys), kt, n, ptr(mask8), lo_bits, hi_bits, flags, ptr(values),
-                                     values.element_size() if values is not None else 0, cap, ptr(out), ptr(out_values), ptr(out_indices), ptr(count)))
+        # (nothing to filter: only the count is written, and an empty tensor has no address to hand over)
+        kp, mp, vp, okp, ovp, oip = [ptr(t if n else None) for t in (keys, mask8, values, out, out_values, out_indices)]
+        self._ok(self._L.msd_compact(self._h, kp, kt, n, mp, lo_bits, hi_bits, flags, vp, values.element_size() if values is not None else 0, cap,
+                                     okp, ovp, oip, ptr(count)))
         return out, out_values, out_indices, count
 
     def masked_select(self, t, mask):
@@ -868,7 +777,7 @@ class MsdContext:
     def search_sorted_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, direct_tile)`` of ``msd_search_sorted_limits``: the elements (keys plus needles together) one
         workgroup of the merge path takes for that key width, and the needles one workgroup of the direct path takes."""
-        return self._limits2(self._L.msd_search_sorted_limits, key_bytes, "key_bytes")
+        return self._limits("msd_search_sorted_limits", 2, key_bytes, "key_bytes")
 
     def searchsorted(self, sorted_keys, needles, right: bool = False, needles_sorted: bool = False, sort_needles: bool = False,
                      positions=None, out=None):
@@ -894,30 +803,24 @@ class MsdContext:
         host."""
         torch = _torch()
         kt = self._key_type(sorted_keys)
-        if needles.dtype != sorted_keys.dtype:
-            raise MsdError(f"sorted_keys and needles differ in dtype: {sorted_keys.dtype} and {needles.dtype}")
-        if sorted_keys.dim() != 1:
-            raise MsdError("searchsorted takes 1-D sorted_keys")
-        if not sorted_keys.is_contiguous() or not needles.is_contiguous():
-            raise MsdError("searchsorted takes contiguous tensors")
+        _args.same_dtype(sorted_keys, needles, "sorted_keys and needles")
+        _args.one_dim("searchsorted", sorted_keys, what="sorted_keys")
+        _args.contiguous("searchsorted", sorted_keys, needles)
         m = needles.numel()
-        self._check_positions(positions, m, "needles")
+        _args.positions(positions, m, "needles")
         if positions is not None and sort_needles:
             raise MsdError("positions together with sort_needles: the sort makes positions of its own")
         shape = tuple(needles.shape)
-        if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous()):
-            raise MsdError(f"out must be a contiguous int64 tensor of shape {shape}")
+        _args.output(out, torch.int64, shape, "out must be a contiguous int64 tensor of shape {shape}")
         self._on_gpu(sorted_keys, needles, positions, out)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.int64, device=needles.device)
+        out = _args.output(out, torch.int64, shape, None, needles.device)
         if m == 0:
             return out
         if sort_needles:
             needles, positions = self._sorted_with_positions(needles.reshape(-1))
             needles_sorted = True
-        self._ok(self._L.msd_search_sorted(self._h, C.c_void_p(sorted_keys.data_ptr()), kt, sorted_keys.numel(), C.c_void_p(needles.data_ptr()), m,
-                                           1 if needles_sorted else 0, 1 if right else 0,
-                                           C.c_void_p(positions.data_ptr() if positions is not None else 0), C.c_void_p(out.data_ptr())))
+        self._ok(self._L.msd_search_sorted(self._h, ptr(sorted_keys), kt, sorted_keys.numel(), ptr(needles), m,
+                                           1 if needles_sorted else 0, 1 if right else 0, ptr(positions), ptr(out)))
         return out
 
     def bucketize(self, values, boundaries, right: bool = False):
@@ -930,10 +833,7 @@ class MsdContext:
     def merge_sorted_limits(self, key_bytes: int) -> int:
         """``tile`` of ``msd_merge_sorted_limits``: the elements (of both inputs together) one workgroup takes for that
         key width."""
-        t = C.c_uint64()
-        if self._L.msd_merge_sorted_limits(int(key_bytes), C.byref(t)) != 0:
-            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
-        return int(t.value)
+        return self._limits("msd_merge_sorted_limits", 1, key_bytes, "key_bytes")
 
     def merge_sorted(self, a, b, values_a=None, values_b=None, origin: bool = False, out=None, out_values=None, out_origin=None):
         """The merge of two sorted tensors: ``a`` and ``b`` are 1-D, contiguous, of the same dtype (float32, int32,
@@ -954,43 +854,30 @@ class MsdContext:
         ``(n + m,)``, the dtype of the keys, of the values, int64) receive the results and must not overlap an input:
         the merge is not in place.  The inputs are not modified.  Nothing waits on the host."""
         torch = _torch()
-        kt = self._key_type(a)
-        if b.dtype != a.dtype:
-            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
-        if a.dim() != 1 or b.dim() != 1:
-            raise MsdError("merge_sorted takes 1-D tensors")
+        kt = _args.sorted_pair("merge_sorted", a, b, contiguous_too=False)   # (all four inputs below)
         if (values_a is None) != (values_b is None):
             raise MsdError("values_a and values_b are given both or neither")
-        tensors = [a, b] + ([values_a, values_b] if values_a is not None else [])
         if values_a is not None:
-            if values_a.dim() != 1 or values_b.dim() != 1:
-                raise MsdError("merge_sorted takes 1-D tensors")
+            _args.one_dim("merge_sorted", values_a, values_b)
             if values_a.dtype != values_b.dtype or values_a.dtype not in [torch.int64, torch.float64] + ([torch.uint64] if hasattr(torch, "uint64") else []):
                 raise MsdError(f"the values must have 8-byte elements of one dtype (int64, uint64 or float64), not {values_a.dtype} and {values_b.dtype}")
             if values_a.numel() != a.numel() or values_b.numel() != b.numel():
                 raise MsdError("the values must be as long as their keys")
         elif out_values is not None:
             raise MsdError("out_values without values_a and values_b")
-        if any(not t.is_contiguous() for t in tensors):
-            raise MsdError("merge_sorted takes contiguous tensors")
+        _args.contiguous("merge_sorted", a, b, values_a, values_b)
         n, m = a.numel(), b.numel()
         want_origin = origin or out_origin is not None
-        wanted = [("out", out, a.dtype)]
-        if values_a is not None:
-            wanted.append(("out_values", out_values, values_a.dtype))
-        if want_origin:
-            wanted.append(("out_origin", out_origin, torch.int64))
+        # (the outputs: name, the tensor given, its dtype -- None: not asked for)
+        wanted = [("out", out, a.dtype), ("out_values", out_values, values_a.dtype if values_a is not None else None),
+                  ("out_origin", out_origin, torch.int64 if want_origin else None)]
         for name, t, dt in wanted:
-            if t is not None and (t.dtype != dt or tuple(t.shape) != (n + m,) or not t.is_contiguous()):
-                raise MsdError(f"{name} must be a contiguous {dt} tensor of shape {(n + m,)}")
-        self._on_gpu(*tensors, out, out_values, out_origin)
-        res = [t if t is not None else torch.empty(n + m, dtype=dt, device=a.device) for _, t, dt in wanted]
-        ptr = {name: C.c_void_p(t.data_ptr()) for (name, _, _), t in zip(wanted, res)}
-        null = C.c_void_p(0)
-        self._ok(self._L.msd_merge_sorted(self._h, C.c_void_p(a.data_ptr()), n, C.c_void_p(b.data_ptr()), m, kt,
-                                          C.c_void_p(values_a.data_ptr()) if values_a is not None else null,
-                                          C.c_void_p(values_b.data_ptr()) if values_b is not None else null,
-                                          ptr["out"], ptr.get("out_values", null), ptr.get("out_origin", null)))
+            _args.output(t, dt, (n + m,), name + " must be a contiguous {dtype} tensor of shape {shape}")
+        self._on_gpu(a, b, values_a, values_b, out, out_values, out_origin)
+        res = [_args.output(t, dt, (n + m,), None, a.device) for _, t, dt in wanted]
+        self._ok(self._L.msd_merge_sorted(self._h, ptr(a), n, ptr(b), m, kt, ptr(values_a), ptr(values_b),
+                                          *[ptr(t) for t in res]))
+        res = [t for t in res if t is not None]
         return res[0] if len(res) == 1 else tuple(res)
 
     # ---- set operations on two sorted arrays (include/msd_setops_hip.h)
@@ -999,7 +886,7 @@ class MsdContext:
     def set_sorted_limits(self, key_bytes: int) -> Tuple[int, int]:
         """``(tile, scan_tile)`` of ``msd_set_sorted_limits``: the elements (of both inputs together) one workgroup takes
         for that key width, and how many tile counts one workgroup of the tile-count scan takes at once."""
-        return self._limits2(self._L.msd_set_sorted_limits, key_bytes, "key_bytes")
+        return self._limits("msd_set_sorted_limits", 2, key_bytes, "key_bytes")
 
     @staticmethod
     def _set_bound(op: str, n: int, m: int) -> int:
@@ -1027,37 +914,23 @@ class MsdContext:
         ``out`` and ``out_origin`` (contiguous, shape ``(cap,)``) receive the results and must not overlap an input.
         The inputs are not modified.  Nothing waits on the host."""
         torch = _torch()
-        kt = self._key_type(a)
-        if b.dtype != a.dtype:
-            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
-        if a.dim() != 1 or b.dim() != 1:
-            raise MsdError("set_sorted takes 1-D tensors")
-        if not a.is_contiguous() or not b.is_contiguous():
-            raise MsdError("set_sorted takes contiguous tensors")
-        if op not in self.SET_OPS:
-            raise MsdError(f"op must be one of {sorted(self.SET_OPS)}, not {op!r}")
+        kt = _args.sorted_pair("set_sorted", a, b)
+        code = _args.op_code(self.SET_OPS, op)
         n, m = a.numel(), b.numel()
-        cap = self._set_bound(op, n, m) if cap is None else int(cap)
-        if cap < 0:
-            raise MsdError("cap must not be negative")
+        cap = _args.cap_or(cap, self._set_bound(op, n, m))
         want_origin = origin or out_origin is not None
         wanted = [("out", out, a.dtype)] + ([("out_origin", out_origin, torch.int64)] if want_origin else [])
         for name, t, dt in wanted:
-            if t is not None and (t.dtype != dt or tuple(t.shape) != (cap,) or not t.is_contiguous()):
-                raise MsdError(f"{name} must be a contiguous {dt} tensor of shape {(cap,)}")
+            _args.output(t, dt, (cap,), name + " must be a contiguous {dtype} tensor of shape {shape}")
         self._on_gpu(a, b, out, out_origin)
-        num = torch.empty(1, dtype=torch.int64, device=a.device)
-        res = [t if t is not None else torch.empty(cap, dtype=dt, device=a.device) for _, t, dt in wanted]
-        self._ok(self._L.msd_set_sorted(self._h, self.SET_OPS[op], C.c_void_p(a.data_ptr()), n, C.c_void_p(b.data_ptr()), m, kt, cap,
-                                        C.c_void_p(res[0].data_ptr()), C.c_void_p(res[1].data_ptr() if want_origin else 0), C.c_void_p(num.data_ptr())))
+        num = _args.count_cell(a.device)
+        res = [_args.output(t, dt, (cap,), None, a.device) for _, t, dt in wanted]
+        self._ok(self._L.msd_set_sorted(self._h, code, ptr(a), n, ptr(b), m, kt, cap, ptr(res[0]),
+                                        ptr(res[1] if want_origin else None), ptr(num)))
         return (num, *res)
 
     def _set1d(self, a, b, op: str, name: str):
-        self._key_type(a)
-        if b.dtype != a.dtype:
-            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
-        if a.dim() != 1 or b.dim() != 1:
-            raise MsdError(f"{name} takes 1-D tensors")
+        _args.sorted_pair(name, a, b, contiguous_too=False)   # (the copies are contiguous)
         self._on_gpu(a, b)
         sa, sb = a.clone(), b.clone()   # (contiguous copies)
         self.sort_typed(sa)
@@ -1096,18 +969,7 @@ class MsdContext:
         """``(tile, scan_tile, pair_tile)`` of ``msd_join_limits``: the elements (of both inputs together) one workgroup
         of the groups call takes for that key width, the counts one workgroup of a scan takes, and the pair ranks one
         workgroup of the expansion takes."""
-        t, s, p = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        if self._L.msd_join_limits(int(key_bytes), C.byref(t), C.byref(s), C.byref(p)) != 0:
-            raise MsdError(f"error -1: key_bytes must be 4 or 8, not {key_bytes}")
-        return int(t.value), int(s.value), int(p.value)
-
-    def _join_inputs(self, a, b, name: str) -> int:
-        kt = self._key_type(a)
-        if b.dtype != a.dtype:
-            raise MsdError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
-        if a.dim() != 1 or b.dim() != 1:
-            raise MsdError(f"{name} takes 1-D tensors")
-        return kt
+        return self._limits("msd_join_limits", 3, key_bytes, "key_bytes")
 
     def join_groups(self, a, b, cap: Optional[int] = None, keys: bool = True):
         """The matched groups of two sorted tensors: ``a`` and ``b`` are 1-D, contiguous, of the same dtype (float32,
@@ -1126,19 +988,15 @@ class MsdContext:
         ``keys`` has the inputs' dtype (``None`` with ``keys=False``), the others are int64.  The inputs are not
         modified.  Nothing waits on the host."""
         torch = _torch()
-        kt = self._join_inputs(a, b, "join_groups")
-        if not a.is_contiguous() or not b.is_contiguous():
-            raise MsdError("join_groups takes contiguous tensors")
+        kt = _args.sorted_pair("join_groups", a, b)
         n, m = a.numel(), b.numel()
-        cap = min(n, m) if cap is None else int(cap)
-        if cap < 0:
-            raise MsdError("cap must not be negative")
+        cap = _args.cap_or(cap, min(n, m))
         self._on_gpu(a, b)
-        num = torch.empty(1, dtype=torch.int64, device=a.device)
+        num = _args.count_cell(a.device)
         k = torch.empty(cap, dtype=a.dtype, device=a.device) if keys else None
         four = [torch.empty(cap, dtype=torch.int64, device=a.device) for _ in range(4)]
-        self._ok(self._L.msd_join_groups(self._h, C.c_void_p(a.data_ptr()), n, C.c_void_p(b.data_ptr()), m, kt, cap, C.c_void_p(k.data_ptr() if keys else 0),
-                                         *[C.c_void_p(t.data_ptr()) for t in four], C.c_void_p(num.data_ptr())))
+        self._ok(self._L.msd_join_groups(self._h, ptr(a), n, ptr(b), m, kt, cap, ptr(k), *[ptr(t) for t in four],
+                                         ptr(num)))
         return (num, k, *four)
 
     def join_pairs(self, groups, n: int, m: int, cap: int, positions_a=None, positions_b=None, out_a=None, out_b=None):
@@ -1156,26 +1014,22 @@ class MsdContext:
         torch = _torch()
         num_groups, _, a_first, a_count, b_first, b_count = groups
         n, m, cap = int(n), int(m), int(cap)
-        if n < 0 or m < 0 or cap < 0:
-            raise MsdError("n, m and cap must not be negative")
+        _args.non_negative("n, m and cap", n, m, cap)
         four = (a_first, a_count, b_first, b_count)
         gcap = a_first.numel()
         if num_groups.dtype != torch.int64 or num_groups.numel() != 1:
             raise MsdError("num_groups must be a one-element int64 tensor")
         if any(t.dtype != torch.int64 or t.dim() != 1 or t.numel() != gcap or not t.is_contiguous() for t in four):
             raise MsdError("the groups must be contiguous 1-D int64 tensors of one length")
-        for name, t, count in (("positions_a", positions_a, n), ("positions_b", positions_b, m)):
-            if t is not None and (t.dtype != torch.int64 or t.dim() != 1 or t.numel() != count or not t.is_contiguous()):
-                raise MsdError(f"{name} must be a contiguous 1-D int64 tensor of {count} elements")
+        _args.positions(positions_a, n, name="positions_a")
+        _args.positions(positions_b, m, name="positions_b")
         for name, t in (("out_a", out_a), ("out_b", out_b)):
-            if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (cap,) or not t.is_contiguous()):
-                raise MsdError(f"{name} must be a contiguous int64 tensor of shape {(cap,)}")
+            _args.output(t, torch.int64, (cap,), name + " must be a contiguous int64 tensor of shape {shape}")
         self._on_gpu(num_groups, *four, positions_a, positions_b, out_a, out_b)
         dev = num_groups.device
-        num = torch.empty(1, dtype=torch.int64, device=dev)
-        ia = out_a if out_a is not None else torch.empty(cap, dtype=torch.int64, device=dev)
-        ib = out_b if out_b is not None else torch.empty(cap, dtype=torch.int64, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        num = _args.count_cell(dev)
+        ia = _args.output(out_a, torch.int64, (cap,), None, dev)
+        ib = _args.output(out_b, torch.int64, (cap,), None, dev)
         self._ok(self._L.msd_join_pairs(self._h, gcap, ptr(num_groups), ptr(a_first), ptr(a_count), ptr(b_first), ptr(b_count), n, m, ptr(positions_a),
                                         ptr(positions_b), cap, ptr(ia), ptr(ib), ptr(num)))
         return num, ia, ib
@@ -1188,7 +1042,7 @@ class MsdContext:
         +0.0 do not join, NaNs with equal bits do.  Both inputs are sorted with positions (copies; the inputs are not
         modified), :meth:`join_groups` finds the groups and :meth:`join_pairs` expands them through both position
         arrays.  One host wait beyond the sorts' own: the number of pairs sizes the result."""
-        self._join_inputs(a, b, "join")
+        _args.sorted_pair("join", a, b, contiguous_too=False)   # (the sorts take contiguous copies)
         self._on_gpu(a, b)
         n, m = a.numel(), b.numel()
         if n == 0 or m == 0:
