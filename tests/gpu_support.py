@@ -10,6 +10,20 @@ import sort_rows_expect as E
 
 TAIL = 64                           # elements of every output buffer behind the ones that a call may write
 _INT = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+# Every name msd_set_option takes, with the initialiser of the same-named member of struct msd_ctx (csrc/msd_radix.hip;
+# tests/test_option_defaults.py reads both from the source and compares).  Whoever changes an option on the session's
+# context restores DEFAULTS[name], never a literal: the next file is to meet the library as it ships.
+DEFAULTS = {
+    "direct_mode": 1, "direct_min": 1 << 22, "direct_min_parent": 1 << 17, "regpart": 1, "count16": 1, "leaf17": 1, "mid_leaf": 1,
+    "early_leaves": 1, "early_plan": 1, "front_count": 1, "front_min": 1 << 29, "merge_leaf": 0, "select_cap": 1 << 20,
+    "topk_rows_mode": 0, "topk_rows_lanes": 0, "sort_rows_mode": 0, "sort_rows_lanes": 0, "search_mode": 0, "search_merge_ratio": 32,
+}
+
+
+def restore_defaults(ctx, *names):
+    """put the named options (all of them if none is named) back to the library's defaults"""
+    for name in names or DEFAULTS:
+        ctx.set_option(name, DEFAULTS[name])
 
 
 def int_dtype(es):

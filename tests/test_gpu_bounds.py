@@ -47,6 +47,7 @@ import pytest
 import torch
 
 import guardband
+from gpu_support import DEFAULTS   # the options' defaults; other GPU test files share the session's context
 from guardband import Arena
 from oracle import oracle as O
 from sort_rows_expect import np_encode
@@ -62,9 +63,6 @@ KSCANTILE = 2048        # kScanTile (csrc/msd_device.hpp: 256 threads x 8 items)
 TDT = {2: torch.int16, 4: torch.int32, 8: torch.int64, 1: torch.uint8}
 UDT = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
 KEYB = {"u32": 4, "u64": 8, "pairs": 8}
-# the options' defaults (include/msd_radix_hip.h); other GPU test files share the session's context and leave some changed
-DEFAULTS = {"direct_mode": 1, "direct_min": 1 << 22, "direct_min_parent": 1 << 17, "count16": 1, "leaf17": 1, "mid_leaf": 1,
-            "merge_leaf": 0, "regpart": 1, "select_cap": 1 << 20}
 
 
 @pytest.fixture(autouse=True)
@@ -256,7 +254,7 @@ def test_sort_option_mid_leaf_and_escalation(ctx, mid_leaf, hot_share, lead):
     try:
         st = run_sort(ctx, "u32", k, 32, lead, "low", what=f"mid_leaf={mid_leaf} hot={hot_share}")
     finally:
-        ctx.set_option("mid_leaf", 1)
+        ctx.set_option("mid_leaf", DEFAULTS["mid_leaf"])
     assert st.get("count_segments", 0) >= 1, st
     if mid_leaf == 0 or hot_share > 0.8:
         assert st.get("big_count_segments", 0) >= 1, st
@@ -275,7 +273,7 @@ def test_sort_option_count16(ctx, count16, role, lead):
     try:
         st = run_sort(ctx, "u32", k, 32, lead, NEIGH[count16 % 2], what=f"count16={count16} n={n}")
     finally:
-        ctx.set_option("count16", 1)
+        ctx.set_option("count16", DEFAULTS["count16"])
     assert st.get("rounds", 0) == 1 and st.get("count_segments", 0) >= 250 and st.get("skipped_bits", 0) == 8, st
 
 
@@ -303,7 +301,7 @@ def test_sort_option_direct_off(ctx):
     try:
         st = run_sort(ctx, "u32", k, 32, 48, "low", what="direct_mode=0")
     finally:
-        ctx.set_option("direct_mode", 1)
+        ctx.set_option("direct_mode", DEFAULTS["direct_mode"])
     assert st.get("direct_rounds", 0) == 0 and st.get("rounds", 0) >= 1, st
 
 
@@ -345,8 +343,8 @@ def test_sort_option_regpart_and_leaf17(ctx, typ, regpart, leaf17, lead):
     try:
         st = run_sort(ctx, typ, k, 64, lead, NEIGH[regpart], what=f"{typ} regpart={regpart} leaf17={leaf17}")
     finally:
-        ctx.set_option("regpart", 1)
-        ctx.set_option("leaf17", 1)
+        ctx.set_option("regpart", DEFAULTS["regpart"])
+        ctx.set_option("leaf17", DEFAULTS["leaf17"])
     if typ == "pairs":
         if regpart == 0:
             assert st.get("regpart_rounds", 0) == 0 and st.get("leaf17_segments", 0) == 0, st
@@ -747,7 +745,7 @@ def test_merge_buckets(ctx, form, leaf, nsrc, nb, per_bucket, open_bits, lead):
     try:
         out, fill, st = _merge(ctx, form, src, counts, base, nb, open_bits, first, n, lead, 37, rng)
     finally:
-        ctx.set_option("merge_leaf", 0)
+        ctx.set_option("merge_leaf", DEFAULTS["merge_leaf"])
     assert (out[:n] == np.sort(np.concatenate(rows))).all()
     assert (out[n:] == fill[n:]).all(), "the surplus of the destination was written"
 
@@ -771,7 +769,7 @@ def test_merge_buckets_rejected(ctx, form, leaf):
     try:
         out, fill, st = _merge(ctx, form, src, counts, base, nb, 16, 0, n, 48, 5, rng)
     finally:
-        ctx.set_option("merge_leaf", 0)
+        ctx.set_option("merge_leaf", DEFAULTS["merge_leaf"])
     assert (out[:n] == np.sort(allk)).all() and (out[n:] == fill[n:]).all()
     assert st.get("merge_rejected", 0) >= 2, st
 

@@ -9,7 +9,7 @@ The reference has no counterpart; the oracle is numpy's sort of the same keys (b
 import numpy as np
 import pytest
 
-from gpu_support import dev_bits as dev, host_bits as host, shapes
+from gpu_support import dev_bits as dev, host_bits as host, restore_defaults, shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -20,9 +20,7 @@ def dctx(ctx):
     ctx.set_option("direct_min_parent", 1 << 12)
     ctx.set_option("direct_mode", 1)
     yield ctx
-    ctx.set_option("direct_min", 1 << 26)
-    ctx.set_option("direct_min_parent", 1 << 17)
-    ctx.set_option("direct_mode", 1)
+    restore_defaults(ctx, "direct_min", "direct_min_parent", "direct_mode")
 
 
 KINDS_EVEN = ["uniform", "sorted", "reversed", "stride", "runs", "lowbits"]

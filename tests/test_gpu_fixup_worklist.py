@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import guardband
-from gpu_support import shapes
+from gpu_support import restore_defaults, shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -31,10 +31,7 @@ def wctx(ctx):
     ctx.set_option("direct_mode", 1)
     ctx.set_option("early_plan", 1)
     yield ctx
-    ctx.set_option("direct_min", 1 << 22)
-    ctx.set_option("direct_min_parent", 1 << 17)
-    ctx.set_option("direct_mode", 1)
-    ctx.set_option("early_plan", 1)
+    restore_defaults(ctx, "direct_min", "direct_min_parent", "direct_mode", "early_plan")
 
 
 def sort_checked(ctx, k, typ="u32", lead=0, what="", expect=None):

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import guardband
-from gpu_support import dev_bits as dev, host_bits as host
+from gpu_support import DEFAULTS, dev_bits as dev, host_bits as host, restore_defaults
 from inplacemsdradixsort_amd import MsdError
 
 pytestmark = pytest.mark.gpu
@@ -45,11 +45,11 @@ def base_sorted(ctx, n):
 @pytest.fixture()
 def fctx(ctx):
     """the library's defaults, whatever an earlier test of the session left, and `front_min` lowered to sizes numpy sorts in a moment"""
-    for name, v in (("front_count", 1), ("front_min", 1 << 27), ("direct_mode", 1), ("direct_min", 1 << 22), ("direct_min_parent", 1 << 17)):
-        ctx.set_option(name, v)
+    names = ("front_count", "front_min", "direct_mode", "direct_min", "direct_min_parent")
+    restore_defaults(ctx, *names)
+    ctx.set_option("front_min", 1 << 27)
     yield ctx
-    for name, v in (("front_count", 1), ("front_min", 1 << 29), ("direct_mode", 1), ("direct_min", 1 << 22), ("direct_min_parent", 1 << 17)):
-        ctx.set_option(name, v)
+    restore_defaults(ctx, *names)
 
 
 def way(ctx):
@@ -73,7 +73,7 @@ def sort_both(ctx, k, ref, expect):
     ctx.sort_u32(t0)
     assert way(ctx) == (0, 0), ctx.stats()
     assert torch.equal(t, t0), "front_count = 0 gives another array"
-    ctx.set_option("front_count", 1)
+    ctx.set_option("front_count", DEFAULTS["front_count"])
     return got
 
 
@@ -101,8 +101,7 @@ def test_small_shapes_are_not_tried(fctx, n):
             assert way(fctx) == (0, 0), fctx.stats()
             assert (host(t) == ref).all()
     finally:
-        fctx.set_option("direct_min", 1 << 22)
-        fctx.set_option("direct_min_parent", 1 << 17)
+        restore_defaults(fctx, "direct_min", "direct_min_parent")
 
 
 def test_view_off_the_block_grid(fctx):
@@ -128,7 +127,7 @@ def test_view_off_the_16_byte_grid_is_refused_as_before(fctx, off):
         with pytest.raises(MsdError):
             fctx.sort_u32(whole[off:off + N])
         assert (host(whole) == k).all()
-    fctx.set_option("front_count", 1)
+    fctx.set_option("front_count", DEFAULTS["front_count"])
 
 
 def test_top_byte_zero_declined(fctx):

@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEFAULTS
+
 pytestmark = pytest.mark.gpu
 
 CAP = 17408             # kC16Cap (csrc/msd_count16.hpp): elements on the 16-byte grid
@@ -25,7 +27,7 @@ KCOUNTMEDMAX = 1 << 17  # kCountMedMax (csrc/msd_device.hpp): longest segment of
 def count16_always(ctx):
     ctx.set_option("count16", 2)
     yield
-    ctx.set_option("count16", 1)
+    ctx.set_option("count16", DEFAULTS["count16"])
 
 
 def run_segments(ctx, segs, end_bit, lead=0, trail=0, seed=0):

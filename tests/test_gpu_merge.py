@@ -6,7 +6,7 @@ import sys
 
 import numpy as np
 import pytest
-from gpu_support import dev_bits as dev
+from gpu_support import DEFAULTS, dev_bits as dev
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -131,7 +131,7 @@ def test_merge_buckets_counting_kernel(ctx, nsrc, nb, per_bucket, open_bits):
     try:
         ctx.merge_buckets(dev(src), torch.from_numpy(counts).cuda(), base, open_bits, first, dst, n)
     finally:
-        ctx.set_option("merge_leaf", 0)
+        ctx.set_option("merge_leaf", DEFAULTS["merge_leaf"])
     out = host(dst, np.uint32)
     assert (out[:n] == np.sort(allk)).all()
     assert (out[n:] == 0xFFFFFFFF).all()
@@ -179,7 +179,7 @@ def test_merge_counting_kernel_duplicates(ctx):
     try:
         ctx.merge_buckets(dev(src), torch.from_numpy(counts).cuda(), base, 16, 0, dst, n)
     finally:
-        ctx.set_option("merge_leaf", 0)
+        ctx.set_option("merge_leaf", DEFAULTS["merge_leaf"])
     assert (host(dst, np.uint32) == np.sort(allk)).all()
     assert ctx.stats().get("merge_rejected", 0) == 2
 

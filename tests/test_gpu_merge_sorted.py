@@ -361,7 +361,7 @@ def test_two_calls_back_to_back_with_a_search_between(ctx, kb):
         ctx._ok(ctx._L.msd_search_sorted(ctx._h, C.c_void_p(c1.da.ptr), UKT[kb], a1.size, C.c_void_p(c1.db.ptr), b1.size, 1, 1, None, C.c_void_p(found.ptr)))
         ctx._ok(c2.launch(ctx, False, True))
     finally:
-        ctx.set_option("search_mode", 0)
+        ctx.set_option("search_mode", D.DEFAULTS["search_mode"])
     torch.cuda.synchronize()
     c1.verify(True, True, "in front of the search")
     c2.verify(False, True, "behind the search")

@@ -2,7 +2,8 @@
 the same seeded inputs -- bit-exact for keys, same key sequence + same multiset
 of (key, rid) tuples for pairs (the reference is unstable).
 Full BASELINE.json sizes are covered by size-independent properties: sortedness,
-sum and xor checksums, idempotence."""
+sum and xor checksums, idempotence -- and by the exact on-device verdict of
+tests/exact_verdict.py (ascending + the input's multiset, by a fingerprint)."""
 import json
 import os
 
@@ -10,7 +11,8 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from gpu_support import host_bits as host
+import exact_verdict as V
+from gpu_support import DEFAULTS, host_bits as host
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -118,7 +120,7 @@ def test_counting_leaf_overflow_escalates(ctx, mid_leaf, hot_share):
     try:
         ctx.sort_u32(t)
     finally:
-        ctx.set_option("mid_leaf", 1)
+        ctx.set_option("mid_leaf", DEFAULTS["mid_leaf"])
     st = ctx.stats()
     assert (host(t) == np.sort(k)).all()
     assert st.get("count_segments", 0) >= 1, st
@@ -460,46 +462,34 @@ def test_reference_api_rewrites_size_at_key_boundaries():
 
 
 def _independent_check(t, rids=None, chunk=1 << 26):
-    """(order violations, key sum mod 2^64, key != rid) by chunked torch reductions -- independent of the library's own
-    check kernel (the full-size tests relied on msd_check_* alone).  u32 / u64 bit patterns in int32 / int64."""
-    import torch
-    n, viol, total, mism, prev = t.numel(), 0, 0, 0, None
-    for a in range(0, n, chunk):
-        c = t[a:a + chunk]
-        if t.element_size() == 4:
-            u = c.to(torch.int64) & 0xFFFFFFFF
-            total += int(u.sum().item())
-        else:
-            u = c ^ (-(1 << 63))                     # unsigned order as signed order
-            total += int(c.sum().item())             # (wraps like the device's sum)
-        viol += int((u[1:] < u[:-1]).sum().item())
-        if prev is not None and int(u[0].item()) < prev:
-            viol += 1
-        prev = int(u[-1].item())
-        if rids is not None:
-            mism += int((c != rids[a:a + chunk]).sum().item())
-    return viol, total & ((1 << 64) - 1), mism
+    """(order violations, key sum mod 2^64, key != rid) by the chunked torch reductions of tests/exact_verdict.py --
+    independent of the library's own check kernel (the full-size tests relied on msd_check_* alone).  u32 / u64
+    bit patterns in int32 / int64.  The exact verdict is exact_verdict.assert_sorted_permutation, next to each call of this."""
+    return V.order_violations(t, chunk), V.key_sum(t, chunk), 0 if rids is None else V.mismatches(t, rids, chunk)
 
 
 @pytest.mark.parametrize("logn,kind", [(26, "uniform"), (26, "zipf"), (30, "uniform"), (30, "zipf"), (32, "uniform")])
 def test_full_size_properties(ctx, logn, kind):
-    """BASELINE.json configs[1], [2] at full size: sorted, checksums preserved, idempotent."""
+    """BASELINE.json configs[1], [2] at full size: sorted, checksums preserved, idempotent -- and exactly the sorted form
+    of the generated keys (tests/exact_verdict.py: ascending, and the input's multiset by a fingerprint taken before the sort)."""
     import torch
     n = 1 << logn
     t = torch.empty(n, dtype=torch.int32, device="cuda")
     (ctx.gen_uniform_u32 if kind == "uniform" else ctx.gen_zipf_u32)(t)
+    fp = V.fingerprint(t)
     v0, s0, x0 = ctx.check(t)
     assert v0 > 0
     ctx.sort_u32(t)
     v, s, x = ctx.check(t)
     assert (v, s, x) == (0, s0, x0)
     assert _independent_check(t) == (0, s0, 0)          # the same verdict without the library's check kernel
+    V.assert_sorted_permutation(fp, t)                  # exact: no key that was not in the input, none lost or doubled
     if logn <= 26:
         first = t.clone()
         ctx.sort_u32(t)  # idempotence
         assert torch.equal(first, t)
         assert (host(t) == np.sort(host(first))).all()
-    # spot-check against the oracle on a prefix of the sorted output: the smallest 2^20 keys
+    # the smallest 2^20 keys once more on the host: ascending by numpy's comparison (no oracle is called here)
     m = 1 << 20
     h = host(t[:m])
     assert (np.diff(h.astype(np.int64)) >= 0).all()
@@ -517,6 +507,7 @@ def test_pairs_at_baseline_size(ctx, shr, name):
     k = torch.empty(n, dtype=torch.int64, device="cuda")
     ctx.gen_uniform_u64(k, shift_right=shr)
     r = k.clone()
+    fp = V.fingerprint(k, r)
     v0, s0, x0 = ctx.check(k)
     assert v0 > 0
     ctx.sort_pairs_u64(k, r)
@@ -524,10 +515,11 @@ def test_pairs_at_baseline_size(ctx, shr, name):
     v, s, x = ctx.check(k, r)  # order + key == rid
     assert (v, s, x) == (0, s0, x0)
     assert _independent_check(k, r) == (0, s0, 0)       # order, sum and key == rid without the library's check kernel
+    V.assert_sorted_permutation(fp, k, r)               # exact: keys ascending, the input's multiset of tuples
     assert st.get("direct_rounds", 0) >= 2, st
     if shr:
         assert st.get("skipped_bits", 0) == 32, st
-    m = 1 << 20   # spot-check against the oracle's order on the smallest 2^20 tuples
+    m = 1 << 20   # the smallest 2^20 tuples once more on the host: keys ascending, rid == key (no oracle is called here)
     h = host(k[:m])
     assert (np.diff(h.astype(np.float64)) >= 0).all() and (h == host(r[:m])).all()
     del k, r
@@ -542,9 +534,11 @@ def test_pairs_full_size_properties(ctx):
         k = torch.empty(n, dtype=torch.int64, device="cuda")
         ctx.gen_uniform_u64(k, shift_right=shr)
         r = k.clone()
+        fp = V.fingerprint(k, r)
         v0, s0, x0 = ctx.check(k)
         ctx.sort_pairs_u64(k, r)
         v, s, x = ctx.check(k, r)  # order + key == rid
         assert (v, s, x) == (0, s0, x0)
+        V.assert_sorted_permutation(fp, k, r)   # exact: keys ascending, the input's multiset of tuples
         del k, r
     torch.cuda.empty_cache()

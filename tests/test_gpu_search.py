@@ -15,6 +15,7 @@ import pytest
 
 import search_expect as S
 import sort_rows_expect as E
+from gpu_support import DEFAULTS
 from guardband import Buf
 from sort_rows_expect import UKT, WIDTHS, special_bits, top, uniform
 
@@ -44,7 +45,7 @@ class Mode:
         self.ctx.set_option("search_mode", self.mode)
 
     def __exit__(self, *exc):
-        self.ctx.set_option("search_mode", 0)
+        self.ctx.set_option("search_mode", DEFAULTS["search_mode"])
 
 
 class Case:
@@ -298,8 +299,8 @@ def test_the_modes_agree_and_bad_options_are_refused(ctx):
         ctx.set_option("search_merge_ratio", 1 << 20)
         case.run(ctx, 0, True, needles_sorted=True)
     finally:
-        ctx.set_option("search_mode", 0)
-        ctx.set_option("search_merge_ratio", 32)
+        ctx.set_option("search_mode", DEFAULTS["search_mode"])
+        ctx.set_option("search_merge_ratio", DEFAULTS["search_merge_ratio"])
 
 
 def test_the_phase_is_named(ctx):

@@ -8,6 +8,8 @@ import time
 
 import pytest
 
+from gpu_support import DEFAULTS
+
 pytestmark = pytest.mark.gpu
 
 LOGN = 26
@@ -69,5 +71,5 @@ def test_structured_inputs_with_direct_placement_off_and_forced(ctx, direct):
             ctx.sort_u32(t)
             assert bool((_as_u32(torch, t) == torch.sort(_as_u32(torch, src)).values).all()), (name, direct)
     finally:
-        ctx.set_option("direct_mode", 1)
-        ctx.set_option("direct_min", 1 << 26)
+        ctx.set_option("direct_mode", DEFAULTS["direct_mode"])
+        ctx.set_option("direct_min", DEFAULTS["direct_min"])

@@ -16,7 +16,7 @@ import pytest
 
 import guardband
 import sort_rows_expect as E
-from gpu_support import int_dtype_of_key as int_dtype
+from gpu_support import DEFAULTS, int_dtype_of_key as int_dtype
 from sort_rows_expect import F32, F64, I32, I64, NAMES, U32, U64, UT, make_rows, seed_of
 
 pytestmark = pytest.mark.gpu
@@ -102,7 +102,7 @@ def run_case(ctx, bits, kt, pad=0, lead=0, out_lead=0, dirs=(False, True), idxs=
                 _run_case(ctx, bits, kt, pad, lead, out_lead, dirs, with_idx, check_path, mode == 2)
     finally:
         if check_path:
-            ctx.set_option("sort_rows_mode", 0)
+            ctx.set_option("sort_rows_mode", DEFAULTS["sort_rows_mode"])
 
 
 def n_inside(ctx, kt, with_idx, n):
@@ -206,7 +206,7 @@ def test_forced_lanes(ctx, kt, lanes):
         if lanes == 64:     # a row that does not fit the forced shape takes the shape of its length
             run_case(ctx, make_rows(3, W + 1, E.default_kind(kt), kt, seed_of(4, kt)), kt)
     finally:
-        ctx.set_option("sort_rows_lanes", 0)
+        ctx.set_option("sort_rows_lanes", DEFAULTS["sort_rows_lanes"])
 
 
 # ---- modes
@@ -236,7 +236,7 @@ def test_kernel_and_segment_path_agree_inside_the_envelope(ctx, kt):
                     assert np.array_equal(got[1], got[2])
                 assert up.unchanged()
     finally:
-        ctx.set_option("sort_rows_mode", 0)
+        ctx.set_option("sort_rows_mode", DEFAULTS["sort_rows_mode"])
 
 
 class Buffers:
@@ -267,7 +267,7 @@ def test_mode_2_beyond_the_envelope_is_refused(ctx, kt):
             assert "sort_rows_mode 2" in ctx._L.msd_last_error(ctx._h).decode()
             assert b.untouched()
     finally:
-        ctx.set_option("sort_rows_mode", 0)
+        ctx.set_option("sort_rows_mode", DEFAULTS["sort_rows_mode"])
 
 
 # ---- padded and misaligned rows: the padding must never be read, and no base needs more than its element's alignment
@@ -306,7 +306,7 @@ def test_in_place(ctx, kt):
                     ctx.set_option("sort_rows_mode", mode)
                     ctx._ok(raw_call(ctx, t.data_ptr(), kt, rows, n, n, desc, t.data_ptr(), idx.data_ptr() if with_idx else 0))
                 finally:
-                    ctx.set_option("sort_rows_mode", 0)
+                    ctx.set_option("sort_rows_mode", DEFAULTS["sort_rows_mode"])
                 hv = t.cpu().numpy().view(UT[kt]).reshape(rows, n)
                 check_values(kt, bits, desc, hv, "in place")
                 if with_idx:
@@ -340,7 +340,7 @@ def test_guard_bands(ctx, case):
                 ctx.set_option("sort_rows_mode", 2 if n <= M else 0)      # (the cases inside the envelope are the kernel's)
                 ctx._ok(raw_call(ctx, a_in.ptr, kt, rows, n, stride, desc, a_out.ptr, a_idx.ptr))
             finally:
-                ctx.set_option("sort_rows_mode", 0)
+                ctx.set_option("sort_rows_mode", DEFAULTS["sort_rows_mode"])
             for a, what in ((a_in, "input"), (a_out, "output"), (a_idx, "positions")):
                 a.check("%s %s %s" % (case, NAMES[kt], what))
             hv = a_out.host(UT[kt]).reshape(rows, n)

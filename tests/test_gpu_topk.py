@@ -5,11 +5,11 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from gpu_support import host_bits as host
+from gpu_support import DEFAULTS, host_bits as host
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT_CAP = 1 << 20  # the library's default "select_cap" (include/msd_radix_hip.h)
+DEFAULT_CAP = DEFAULTS["select_cap"]  # the library's default "select_cap" (include/msd_radix_hip.h)
 
 
 def dev(a):

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import guardband
-from gpu_support import int_dtype_of_key as int_dtype
+from gpu_support import DEFAULTS, int_dtype_of_key as int_dtype
 from sort_rows_expect import F32, F64, I32, I64, NAMES, U32, U64, UT, float_specials, np_decode, np_encode, row_bits, row_normal
 
 pytestmark = pytest.mark.gpu
@@ -216,7 +216,7 @@ def run_case(ctx, bits, kt, pad=0, lead=0, ks=None, modes=None):
                             first = hv
                         assert np.array_equal(first, hv), "the row kernel and the loop disagree"
     finally:
-        ctx.set_option("topk_rows_mode", 0)
+        ctx.set_option("topk_rows_mode", DEFAULTS["topk_rows_mode"])
     assert up.unchanged(), "the input (or its padding) was modified"
 
 
@@ -373,7 +373,7 @@ def test_bad_arguments_are_refused_and_touch_nothing(ctx):
         with pytest.raises(MsdError):
             ctx.set_option("topk_rows_mode", 3)
     finally:
-        ctx.set_option("topk_rows_mode", 0)
+        ctx.set_option("topk_rows_mode", DEFAULTS["topk_rows_mode"])
     # k == 0 and rows == 0: success, nothing touched
     assert raw_call(ctx, ip, F32, rows, n, n, 0, False, op, xp) == 0
     assert raw_call(ctx, ip, F32, 0, n, n, k, True, op, xp) == 0

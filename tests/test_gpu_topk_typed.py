@@ -12,12 +12,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from gpu_support import dev
+from gpu_support import DEFAULTS, dev
 from sort_rows_expect import F32, F64, I32, I64, U32, U64, VIEWS, make_float, make_int, np_decode, np_encode
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT_CAP = 1 << 20  # the library's default "select_cap" (include/msd_radix_hip.h)
+DEFAULT_CAP = DEFAULTS["select_cap"]  # the library's default "select_cap" (include/msd_radix_hip.h)
 
 
 # ---- the expectation

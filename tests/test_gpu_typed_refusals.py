@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import sort_rows_expect as E
+from gpu_support import DEFAULTS
 from guardband import Buf
 
 pytestmark = pytest.mark.gpu
@@ -283,7 +284,7 @@ def test_sort_rows_refusals_in_order_touch_nothing(ctx, es):
         refused(("16-byte", "segment sort"), idx=dx.ptr + 8)
         refused("aligned to their element size", idx=dx.ptr + 4)
     finally:
-        ctx.set_option("sort_rows_mode", 0)
+        ctx.set_option("sort_rows_mode", DEFAULTS["sort_rows_mode"])
     # the order
     refused("unknown key type", kt=9, order=5)
     refused("unknown key type", kt=9, rows=0)
