@@ -35,7 +35,14 @@ constexpr int kC16Th = MSD_C16_TH;
 #ifndef MSD_C16_SV // 16-byte vectors of the store phase in flight per thread
 #define MSD_C16_SV 8
 #endif
-constexpr int kC16Vec = 4096 / kC16Th;                       // 16-byte vectors per thread: TH * NV * 4 = 16384 elements
+// cache policy (overridable for experiments, tools/nt_variants.py): bit 0 nontemporal key loads (prefetch), bit 1
+// nontemporal full-vector stores (put); a segment is read once and written once per launch.  2^30 keys, per launch
+// (profiles/nt_variants.jsonl): plain 1765 us, loads 1756 (inside the plain build's range of 20), stores 1726, both 1747.
+#ifndef MSD_C16_NT
+#define MSD_C16_NT 2
+#endif
+constexpr bool kC16NtLoad = (MSD_C16_NT & 1) != 0, kC16NtStore = (MSD_C16_NT & 2) != 0;
+constexpr int kC16Vec = 4096 / kC16Th;                      // 16-byte vectors per thread: TH * NV * 4 = 16384 elements
 constexpr int kC16Tail = 1024 / kC16Th;                      // + scalar elements per thread behind them
 constexpr uint32_t kC16Cap = kC16Th * (kC16Vec * 4 + kC16Tail); // 17408 elements on the 16-byte grid
 constexpr uint32_t kC16MinBits = 9;                          // fewer open bits: more than 255 copies per value are the rule (byte counters)
@@ -46,12 +53,14 @@ static_assert(kC16CwWords == kC16Cap, "counters and output buffer share one LDS 
 constexpr size_t kC16Lds = (size_t)kC16Cap * 4 + kC16Th * 4 + 128 * 4 + 128;
 __device__ __forceinline__ uint32_t c16_at(uint32_t w) { return w + ((w >> 6) << 2); }
 
+template <bool BIG> // BIG: the array exceeds the memory-side cache, MSD_C16_NT applies (kStreamMinBytes, msd_device.hpp)
 __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place16_kernel(uint32_t *__restrict__ keys,
 	const Segment *__restrict__ segs, uint32_t nsegs, Segment *__restrict__ rejected, Counters *__restrict__ ctr,
 	uint64_t n_total)
 {
 	constexpr int TH = kC16Th, NV = kC16Vec, NT = kC16Tail, NK = NV * 4 + NT;
 	constexpr int CH = TH >= 1024 ? 4 : 8; // fetch-adds / look-ups in flight per thread (register budget: 64 or 128 VGPRs)
+	constexpr bool NTL = BIG && kC16NtLoad, NTS = BIG && kC16NtStore;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	uint32_t *cw = reinterpret_cast<uint32_t *>(smem);  // packed byte counters (padded layout) ...
 	uint32_t *out = reinterpret_cast<uint32_t *>(smem); // ... later the output buffer, on the array's 16-byte grid
@@ -114,11 +123,15 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		const uint32_t lastv = (totc - 1u) >> 2;
 #pragma unroll
 		for (int v = 0; v < NV; ++v) {
-			const u32x4 q = *reinterpret_cast<const u32x4 *>(base + min((uint32_t)(v * TH) + tp, lastv) * 4u);
+			const u32x4 q = ld16<NTL>(base + min((uint32_t)(v * TH) + tp, lastv) * 4u);
 			rk[v * 4 + 0] = q.x; rk[v * 4 + 1] = q.y; rk[v * 4 + 2] = q.z; rk[v * 4 + 3] = q.w;
 		}
 #pragma unroll
-		for (int s = 0; s < NT; ++s) rk[NV * 4 + s] = base[min((uint32_t)(NV * TH * 4 + s * TH) + tp, totc - 1u)];
+		for (int s = 0; s < NT; ++s) {
+			const uint32_t *e = base + min((uint32_t)(NV * TH * 4 + s * TH) + tp, totc - 1u);
+			if constexpr (NTL) rk[NV * 4 + s] = __builtin_nontemporal_load(e);
+			else rk[NV * 4 + s] = *e;
+		}
 	};
 	// the whole counter / output area to zero (16-byte stores): before the first segment and behind a rejected one;
 	// behind a sorted segment the store phase leaves the area cleared
@@ -303,7 +316,7 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 			const uint32_t v_first = off ? 1u : 0u, v_end = tot >> 2; // full vectors: [v_first, v_end)
 			auto put = [&](uint32_t q, const u32x4 &t) __attribute__((always_inline)) {
 				if (q >= v_first && q < v_end)
-					reinterpret_cast<u32x4 *>(segb)[q] = t;
+					st16<NTS>(reinterpret_cast<u32x4 *>(segb) + q, t);
 				else if (q == v_end || q < v_first) { // (one or two vectors per segment)
 					const uint32_t e0 = q << 2;
 					if (e0 + 0 >= off && e0 + 0 < tot) segb[e0 + 0] = t.x;

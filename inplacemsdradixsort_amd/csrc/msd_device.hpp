@@ -43,6 +43,25 @@ constexpr uint32_t kRposStride = 32;    // claim cursors sit on separate 128-byt
 
 struct NoVal {};
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4))); // one 16-byte register quad
+// one aligned 16 bytes from / to the array, with the cache policy as a compile-time switch (NT: nontemporal, for data
+// that is touched once per launch; the per-kernel knobs MSD_D2_NT / MSD_C16_NT choose: bit 0 loads, bit 1 stores)
+// The nontemporal policy pays where the array exceeds the memory-side cache (256 MiB): a smaller one is found there by
+// the next kernel, and loses 1-2 % without it (2^23 .. 2^25 u32 keys, profiles/nt_size_sweep.jsonl).  Both kernels
+// exist twice, the host launches the plain one (BIG = false) for arrays below this many bytes (keys and payloads).
+#ifndef MSD_NT_MIN_BYTES // (overridable for experiments)
+#define MSD_NT_MIN_BYTES (256ull << 20)
+#endif
+constexpr uint64_t kStreamMinBytes = MSD_NT_MIN_BYTES;
+template <bool NT> __device__ __forceinline__ u32x4 ld16(const void *p)
+{
+	if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+	else return *reinterpret_cast<const u32x4 *>(p);
+}
+template <bool NT> __device__ __forceinline__ void st16(void *p, const u32x4 v)
+{
+	if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
+	else *reinterpret_cast<u32x4 *>(p) = v;
+}
 
 template <typename V> struct has_val { static constexpr bool value = true; };
 template <> struct has_val<NoVal> { static constexpr bool value = false; };

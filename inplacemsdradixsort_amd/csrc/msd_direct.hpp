@@ -31,18 +31,35 @@ template <typename K, typename V> struct Direct2Cfg;
 #define MSD_D2_NV 2
 #define MSD_D2_WPE 4
 #endif
-template <> struct Direct2Cfg<uint32_t, NoVal> { static constexpr int TH = MSD_D2_TH, NV = MSD_D2_NV, WPE = MSD_D2_WPE; };
+// Cache policy of the kernel's streams (overridable for experiments, tools/nt_variants.py): bit 0 makes the 16-byte
+// key / payload loads of load_tile nontemporal, bit 1 the block stores of flush_block and flush_round.  Every slot
+// is read once and overwritten once per launch, and the slots in flight (512 workgroups x 64-128 KiB) exceed the L2:
+// keeping them buys nothing.  MSD_D2_NT sets all three instantiations, MSD_D2K_NT / MSD_D2P_NT the u64 and the tuple
+// one alone.  2^30 keys, both direct rounds of a sort together, plain -> loads -> stores -> both
+// (profiles/nt_variants.jsonl): u32 3.79 -> 3.70 -> 3.69 -> 3.62 ms, u64 7.97 -> 7.65 -> 7.56 -> 7.18,
+// tuples 15.54 -> 14.62 -> 14.22 -> 13.92; the pattern alone (tools/microbench/stream_copy.hip) 4.87 -> 4.78 ->
+// 4.95 -> 4.99 TB/s.
+#ifndef MSD_D2_NT
+#define MSD_D2_NT 3
+#endif
+#ifndef MSD_D2K_NT
+#define MSD_D2K_NT MSD_D2_NT
+#endif
+#ifndef MSD_D2P_NT
+#define MSD_D2P_NT MSD_D2_NT
+#endif
+template <> struct Direct2Cfg<uint32_t, NoVal> { static constexpr int TH = MSD_D2_TH, NV = MSD_D2_NV, WPE = MSD_D2_WPE, NT = MSD_D2_NT; };
 #ifndef MSD_D2K_TH // (u64 keys, overridable for experiments; 2^30 keys: two vectors per thread 3.97 ms per round, four 4.15, one 4.68)
 #define MSD_D2K_TH 512
 #define MSD_D2K_NV 2
 #define MSD_D2K_WPE 4
 #endif
-template <> struct Direct2Cfg<uint64_t, NoVal> { static constexpr int TH = MSD_D2K_TH, NV = MSD_D2K_NV, WPE = MSD_D2K_WPE; };
+template <> struct Direct2Cfg<uint64_t, NoVal> { static constexpr int TH = MSD_D2K_TH, NV = MSD_D2K_NV, WPE = MSD_D2K_WPE, NT = MSD_D2K_NT; };
 // tuples: key and payload buffers fill the LDS, one workgroup per CU
 #ifndef MSD_D2P_NV // (tuples, overridable for experiments; 2^30 tuples: two vectors per thread 6.15 ms per round, one 6.31, four 9.9)
 #define MSD_D2P_NV 2
 #endif
-template <> struct Direct2Cfg<uint64_t, uint64_t> { static constexpr int TH = 1024, NV = MSD_D2P_NV, WPE = 4; };
+template <> struct Direct2Cfg<uint64_t, uint64_t> { static constexpr int TH = 1024, NV = MSD_D2P_NV, WPE = 4, NT = MSD_D2P_NT; };
 
 template <typename K, typename V> struct Direct2Lds {
 	using C = Cfg<K, V>;
@@ -60,7 +77,7 @@ template <typename K, typename V> struct Direct2Lds {
 	static constexpr size_t bytes = kbuf + vbuf + head + small;
 };
 
-template <typename K, typename V>
+template <typename K, typename V, bool BIG> // BIG: the array exceeds the memory-side cache, Direct2Cfg::NT applies
 __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) void classify_direct2_kernel(
 	K *__restrict__ keys, uint64_t *__restrict__ vals, const Stripe *__restrict__ stripes,
 	const Parent *__restrict__ parents, const DirectPlan *__restrict__ plans, uint8_t *__restrict__ block_map,
@@ -74,6 +91,7 @@ __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) vo
 	using L = Direct2Lds<K, V>;
 	constexpr bool HV = has_val<V>::value;
 	constexpr int B = C::B, TH = D::TH, NV = D::NV;
+	constexpr bool NTL = BIG && (D::NT & 1) != 0, NTS = BIG && (D::NT & 2) != 0; // nontemporal loads / stores of the slot streams
 	constexpr int VEC = Vec16<K>::N;
 	constexpr int LPB = L::LPB, GPW = L::GPW, GPT = L::GPT;
 	constexpr int SPW = GPT / 4;   // slots each of the 4 bucket waves may request per tile
@@ -210,16 +228,29 @@ __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) vo
 			const bool ok = slot >= slot0 && slot < slotN; // NONE fails the test
 			okm |= ok ? 1u << v : 0u;
 			const uint64_t at = (ok ? (uint64_t)slot * B : 0ull) + sub * VEC;
-			if constexpr (sizeof(K) == 4) {
-				const uint4 q = *reinterpret_cast<const uint4 *>(keys + at);
-				kr[v * VEC + 0] = q.x; kr[v * VEC + 1] = q.y; kr[v * VEC + 2] = q.z; kr[v * VEC + 3] = q.w;
+			if constexpr (NTL) { // (the builtin takes scalars and extended vectors)
+				const u32x4 q = ld16<true>(keys + at);
+				if constexpr (sizeof(K) == 4) {
+					kr[v * VEC + 0] = q.x; kr[v * VEC + 1] = q.y; kr[v * VEC + 2] = q.z; kr[v * VEC + 3] = q.w;
+				} else {
+					kr[v * VEC + 0] = q.x | (uint64_t)q.y << 32; kr[v * VEC + 1] = q.z | (uint64_t)q.w << 32;
+				}
+				if constexpr (HV) {
+					const u32x4 p = ld16<true>(vals + at);
+					vr[v * VEC + 0] = p.x | (uint64_t)p.y << 32; vr[v * VEC + 1] = p.z | (uint64_t)p.w << 32;
+				}
 			} else {
-				const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(keys + at);
-				kr[v * VEC + 0] = q.x; kr[v * VEC + 1] = q.y;
-			}
-			if constexpr (HV) {
-				const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(vals + at);
-				vr[v * VEC + 0] = q.x; vr[v * VEC + 1] = q.y;
+				if constexpr (sizeof(K) == 4) {
+					const uint4 q = *reinterpret_cast<const uint4 *>(keys + at);
+					kr[v * VEC + 0] = q.x; kr[v * VEC + 1] = q.y; kr[v * VEC + 2] = q.z; kr[v * VEC + 3] = q.w;
+				} else {
+					const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(keys + at);
+					kr[v * VEC + 0] = q.x; kr[v * VEC + 1] = q.y;
+				}
+				if constexpr (HV) {
+					const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(vals + at);
+					vr[v * VEC + 0] = q.x; vr[v * VEC + 1] = q.y;
+				}
 			}
 		}
 		return okm;
@@ -228,9 +259,14 @@ __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) vo
 	auto flush_block = [&](uint32_t d, uint32_t slot) {
 		if (slot >= slot0 && slot < slotN) {
 			const uint64_t dst = (uint64_t)slot * B + sub * VEC;
-			*reinterpret_cast<uint4 *>(keys + dst) = *reinterpret_cast<const uint4 *>(kbuf + d * B + sub * VEC);
-			if constexpr (HV)
-				*reinterpret_cast<uint4 *>(vals + dst) = *reinterpret_cast<const uint4 *>(vbuf + d * B + sub * VEC);
+			if constexpr (NTS) {
+				st16<true>(keys + dst, *reinterpret_cast<const u32x4 *>(kbuf + d * B + sub * VEC));
+				if constexpr (HV) st16<true>(vals + dst, *reinterpret_cast<const u32x4 *>(vbuf + d * B + sub * VEC));
+			} else {
+				*reinterpret_cast<uint4 *>(keys + dst) = *reinterpret_cast<const uint4 *>(kbuf + d * B + sub * VEC);
+				if constexpr (HV)
+					*reinterpret_cast<uint4 *>(vals + dst) = *reinterpret_cast<const uint4 *>(vbuf + d * B + sub * VEC);
+			}
 		} else if (sub == 0)
 			msd_note_error(ctr, 8u);
 	};
@@ -300,8 +336,8 @@ __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) vo
 				for (uint32_t u = 0; u < U; ++u) {
 					if (ss[u] >= slot0 && ss[u] < slotN) {
 						const uint64_t dst = (uint64_t)ss[u] * B + sub * VEC;
-						*reinterpret_cast<u32x4 *>(keys + dst) = q[u];
-						if constexpr (HV) *reinterpret_cast<u32x4 *>(vals + dst) = qv[u];
+						st16<NTS>(keys + dst, q[u]);
+						if constexpr (HV) st16<NTS>(vals + dst, qv[u]);
 					} else if (ss[u] != NONE && sub == 0)
 						msd_note_error(ctr, 9u);
 				}

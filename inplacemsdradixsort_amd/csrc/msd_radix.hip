@@ -1155,8 +1155,10 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		// launched behind it if it is zero.  The host learns it with the round's summary.
 		r.tried_direct = true;
 		const uint32_t force = c->direct_mode == 2 ? 1u : 0u;
-		LAUNCH(c, (classify_direct2_kernel<K, V>), ns, (Direct2Cfg<K, V>::TH), (Direct2Lds<K, V>::bytes), keys, vals, rb.stripes, rb.parents, rb.plans,
-		       block_map, slot_full, rb.fb, rb.lo_cnt, rb.lo_off, rb.lo_keys, rb.lo_vals, rb.nfull, ctr, force);
+		// (an array beyond the memory-side cache is streamed with the kernel's nontemporal policy: kStreamMinBytes)
+		const bool big = (uint64_t)n * (sizeof(K) + (HV ? sizeof(uint64_t) : 0)) >= kStreamMinBytes;
+		LAUNCH(c, (big ? classify_direct2_kernel<K, V, true> : classify_direct2_kernel<K, V, false>), ns, (Direct2Cfg<K, V>::TH), (Direct2Lds<K, V>::bytes), keys,
+		       vals, rb.stripes, rb.parents, rb.plans, block_map, slot_full, rb.fb, rb.lo_cnt, rb.lo_off, rb.lo_keys, rb.lo_vals, rb.nfull, ctr, force);
 		phase_mark(c, "A classify direct");
 		return MSD_OK;
 	}
@@ -1490,7 +1492,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// 2^16 counters dominates and 1024-thread workgroups hide its latency better: 1.15 vs 1.44 ms at 2^28)
 			const bool c16 = sizeof(K) == 4 && (c->count16 == 2 || (c->count16 == 1 && n / ncount_host >= 12000));
 			if constexpr (sizeof(K) == 4)
-				if (c16) LAUNCH(c, count_place16_kernel, count_grid, kC16Th, kC16Lds, keys, small_count(), ncount_host, rej16, ctr, n);
+				if (c16) LAUNCH(c, ((uint64_t)n * sizeof(K) >= kStreamMinBytes ? count_place16_kernel<true> : count_place16_kernel<false>), count_grid, kC16Th, kC16Lds, keys, small_count(), ncount_host, rej16, ctr, n);
 			LAUNCH(c, (count_place_kernel<K>), count_grid, kCountTh, kCountLds, keys, c16 ? rej16 : small_count(), c16 ? 0u : ncount_host,
 			       c16 ? &ctr->nslow16 : nullptr, slow, ctr);
 			const uint32_t *walk_n = &ctr->nslow;
@@ -1750,7 +1752,8 @@ template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
 	HIPCHK(c, max_lds(&classify_stream2_kernel<K, V, false>, Stream2Lds<K, V>::bytes));
 	HIPCHK(c, max_lds(&classify_stream2_kernel<K, V, true>, Stream2Lds<K, V>::range_bytes));
 	HIPCHK(c, max_lds(&lds_sort_kernel<K, V>, SortLds<K, V>::bytes));
-	HIPCHK(c, max_lds(&classify_direct2_kernel<K, V>, Direct2Lds<K, V>::bytes));
+	HIPCHK(c, max_lds(&classify_direct2_kernel<K, V, false>, Direct2Lds<K, V>::bytes));
+	HIPCHK(c, max_lds(&classify_direct2_kernel<K, V, true>, Direct2Lds<K, V>::bytes));
 	if constexpr (sizeof(K) == 8) {
 		HIPCHK(c, max_lds(&regpart_kernel<V>, kRpLds));
 		HIPCHK(c, max_lds(&leaf17_kernel<V>, kL17Lds));
@@ -1759,7 +1762,8 @@ template <typename K, typename V> static int set_lds_attrs(msd_ctx *c)
 	if constexpr (!has_val<V>::value) {
 		if constexpr (sizeof(K) == 4) {
 			HIPCHK(c, max_lds(&front_count16_kernel<K>, kF16Lds));
-			HIPCHK(c, max_lds(&count_place16_kernel, kC16Lds));
+			HIPCHK(c, max_lds(&count_place16_kernel<false>, kC16Lds));
+			HIPCHK(c, max_lds(&count_place16_kernel<true>, kC16Lds));
 			HIPCHK(c, max_lds(&merge_place16_kernel<2>, kC16Lds));
 			HIPCHK(c, max_lds(&merge_place16_kernel<4>, kC16Lds));
 			HIPCHK(c, max_lds(&merge_place16_kernel<8>, kC16Lds));

@@ -2,7 +2,7 @@
 // The sort's big kernels are judged against these numbers, not against
 // torch.Tensor.copy_ or the 8 TB/s spec figure alone.
 //
-//   hipcc --offload-arch=gfx950 -O3 stream_copy.hip -o stream_copy && ./stream_copy [GiB]
+//   hipcc --offload-arch=gfx950 -O3 stream_copy.hip -o stream_copy && ./stream_copy [GiB] [nt]
 //
 // Variants: copy / read-only / write-only; 256- and 1024-thread workgroups; U 16-byte loads in
 // flight per lane (all U issued before the first store); plain and nontemporal accesses; one
@@ -166,7 +166,7 @@ template <int BLK> static void permute_suite(const char *src, char *dst, size_t 
 // starting offset, SPV consecutive slots per visit of a piece) and writes 128 blocks into slots of the same pieces it has
 // read earlier (in place: write behind read; OOP: into a second buffer at the same positions).  What this reaches is the
 // memory-side ceiling of that kernel.
-template <int TH, int NV, int SPV, bool OOP>
+template <int TH, int NV, int SPV, bool OOP, bool NTL = false, bool NTS = false>
 __global__ __launch_bounds__(TH) void pieces_kernel(char *__restrict__ data, char *__restrict__ other, unsigned nslots, int lag)
 {
 	extern __shared__ unsigned pad_lds[]; // occupancy control only
@@ -190,28 +190,28 @@ __global__ __launch_bounds__(TH) void pieces_kernel(char *__restrict__ data, cha
 #pragma unroll
 		for (int k = 0; k < NV; ++k) {
 			const unsigned j = t * GPT + k * GPW + grp;
-			if (t < tiles) v[k] = *reinterpret_cast<const u32x4 *>(data + (size_t)slot_of(j) * 256 + sub * 16);
+			if (t < tiles) v[k] = ld<NTL>(reinterpret_cast<const u32x4 *>(data + (size_t)slot_of(j) * 256 + sub * 16));
 			wa[k] = (size_t)slot_of(j - lag * GPT) * 256 + sub * 16; // where this lane group read `lag` tiles ago
 		}
 		if (t >= (unsigned)lag) {
 #pragma unroll
-			for (int k = 0; k < NV; ++k) *reinterpret_cast<u32x4 *>(wbase + wa[k]) = (t < tiles) ? v[k] : u32x4{ 1, 2, 3, 4 };
+			for (int k = 0; k < NV; ++k) st<NTS>(reinterpret_cast<u32x4 *>(wbase + wa[k]), (t < tiles) ? v[k] : u32x4{ 1, 2, 3, 4 });
 		}
 	}
 }
 
-template <int TH, int NV, int SPV, bool OOP> static void run_pieces(char *data, char *other, size_t bytes, int lag, int lds_kb)
+template <int TH, int NV, int SPV, bool OOP, bool NTL = false, bool NTS = false> static void run_pieces(char *data, char *other, size_t bytes, int lag, int lds_kb)
 {
 	const unsigned nslots = (unsigned)(bytes / 256);
 	hipEvent_t e0, e1;
 	CK(hipEventCreate(&e0));
 	CK(hipEventCreate(&e1));
-	CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&pieces_kernel<TH, NV, SPV, OOP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_kb * 1024));
+	CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&pieces_kernel<TH, NV, SPV, OOP, NTL, NTS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_kb * 1024));
 	float best = 1e9f, sum = 0;
 	const int reps = 5;
 	for (int rep = 0; rep < reps + 1; ++rep) {
 		CK(hipEventRecord(e0));
-		hipLaunchKernelGGL((pieces_kernel<TH, NV, SPV, OOP>), dim3(1024), dim3(TH), lds_kb * 1024, 0, data, other, nslots, lag);
+		hipLaunchKernelGGL((pieces_kernel<TH, NV, SPV, OOP, NTL, NTS>), dim3(1024), dim3(TH), lds_kb * 1024, 0, data, other, nslots, lag);
 		CK(hipEventRecord(e1));
 		CK(hipEventSynchronize(e1));
 		float t;
@@ -222,11 +222,92 @@ template <int TH, int NV, int SPV, bool OOP> static void run_pieces(char *data, 
 		}
 	}
 	printf("{\"kernel\": \"pieces_%s\", \"threads\": %d, \"slots_per_thread_per_tile\": %d, \"consecutive_slots_per_piece_visit\": %d, "
-	       "\"write_lag_tiles\": %d, \"lds_KiB\": %d, \"best_ms\": %.3f, \"best_TBps\": %.3f, \"avg_TBps\": %.3f}\n",
-	       OOP ? "out_of_place" : "in_place", TH, NV, SPV, lag, lds_kb, best, 2.0 * bytes / best / 1e9, 2.0 * bytes / (sum / reps) / 1e9);
+	       "\"write_lag_tiles\": %d, \"lds_KiB\": %d, \"nt_load\": %d, \"nt_store\": %d, \"best_ms\": %.3f, \"best_TBps\": %.3f, \"avg_TBps\": %.3f}\n",
+	       OOP ? "out_of_place" : "in_place", TH, NV, SPV, lag, lds_kb, (int)NTL, (int)NTS, best, 2.0 * bytes / best / 1e9, 2.0 * bytes / (sum / reps) / 1e9);
 	fflush(stdout);
 }
 
+// The counting leaf's access pattern without any of its work: persistent workgroups (two per CU, LDS-limited like the
+// kernel), each takes 64 KiB segments in turn; it holds one segment in registers, requests the next one (the kernel's
+// prefetch) and only then writes the held one back to where it came from -- every byte read once and written once.
+template <int TH, int U, bool NTL, bool NTS>
+__global__ __launch_bounds__(TH) void leaf_kernel(u32x4 *__restrict__ data, size_t nseg)
+{
+	extern __shared__ unsigned pad_lds[]; // occupancy control only
+	if (threadIdx.x == 0) pad_lds[0] = 0;
+	u32x4 a[U], b[U];
+	auto load = [&](u32x4 (&r)[U], size_t s) {
+#pragma unroll
+		for (int u = 0; u < U; ++u) r[u] = ld<NTL>(data + (s * U + u) * TH + threadIdx.x);
+	};
+	auto store = [&](const u32x4 (&r)[U], size_t s) {
+#pragma unroll
+		for (int u = 0; u < U; ++u) st<NTS>(data + (s * U + u) * TH + threadIdx.x, r[u]);
+	};
+	size_t s = blockIdx.x;
+	if (s >= nseg) return;
+	load(a, s);
+	for (;;) { // (the loop body twice with the register sets' roles swapped, as in the kernel; behind the last segment
+		// the "next" load re-reads the segment in hand)
+		size_t n = s + gridDim.x;
+		load(b, n < nseg ? n : s);
+		store(a, s);
+		if (n >= nseg) break;
+		s = n;
+		n = s + gridDim.x;
+		load(a, n < nseg ? n : s);
+		store(b, s);
+		if (n >= nseg) break;
+		s = n;
+	}
+}
+
+template <int TH, int U, bool NTL, bool NTS> static void run_leaf(u32x4 *data, size_t bytes, int lds_kb)
+{
+	const size_t nseg = bytes / ((size_t)TH * U * 16);
+	hipEvent_t e0, e1;
+	CK(hipEventCreate(&e0));
+	CK(hipEventCreate(&e1));
+	CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&leaf_kernel<TH, U, NTL, NTS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_kb * 1024));
+	float best = 1e9f, sum = 0;
+	const int reps = 5;
+	for (int rep = 0; rep < reps + 1; ++rep) {
+		CK(hipEventRecord(e0));
+		hipLaunchKernelGGL((leaf_kernel<TH, U, NTL, NTS>), dim3(2 * g_cus), dim3(TH), lds_kb * 1024, 0, data, nseg);
+		CK(hipEventRecord(e1));
+		CK(hipEventSynchronize(e1));
+		float t;
+		CK(hipEventElapsedTime(&t, e0, e1));
+		if (rep) {
+			best = std::min(best, t);
+			sum += t;
+		}
+	}
+	printf("{\"kernel\": \"leaf_in_place\", \"threads\": %d, \"segment_KiB\": %d, \"workgroups\": %d, \"lds_KiB\": %d, \"nt_load\": %d, \"nt_store\": %d, "
+	       "\"best_ms\": %.3f, \"avg_ms\": %.3f, \"best_TBps\": %.3f, \"avg_TBps\": %.3f}\n",
+	       TH, TH * U * 16 / 1024, 2 * g_cus, lds_kb, (int)NTL, (int)NTS, best, sum / reps, 2.0 * bytes / best / 1e9, 2.0 * bytes / (sum / reps) / 1e9);
+	fflush(stdout);
+}
+
+// Cache policy of the two in-place patterns: plain / nontemporal loads x plain / nontemporal stores, the four settings
+// of each pattern interleaved twice (profiles/nt_stream_ceiling.jsonl)
+static void policy_suite(u32x4 *src, u32x4 *dst, size_t bytes)
+{
+	for (int pass = 0; pass < 2; ++pass) {
+		run_pieces<512, 4, 1, false, false, false>((char *)src, (char *)dst, bytes, 2, 78);
+		run_pieces<512, 4, 1, false, true, false>((char *)src, (char *)dst, bytes, 2, 78);
+		run_pieces<512, 4, 1, false, false, true>((char *)src, (char *)dst, bytes, 2, 78);
+		run_pieces<512, 4, 1, false, true, true>((char *)src, (char *)dst, bytes, 2, 78);
+	}
+	for (int pass = 0; pass < 2; ++pass) {
+		run_leaf<512, 8, false, false>(src, bytes, 72);
+		run_leaf<512, 8, true, false>(src, bytes, 72);
+		run_leaf<512, 8, false, true>(src, bytes, 72);
+		run_leaf<512, 8, true, true>(src, bytes, 72);
+	}
+}
+
+// ./stream_copy [GiB] [nt]   ("nt": only the cache-policy suite of the two in-place patterns)
 int main(int argc, char **argv)
 {
 	const size_t gib = argc > 1 ? (size_t)atoi(argv[1]) : 4;
@@ -243,6 +324,13 @@ int main(int argc, char **argv)
 	CK(hipMemset(src, 0x5a, bytes));
 	CK(hipMemset(dst, 0, bytes));
 	CK(hipDeviceSynchronize());
+	if (argc > 2 && argv[2][0] == 'n') {
+		policy_suite(src, dst, bytes);
+		CK(hipFree(src));
+		CK(hipFree(dst));
+		CK(hipFree(sink));
+		return 0;
+	}
 
 	// ---- copy
 	run<256, 4, false, false, 0>("copy", src, dst, bytes, sink, 0);
@@ -287,6 +375,8 @@ int main(int argc, char **argv)
 	permute_suite<512>((const char *)src, (char *)dst, bytes);
 	permute_suite<1024>((const char *)src, (char *)dst, bytes);
 	permute_suite<4096>((const char *)src, (char *)dst, bytes);
+	// ---- cache policy of the in-place patterns
+	policy_suite(src, dst, bytes);
 	CK(hipFree(src));
 	CK(hipFree(dst));
 	CK(hipFree(sink));
