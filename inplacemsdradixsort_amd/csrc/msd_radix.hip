@@ -58,7 +58,7 @@ struct msd_ctx {
 	size_t lists_cap = 0;
 	void *pinned = nullptr; // small host staging (pinned)
 	size_t pinned_bytes = 0;
-	hipEvent_t ev_early = nullptr; // behind a round's early copy of its counters (SortRun::early_counters)
+	hipEvent_t ev_early = nullptr; // behind a round's early copy of its counters (SortRun::send_early, read_early)
 	std::string err;
 	bool profiling = false;
 	hipEvent_t ev_start = nullptr;
@@ -895,13 +895,16 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				if (!job.single_pass() && c->regpart) {
 					std::vector<Segment> fit, rest;
 					if (!dev_np)
-						for (auto &sg : cur) (sg.count + 1 <= kRpCap && sg.count > small_max ? fit : rest).push_back(sg);
-					if (dev_np || fit.size() >= 64 || (!fit.empty() && rest.empty())) {
+						for (auto &sg : cur) (register_parent(sg) ? fit : rest).push_back(sg);
+					if (dev_np || register_pass(fit.size(), cur.size())) {
+						if (parked.open) return fail(c, MSD_EINTERNAL, "a register-resident pass behind a round whose summary is parked");
+						const uint32_t np = dev_np ? dev_np : (uint32_t)fit.size(); // (dev_np of them on the device: `fit` is empty)
+						dev_np = 0;
 						// (tuples: such a segment is finished by leaf17_kernel instead, while nothing stands against it)
 						if constexpr (HV)
-							rc = c->leaf17 && leaf17_ok && !unverified ? leaf17_pass(fit, rest) : regpart_round(fit, rest);
+							rc = c->leaf17 && leaf17_ok && !unverified ? leaf17_pass(fit, rest, np) : regpart_round(fit, rest, np);
 						else
-							rc = regpart_round(fit, rest);
+							rc = regpart_round(fit, rest, np);
 						if (rc) return rc;
 						continue;
 					}
@@ -909,23 +912,37 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			}
 			// ---- the general round: plan + upload, A classify, B block metadata + permutation, C cleanup + collect, summary
 			Round r;
-			if ((rc = plan_upload(r)) || (rc = classify(r)) || (rc = permute_blocks(r)) || (rc = cleanup_collect(r)) ||
-			    (rc = r.leaves_follow ? early_summary(r) : r.plan_ahead ? plan_next_early(r) : round_summary(r)))
-				return rc;
+			if ((rc = plan_upload(r)) || (rc = classify(r))) return rc;
+			choose_end(r);
+			if ((rc = permute_blocks(r)) || (rc = cleanup_collect(r))) return rc;
+			// an early ending that declines (it says why) has changed nothing: the ordinary summary then
+			bool ended = false;
+			switch (r.end) {
+			case Round::kLeavesFollow: rc = early_summary(r, ended); break;
+			case Round::kPlanAhead: rc = plan_next_early(r, ended); break;
+			case Round::kOrdinary: break;
+			}
+			if (!rc && !ended) rc = round_summary(r);
+			if (rc) return rc;
 		}
 		return MSD_OK;
 	}
+
+	// ---- the register-pass rule (8-byte keys): a parent that fits the registers of one workgroup and no leaf takes a
+	// register-resident pass, if at least kRegPassMin parents of the round do, or all of them
+	static constexpr size_t kRegPassMin = 64;
+	static bool fits_registers(uint64_t count) { return count + 1 <= kRpCap; }
+	static bool register_parent(const Segment &sg) { return fits_registers(sg.count) && sg.count > small_max; }
+	static bool register_pass(size_t fit, size_t all) { return fit >= kRegPassMin || (fit && fit == all); }
 
 	// ---- tuples: a segment that fits the registers is FINISHED in one pass by leaf17_kernel (msd_leaf17.hpp: read once, sorted
 	// in registers and LDS, written once) instead of a register partition + the small leaves; what it rejects (a group of > 48
 	// tuples equal on the counted bits) takes that way.  A leaf must not run behind an unconfirmed leading-bit skip.
 	// (segments with <= 16 open bits -- tuples whose upper key half is constant, config 5b -- too: the leaf counts up to
 	// 16 bits, such a segment has no groups to put in order at all)
-	int leaf17_pass(const std::vector<Segment> &fit, const std::vector<Segment> &rest)
+	int leaf17_pass(const std::vector<Segment> &fit, const std::vector<Segment> &rest, const uint32_t np)
 	{
-		const bool on_device = dev_np != 0;
-		const uint32_t np = on_device ? dev_np : (uint32_t)fit.size();
-		dev_np = 0;
+		const bool on_device = fit.empty();
 		int rc = slab_reserve(c, 2 * (size_t)np * sizeof(Segment) + 4096);
 		if (!rc) rc = pinned_reserve(c, (size_t)np * sizeof(Segment) + 4096);
 		if (rc) return rc;
@@ -955,9 +972,9 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	}
 
 	// ---- the register-resident partition round (msd_regpart.hpp)
-	int regpart_round(const std::vector<Segment> &fit, const std::vector<Segment> &rest)
+	int regpart_round(const std::vector<Segment> &fit, const std::vector<Segment> &rest, const uint32_t np)
 	{
-		const bool on_device = dev_np != 0;
+		const bool on_device = fit.empty();
 		const uint32_t wmax = regpart_width(kRpCap, 64, small_max); // (the widest digit of the rule)
 		std::vector<Parent> ps;
 		uint32_t nc = 0;
@@ -966,9 +983,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			ps.push_back({ sg.start, sg.count, sg.bits - w, w, nc, 0, 0, 0 }); // (shift, width, child_base, no stripes)
 			nc += 1u << w;
 		}
-		if (on_device) nc = dev_np << wmax; // (an upper bound)
-		const uint32_t np = on_device ? dev_np : (uint32_t)ps.size();
-		dev_np = 0;
+		if (on_device) nc = np << wmax; // (an upper bound)
 		const size_t next_cap = (size_t)nc + 2; // (children above the leaf capacity: none on sane input, all at worst)
 		Parent *d_parents = nullptr;
 		ChildArrays ca = {};
@@ -982,7 +997,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			d_scr = b.take<uint32_t>(64);
 		});
 		if (!rc) rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + nc + 16, nsmall_host, ncount_host);
-		if (!rc) rc = pinned_reserve(c, std::max<size_t>(on_device ? 0 : np * sizeof(Parent), 256 + 2048 * sizeof(Segment)));
+		if (!rc) rc = pinned_reserve(c, std::max<size_t>(on_device ? 0 : np * sizeof(Parent), offsetof(Staging, sum.early))); // (the counters, the next parents)
 		if (rc) return rc;
 		LAUNCH(c, round_init_kernel, 1, 256, 0, ctr, d_scr + 16, 0, reinterpret_cast<unsigned long long *>(d_scr + 32), 0, d_scr,
 		       nullptr, nullptr, 0, nullptr, 0, nullptr); // (this round's plan is uploaded or made on the device below)
@@ -998,21 +1013,17 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		       nullptr, nc, job.stop_bits);
 		phase_mark(c, "C cleanup");
 		Counters hc;
-		const size_t ahead = std::min<size_t>(next_cap, 2048); // (next parents that travel with the counters)
-		if ((rc = read_counters(c, ctr, hc, { { 256, d_next, ahead * sizeof(Segment) } }))) return rc;
+		const size_t ahead = std::min<size_t>(next_cap, kReadAhead); // (next parents that travel with the counters)
+		if ((rc = read_counters(c, ctr, hc, { { offsetof(Staging, sum.segs), d_next, ahead * sizeof(Segment) } }))) return rc;
 		if (hc.errors) return fail(c, MSD_EINTERNAL, "register partition round: %u internal invariant violations (checks 0x%x)", hc.errors, hc.err_sites);
-		nsmall_host = hc.nsmall;
-		ncount_host = hc.ncount;
-		nbig_host = hc.nbig;
+		adopt(hc, false);
 		add_stat(c, "rounds", 1);
 		add_stat(c, "regpart_rounds", 1);
 		add_stat(c, "parents", np);
 		add_stat(c, "children", nc);
 		cur = rest;
-		if (hc.next_parents && (rc = fetch_segments(c, d_next, hc.next_parents, cur, (char *)c->pinned + 256, ahead))) return rc;
-		phase_mark(c, "readback");
-		prev_direct = false;
-		++round;
+		if (hc.next_parents && (rc = fetch_segments(c, d_next, hc.next_parents, cur, staged(offsetof(Staging, sum.segs)), ahead))) return rc;
+		next_round();
 		return MSD_OK;
 	}
 
@@ -1022,34 +1033,65 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		uint32_t np = 0, ns = 0, nc = 0;
 		bool tried_direct = false; // a direct placement was attempted (its verdict stays on the device until the summary)
 		bool hist_checks = false;  // its exact histogram pass carries the check behind a sampled leading-bit skip
-		bool leaves_follow = false; // by the plan no child can become a parent: the counters travel early, the leaves go behind at once
-		size_t plan_ahead = 0;      // > 0: the counters and this many next parents travel early, for the next round's plan (plan_next_early)
+		// how the round ends (choose_end): with round_summary; with early_summary -- by the plan no child can become a parent, the
+		// counters travel early and the leaves go behind at once; or with plan_next_early -- the counters and early_segs next
+		// parents travel early, for the next round's plan
+		enum End { kOrdinary, kLeavesFollow, kPlanAhead } end = kOrdinary;
+		size_t early_segs = 0;
 	};
-	// where the early copy of a round's counters lands in the staging buffer: behind the summary's own pieces
-	static constexpr size_t kReadAhead = 2048, kSegOff = 256, kVresOff = kSegOff - 2 * sizeof(unsigned long long);
-	static constexpr size_t kEarlyOff = kSegOff + kReadAhead * sizeof(Segment), kStagingBytes = kEarlyOff + sizeof(Counters);
-	static_assert(sizeof(Counters) <= kVresOff, "counters and the OR/AND words share the head of the staging buffer");
-	// behind them, for a round planned while the one before it still runs (early_plan): the early copy of that round's
-	// counters and first next parents, its parked counters once they are read, and a staging region of its own for the
-	// plan -- the first one is only free after a synchronisation
-	static constexpr size_t kPlanCtrOff = (kStagingBytes + 255) / 256 * 256, kPlanSegOff = kPlanCtrOff + 256;
-	static constexpr size_t kParkOff = kPlanSegOff + kReadAhead * sizeof(Segment), kStage2Off = (kParkOff + sizeof(Counters) + 255) / 256 * 256;
-	static_assert(sizeof(Counters) <= 256, "the early copy of the counters has 256 bytes");
-	// a round whose fix-up is still running when the host went on to the leaves: its summary comes with the leaves' counters
-	struct Pending {
+	// The pinned staging buffer as the rounds lay it out: `sum` is what an ordinary summary reads; behind it, for a round
+	// planned while the one before it still runs (early_plan), the early copy of that round's counters and first next
+	// parents, its parked counters once they are read, and a staging region of its own for the plan -- the first one is
+	// only free after a synchronisation.
+	static constexpr size_t kReadAhead = 2048;
+	struct Staging {
+		struct Summary {
+			Counters ctr; // where read_counters lands the counters: in front of a 256-byte head, the OR / AND words at its end
+			char gap[256 - sizeof(Counters) - 2 * sizeof(unsigned long long)];
+			unsigned long long vres[2];
+			Segment segs[kReadAhead]; // the first next parents
+			Counters early;           // the early copy of the counters of a round that the leaves follow
+		} sum;
+		alignas(256) Counters plan_ctr;             // the early copy of a round that plans ahead: its counters ...
+		alignas(256) Segment plan_segs[kReadAhead]; // ... and first next parents
+		Counters parked;                            // a parked round's counters (Deferred::kParkSlot)
+		alignas(256) char stage2[256];              // where the second staging region starts
+	};
+	char *staged(size_t at) const { return (char *)c->pinned + at; }
+	// (pinned bytes the second staging region needs for a plan)
+	static size_t stage2_bytes(size_t np, size_t ns) { return offsetof(Staging, stage2) + np * sizeof(Parent) + ns * sizeof(Stripe); }
+
+	// A round whose summary comes later, because its fix-up was still running when the host went on: to the leaves
+	// (early_summary; the summary comes with the leaves' counters, count_leaves) or to the next round (plan_next_early; that
+	// round's round_init_kernel parks the counters, and they come with the next readback, parked_piece).  One of each at most.
+	struct Deferred {
+		enum Source { kLeavesCounters, kParkSlot } source;
 		bool open = false;
 		int round = 0;
 		uint32_t np = 0, ns = 0, nc = 0;
 		uint64_t nslots = 0;
-	} pending;
-	// a round whose fix-up was still running when the host planned and enqueued the next round (plan_next_early): the next
-	// round's round_init_kernel parks its counters, and they come with the next readback
-	Pending parked;
-	bool parked_direct = false;
+		const char *direct = ""; // "direct placement ..." of the message
+	};
+	Deferred pending = { Deferred::kLeavesCounters }, parked = { Deferred::kParkSlot };
 	bool enqueue_ahead = false; // the round being enqueued now goes behind a running one: no synchronisation, no allocation
 	Counters *park() const { return ctr + 2; }
-	// (pinned bytes the second staging region needs for a plan)
-	static size_t stage2_bytes(size_t np, size_t ns) { return kStage2Off + np * sizeof(Parent) + ns * sizeof(Stripe); }
+	static constexpr uint32_t kCountWalkSites = 1u << 7; // msd_note_error sites in the leaves' counters that are no round's: count_walk_kernel's
+	// (behind adopt, ahead of next_round)
+	void defer(Deferred &d, const Round &r) { d = { d.source, true, round, r.np, r.ns, r.nc, r.rp.nslots, prev_direct ? "used" : "not used" }; }
+	ToHost parked_piece() const { return { offsetof(Staging, parked), park(), parked.open ? sizeof(Counters) : 0 }; }
+	// A readback has brought the deferred summary's counters -- `hc` itself, or behind it the park slot's (parked_piece): the
+	// round's errors, under its own number and shape, or its statistics
+	int settle(Deferred &d, Counters hc)
+	{
+		if (!d.open) return MSD_OK;
+		d.open = false;
+		const bool slot = d.source == Deferred::kParkSlot;
+		if (slot) memcpy(&hc, staged(offsetof(Staging, parked)), sizeof hc);
+		// (a scan tile's time-out leaves no site)
+		if (hc.errors && (hc.err_sites & ~(slot ? 0u : kCountWalkSites) || !hc.err_sites)) return round_errors(hc, d.round, d.np, d.ns, d.direct);
+		round_stats(hc, d.np, d.ns, d.nc, d.nslots);
+		return MSD_OK;
+	}
 	void plan_next(const std::vector<Segment> &segs, RoundPlan &rp) const
 	{
 		plan_round<K, V>(segs, small_max, c->sm_count, rp, count_bits, job.single_pass() ? job.width : 0u, job.splitters ? job.nsplit : 0u);
@@ -1065,13 +1107,6 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				    first && !job.single_pass() ? round_bytes_estimate<K, V>(n, c->sm_count) : 0, first);
 		if (rc) return rc;
 		r.np = (uint32_t)r.rp.parents.size(), r.ns = (uint32_t)r.rp.stripes.size(), r.nc = r.rp.nchildren;
-		// A keys-only round in which no parent leaves more open bits than one counting pass takes has no next parents
-		// (route_child; a full big list or a child of 2^32 keys would make one: the early counters show it).  Not behind an
-		// unconfirmed leading-bit skip: no leaf may run before the check.
-		if constexpr (!HV) {
-			r.leaves_follow = !job.single_pass() && !unverified && c->early_leaves;
-			for (size_t i = 0; i < r.np && r.leaves_follow; ++i) r.leaves_follow = r.rp.parents[i].shift <= count_bits;
-		}
 		// every child of this round may become a leaf
 		if ((rc = lists_reserve(c, (size_t)std::max(nsmall_host, ncount_host) + r.nc + 16, nsmall_host, ncount_host))) return rc;
 		{ // per-round counters, per-parent plans, scan state, and the plan itself from the staging buffer: one launch
@@ -1083,8 +1118,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// stripes as a round of all n keys has, one more per parent)
 			const size_t next_stripes = (size_t)std::max<uint64_t>((uint64_t)c->sm_count * MSD_STRIPE_WANT, n >> MSD_STRIPE_CAP_LOG) + 2 * kReadAhead + 64;
 			const size_t want = !ahead && c->early_plan && !job.single_pass() ? stage2_bytes(kReadAhead, next_stripes) : 0;
-			if ((rc = pinned_reserve(c, std::max({ kStagingBytes, r.np * sizeof(Parent) + r.ns * sizeof(Stripe), want })))) return rc;
-			char *stage = (char *)c->pinned + (ahead ? kStage2Off : 0);
+			if ((rc = pinned_reserve(c, std::max({ sizeof(typename Staging::Summary), r.np * sizeof(Parent) + r.ns * sizeof(Stripe), want })))) return rc;
+			char *stage = staged(ahead ? offsetof(Staging, stage2) : 0);
 			if (!ahead) HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
 			memcpy(stage, r.rp.parents.data(), r.np * sizeof(Parent));
 			memcpy(stage + r.np * sizeof(Parent), r.rp.stripes.data(), r.ns * sizeof(Stripe));
@@ -1234,8 +1269,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		return false;
 	}
 
-	// ---- the children to the next round or the leaf lists (behind the child scan); a round that the leaves follow sends a
-	// copy of the counters to the host behind it -- the kernels behind the copy do not wait for the host
+	// ---- the children to the next round or the leaf lists (behind the child scan); a round with an early ending sends
+	// a copy of the counters to the host behind it (send_early) -- the kernels behind the copy do not wait for the host
 	int collect(Round &r)
 	{
 		const RoundBufs &rb = r.rb;
@@ -1249,21 +1284,61 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		       small_cap, sp ? 0u : count_bits,
 		       rb.next_parents, small(), small_count(), (HV || sp) ? nullptr : big, big_cap, ctr,
 		       (sp && job.counts) ? job.counts : nullptr, job.splitters ? job.nsplit + 1u : nc, job.stop_bits);
-		if (r.leaves_follow) {
-			if (front && round == 1) return MSD_OK; // (the lists' lengths are known: front_plan_kernel has counted the children by route)
-			if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
-			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kEarlyOff, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(c, hipEventRecord(c->ev_early, c->stream));
-		} else if (c->early_plan && !sp && !r.hist_checks && !parked.open && c->pinned_bytes >= kStage2Off && may_leave_parents(r)) {
+		return send_early(r);
+	}
+
+	// ---- how the round ends, decided once its plan and its classify pass are known
+	void choose_end(Round &r) const
+	{
+		const bool sp = job.single_pass();
+		// A keys-only round in which no parent leaves more open bits than one counting pass takes has no next parents
+		// (route_child; a full big list or a child of 2^32 keys would make one: the early counters show it).  Not behind an
+		// unconfirmed leading-bit skip: no leaf may run before the check.
+		bool leaves_follow = !HV && !sp && !unverified && c->early_leaves;
+		for (size_t i = 0; i < r.np && leaves_follow; ++i) leaves_follow = r.rp.parents[i].shift <= count_bits;
+		if (leaves_follow)
+			r.end = Round::kLeavesFollow;
+		else if (c->early_plan && !sp && !r.hist_checks && !parked.open && c->pinned_bytes >= offsetof(Staging, stage2) && may_leave_parents(r)) {
 			// a round that may leave parents (one that carries the check behind a sampled bit skip decides about a restart
-			// first; one parked round at a time): the counters and the first next parents travel now, so that the host can
+			// first; one parked round at a time): the counters and the first next parents travel early, so that the host can
 			// plan the next round while this one's fix-up runs
-			r.plan_ahead = std::min<size_t>(r.rp.round_keys / (small_max + 1) + 2, kReadAhead);
-			if (front && round == 0) return MSD_OK; // (the next parents are known: the front pass's row sums)
-			if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
-			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kPlanCtrOff, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(c, hipMemcpyAsync((char *)c->pinned + kPlanSegOff, rb.next_parents, r.plan_ahead * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(c, hipEventRecord(c->ev_early, c->stream));
+			r.end = Round::kPlanAhead;
+			r.early_segs = std::min<size_t>(r.rp.round_keys / (small_max + 1) + 2, kReadAhead);
+		}
+	}
+
+	// ---- the early copy of a round's counters (and of its first early_segs next parents) to its region of the staging buffer,
+	// with an event behind it: send_early enqueues it (collect), read_early waits for it.  The front path knows what the copy
+	// would say, so nothing is sent and nothing is waited for: round 0 (it plans ahead) leaves the front pass's row sums as
+	// next parents and no leaf -- its errors come with its parked counters like everything else; in round 1 (the leaves follow)
+	// every child is a counting leaf, as front_plan_kernel has counted them.
+	bool early_known(const Round &r) const { return front && round == (r.end == Round::kPlanAhead ? 0 : 1); }
+	static size_t early_at(const Round &r) { return r.end == Round::kPlanAhead ? offsetof(Staging, plan_ctr) : offsetof(Staging, sum.early); }
+	int send_early(const Round &r)
+	{
+		if (r.end == Round::kOrdinary || early_known(r)) return MSD_OK;
+		if (!c->ev_early) HIPCHK(c, hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
+		HIPCHK(c, hipMemcpyAsync(staged(early_at(r)), ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+		if (r.early_segs)
+			HIPCHK(c, hipMemcpyAsync(staged(offsetof(Staging, plan_segs)), r.rb.next_parents, r.early_segs * sizeof(Segment), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(c, hipEventRecord(c->ev_early, c->stream));
+		return MSD_OK;
+	}
+	int read_early(const Round &r, Counters &hc, std::vector<Segment> *next = nullptr) // (next: the next parents, if all of them travelled)
+	{
+		hc = {};
+		if (early_known(r)) {
+			if (r.end == Round::kLeavesFollow)
+				hc.ncount = fsum.nroute[kRouteCount + 1];
+			else
+				hc.next_parents = kP, *next = front_parents();
+			return MSD_OK;
+		}
+		HIPCHK(c, hipEventSynchronize(c->ev_early));
+		memcpy(&hc, staged(early_at(r)), sizeof hc);
+		if (next && hc.next_parents <= r.early_segs) {
+			const Segment *sg = (const Segment *)staged(offsetof(Staging, plan_segs));
+			next->assign(sg, sg + hc.next_parents);
 		}
 		return MSD_OK;
 	}
@@ -1297,103 +1372,64 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		set_stat(c, "excess_blocks", hc.nexcess);
 	}
 
-	// ---- the counters of a parked round have come with a readback (to kParkOff): its errors and statistics, under its own
-	// number and shape
-	int parked_summary()
+	// ---- a round's counters have reached the host, early or with its summary: whether it placed directly, and the leaf lists'
+	// lengths (regpart_round: a round that tries no direct placement); next_round closes the round on the host
+	void adopt(const Counters &hc, bool tried_direct)
 	{
-		if (!parked.open) return MSD_OK;
-		parked.open = false;
-		Counters pc;
-		memcpy(&pc, (char *)c->pinned + kParkOff, sizeof pc);
-		if (pc.errors) return round_errors(pc, parked.round, parked.np, parked.ns, parked_direct ? "used" : "not used");
-		round_stats(pc, parked.np, parked.ns, parked.nc, parked.nslots);
-		return MSD_OK;
+		prev_direct = tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
+		if (prev_direct) add_stat(c, "direct_rounds", 1);
+		nsmall_host = hc.nsmall, ncount_host = hc.ncount, nbig_host = hc.nbig;
 	}
-	ToHost parked_piece() const { return { kParkOff, park(), parked.open ? sizeof(Counters) : 0 }; }
+	void next_round() { phase_mark(c, "readback"), ++round; }
 
 	// ---- a round that is not the last: the next round is planned from the early copy of the counters and the next parents
-	// (collect) and enqueued behind this round's cleanup while its fix-up still runs; this round's summary is parked.  The
-	// ordinary summary instead, with nothing enqueued ahead, if the round failed a check or left no parent or more than
-	// travelled, if its next parents stay on the device or take a register-resident pass, or if a buffer of the next round
-	// would have to grow (that synchronises).
-	int plan_next_early(Round &r)
+	// and enqueued behind this round's cleanup while its fix-up still runs; this round's summary is parked.  Declined, with
+	// nothing enqueued ahead ...
+	int plan_next_early(Round &r, bool &ended)
 	{
-		// (the front path, round 0: nothing travelled and nothing is waited for -- the next parents are the front pass's row
-		// sums, no child went to a leaf list, and the round's errors come with its parked counters like everything else)
-		const bool known = front && round == 0;
-		Counters hc = {};
-		if (known)
-			hc.next_parents = kP;
-		else {
-			HIPCHK(c, hipEventSynchronize(c->ev_early));
-			memcpy(&hc, (char *)c->pinned + kPlanCtrOff, sizeof hc);
-		}
-		bool ok = !hc.errors && hc.next_parents != 0 && hc.next_parents <= r.plan_ahead;
+		Counters hc;
 		std::vector<Segment> next;
-		if (ok) {
-			if (known)
-				next = front_parents();
-			else {
-				const Segment *sg = (const Segment *)((char *)c->pinned + kPlanSegOff);
-				next.assign(sg, sg + hc.next_parents);
-			}
-			sort_by_start(next);
-			if constexpr (sizeof(K) == 8) {
-				if (c->regpart) { // (rounds(): such parents take a register-resident pass, or their list stays on the device)
-					size_t fit = 0;
-					for (auto &s : next) fit += s.count + 1 <= kRpCap && s.count > small_max;
-					if (fit >= 64 || (fit && fit == next.size())) ok = false;
-				}
-			}
-		}
-		if (ok) {
+		if (int rc = read_early(r, hc, &next)) return rc;
+		// ... if the round failed a check, or left no parent or more than travelled,
+		if (hc.errors || hc.next_parents == 0 || hc.next_parents > r.early_segs) return MSD_OK;
+		sort_by_start(next);
+		// ... if its next parents take a register-resident pass or stay on the device (rounds(), round_summary),
+		if constexpr (sizeof(K) == 8)
+			if (c->regpart && register_pass((size_t)std::count_if(next.begin(), next.end(), register_parent), next.size())) return MSD_OK;
+		{ // ... or if a buffer of the next round would have to grow (that synchronises)
 			RoundPlan rp;
 			RoundBufs rb;
 			plan_next(next, rp);
 			Bump sz(nullptr);
 			carve_round<K, V>(sz, rp, small_max, rb);
-			ok = sz.off + 4096 <= c->slab_bytes && (size_t)std::max(hc.nsmall, hc.ncount) + rp.nchildren + 16 <= c->lists_cap &&
-			     stage2_bytes(rp.parents.size(), rp.stripes.size()) <= c->pinned_bytes;
+			if (sz.off + 4096 > c->slab_bytes || (size_t)std::max(hc.nsmall, hc.ncount) + rp.nchildren + 16 > c->lists_cap ||
+			    stage2_bytes(rp.parents.size(), rp.stripes.size()) > c->pinned_bytes)
+				return MSD_OK;
 		}
-		if (!ok) return round_summary(r);
-		prev_direct = r.tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
-		if (prev_direct) add_stat(c, "direct_rounds", 1);
-		nsmall_host = hc.nsmall;
-		ncount_host = hc.ncount;
-		nbig_host = hc.nbig;
-		parked = { true, round, r.np, r.ns, r.nc, r.rp.nslots };
-		parked_direct = prev_direct;
+		adopt(hc, r.tried_direct);
+		defer(parked, r);
 		enqueue_ahead = true;
 		add_stat(c, "rounds_planned_early", 1);
 		cur = std::move(next);
-		phase_mark(c, "readback");
-		++round;
+		next_round();
+		ended = true;
 		return MSD_OK;
 	}
 
 	// ---- the summary of a round that the leaves follow: the lists' lengths from the early copy of the counters, while the
 	// round's fix-up still runs; the rest of the summary (errors, holes, chain steps) comes with the leaves' counters
-	// (count_leaves).  If the round left a parent after all, or no counting leaf: the ordinary summary.
-	int early_summary(Round &r)
+	// (count_leaves).  Declined if the round left a parent after all, or no counting leaf, or failed a check.
+	int early_summary(Round &r, bool &ended)
 	{
-		Counters hc = {};
-		if (front && round == 1) // (nothing travelled: every child is a counting leaf, as front_plan_kernel has counted them)
-			hc.ncount = fsum.nroute[kRouteCount + 1];
-		else {
-			HIPCHK(c, hipEventSynchronize(c->ev_early));
-			memcpy(&hc, (char *)c->pinned + kEarlyOff, sizeof hc);
-		}
-		if (hc.next_parents || hc.ncount == 0 || hc.errors) return round_summary(r);
-		prev_direct = r.tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
-		if (prev_direct) add_stat(c, "direct_rounds", 1);
-		nsmall_host = hc.nsmall;
-		ncount_host = hc.ncount;
-		nbig_host = hc.nbig;
-		pending = { true, round, r.np, r.ns, r.nc, r.rp.nslots };
+		Counters hc;
+		if (int rc = read_early(r, hc)) return rc;
+		if (hc.next_parents || hc.ncount == 0 || hc.errors) return MSD_OK;
+		adopt(hc, r.tried_direct);
+		defer(pending, r);
 		add_stat(c, "leaves_behind_round", 1);
 		cur.clear();
-		phase_mark(c, "readback");
-		++round;
+		next_round();
+		ended = true;
 		return MSD_OK;
 	}
 
@@ -1403,14 +1439,14 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	{
 		const size_t np_cap = r.rp.round_keys / (small_max + 1) + 2, ahead = job.single_pass() ? 0 : std::min(np_cap, kReadAhead);
 		Counters hc;
-		int rc = pinned_reserve(c, kStagingBytes);
-		if (rc || (rc = read_counters(c, ctr, hc, { { kSegOff, r.rb.next_parents, ahead * sizeof(Segment) },
-							    { kVresOff, vres, r.hist_checks ? 2 * sizeof(unsigned long long) : 0 }, parked_piece() })))
+		int rc = pinned_reserve(c, sizeof(typename Staging::Summary));
+		if (rc || (rc = read_counters(c, ctr, hc, { { offsetof(Staging, sum.segs), r.rb.next_parents, ahead * sizeof(Segment) },
+							    { offsetof(Staging, sum.vres), vres, r.hist_checks ? 2 * sizeof(unsigned long long) : 0 }, parked_piece() })))
 			return rc;
-		if ((rc = parked_summary())) return rc;
+		if ((rc = settle(parked, hc))) return rc;
 		if (hc.errors) return round_errors(hc, round, r.np, r.ns, r.tried_direct ? (hc.direct_uneven ? "declined" : "used") : "not tried");
 		if (r.hist_checks) {
-			const unsigned long long *h = (const unsigned long long *)((char *)c->pinned + kVresOff);
+			const unsigned long long *h = (const unsigned long long *)staged(offsetof(Staging, sum.vres));
 			if ((h[0] ^ h[1]) & claimed_const) { // some key differs in a bit the sample found constant
 				exact_vary = h[0] ^ h[1];
 				phase_mark(c, "readback");
@@ -1418,28 +1454,24 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			}
 			unverified = false;
 		}
-		prev_direct = r.tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
-		if (prev_direct) add_stat(c, "direct_rounds", 1);
-		nsmall_host = hc.nsmall;
-		ncount_host = hc.ncount;
-		nbig_host = hc.nbig;
+		adopt(hc, r.tried_direct);
 		round_stats(hc, r.np, r.ns, r.nc, r.rp.nslots);
 		cur.clear();
 		if (job.single_pass()) return MSD_OK;
 		bool stays_on_device = false;
 		if constexpr (sizeof(K) == 8) {
-			// every next parent fits a workgroup's registers: the list stays on the device and is planned there
-			if (c->regpart && hc.next_parents >= 64 && (uint64_t)hc.next_max + 1 <= kRpCap) {
+			// every next parent fits a workgroup's registers, and they are enough for a pass (rounds()): the list stays on the
+			// device and is planned there
+			if (c->regpart && hc.next_parents >= kRegPassMin && fits_registers(hc.next_max)) {
 				HIPCHK(c, hipMemcpyAsync(dev_list, r.rb.next_parents, (size_t)hc.next_parents * sizeof(Segment), hipMemcpyDeviceToDevice, c->stream));
 				dev_np = hc.next_parents;
 				stays_on_device = true;
 			}
 		}
 		if (hc.next_parents && !stays_on_device &&
-		    (rc = fetch_segments(c, r.rb.next_parents, hc.next_parents, cur, (char *)c->pinned + kSegOff, ahead)))
+		    (rc = fetch_segments(c, r.rb.next_parents, hc.next_parents, cur, staged(offsetof(Staging, sum.segs)), ahead)))
 			return rc;
-		phase_mark(c, "readback");
-		++round;
+		next_round();
 		return MSD_OK;
 	}
 
@@ -1513,14 +1545,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			phase_mark(c, "count sort");
 			// byte-counter overflows of segments above the LDS-sort capacity joined the big list
 			Counters hc;
-			if ((rc = read_counters(c, ctr, hc, { parked_piece() })) || (rc = parked_summary())) return rc;
-			if (pending.open) { // the last round's summary travels with the leaves' counters (early_summary)
-				pending.open = false;
-				// (every check but count_walk_kernel's, site 7, is a round's; a scan tile's time-out leaves no site)
-				if (hc.errors && (hc.err_sites & ~0x80u || !hc.err_sites))
-					return round_errors(hc, pending.round, pending.np, pending.ns, prev_direct ? "used" : "not used");
-				round_stats(hc, pending.np, pending.ns, pending.nc, pending.nslots);
-			}
+			// (the last round's summary travels with the leaves' counters: early_summary)
+			if ((rc = read_counters(c, ctr, hc, { parked_piece() })) || (rc = settle(parked, hc)) || (rc = settle(pending, hc))) return rc;
 			if (hc.errors) return fail(c, MSD_EINTERNAL, "counting leaf: %u segments could not be queued", hc.errors);
 			set_stat(c, "count16_rejected", hc.nslow16);     // segments count_place16_kernel left to count_place_kernel
 			set_stat(c, "count_slow_segments", hc.nslow);     // segments the register-resident kernels left to the 16-bit-counter leaf / the walk

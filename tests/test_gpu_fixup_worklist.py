@@ -252,3 +252,46 @@ def test_three_sorts_back_to_back(wctx):
         assert st["rounds"] >= 1, st
         st = sort_checked(wctx, low24(seed, n), what=f"n={n}, 24 bits")
         assert st.get("leaves_behind_round", 0) == 1, st
+
+
+def test_parked_round_blocks_the_next_plan(wctx):
+    """A round is parked, the round behind it must not plan ahead -- its ordinary summary brings the parked counters --
+    and a later round plans ahead again.  2^25 + 4097 u64 keys made on the device: bits 63, 55, 47 and 39 are independent
+    random bits, the low 32 bits uniform, everything else zero, and no register-resident pass (`regpart` 0).  So the general
+    rounds have 1, 2, 4, 8 and 16 parents (an 8-bit digit each, of which one bit varies); rounds 0 and 2 are planned early,
+    round 1 finds round 0 parked, round 3 finds round 2 parked (and its average child, 16384 keys, is below the leaf
+    capacity, 17408), round 4 is the last.  The verdict is that of tests/exact_verdict.py.
+    (The stats of the commit before the host code was rewritten, `early_plan` 1 and 0 alike but for the first: rounds_planned_early
+    2 / 0, rounds 5, parents 31, stripes 4555, children 7936, slots 5243496, small_segments 4096, no direct round, no leaves
+    behind a round, no restart.)"""
+    import torch
+
+    import exact_verdict as V
+    from gpu_support import DEFAULTS
+    n = (1 << 25) + 4097
+    g = torch.Generator("cuda").manual_seed(52)
+    src = torch.randint(0, 1 << 32, (n,), dtype=torch.int64, device="cuda", generator=g)
+    for bit in (63, 55, 47, 39):
+        coin = torch.randint(0, 2, (n,), dtype=torch.int64, device="cuda", generator=g)
+        src.bitwise_or_(coin.mul_(1 << bit if bit < 63 else -(1 << 63)))
+        del coin
+    fp = V.fingerprint(src)
+    t = torch.empty_like(src)
+    wctx.set_option("regpart", 0)
+    try:
+        stats = []
+        for early_plan, what in ((1, "warm-up (buffers grow once)"), (1, "early_plan=1"), (0, "early_plan=0")):
+            wctx.set_option("early_plan", early_plan)
+            t.copy_(src)
+            wctx.sort_u64(t)
+            stats.append(wctx.stats())
+            V.assert_sorted_permutation(fp, t)
+    finally:
+        wctx.set_option("regpart", DEFAULTS["regpart"])
+    _, st1, st0 = stats
+    print(st1, st0)
+    assert st1["rounds"] >= 5, st1
+    assert 2 <= st1.get("rounds_planned_early", 0) < st1["rounds"], st1
+    assert st1.get("bit_skip_restarts", 0) == 0, st1
+    for key in PLAN_STATS:
+        assert st1.get(key, 0) == st0.get(key, 0), (key, st1, st0)
