@@ -41,7 +41,7 @@ struct msd_shard {
 	bool force_exchange = false; // (tests) a single rank with a communicator goes through the whole exchange instead of sorting locally
 	bool low16 = true;           // fine scheme: only the low halves of the keys are exchanged ("low16" = 0: whole keys; all ranks alike)
 	bool hist = true;            // fine scheme: dense buckets are exchanged as histogram records ("hist" = 0: never; all ranks alike)
-	uint64_t hist_min = 3ull << 28; // ("hist_min_keys": tests)
+	uint64_t hist_min = kHistMinKeys; // ("hist_min_keys": tests)
 	int hist_max_world = 4;         // ("hist_max_world")
 	uint32_t *d_flag = nullptr;
 	std::string err;
@@ -78,11 +78,11 @@ int fail(msd_shard *sh, int code, const char *fmt, ...)
 
 constexpr uint32_t kRowLen = kFineBuckets + 2; // bucket counts, receive capacity, keys held
 
-// row[b] = bounds[b + 1] - bounds[b]; row[nb] = capacity; row[nb + 1] = n
+// row[b] = bounds[b + 1] - bounds[b] (no bounds: the counts are in the row already); row[nb] = capacity; row[nb + 1] = n
 __global__ void counts_row_kernel(const uint64_t *__restrict__ bounds, uint32_t nb, uint64_t cap, uint64_t n, uint64_t *__restrict__ row)
 {
 	const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-	if (b < nb) row[b] = bounds[b + 1] - bounds[b];
+	if (b < nb && bounds) row[b] = bounds[b + 1] - bounds[b];
 	if (b == nb) row[nb] = cap;
 	if (b == nb + 1) row[nb + 1] = n;
 }
@@ -91,12 +91,6 @@ __global__ void counts_row_kernel(const uint64_t *__restrict__ bounds, uint32_t 
 __global__ void hist_ready_kernel(const uint32_t *__restrict__ overflow, uint64_t *__restrict__ held)
 {
 	if (*overflow == 0) *held |= kHistReady;
-}
-
-__global__ void row_tail_kernel(uint32_t nb, uint64_t cap, uint64_t n, uint64_t *__restrict__ row)
-{
-	row[nb] = cap;
-	row[nb + 1] = n;
 }
 
 // small[src * world + dst] = keys source src holds for destination dst; small[world^2 + r] = capacity of rank r;
@@ -169,16 +163,6 @@ int exchange_counts(msd_shard *sh, uint32_t nb, uint32_t row_len, const char *wh
 	return MSD_OK;
 }
 
-// the coarse schemes' row: 256 top-digit counts (written by msd_partition_*), then capacity and size
-int finish_coarse_row(msd_shard *sh, uint64_t cap, uint64_t n)
-{
-	sh->h_small[0] = cap;
-	sh->h_small[1] = n;
-	SH_HIP(sh, hipMemcpyAsync(sh->d_row + 256, sh->h_small, 2 * sizeof(uint64_t), hipMemcpyHostToDevice, sh->stream));
-	SH_HIP(sh, hipStreamSynchronize(sh->stream)); // (the pinned words are reused by the count exchange)
-	return MSD_OK;
-}
-
 template <typename T>
 int all_to_all(msd_shard *sh, const T *src, T *dst, const std::vector<uint64_t> &send_cnt, const std::vector<uint64_t> &recv_cnt, bool group_open)
 {
@@ -200,6 +184,146 @@ int all_to_all(msd_shard *sh, const T *src, T *dst, const std::vector<uint64_t> 
 		ro += recv_cnt[p];
 	}
 	if (!group_open) SH_NCCL(sh, ncclGroupEnd());
+	return MSD_OK;
+}
+
+// The coarse exchange of the u32 and the tuple entry points, after the top-digit pass (msd_partition_*) has written its
+// 256 counts into the row: capacity and size behind them, count exchange, then keys -- and rids, with the same splits -- in ONE group (tuples: 2 x (world - 1) sends and
+// receives in flight together).  *m = what arrived.
+template <typename T>
+int coarse_exchange(msd_shard *sh, const char *what, uint64_t n, uint64_t recv_cap, const T *d_keys, T *d_recv_keys, const T *d_rids, T *d_recv_rids,
+		    uint64_t *m)
+{
+	std::vector<uint64_t> send_cnt, recv_cnt;
+	sh->h_small[0] = recv_cap;
+	sh->h_small[1] = n;
+	SH_HIP(sh, hipMemcpyAsync(sh->d_row + 256, sh->h_small, 2 * sizeof(uint64_t), hipMemcpyHostToDevice, sh->stream));
+	SH_HIP(sh, hipStreamSynchronize(sh->stream)); // (the pinned words are reused by the count exchange)
+	int rc = exchange_counts(sh, 256, 258, what, send_cnt, recv_cnt);
+	if (rc) return rc;
+	*m = 0;
+	for (int s = 0; s < sh->world; ++s) *m += recv_cnt[s];
+	SH_NCCL(sh, ncclGroupStart());
+	rc = all_to_all<T>(sh, d_keys, d_recv_keys, send_cnt, recv_cnt, true);
+	if (!rc && d_rids) rc = all_to_all<T>(sh, d_rids, d_recv_rids, send_cnt, recv_cnt, true);
+	SH_NCCL(sh, ncclGroupEnd());
+	return rc;
+}
+
+// The scheme must be the same on every rank: it is decided from what every rank can see before any exchange -- the
+// arguments all ranks pass alike (scheme, work buffer or not) -- and, for scheme 0, from the smallest shard, which
+// every rank learns from a first tiny all-gather of the shard sizes.
+int choose_scheme(msd_shard *sh, int scheme, uint64_t n, bool have_work, bool *fine)
+{
+	const int W = sh->world;
+	*fine = scheme == 1 || (scheme == 0 && have_work && W <= 8);
+	if (scheme == 0 && *fine) {
+		sh->h_small[0] = n;
+		SH_HIP(sh, hipMemcpyAsync(sh->d_row, sh->h_small, sizeof(uint64_t), hipMemcpyHostToDevice, sh->stream));
+		SH_HIP(sh, hipStreamSynchronize(sh->stream));
+		SH_NCCL(sh, ncclAllGather(sh->d_row, sh->d_all, 1, ncclUint64, sh->comm, sh->stream));
+		SH_HIP(sh, hipMemcpyAsync(sh->h_small, sh->d_all, (size_t)W * sizeof(uint64_t), hipMemcpyDeviceToHost, sh->stream));
+		SH_HIP(sh, hipStreamSynchronize(sh->stream));
+		for (int r = 0; r < W; ++r) *fine = *fine && sh->h_small[r] >= kFineMinKeys;
+	}
+	if (*fine && (!have_work || W > 8)) return fail(sh, MSD_EINVAL, "sort_u32_sharded: the fine scheme needs a work buffer and at most 8 ranks");
+	return MSD_OK;
+}
+
+// What a rank has ready to send after fine_prepare; what travels is decided after the count exchange (fine_send).
+struct fine_ready {
+	bool want_hist, low16;      // asked for: records (the rule of dist.py's _wants_records, same inputs) / low halves
+	bool packed = false;        // the low halves are in the work buffer
+	uint8_t *d_rec;             // the records, in the work buffer
+};
+
+enum fine_form { kRecords, kLowHalves, kWholeKeys };
+
+// Fine scheme, before the exchange: the shard ordered by its top 16 bits, the row [2^16 counts | capacity | n (| records ready)]
+int fine_prepare(msd_shard *sh, uint32_t *d_keys, uint64_t n, uint64_t recv_cap, uint32_t *d_work, uint64_t work_cap, fine_ready *rd)
+{
+	const uint64_t rec_total = (uint64_t)kFineBuckets * msd_hist2_record_bytes(), cap = recv_cap < work_cap ? recv_cap : work_cap;
+	// Dense buckets travel as HISTOGRAMS of their low halves (msd_hist2_pack_u32: one record of 17408 bytes per bucket,
+	// whatever it holds -- a quarter of the whole keys' bytes at 2^14 keys per bucket), packed into the work buffer; a rank
+	// whose packing did not overflow says so in its row, and the records travel only if every rank's did not.
+	// (up to 4 ranks: there a pair's low halves take longer over their link than the local work they hide behind; at 8 they
+	// do not, and records cost 1.3 ms more to prepare -- the figures are in inplacemsdradixsort_amd/dist.py at FINE_HIST_MAX_WORLD)
+	rd->want_hist = sh->hist && sh->world <= sh->hist_max_world && n >= sh->hist_min && work_cap * 4 >= rec_total && recv_cap * 4 >= rec_total;
+	// Otherwise only the keys' LOW halves travel: once the shard is ordered by the upper halves, the upper half of a key is
+	// its bucket's number, which the receiver knows from the counts -- half the bytes over the links (one xGMI link per
+	// pair of GPUs: at 2^30 keys per rank the exchange of whole keys outlasts a rank's local work at 2 and 4 GPUs) and for
+	// the leaf to read.  msd_order_low16_u32 orders and packs in one go (one in-place round, exact counts, the low halves
+	// scattered into the work buffer -- dead until the leaf writes it).
+	rd->low16 = sh->low16 && work_cap * 2 >= n;
+	// (records are packed from the low halves, behind them in the work buffer, when both fit)
+	const uint64_t rec_at = (2 * n + 255) / 256 * 256;
+	rd->packed = rd->low16 && (!rd->want_hist || work_cap * 4 >= rec_at + rec_total);
+	rd->d_rec = (uint8_t *)d_work + (rd->packed && rd->want_hist ? rec_at : 0);
+	if (rd->packed) {
+		SH_MSD(sh, msd_order_low16_u32(sh->ctx, d_keys, n, (uint16_t *)d_work, sh->d_row)); // (the row's first 2^16 words: the bucket sizes)
+	} else {
+		SH_MSD(sh, msd_sort_u32_top(sh->ctx, d_keys, n, 32, 32 - kFineBits));
+		SH_MSD(sh, msd_bucket_bounds_u32(sh->ctx, d_keys, n, 32 - kFineBits, 0, kFineBuckets, sh->d_bounds));
+	}
+	hipLaunchKernelGGL(counts_row_kernel, dim3((kRowLen + 255) / 256), dim3(256), 0, sh->stream, (const uint64_t *)(rd->packed ? nullptr : sh->d_bounds),
+			   kFineBuckets, cap, n, sh->d_row);
+	SH_HIP(sh, hipGetLastError());
+	if (!rd->want_hist) return MSD_OK;
+	if (rd->packed) {
+		SH_MSD(sh, msd_bounds_from_counts16(sh->ctx, sh->d_row, sh->d_bounds));
+		SH_MSD(sh, msd_hist2_pack_u32_low16(sh->ctx, (const uint16_t *)d_work, n, sh->d_bounds, kFineBuckets, rd->d_rec, work_cap * 4 - rec_at, sh->d_flag));
+	} else
+		SH_MSD(sh, msd_hist2_pack_u32(sh->ctx, d_keys, n, sh->d_bounds, kFineBuckets, d_work, work_cap * 4, sh->d_flag));
+	hipLaunchKernelGGL(hist_ready_kernel, dim3(1), dim3(1), 0, sh->stream, (const uint32_t *)sh->d_flag, sh->d_row + kFineBuckets + 1);
+	SH_HIP(sh, hipGetLastError());
+	return MSD_OK;
+}
+
+// The one all-to-all, in the form every rank agrees on (the count exchange has run): records if every rank has them
+// ready, else low halves (packed here if the records were packed from the keys), else whole keys.
+int fine_send(msd_shard *sh, const fine_ready &rd, const uint32_t *d_keys, uint64_t n, uint32_t *d_recv, uint32_t *d_work,
+	      const std::vector<uint64_t> &send_cnt, const std::vector<uint64_t> &recv_cnt, fine_form *form)
+{
+	bool use_hist = true;
+	for (int r = 0; r < sh->world; ++r) use_hist = use_hist && (sh->h_small[(size_t)sh->world * sh->world + sh->world + r] & kHistReady) != 0;
+	if (use_hist) {
+		*form = kRecords;
+		std::vector<uint64_t> blocks(sh->world, (uint64_t)kFineBuckets * msd_hist2_record_bytes() / (uint64_t)sh->world);
+		return all_to_all<uint8_t>(sh, rd.d_rec, (uint8_t *)d_recv, blocks, blocks, false);
+	}
+	if (!rd.low16) {
+		*form = kWholeKeys;
+		return all_to_all<uint32_t>(sh, d_keys, d_recv, send_cnt, recv_cnt, false);
+	}
+	*form = kLowHalves;
+	if (!rd.packed) SH_MSD(sh, msd_pack_low16_u32(sh->ctx, d_keys, n, (uint16_t *)d_work)); // (the records did not travel after all)
+	return all_to_all<uint16_t>(sh, (const uint16_t *)d_work, (uint16_t *)d_recv, send_cnt, recv_cnt, false);
+}
+
+// The counting leaf over what arrived, whatever its form: this rank's extents per source (mine_kernel), the sources'
+// bases, one merge into the work buffer.
+int fine_finish(msd_shard *sh, fine_form form, const uint32_t *d_recv, uint64_t recv_cap, const std::vector<uint64_t> &recv_cnt, uint32_t *d_work,
+		uint64_t work_cap, uint32_t **d_out, uint64_t *n_out)
+{
+	const uint32_t W = (uint32_t)sh->world, per = kFineBuckets / W, first = (uint32_t)sh->rank * per;
+	hipLaunchKernelGGL(mine_kernel, dim3((kFineBuckets + 255) / 256), dim3(256), 0, sh->stream, (const uint64_t *)sh->d_all, kRowLen, per,
+			   (uint32_t)sh->rank, W, sh->d_mine);
+	SH_HIP(sh, hipGetLastError());
+	std::vector<uint64_t> base(W);
+	uint64_t m = 0;
+	for (uint32_t s = 0; s < W; ++s) {
+		base[s] = m;
+		m += recv_cnt[s];
+	}
+	if (form == kRecords) // (source s's records lie at s * per records: no bases)
+		SH_MSD(sh, msd_merge_buckets_u32_hist2(sh->ctx, d_recv, recv_cap * 4, sh->d_mine, W, per, first, d_work, work_cap, m));
+	else if (form == kLowHalves)
+		SH_MSD(sh, msd_merge_buckets_u32_low16(sh->ctx, (const uint16_t *)d_recv, recv_cap * 2, sh->d_mine, base.data(), W, per, first, d_work, work_cap, m));
+	else
+		SH_MSD(sh, msd_merge_buckets_u32(sh->ctx, d_recv, recv_cap, sh->d_mine, base.data(), W, per, 32 - kFineBits, first, d_work, work_cap, m));
+	SH_HIP(sh, hipStreamSynchronize(sh->stream));
+	*d_out = d_work;
+	*n_out = m;
 	return MSD_OK;
 }
 
@@ -305,117 +429,25 @@ int msd_sort_u32_sharded(msd_shard *sh, uint32_t *d_keys, uint64_t n, uint32_t *
 		return MSD_OK;
 	}
 	if (!d_recv) return fail(sh, MSD_EINVAL, "sort_u32_sharded: null receive buffer");
-	std::vector<uint64_t> send_cnt, recv_cnt;
-	// The scheme must be the same on every rank: it is decided from what every rank can see before any exchange -- the
-	// arguments all ranks pass alike (scheme, work buffer or not) -- and, for scheme 0, from the smallest shard, which
-	// every rank learns from the all-gathered rows; the fine scheme's rows are therefore produced only after a first
-	// tiny all-gather of the shard sizes when scheme == 0.
-	bool fine = scheme == 1 || (scheme == 0 && d_work != nullptr && W <= 8);
-	if (scheme == 0 && fine) {
-		sh->h_small[0] = n;
-		SH_HIP(sh, hipMemcpyAsync(sh->d_row, sh->h_small, sizeof(uint64_t), hipMemcpyHostToDevice, sh->stream));
-		SH_HIP(sh, hipStreamSynchronize(sh->stream));
-		SH_NCCL(sh, ncclAllGather(sh->d_row, sh->d_all, 1, ncclUint64, sh->comm, sh->stream));
-		SH_HIP(sh, hipMemcpyAsync(sh->h_small, sh->d_all, (size_t)W * sizeof(uint64_t), hipMemcpyDeviceToHost, sh->stream));
-		SH_HIP(sh, hipStreamSynchronize(sh->stream));
-		for (int r = 0; r < W; ++r) fine = fine && sh->h_small[r] >= kFineMinKeys;
-	}
-	if (fine && (!d_work || W > 8)) return fail(sh, MSD_EINVAL, "sort_u32_sharded: the fine scheme needs a work buffer and at most 8 ranks");
+	// the same steps as dist.py's one-shot: choose the scheme, prepare, exchange counts, send, finish
+	bool fine = false;
+	int rc = choose_scheme(sh, scheme, n, d_work != nullptr, &fine);
+	if (rc) return rc;
 	if (fine) {
-		const uint32_t per = kFineBuckets / (uint32_t)W;
-		const uint64_t rec_total = (uint64_t)kFineBuckets * msd_hist2_record_bytes();
-		// Dense buckets travel as HISTOGRAMS of their low halves (msd_hist2_pack_u32: one record of 17408 bytes per bucket,
-		// whatever it holds -- a quarter of the whole keys' bytes at 2^14 keys per bucket), packed into the work buffer; a rank
-		// whose packing did not overflow says so in its row, and the records travel only if every rank's did not.
-		// (up to 4 ranks: there a pair's low halves take longer over their link than the local work they hide behind; at 8 they
-		// do not, and records cost 1.3 ms more to prepare -- the figures are in inplacemsdradixsort_amd/dist.py at FINE_HIST_MAX_WORLD)
-		const bool want_hist = sh->hist && W <= sh->hist_max_world && n >= sh->hist_min && work_cap * 4 >= rec_total && recv_cap * 4 >= rec_total;
-		// Otherwise only the keys' LOW halves travel: once the shard is ordered by the upper halves, the upper half of a key is
-		// its bucket's number, which the receiver knows from the counts -- half the bytes over the links (one xGMI link per
-		// pair of GPUs: at 2^30 keys per rank the exchange of whole keys outlasts a rank's local work at 2 and 4 GPUs) and for
-		// the leaf to read.  msd_order_low16_u32 orders and packs in one go (one in-place round, exact counts, the low halves
-		// scattered into the work buffer -- dead until the leaf writes it).
-		const bool low16 = sh->low16 && work_cap * 2 >= n;
-		bool packed = false;
-		// (records are packed from the low halves, behind them in the work buffer, when both fit)
-		const uint64_t rec_at = (2 * n + 255) / 256 * 256;
-		unsigned char *d_rec = (unsigned char *)d_work;
-		if (low16 && (!want_hist || work_cap * 4 >= rec_at + rec_total)) {
-			SH_MSD(sh, msd_order_low16_u32(sh->ctx, d_keys, n, (uint16_t *)d_work, sh->d_row)); // (the row's first 2^16 words: the bucket sizes)
-			hipLaunchKernelGGL(row_tail_kernel, dim3(1), dim3(1), 0, sh->stream, kFineBuckets, recv_cap < work_cap ? recv_cap : work_cap, n, sh->d_row);
-			SH_HIP(sh, hipGetLastError());
-			packed = true;
-			if (want_hist) {
-				d_rec += rec_at;
-				SH_MSD(sh, msd_bounds_from_counts16(sh->ctx, sh->d_row, sh->d_bounds));
-				SH_MSD(sh, msd_hist2_pack_u32_low16(sh->ctx, (const uint16_t *)d_work, n, sh->d_bounds, kFineBuckets, d_rec, work_cap * 4 - rec_at, sh->d_flag));
-			}
-		} else {
-			SH_MSD(sh, msd_sort_u32_top(sh->ctx, d_keys, n, 32, 32 - kFineBits));
-			SH_MSD(sh, msd_bucket_bounds_u32(sh->ctx, d_keys, n, 32 - kFineBits, 0, kFineBuckets, sh->d_bounds));
-			hipLaunchKernelGGL(counts_row_kernel, dim3((kRowLen + 255) / 256), dim3(256), 0, sh->stream, (const uint64_t *)sh->d_bounds, kFineBuckets,
-					   recv_cap < work_cap ? recv_cap : work_cap, n, sh->d_row);
-			SH_HIP(sh, hipGetLastError());
-		}
-		if (want_hist) {
-			if (!packed) SH_MSD(sh, msd_hist2_pack_u32(sh->ctx, d_keys, n, sh->d_bounds, kFineBuckets, d_work, work_cap * 4, sh->d_flag));
-			hipLaunchKernelGGL(hist_ready_kernel, dim3(1), dim3(1), 0, sh->stream, (const uint32_t *)sh->d_flag, sh->d_row + kFineBuckets + 1);
-			SH_HIP(sh, hipGetLastError());
-		}
-		int rc = exchange_counts(sh, kFineBuckets, kRowLen, "keys", send_cnt, recv_cnt);
-		if (rc) return rc;
-		bool use_hist = true;
-		for (int r = 0; r < W; ++r) use_hist = use_hist && (sh->h_small[(size_t)W * W + W + r] & kHistReady) != 0;
-		if (use_hist) {
-			std::vector<uint64_t> blocks(W, rec_total / (uint64_t)W);
-			rc = all_to_all<uint8_t>(sh, (const uint8_t *)d_rec, (uint8_t *)d_recv, blocks, blocks, false);
-			if (rc) return rc;
-			hipLaunchKernelGGL(mine_kernel, dim3((kFineBuckets + 255) / 256), dim3(256), 0, sh->stream, (const uint64_t *)sh->d_all, kRowLen, per,
-					   (uint32_t)sh->rank, (uint32_t)W, sh->d_mine);
-			SH_HIP(sh, hipGetLastError());
-			uint64_t m = 0;
-			for (int s2 = 0; s2 < W; ++s2) m += recv_cnt[s2];
-			SH_MSD(sh, msd_merge_buckets_u32_hist2(sh->ctx, d_recv, recv_cap * 4, sh->d_mine, (uint32_t)W, per, (uint32_t)sh->rank * per, d_work, work_cap, m));
-			SH_HIP(sh, hipStreamSynchronize(sh->stream));
-			*d_out = d_work;
-			*n_out = m;
-			return MSD_OK;
-		}
-		if (low16) {
-			if (!packed) SH_MSD(sh, msd_pack_low16_u32(sh->ctx, d_keys, n, (uint16_t *)d_work)); // (the records did not travel after all)
-			rc = all_to_all<uint16_t>(sh, (const uint16_t *)d_work, (uint16_t *)d_recv, send_cnt, recv_cnt, false);
-		} else
-			rc = all_to_all<uint32_t>(sh, d_keys, d_recv, send_cnt, recv_cnt, false);
-		if (rc) return rc;
-		hipLaunchKernelGGL(mine_kernel, dim3((kFineBuckets + 255) / 256), dim3(256), 0, sh->stream, (const uint64_t *)sh->d_all, kRowLen, per,
-				   (uint32_t)sh->rank, (uint32_t)W, sh->d_mine);
-		SH_HIP(sh, hipGetLastError());
-		std::vector<uint64_t> base(W);
-		uint64_t m = 0;
-		for (int s = 0; s < W; ++s) {
-			base[s] = m;
-			m += recv_cnt[s];
-		}
-		if (low16)
-			SH_MSD(sh, msd_merge_buckets_u32_low16(sh->ctx, (const uint16_t *)d_recv, recv_cap * 2, sh->d_mine, base.data(), (uint32_t)W, per,
-							       (uint32_t)sh->rank * per, d_work, work_cap, m));
-		else
-			SH_MSD(sh, msd_merge_buckets_u32(sh->ctx, d_recv, recv_cap, sh->d_mine, base.data(), (uint32_t)W, per, 32 - kFineBits,
-							 (uint32_t)sh->rank * per, d_work, work_cap, m));
-		SH_HIP(sh, hipStreamSynchronize(sh->stream));
-		*d_out = d_work;
-		*n_out = m;
-		return MSD_OK;
+		std::vector<uint64_t> send_cnt, recv_cnt;
+		fine_ready rd;
+		fine_form form;
+		rc = fine_prepare(sh, d_keys, n, recv_cap, d_work, work_cap, &rd);
+		if (!rc) rc = exchange_counts(sh, kFineBuckets, kRowLen, "keys", send_cnt, recv_cnt);
+		if (!rc) rc = fine_send(sh, rd, d_keys, n, d_recv, d_work, send_cnt, recv_cnt, &form);
+		if (!rc) rc = fine_finish(sh, form, d_recv, recv_cap, recv_cnt, d_work, work_cap, d_out, n_out);
+		return rc;
 	}
 	// coarse: one top-digit pass; the 256 bucket counts go into the row in front of capacity and size
-	SH_MSD(sh, msd_partition_u32(sh->ctx, d_keys, n, 24, 8, sh->d_row));
-	int rc = finish_coarse_row(sh, recv_cap, n);
-	if (!rc) rc = exchange_counts(sh, 256, 258, "keys", send_cnt, recv_cnt);
-	if (rc) return rc;
-	rc = all_to_all<uint32_t>(sh, d_keys, d_recv, send_cnt, recv_cnt, false);
-	if (rc) return rc;
 	uint64_t m = 0;
-	for (int s = 0; s < W; ++s) m += recv_cnt[s];
+	SH_MSD(sh, msd_partition_u32(sh->ctx, d_keys, n, 24, 8, sh->d_row));
+	rc = coarse_exchange<uint32_t>(sh, "keys", n, recv_cap, d_keys, d_recv, nullptr, nullptr, &m);
+	if (rc) return rc;
 	SH_MSD(sh, msd_sort_u32_bits(sh->ctx, d_recv, m, 32 - lg));
 	SH_HIP(sh, hipStreamSynchronize(sh->stream));
 	*d_out = d_recv;
@@ -441,17 +473,8 @@ int msd_sort_pairs_u64_sharded(msd_shard *sh, uint64_t *d_keys, uint64_t *d_rids
 	}
 	if (!d_recv_keys || !d_recv_rids) return fail(sh, MSD_EINVAL, "sort_pairs_u64_sharded: null receive buffers");
 	SH_MSD(sh, msd_partition_pairs_u64(sh->ctx, d_keys, d_rids, n, 56, 8, sh->d_row));
-	std::vector<uint64_t> send_cnt, recv_cnt;
-	int rc = finish_coarse_row(sh, recv_cap, n);
-	if (!rc) rc = exchange_counts(sh, 256, 258, "tuples", send_cnt, recv_cnt);
-	if (rc) return rc;
 	uint64_t m = 0;
-	for (int s = 0; s < W; ++s) m += recv_cnt[s];
-	// keys and rids in ONE group: 2 x (world - 1) sends and receives in flight together
-	SH_NCCL(sh, ncclGroupStart());
-	rc = all_to_all<uint64_t>(sh, d_keys, d_recv_keys, send_cnt, recv_cnt, true);
-	if (!rc) rc = all_to_all<uint64_t>(sh, d_rids, d_recv_rids, send_cnt, recv_cnt, true);
-	SH_NCCL(sh, ncclGroupEnd());
+	int rc = coarse_exchange<uint64_t>(sh, "tuples", n, recv_cap, d_keys, d_recv_keys, d_rids, d_recv_rids, &m);
 	if (rc) return rc;
 	SH_MSD(sh, msd_sort_pairs_u64_bits(sh->ctx, d_recv_keys, d_recv_rids, m, 64 - lg));
 	SH_HIP(sh, hipStreamSynchronize(sh->stream));

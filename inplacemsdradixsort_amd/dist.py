@@ -163,39 +163,48 @@ def _rank(dist, group=None) -> int:
     return int(dist.get_rank(group)) if group is not None else int(dist.get_rank())
 
 
-def exchange_counts(dist, send, capacity: int, world: int, group=None):
-    """All ranks learn the whole G x G send matrix and every rank's receive capacity
-    (one all-gather of G+1 int64 per rank).  Returns (send_list, recv_list) of this rank;
-    raises :class:`ReceiveOverflow` on every rank if any rank's total exceeds its capacity."""
-    import torch
-    row = torch.cat([send.to(torch.int64), torch.tensor([capacity], dtype=torch.int64, device=send.device)])
-    rows = [torch.empty_like(row) for _ in range(world)]
-    dist.all_gather(rows, row, group=group)
-    mat = torch.stack(rows).cpu()                                # [sender, destination | capacity]: one D2H
-    totals, caps = mat[:, :world].sum(dim=0), mat[:, world]
-    over = [(r, int(totals[r]), int(caps[r])) for r in range(world) if int(totals[r]) > int(caps[r])]
-    if over:
-        raise ReceiveOverflow("receive buffer too small on rank(s) " +
-                              ", ".join(f"{r}: {t} keys for capacity {c}" for r, t, c in over) +
-                              " (raise the slack -- the reference's fudge -- or use sort_sharded_u32_sampled)")
-    me = _rank(dist, group)
-    send_l = _Splits(mat[me, :world].tolist())
-    send_l.max_block = int(mat[:, :world].max())
-    return send_l, mat[:, me].tolist()
+def _takes_async(fn) -> bool:
+    """Does this backend's collective take ``async_op``?  torch.distributed's return Work handles whose wait() orders the
+    current stream after the collective; stand-ins without it (HostStagedDist, tests) run synchronously.  Decided from
+    the signature -- a TypeError raised by the real backend (bad split list, dtype) is an error, not a reason to run the
+    collective again."""
+    import inspect
+    try:
+        return "async_op" in inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
 
 
-def exchange_bucket_counts(dist, counts, capacity: int, world: int, group=None):
-    """Like :func:`exchange_counts`, at the granularity of the 256 top-digit buckets: every rank learns every rank's
-    bucket sizes (one all-gather of 257 int64 per rank).  Returns (send_list, recv_list, mine): ``mine[s][j]`` = keys of
-    this rank's j-th bucket that source rank s holds -- the lengths of the runs this rank receives, in arrival order."""
+def _exchange_rows(dist, counts, capacity: int, world: int, group, flag=None, between=None, on_host: bool = True):
+    """The count exchange under :func:`exchange_counts`, :func:`exchange_bucket_counts` and :func:`exchange_fine_counts`:
+    one all-gather of a row [``counts`` | capacity (| ``flag``)] of int64 per rank; ``counts`` = this rank's keys per
+    bucket, ``world`` destinations of equally many buckets each.  Returns (send_list, recv_list, mine, flags): ``mine`` =
+    [world, buckets per rank]: row s = the sizes of source s's extents of this rank's buckets, in arrival order; ``flags``
+    = every rank's flag word, on the host.  ``on_host`` False: the per-bucket counts stay on the device, only the world x
+    world send matrix, the capacities and the flags come to the host, in ONE small copy.  Raises :class:`ReceiveOverflow`
+    on every rank if any rank's total exceeds its capacity.
+    ``between``: device work that does not depend on the other ranks' counts is queued while the counts travel and the
+    host waits for them; with a backend whose collectives block the host it is queued first."""
     import torch
-    row = torch.cat([counts.to(torch.int64), torch.tensor([capacity], dtype=torch.int64, device=counts.device)])
+    nb = counts.numel()
+    row = torch.cat([counts.to(torch.int64), torch.tensor([capacity], dtype=torch.int64, device=counts.device)] + ([flag] if flag is not None else []))
     rows = [torch.empty_like(row) for _ in range(world)]
-    dist.all_gather(rows, row, group=group)
-    mat = torch.stack(rows).cpu()                                # [sender, bucket | capacity]: one D2H
-    per = 256 // world
-    to_rank = mat[:, :256].view(world, world, per).sum(dim=2)    # [sender, destination]
-    totals, caps = to_rank.sum(dim=0), mat[:, 256]
+    if between is not None and _takes_async(dist.all_gather):
+        h = dist.all_gather(rows, row, group=group, async_op=True)
+        between()
+        h.wait()
+    else:
+        if between is not None:
+            between()
+        dist.all_gather(rows, row, group=group)
+    allc = torch.stack(rows)                                      # [sender, bucket | capacity (| flag)]
+    if on_host:
+        allc = allc.cpu()                                         # one D2H
+    per = nb // world
+    to_rank = allc[:, :nb].view(world, world, per).sum(dim=2)     # [sender, destination]
+    small = torch.cat([to_rank.reshape(-1)] + [allc[:, c] for c in range(nb, row.numel())]).cpu()   # (on the device: one D2H)
+    to_rank, caps, flags = small[:world * world].view(world, world), small[world * world:world * world + world], small[world * world + world:]
+    totals = to_rank.sum(dim=0)
     over = [(r, int(totals[r]), int(caps[r])) for r in range(world) if int(totals[r]) > int(caps[r])]
     if over:
         raise ReceiveOverflow("receive buffer too small on rank(s) " +
@@ -204,7 +213,22 @@ def exchange_bucket_counts(dist, counts, capacity: int, world: int, group=None):
     me = _rank(dist, group)
     send_l = _Splits(to_rank[me].tolist())
     send_l.max_block = int(to_rank.max())
-    return send_l, to_rank[:, me].tolist(), mat[:, me * per:(me + 1) * per].tolist()
+    return send_l, to_rank[:, me].tolist(), allc[:, me * per:(me + 1) * per], flags
+
+
+def exchange_counts(dist, send, capacity: int, world: int, group=None):
+    """All ranks learn the whole G x G send matrix and every rank's receive capacity
+    (one all-gather of G+1 int64 per rank).  Returns (send_list, recv_list) of this rank;
+    raises :class:`ReceiveOverflow` on every rank if any rank's total exceeds its capacity."""
+    return _exchange_rows(dist, send, capacity, world, group)[:2]
+
+
+def exchange_bucket_counts(dist, counts, capacity: int, world: int, group=None):
+    """Like :func:`exchange_counts`, at the granularity of the 256 top-digit buckets: every rank learns every rank's
+    bucket sizes (one all-gather of 257 int64 per rank).  Returns (send_list, recv_list, mine): ``mine[s][j]`` = keys of
+    this rank's j-th bucket that source rank s holds -- the lengths of the runs this rank receives, in arrival order."""
+    send_l, got_l, mine, _ = _exchange_rows(dist, counts, capacity, world, group)
+    return send_l, got_l, mine.tolist()
 
 
 FINE_BITS = 16          # the fine scheme orders a shard by its top 16 bits before the exchange ...
@@ -222,55 +246,20 @@ def use_fine(n_keys: int, world: int, have_work: bool, scheme=None, _force_excha
     return world <= 8 and n_keys >= FINE_MIN_KEYS
 
 
-def _takes_async(fn) -> bool:
-    import inspect
-    try:
-        return "async_op" in inspect.signature(fn).parameters
-    except (TypeError, ValueError):
-        return False
-
-
 def exchange_fine_counts(dist, counts, capacity: int, world: int, group=None, hist_ok=None, between=None):
     """The fine scheme's count exchange: ``counts`` = this rank's 2^16 bucket sizes (int64, on the device).  One
-    all-gather of 2^16 + 1 int64 per rank; the world x world send matrix and the capacities come to the host in ONE
+    all-gather of 2^16 + 2 int64 per rank; the world x world send matrix and the capacities come to the host in ONE
     small copy, the per-bucket counts stay on the device.  Returns (send_list, recv_list, mine): ``mine`` = int64
     [world, 2^16 / world] on the device -- row s: the lengths of source s's extents of this rank's buckets, in arrival
-    order.  Raises :class:`ReceiveOverflow` on every rank if any rank's total exceeds its capacity."""
+    order.  Raises :class:`ReceiveOverflow` on every rank if any rank's total exceeds its capacity.
+    ``hist_ok``: a one-element tensor on the device, non-zero = this rank has its buckets ready as histogram records; the
+    records travel only if EVERY rank has -- the verdict is returned as ``send_list.use_hist``.  ``between``: the scatter
+    of the low halves (:func:`_exchange_rows`)."""
     import torch
-    nb = 1 << FINE_BITS
-    # (hist_ok: a one-element tensor on the device, non-zero = this rank has its buckets ready as histogram records; the
-    # records travel only if EVERY rank has -- the verdict is returned as send_l.use_hist)
     flag = (hist_ok.to(torch.int64).reshape(1) != 0).to(torch.int64) if hist_ok is not None else torch.zeros(1, dtype=torch.int64, device=counts.device)
-    row = torch.cat([counts.to(torch.int64), torch.tensor([capacity], dtype=torch.int64, device=counts.device), flag])
-    rows = [torch.empty_like(row) for _ in range(world)]
-    # (between: device work that does not depend on the other ranks' counts -- the scatter of the low halves -- is queued while
-    # the counts travel and the host waits for them; with a backend whose collectives block the host it is queued first)
-    if between is not None and _takes_async(dist.all_gather):
-        h = dist.all_gather(rows, row, group=group, async_op=True)
-        between()
-        h.wait()
-    else:
-        if between is not None:
-            between()
-        dist.all_gather(rows, row, group=group)
-    allc = torch.stack(rows)                                      # [sender, bucket | capacity | records ready], on the device
-    nbl = nb // world
-    to_rank = allc[:, :nb].view(world, world, nbl).sum(dim=2)     # [sender, destination]
-    small = torch.cat([to_rank.reshape(-1), allc[:, nb], allc[:, nb + 1]]).cpu()   # one D2H: world^2 + 2 world numbers
-    to_rank_h, caps = small[:world * world].view(world, world), small[world * world:world * world + world]
-    all_hist = bool((small[world * world + world:] != 0).all())
-    totals = to_rank_h.sum(dim=0)
-    over = [(r, int(totals[r]), int(caps[r])) for r in range(world) if int(totals[r]) > int(caps[r])]
-    if over:
-        raise ReceiveOverflow("receive buffer too small on rank(s) " +
-                              ", ".join(f"{r}: {t} keys for capacity {c}" for r, t, c in over) +
-                              " (raise the slack -- the reference's fudge -- or use sort_sharded_u32_sampled)")
-    me = _rank(dist, group)
-    mine = allc[:, me * nbl:(me + 1) * nbl].contiguous()
-    send_l = _Splits(to_rank_h[me].tolist())
-    send_l.max_block = int(to_rank_h.max())
-    send_l.use_hist = all_hist
-    return send_l, to_rank_h[:, me].tolist(), mine
+    send_l, got_l, mine, flags = _exchange_rows(dist, counts, capacity, world, group, flag, between, on_host=False)
+    send_l.use_hist = bool((flags != 0).all())
+    return send_l, got_l, mine.contiguous()
 
 
 # The fine scheme exchanges only the keys' LOW halves: once the shard is ordered by its top 16 bits the upper half of a
@@ -298,6 +287,14 @@ FINE_HIST_MIN_KEYS = 3 << 28     # 12288 keys per bucket: a record is then 0.7 o
 # low halves where the exchange hides either way (8 ranks).
 FINE_HIST_MAX_WORLD = 4
 HIST2_RECORD_BYTES = 17408
+RECORDS_BYTES = (1 << FINE_BITS) * HIST2_RECORD_BYTES   # a shard's buckets as records
+
+
+def _wants_records(n_keys: int, world: int, send_room: int, recv_room: int) -> bool:
+    """Does this rank prepare its buckets as histogram records?  (msd_sort_u32_sharded, csrc/msd_sharded.hip, states the
+    same rule with the same inputs.)  Few ranks, a big shard, and room (bytes) for 2^16 records where they are packed AND
+    where they arrive: records that cannot be received are never sent, so they are not packed either."""
+    return FINE_HIST and world <= FINE_HIST_MAX_WORLD and n_keys >= FINE_HIST_MIN_KEYS and min(send_room, recv_room) >= RECORDS_BYTES
 
 
 def _bytes_view(buf):
@@ -306,7 +303,7 @@ def _bytes_view(buf):
 
 
 def _hist_splits(world: int):
-    nbytes = ((1 << FINE_BITS) // world) * HIST2_RECORD_BYTES
+    nbytes = RECORDS_BYTES // world
     sp = _Splits([nbytes] * world)
     sp.max_block = nbytes
     return sp
@@ -318,37 +315,76 @@ def _as_low16(buf):
     return buf.view(torch.int16)
 
 
-def _fine_counts(engine, keys, rec=None, world: int = 1, send16=None):
+def _send_bufs_in_work(work, n: int, low16: bool, records: bool):
+    """The one-shot's send buffers, carved out of the work buffer -- dead until the leaf writes it: (the int16 buffer for
+    the low halves or None, the record area or None, "both can be filled at once").  The records lie behind the low
+    halves, at the next 256-byte boundary; when both do not fit they overlap, the records come first (packed from the
+    keys) and the low halves are written over them only if the records do not travel after all."""
+    send16 = _as_low16(work)[:n] if low16 and 2 * work.numel() >= n else None
+    if not records:
+        return send16, None, True
+    w8 = _bytes_view(work)
+    rec_at = (2 * n + 255) // 256 * 256 if send16 is not None else 0
+    if w8.numel() - rec_at >= RECORDS_BYTES:
+        return send16, w8[rec_at:], True
+    return send16, w8, False
+
+
+def _fine_prepare(engine, keys, send16, rec, apart: bool):
     """What a rank does before the fine exchange.  Returns (its 2^16 bucket sizes -- int64, on the device --, the flag "my
     buckets are ready in ``rec`` as histogram records" or None, "the low halves are ready in ``send16``": True, False, or a
     callable that makes them ready and is to be called once -- while the counts are exchanged).
-    * histogram records wanted (``rec`` holds 2^16 of them, few ranks, a big shard): ``engine.order_low16`` as below, then
-      the records are packed from the low halves (``engine.hist2_pack``); without ``send16`` the shard is ordered in place by
-      its top 16 bits (``engine.sort_top``) and the records are packed from the keys;
-    * else, with an int16 buffer ``send16``: ``engine.order_low16`` -- one in-place round on the top 8 bits, exact counts,
+    * records wanted (``rec``), and ``send16`` beside them: ``engine.order_low16`` as below, then the records are packed
+      from the low halves (``engine.hist2_pack``) -- which are then also ready for the case that some rank's records
+      overflow and every rank sends low halves after all; without ``send16`` (or with the records lying over it) the shard
+      is ordered in place by its top 16 bits (``engine.sort_top``) and the records are packed from the keys;
+    * no records, an int16 buffer ``send16``: ``engine.order_low16`` -- one in-place round on the top 8 bits, exact counts,
       the low halves scattered out of place into ``send16``: two passes over the shard less than ordering in place and
       packing afterwards (5.5 against 6.75 ms per 2^30 keys);
-    * else the shard is ordered in place and whole keys travel."""
-    want_hist = (rec is not None and FINE_HIST and world <= FINE_HIST_MAX_WORLD and keys.numel() >= FINE_HIST_MIN_KEYS
-                 and rec.numel() >= (1 << FINE_BITS) * HIST2_RECORD_BYTES)
-    if not want_hist and FINE_LOW16 and send16 is not None and send16.numel() >= keys.numel() and hasattr(engine, "order_low16"):
-        if hasattr(engine, "order_low16_counts"):   # the scatter runs while the counts are exchanged (exchange_fine_counts' `between`)
+    * else the shard is ordered in place and whole keys (or low halves packed afterwards) travel."""
+    n = keys.numel()
+    if send16 is not None and send16.numel() >= n and hasattr(engine, "order_low16") and (rec is None or apart):
+        if rec is not None:
+            counts = engine.order_low16(keys, send16)
+            return counts, engine.hist2_pack(send16[:n], engine.bounds_from_counts16(counts), rec) == 0, True
+        if hasattr(engine, "order_low16_counts"):   # the scatter runs while the counts are exchanged (_exchange_rows' `between`)
             return engine.order_low16_counts(keys), None, (lambda: engine.order_low16_scatter(keys, send16))
         return engine.order_low16(keys, send16), None, True
-    if want_hist and FINE_LOW16 and send16 is not None and send16.numel() >= keys.numel() and hasattr(engine, "order_low16"):
-        # (the records are packed from the low halves order_low16 has written -- which are then also ready for the case that
-        # some rank's records overflow and every rank sends low halves after all)
-        counts = engine.order_low16(keys, send16)
-        ok = engine.hist2_pack(send16[:keys.numel()], engine.bounds_from_counts16(counts), rec) == 0
-        return counts, ok, True
     engine.sort_top(keys, 32 - FINE_BITS)
     b = engine.bucket_bounds(keys, 32 - FINE_BITS, 1 << FINE_BITS)
-    ok = (engine.hist2_pack(keys, b, rec) == 0) if want_hist else None
-    return b[1:] - b[:-1], ok, False
+    return b[1:] - b[:-1], (engine.hist2_pack(keys, b, rec) == 0) if rec is not None else None, False
 
 
-def _fine_finish(engine, arrived, out, mine, got_l, rank: int, world: int):
-    """The counting leaf over what arrived: source s's extents lie back to back from sum(got_l[:s]) on."""
+def _fine_start(engine, dist, keys, recv, capacity: int, world: int, group, send_room: int, send_bufs, async_op: bool):
+    """First half of the fine scheme for one shard: prepare, exchange the counts (raises on all ranks), start -- or,
+    without ``async_op``, run -- the one all-to-all into ``recv``.  The callers differ only in where the send buffers come
+    from: ``send_bufs(n, low16, records)`` returns (send16, rec, apart) as :func:`_send_bufs_in_work` does, ``send_room`` =
+    the bytes it has for records.  Returns what is in flight: (the view of ``recv`` being filled, the Work handles, ("fine", what
+    :func:`_fine_finish` needs)) and the name of the form that travels."""
+    n = keys.numel()
+    send16, rec, apart = send_bufs(n, FINE_LOW16, _wants_records(n, world, send_room, 4 * recv.numel()))
+    counts, hist_ok, packed = _fine_prepare(engine, keys, send16, rec, apart)
+    between = packed if callable(packed) else None
+    send_l, got_l, mine = exchange_fine_counts(dist, counts, capacity, world, group, hist_ok, between)
+    if send_l.use_hist:      # every rank's buckets are ready as histogram records: equal blocks travel
+        form, sp = "histogram records", _hist_splits(world)
+        arrived, src, m, got, send = _bytes_view(recv), rec[:sum(sp)], sum(sp), list(sp), sp
+    elif send16 is not None:  # the low halves arrive as int16; the leaf puts the upper halves back
+        if not packed:   # (the shard was ordered in place: the records did not travel after all, or no order_low16)
+            engine.pack_low16(keys, send16)
+        form, arrived, src, m, got, send = "low halves", _as_low16(recv), send16, int(sum(got_l)), got_l, send_l
+    else:
+        form, arrived, src, m, got, send = "whole keys", recv, keys, int(sum(got_l)), got_l, send_l
+    out = arrived[:m]
+    return (out, all_to_all_v(dist, out, src, got, send, group, async_op), ("fine", arrived, mine, got_l)), form
+
+
+def _fine_finish(engine, flight, out, rank: int, world: int):
+    """Second half: wait for the exchange, then the counting leaf over what arrived, into ``out`` (a work buffer):
+    source s's extents lie back to back from sum(got_l[:s]) on."""
+    _, handles, (_, arrived, mine, got_l) = flight
+    for h in handles:
+        h.wait()
     base, at = [], 0
     for g in got_l:
         base.append(at)
@@ -381,6 +417,75 @@ def bucket_major(mine):
     return src_off, dst_off, lens, seg_off
 
 
+def _local_sort(engine, keys, rids=None, end_bit=None):
+    """The engine's sort for these keys (int32: u32, int64: u64; with ``rids``: tuples), on all bits or below ``end_bit``."""
+    kw = {} if end_bit is None else {"end_bit": end_bit}
+    if rids is not None:
+        engine.sort_pairs_u64(keys, rids, **kw)
+    else:
+        (engine.sort_u32 if keys.element_size() == 4 else engine.sort_u64)(keys, **kw)
+
+
+def _plain_start(dist, send, keys, recv, world: int, group, rids=None, recv_rids=None, async_op: bool = False):
+    """Keys already partitioned by destination (``send`` = keys per destination rank, on the device): exchange the counts
+    (raises on all ranks), then one all-to-all of the keys -- and of the rids, with the same splits -- into the receive
+    buffers.  Returns (keys view, rids view or None, Work handles)."""
+    send_l, got_l = exchange_counts(dist, send, recv.numel(), world, group)
+    m = int(sum(got_l))
+    out, out_r = recv[:m], None
+    handles = all_to_all_v(dist, out, keys, got_l, send_l, group, async_op)
+    if rids is not None:
+        out_r = recv_rids[:m]
+        handles += all_to_all_v(dist, out_r, rids, got_l, send_l, group, async_op)
+    return out, out_r, handles
+
+
+def _exchange_and_sort(engine, dist, send, keys, recv, world: int, group, rids=None, recv_rids=None, end_bit=None):
+    """:func:`_plain_start`, run to its end, and the local sort of what arrived (``end_bit``: the bits the ranks' ranges
+    share are not sorted again; None: a full sort).  Returns (keys, rids) views of the receive buffers."""
+    out, out_r, _ = _plain_start(dist, send, keys, recv, world, group, rids, recv_rids)
+    _local_sort(engine, out, out_r, end_bit)
+    return out, out_r
+
+
+def _coarse_work(world: int, work_bufs):
+    """The work buffers the coarse scheme uses: the arrived runs are gathered bucket-major into one of them and sorted
+    there as segments on 24 bits (the local sort does not repeat the top-digit pass) -- up to 4 ranks.  Beyond, and
+    without work buffers, the keys are sorted where they arrived.
+    (8 ranks and more: the 32 buckets of a rank hold 2^25 keys each at 2^30 keys per rank, one more 8-bit round leaves
+    2^17-key segments, beyond the fast counting leaf -- sorting the arrived keys on 29 bits measures faster: 8.5 against
+    1.6 + 9.7 ms, tools/multigpu_local_work.py; 2 and 4 ranks: 9.2 and 8.9 against 13.0 and 12.5 ms)"""
+    return list(work_bufs) if work_bufs and world <= 4 else []
+
+
+def _coarse_start(engine, dist, keys, recv, work_bufs, world: int, group, async_op: bool):
+    """First half of the coarse scheme: one top-digit pass, count exchange (raises on all ranks), the all-to-all started
+    or run.  Returns what is in flight: (the view of ``recv`` being filled, the Work handles, the runs' lengths
+    ``mine[s][j]`` for the gather into a work buffer -- or None: sort where they arrived)."""
+    counts = engine.partition(keys, 24, 8)                       # int64[256], device of `keys`
+    if not work_bufs:
+        out, _, handles = _plain_start(dist, counts.view(world, 256 // world).sum(dim=1), keys, recv, world, group, async_op=async_op)
+        return out, handles, None
+    send_l, got_l, mine = exchange_bucket_counts(dist, counts, min(recv.numel(), min(w.numel() for w in work_bufs)), world, group)
+    out = recv[:int(sum(got_l))]
+    return out, all_to_all_v(dist, out, keys, got_l, send_l, group, async_op), mine
+
+
+def _coarse_finish(engine, flight, work, world: int):
+    """Second half: wait, then sort what arrived -- where it is, on the bits below the rank's, or gathered into ``work``."""
+    arrived, handles, mine = flight
+    for h in handles:
+        h.wait()
+    if mine is None:
+        _local_sort(engine, arrived, end_bit=32 - _log2(world))
+        return arrived
+    out = work[:arrived.numel()]
+    src_off, dst_off, lens, seg_off = bucket_major(mine)
+    engine.gather_runs(out, arrived, src_off, dst_off, lens)
+    engine.sort_segments(out, seg_off, 24)
+    return out
+
+
 def sort_sharded_u32(engine, keys, recv, dist, world: int, group=None, work=None, scheme=None, _force_exchange: bool = False):
     """Sorts the union of all ranks' ``keys`` (int32 tensors holding u32 bit patterns).
     Returns this rank's sorted range; rank r's range precedes rank r+1's.
@@ -392,59 +497,20 @@ def sort_sharded_u32(engine, keys, recv, dist, world: int, group=None, work=None
     With a second buffer ``work`` (as large as ``recv``) the local sort does not repeat the top-digit pass: the runs
     that arrived (per source, that source's buckets of this rank's range) are gathered bucket-major into ``work`` in
     one launch and sorted there as segments on the remaining 24 bits -- the result is a view of ``work``.  Without it
-    the received keys are sorted in ``recv`` on all ``32 - log2(world)`` bits."""
-    lg = _log2(world)
+    the received keys are sorted in ``recv`` on all ``32 - log2(world)`` bits.
+
+    Both schemes are a start and a finish (:func:`_fine_start` / :func:`_fine_finish`, :func:`_coarse_start` /
+    :func:`_coarse_finish`), run here one after the other; :class:`ShardedSorter` runs them apart."""
+    _log2(world)
     if world == 1 and not _force_exchange:   # (_force_exchange: tests run the whole exchange over a one-rank process group)
         engine.sort_u32(keys)
         return keys
     if use_fine(keys.numel(), world, work is not None, scheme, _force_exchange):
-        # (low halves and records wait in the work buffer -- dead until the leaf writes it --, the records behind the low halves)
-        w16 = _as_low16(work)[:keys.numel()] if FINE_LOW16 and 2 * work.numel() >= keys.numel() else None
-        rec_at = (2 * keys.numel() + 255) // 256 * 256 if w16 is not None else 0
-        rec, s16 = _bytes_view(work)[rec_at:], w16
-        if rec.numel() < (1 << FINE_BITS) * HIST2_RECORD_BYTES:   # no room for both: records from the keys, low halves only if needed
-            rec = _bytes_view(work)
-            if FINE_HIST and world <= FINE_HIST_MAX_WORLD and keys.numel() >= FINE_HIST_MIN_KEYS and rec.numel() >= (1 << FINE_BITS) * HIST2_RECORD_BYTES:
-                s16 = None
-        counts, hist_ok, packed = _fine_counts(engine, keys, rec, world, s16)
-        finish = packed if callable(packed) else None
-        send_l, got_l, mine = exchange_fine_counts(dist, counts, min(recv.numel(), work.numel()), world, group, hist_ok, finish)
-        packed = True if finish is not None else packed
-        m = int(sum(got_l))
-        if send_l.use_hist and 4 * recv.numel() >= (1 << FINE_BITS) * HIST2_RECORD_BYTES:
-            sp = _hist_splits(world)
-            r8 = _bytes_view(recv)
-            all_to_all_v(dist, r8[:sum(sp)], rec[:sum(sp)], list(sp), sp, group)
-            return _fine_finish(engine, r8, work, mine, got_l, _rank(dist, group), world)
-        if w16 is not None:
-            # the low halves (packed into the work buffer by now, or packed here from the shard ordered in place) arrive in
-            # the receive buffer as int16; the leaf puts the upper halves back
-            r16 = _as_low16(recv)
-            if not packed:
-                engine.pack_low16(keys, w16)
-            all_to_all_v(dist, r16[:m], w16, got_l, send_l, group)
-            return _fine_finish(engine, r16, work, mine, got_l, _rank(dist, group), world)
-        all_to_all_v(dist, recv[:m], keys, got_l, send_l, group)
-        return _fine_finish(engine, recv, work, mine, got_l, _rank(dist, group), world)
-    counts = engine.partition(keys, 24, 8)                       # int64[256], device of `keys`
-    if work is None or world > 4:                                # (8 ranks and more: see ShardedSorter)
-        send = counts.view(world, 256 // world).sum(dim=1)       # keys per destination rank
-        send_l, got_l = exchange_counts(dist, send, recv.numel(), world, group)
-        out = recv[:int(sum(got_l))]
-        all_to_all_v(dist, out, keys, got_l, send_l, group)
-        engine.sort_u32(out, end_bit=32 - lg)
-        return out
-    send_l, got_l, mine = exchange_bucket_counts(dist, counts, min(recv.numel(), work.numel()), world, group)
-    m = int(sum(got_l))
-    all_to_all_v(dist, recv[:m], keys, got_l, send_l, group)
-    return _gather_and_sort(engine, recv[:m], work[:m], mine)
-
-
-def _gather_and_sort(engine, arrived, out, mine):
-    src_off, dst_off, lens, seg_off = bucket_major(mine)
-    engine.gather_runs(out, arrived, src_off, dst_off, lens)
-    engine.sort_segments(out, seg_off, 24)
-    return out
+        flight, _ = _fine_start(engine, dist, keys, recv, min(recv.numel(), work.numel()), world, group, 4 * work.numel(),
+                                lambda n, low16, records: _send_bufs_in_work(work, n, low16, records), False)
+        return _fine_finish(engine, flight, work, _rank(dist, group), world)
+    work_bufs = _coarse_work(world, [work] if work is not None else [])
+    return _coarse_finish(engine, _coarse_start(engine, dist, keys, recv, work_bufs, world, group, False), work, world)
 
 
 def sort_sharded_u64(engine, keys, recv, dist, world: int, group=None):
@@ -452,15 +518,10 @@ def sort_sharded_u64(engine, keys, recv, dist, world: int, group=None):
     local sort with ``end_bit = 64 - log2(world)``."""
     lg = _log2(world)
     if world == 1:
-        engine.sort_u64(keys)
+        _local_sort(engine, keys)
         return keys
-    counts = engine.partition(keys, 56, 8)
-    send = counts.view(world, 256 // world).sum(dim=1)
-    send_l, got_l = exchange_counts(dist, send, recv.numel(), world, group)
-    out = recv[:int(sum(got_l))]
-    all_to_all_v(dist, out, keys, got_l, send_l, group)
-    engine.sort_u64(out, end_bit=64 - lg)
-    return out
+    send = engine.partition(keys, 56, 8).view(world, 256 // world).sum(dim=1)
+    return _exchange_and_sort(engine, dist, send, keys, recv, world, group, end_bit=64 - lg)[0]
 
 
 def sort_sharded_pairs_u64(engine, keys, rids, recv_keys, recv_rids, dist, world: int, group=None):
@@ -473,19 +534,12 @@ def sort_sharded_pairs_u64(engine, keys, rids, recv_keys, recv_rids, dist, world
     precede rank r+1's; like the reference's, the sort is unstable."""
     lg = _log2(world)
     if world == 1:
-        engine.sort_pairs_u64(keys, rids)
+        _local_sort(engine, keys, rids)
         return keys, rids
     if recv_keys.numel() != recv_rids.numel():
         raise ValueError("receive buffers for keys and rids differ in length")
-    counts = engine.partition(keys, 56, 8, rids=rids)
-    send = counts.view(world, 256 // world).sum(dim=1)
-    send_l, got_l = exchange_counts(dist, send, recv_keys.numel(), world, group)
-    m = int(sum(got_l))
-    out_k, out_r = recv_keys[:m], recv_rids[:m]
-    all_to_all_v(dist, out_k, keys, got_l, send_l, group)
-    all_to_all_v(dist, out_r, rids, got_l, send_l, group)
-    engine.sort_pairs_u64(out_k, out_r, end_bit=64 - lg)
-    return out_k, out_r
+    send = engine.partition(keys, 56, 8, rids=rids).view(world, 256 // world).sum(dim=1)
+    return _exchange_and_sort(engine, dist, send, keys, recv_keys, world, group, rids, recv_rids, end_bit=64 - lg)
 
 
 class ShardedSorter:
@@ -497,127 +551,77 @@ class ShardedSorter:
     RCCL's stream (xGMI) while the compute stream sorts shard s-1 -- the exchange is as long as a
     local sort, so hiding it is what weak scaling needs.  ``recv_bufs``: at least two buffers (one
     per exchange in flight plus the one being sorted); the tensor returned by ``collect`` is a view
-    of one of them and is overwritten ``len(recv_bufs)`` submissions later.  ``keys`` must stay
-    untouched until the matching ``collect`` returns.
+    of one of them -- with work buffers, of a WORK buffer -- and is overwritten ``len(recv_bufs)``
+    (``len(work_bufs)``) submissions later.  ``keys`` must stay untouched until the matching ``collect`` returns.
     """
 
     def __init__(self, engine, dist, world: int, recv_bufs, group=None, work_bufs=None, scheme=None, _force_exchange: bool = False):
         self.engine, self.dist, self.world, self.group = engine, dist, world, group
         self.scheme = scheme              # None: by shard size (use_fine); "fine" / "coarse": forced
         self._force = _force_exchange     # (tests) one rank goes through the whole exchange
-        self.fine_work = list(work_bufs) if work_bufs else []   # the fine scheme uses the work buffers at any rank count
-        self.lg = _log2(world)
+        _log2(world)
         self.recv = list(recv_bufs)
         if (world > 1 or _force_exchange) and len(self.recv) < 2:
             raise ValueError("ShardedSorter needs two receive buffers")
-        # work buffers: the arrived runs are gathered bucket-major into one of them and sorted there as segments on
-        # 24 bits (the local sort does not repeat the top-digit pass); collect() then returns a view of a WORK buffer,
-        # overwritten len(work_bufs) collects later.  Without them the keys are sorted where they arrived.
-        # (8 ranks and more: the 32 buckets of a rank hold 2^25 keys each at 2^30 keys per rank, one more 8-bit round leaves
-        # 2^17-key segments, beyond the fast counting leaf -- sorting the arrived keys on 29 bits measures faster: 8.5 against
-        # 1.6 + 9.7 ms, tools/multigpu_local_work.py; 2 and 4 ranks: 9.2 and 8.9 against 13.0 and 12.5 ms)
-        self.work = list(work_bufs) if work_bufs and world <= 4 else []
+        self.fine_work = list(work_bufs) if work_bufs else []   # the fine scheme uses the work buffers at any rank count
+        self.work = _coarse_work(world, work_bufs)
         self._wslot = 0
         self._slot = 0
-        self._pending = []
+        self._pending = []                # per shard in flight: (view being filled, Work handles, ...) -- bench.py reads the first two
         self._async = None
         self._send16 = []                 # fine scheme: the packed low halves of the shards whose exchange is in flight
         self._send8 = []                  # ... or their buckets' histogram records
         self.last_format = None           # what the last fine exchange moved (reporting)
 
-    def _all_to_all(self, out, keys, got_l, send_l):
-        # torch.distributed returns Work handles whose wait() orders the current stream after the exchange; stand-ins without
-        # ``async_op`` (HostStagedDist, tests) exchange synchronously.  Decided once from the signature -- a TypeError
-        # raised by the real backend (bad split list, dtype) is an error, not a reason to run the collective again.
-        if self._async is None:
-            import inspect
-            try:
-                self._async = "async_op" in inspect.signature(self.dist.all_to_all_single).parameters
-            except (TypeError, ValueError):
-                self._async = False
-        return all_to_all_v(self.dist, out, keys, got_l, send_l, self.group, async_op=self._async)
+    def _send_bufs(self, slot: int, device, n: int, low16: bool, records: bool):
+        """The fine scheme's send buffers of a slot: one buffer of low halves and one of records per receive buffer,
+        allocated when first needed; they never overlap."""
+        import torch
+        send16 = rec = None
+        if low16:
+            self._send16 += [None] * (len(self.recv) - len(self._send16))
+            if self._send16[slot] is None or self._send16[slot].numel() < n:
+                self._send16[slot] = torch.empty(n, dtype=torch.int16, device=device)
+            send16 = self._send16[slot][:n]
+        if records:
+            self._send8 += [None] * (len(self.recv) - len(self._send8))
+            if self._send8[slot] is None:
+                self._send8[slot] = torch.empty(RECORDS_BYTES, dtype=torch.uint8, device=device)
+            rec = self._send8[slot]
+        return send16, rec, True
 
     def submit(self, keys) -> None:
         if self.world == 1 and not self._force:
-            self._pending.append((keys, None, None))
+            self._pending.append((keys, [], "local"))
             return
         if len(self._pending) >= len(self.recv):
             raise RuntimeError("collect() before submitting more shards than there are receive buffers")
-        recv = self.recv[self._slot]
+        if self._async is None:
+            self._async = _takes_async(self.dist.all_to_all_single)
+        slot, recv = self._slot, self.recv[self._slot]
         if use_fine(keys.numel(), self.world, bool(self.fine_work), self.scheme, self._force):
             cap = min(recv.numel(), min(w.numel() for w in self.fine_work))
-            slot = self._slot
-            rec = None
-            if (FINE_HIST and self.world <= FINE_HIST_MAX_WORLD and keys.numel() >= FINE_HIST_MIN_KEYS
-                    and 4 * recv.numel() >= (1 << FINE_BITS) * HIST2_RECORD_BYTES):
-                while len(self._send8) < len(self.recv):
-                    self._send8.append(None)
-                if self._send8[slot] is None:
-                    import torch
-                    self._send8[slot] = torch.empty((1 << FINE_BITS) * HIST2_RECORD_BYTES, dtype=torch.uint8, device=keys.device)
-                rec = self._send8[slot]
-            send16 = None
-            if FINE_LOW16:   # the low halves of the shards whose exchange is in flight: one send buffer per receive buffer
-                while len(self._send16) < len(self.recv):
-                    self._send16.append(None)
-                if self._send16[slot] is None or self._send16[slot].numel() < keys.numel():
-                    import torch
-                    self._send16[slot] = torch.empty(keys.numel(), dtype=torch.int16, device=keys.device)
-                send16 = self._send16[slot][:keys.numel()]
-            counts, hist_ok, packed = _fine_counts(self.engine, keys, rec, self.world, send16)
-            finish = packed if callable(packed) else None
-            send_l, got_l, mine = exchange_fine_counts(self.dist, counts, cap, self.world, self.group, hist_ok, finish)  # raises on all ranks
-            packed = True if finish is not None else packed
-            self._slot = (self._slot + 1) % len(self.recv)
-            self.last_format = "histogram records" if send_l.use_hist else "low halves" if FINE_LOW16 else "whole keys"
-            if send_l.use_hist:
-                # every rank's buckets are ready as histogram records (module comment at FINE_HIST): equal blocks travel
-                sp = _hist_splits(self.world)
-                r8 = _bytes_view(recv)
-                out = r8[:sum(sp)]
-                self._pending.append((out, self._all_to_all(out, rec[:sum(sp)], list(sp), sp), ("fine", r8, mine, got_l)))
-                return
-            if send16 is not None:
-                # only the low halves travel (module comment at FINE_LOW16), received as int16
-                if not packed:
-                    self.engine.pack_low16(keys, send16)
-                r16 = _as_low16(recv)
-                out = r16[:int(sum(got_l))]
-                self._pending.append((out, self._all_to_all(out, send16, got_l, send_l), ("fine", r16, mine, got_l)))
-                return
-            out = recv[:int(sum(got_l))]
-            self._pending.append((out, self._all_to_all(out, keys, got_l, send_l), ("fine", recv, mine, got_l)))
-            return
-        counts = self.engine.partition(keys, 24, 8)
-        mine = None
-        if self.work:
-            cap = min(recv.numel(), min(w.numel() for w in self.work))
-            send_l, got_l, mine = exchange_bucket_counts(self.dist, counts, cap, self.world, self.group)  # raises on all ranks
+            flight, self.last_format = _fine_start(self.engine, self.dist, keys, recv, cap, self.world, self.group, RECORDS_BYTES,
+                                                   lambda n, low16, records: self._send_bufs(slot, keys.device, n, low16, records), self._async)
         else:
-            send = counts.view(self.world, 256 // self.world).sum(dim=1)
-            send_l, got_l = exchange_counts(self.dist, send, recv.numel(), self.world, self.group)        # raises on all ranks
-        self._slot = (self._slot + 1) % len(self.recv)
-        out = recv[:int(sum(got_l))]
-        self._pending.append((out, self._all_to_all(out, keys, got_l, send_l), mine))
+            flight = _coarse_start(self.engine, self.dist, keys, recv, self.work, self.world, self.group, self._async)
+        self._slot = (slot + 1) % len(self.recv)
+        self._pending.append(flight)
 
     def collect(self):
-        out, handles, mine = self._pending.pop(0)
-        for h in handles or []:
-            h.wait()
-        if isinstance(mine, tuple):   # fine scheme: the counting leaf reads the extents in the receive buffer, writes a work buffer
-            _, recv, counts, got_l = mine
-            final = self.fine_work[self._wslot]
-            self._wslot = (self._wslot + 1) % len(self.fine_work)
-            return _fine_finish(self.engine, recv, final, counts, got_l, _rank(self.dist, self.group), self.world)
-        if mine is None:
-            if self.world > 1 or self._force:
-                self.engine.sort_u32(out, end_bit=32 - self.lg)
-            else:
-                self.engine.sort_u32(out)
-            return out
-        final = self.work[self._wslot][:out.numel()]
-        self._wslot = (self._wslot + 1) % len(self.work)
-        return _gather_and_sort(self.engine, out, final, mine)
+        flight = self._pending.pop(0)
+        if flight[2] == "local":
+            self.engine.sort_u32(flight[0])
+            return flight[0]
+        fine = isinstance(flight[2], tuple)
+        work = self.fine_work if fine else self.work
+        if not work:
+            return _coarse_finish(self.engine, flight, None, self.world)
+        final = work[self._wslot]                        # (collect() returns a view of a work buffer, overwritten len(work) collects later)
+        self._wslot = (self._wslot + 1) % len(work)
+        if fine:   # the counting leaf reads the extents in the receive buffer, writes the work buffer
+            return _fine_finish(self.engine, flight, final, _rank(self.dist, self.group), self.world)
+        return _coarse_finish(self.engine, flight, final, self.world)
 
     def pending(self) -> int:
         return len(self._pending)
@@ -626,18 +630,8 @@ class ShardedSorter:
 def _sort_sharded_sampled(engine, keys, rids, recv, recv_rids, dist, world: int, group, sample_per_rank: int, seed: int):
     import torch
     pairs = rids is not None
-    es = keys.element_size()
-
-    def local_sort(k, r):
-        if pairs:
-            engine.sort_pairs_u64(k, r)
-        elif es == 4:
-            engine.sort_u32(k)
-        else:
-            engine.sort_u64(k)
-
     if world == 1:
-        local_sort(keys, rids)
+        _local_sort(engine, keys, rids)
         return (keys, rids) if pairs else keys
     if pairs and recv.numel() != recv_rids.numel():
         raise ValueError("receive buffers for keys and rids differ in length")
@@ -656,21 +650,14 @@ def _sort_sharded_sampled(engine, keys, rids, recv, recv_rids, dist, world: int,
     dist.all_gather(allp, pad, group=group)
     sample = torch.cat([p[:s] for p, s in zip(allp, sizes)]).contiguous()
     if sample.numel():
-        (engine.sort_u32 if es == 4 else engine.sort_u64)(sample)
+        _local_sort(engine, sample)
         delim = engine.splitters(sample, world)                         # [world-1] key bit patterns, on the device
     else:
         delim = torch.zeros(world - 1, dtype=keys.dtype, device=keys.device)
     send = engine.partition_by_splitters(keys, delim, world, rids=rids) if pairs else engine.partition_by_splitters(keys, delim, world)
-    send_l, got_l = exchange_counts(dist, send, recv.numel(), world, group)   # int64[world]: range sizes, ranges contiguous
-    m_out = int(sum(got_l))
-    out = recv[:m_out]
-    all_to_all_v(dist, out, keys, got_l, send_l, group)
-    out_r = None
-    if pairs:
-        out_r = recv_rids[:m_out]
-        all_to_all_v(dist, out_r, rids, got_l, send_l, group)
-    local_sort(out, out_r)
+    out, out_r = _exchange_and_sort(engine, dist, send, keys, recv, world, group, rids, recv_rids)   # (send: range sizes, ranges contiguous)
     return (out, out_r) if pairs else out
+
 
 
 def sort_sharded_u32_sampled(engine, keys, recv, dist, world: int, group=None, sample_per_rank: int = 65536,

@@ -15,6 +15,8 @@ section 8c), so these are outputs of the reference's own functions on seeded inp
                          the oracle with it (tests/test_oracle.py, the duplicate rule in
                          tests/test_dist_gloo.py): sha256 of single-thread core, histogram,
                          partition and rand.c outputs, extract_delimiters as they are
+* dist_steps.json        (``make_golden.py dist_steps``; not from the reference) the sharded front
+                         ends' engine calls and collectives, for tests/test_dist_steps.py
 """
 import hashlib
 import json
@@ -96,8 +98,26 @@ def ref_outputs():
     json.dump(rec, open(os.path.join(HERE, "golden_ref_outputs.json"), "w"), indent=0)
 
 
+def dist_steps():
+    """dist_steps.json: the engine calls and collectives of the sharded front ends (tests/test_dist_steps.py), traced
+    from the code as it stands -- this project's own output, the reference is not needed.  Keys ending in "@before" hold
+    a trace of an earlier commit that a later one changed on purpose; they are carried over as they are."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_dist_steps as S
+    kept = {}
+    if os.path.exists(S.GOLDEN):
+        kept = {k: v for k, v in json.load(open(S.GOLDEN)).items() if k.endswith("@before")}
+    rec = S.record_all()
+    rec.update(kept)
+    with open(S.GOLDEN, "w") as f:   # one call per line: a changed step shows as a changed line
+        f.write("{\n" + ",\n".join(json.dumps(k) + ": [\n" + ",\n".join(" " + json.dumps(e) for e in rec[k]) + "\n]" for k in sorted(rec)) + "\n}\n")
+    print("dist_steps.json written:", len(rec), "traces")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["ref_outputs"]:
+    if sys.argv[1:] == ["dist_steps"]:
+        dist_steps()
+    elif sys.argv[1:] == ["ref_outputs"]:
         assert O.have_ref(), "reference library not built"
         ref_outputs()
     else:

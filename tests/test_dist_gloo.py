@@ -3,17 +3,17 @@
 infrastructure) in place of the HIP context."""
 import json
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from spawn_support import init_gloo, run_ranks  # noqa: E402
 
 
 class NumpyEngine:
@@ -191,18 +191,8 @@ class NumpyEngine:
         return torch.from_numpy(np.bincount(r, minlength=parts).astype(np.int64))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, n, kind, q, sampled=False, piece_bytes=0):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker(rank, world, port, q, n, kind, sampled=False, piece_bytes=0):
+    init_gloo(rank, world, port)
     if piece_bytes:   # exchanges in several rounds of small pieces (the product's limit is 512 MiB per pair and round)
         import inplacemsdradixsort_amd.dist as D
         D.A2A_MAX_BYTES = piece_bytes
@@ -231,16 +221,7 @@ def _worker(rank, world, port, n, kind, q, sampled=False, piece_bytes=0):
                                              (2, "uniform", "fine"), (4, "zipf", "fine"), (8, "uniform", "fine")])
 def test_sharded_sort_over_gloo(world, kind, work):
     n = 20000 if world < 8 else 6000   # (8 ranks: each owns 32 top-digit buckets, BASELINE config C4's geometry)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, kind, q, work if isinstance(work, str) else ("work" if work else False))) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = dict(run_ranks(_worker, world, (n, kind, work if isinstance(work, str) else ("work" if work else False))))
     from oracle import oracle as O
     gen = O.gen_uniform_u32 if kind == "uniform" else O.gen_zipf_u32
     allk = np.concatenate([gen(n, first=r * n) for r in range(world)])
@@ -258,26 +239,15 @@ def test_exchange_in_pieces_over_gloo(world, kind, how, piece_bytes):
     """The all-to-all in rounds of bounded pieces (RCCL 2.26 moves only half of a >= 2 GiB message): ragged blocks, blocks
     smaller than a piece, piece sizes that do not divide the blocks, every scheme."""
     n = 20000 if world < 8 else 6000
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, kind, q, how, piece_bytes)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = dict(run_ranks(_worker, world, (n, kind, how, piece_bytes)))
     from oracle import oracle as O
     gen = O.gen_uniform_u32 if kind == "uniform" else O.gen_zipf_u32
     allk = np.concatenate([gen(n, first=r * n) for r in range(world)])
     assert (np.concatenate([res[r] for r in range(world)]) == O.sort_u32(allk)).all()
 
 
-def _hist_worker(rank, world, port, n, q, pipelined, dups):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _hist_worker(rank, world, port, q, n, pipelined, dups):
+    init_gloo(rank, world, port)
     import inplacemsdradixsort_amd.dist as D
     from oracle import oracle as O
     D.FINE_HIST_MIN_KEYS = 0                     # (the product asks for 3 * 2^28 keys per rank)
@@ -315,19 +285,7 @@ def test_histogram_exchange_over_gloo(pipelined, dups):
     """The fine scheme's histogram form (dist.FINE_HIST): every rank packs its 2^16 buckets into records, equal blocks
     travel, the receiver sums histograms; a record that overflows on ONE rank sends every rank back to the low halves."""
     world, n = 2, 150_000
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_hist_worker, args=(r, world, port, n, q, pipelined, dups)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = {}
-    for _ in range(world):
-        r, out, calls, k = q.get(timeout=600)
-        res[r] = (out, calls, k)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = {r: (out, calls, k) for r, out, calls, k in run_ranks(_hist_worker, world, (n, pipelined, dups), get_timeout=600, join_timeout=120)}
     allk = np.concatenate([res[r][2] for r in range(world)])
     got = np.concatenate([res[r][0] for r in range(world)])
     assert (got == np.sort(allk)).all()
@@ -367,10 +325,8 @@ def test_all_to_all_v_rounds_match_one_call():
         D.A2A_MAX_BYTES = old
 
 
-def _pipeline_worker(rank, world, port, n, shards, q, scheme=None):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _pipeline_worker(rank, world, port, q, n, shards, scheme=None):
+    init_gloo(rank, world, port)
     from inplacemsdradixsort_amd.dist import ShardedSorter
     from oracle import oracle as O
     bufs = [torch.from_numpy(O.gen_uniform_u32(n, seed=100 + s, first=rank * n).view(np.int32).copy()) for s in range(shards)]
@@ -393,16 +349,7 @@ def _pipeline_worker(rank, world, port, n, shards, q, scheme=None):
 def test_pipelined_sharded_sorter_over_gloo(world, scheme):
     """ShardedSorter (exchange of shard s in flight while shard s-1 is sorted) gives every shard's sorted ranges."""
     n, shards = (12000, 4) if world < 8 else (4000, 3)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_pipeline_worker, args=(r, world, port, n, shards, q, scheme)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = dict(run_ranks(_pipeline_worker, world, (n, shards, scheme)))
     from oracle import oracle as O
     for s in range(shards):
         allk = np.concatenate([O.gen_uniform_u32(n, seed=100 + s, first=r * n) for r in range(world)])
@@ -415,16 +362,7 @@ def test_sampled_splitter_sort_over_gloo(world, kind):
     """Skew path: random sample of the unsorted shards, equi-depth splitters with the reference's duplicate rule, one
     range partition, one exchange, one local sort; ranks stay balanced on Zipf keys."""
     n = 30000 if world < 8 else 8000
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, kind, q, True)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = dict(run_ranks(_worker, world, (n, kind, True)))
     from oracle import oracle as O
     gen = O.gen_uniform_u32 if kind == "uniform" else O.gen_zipf_u32
     allk = np.concatenate([gen(n, first=r * n) for r in range(world)])
@@ -434,10 +372,8 @@ def test_sampled_splitter_sort_over_gloo(world, kind):
     assert max(sizes) < (1.35 if world < 8 else 1.6) * n, sizes   # the radix split would put ~75 % of Zipf keys on rank 0
 
 
-def _overflow_worker(rank, world, port, n, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _overflow_worker(rank, world, port, q, n):
+    init_gloo(rank, world, port)
     from inplacemsdradixsort_amd.dist import ReceiveOverflow, ShardedSorter, sort_sharded_u32
     from oracle import oracle as O
     keys = torch.from_numpy(O.gen_zipf_u32(n, first=rank * n).view(np.int32).copy())   # ~75 % of the keys go to rank 0
@@ -460,16 +396,7 @@ def test_receive_overflow_is_raised_on_every_rank():
     """A receive buffer that is too small for ONE rank's range fails the call on ALL ranks, before the data
     exchange (the decision comes from the all-gathered send matrix): no rank is left waiting in the collective."""
     world, n = 4, 20000
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_overflow_worker, args=(r, world, port, n, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = dict(q.get(timeout=120) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = dict(run_ranks(_overflow_worker, world, (n,)))
     for r in range(world):
         assert len(res[r]) == 3 and all("receive buffer too small on rank(s) 0:" in m for m in res[r]), res[r]
 
@@ -499,10 +426,8 @@ def test_splitters_follow_the_reference_duplicate_rule():
         assert got == delim[:parts - 1].tolist()
 
 
-def _wide_worker(rank, world, port, n, pairs, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _wide_worker(rank, world, port, q, n, pairs):
+    init_gloo(rank, world, port)
     from inplacemsdradixsort_amd.dist import sort_sharded_pairs_u64, sort_sharded_u64
     from oracle import oracle as O
     k = O.gen_uniform_u64(n, first=rank * n)
@@ -524,19 +449,7 @@ def test_sharded_u64_and_tuple_sort_over_gloo(world, pairs):
     """u64 keys and (u64 key, u64 rid) tuples -- the reference's sort() with one pair of arrays per memory node,
     src/msb_64.c:2261 -- across ranks: global order, every rid still with its key, rank r owns top bits == r."""
     n = 15000 if world < 8 else 5000
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_wide_worker, args=(r, world, port, n, pairs, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = {}
-    for _ in range(world):
-        r, k, v = q.get(timeout=120)
-        res[r] = (k, v)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = {r: (k, v) for r, k, v in run_ranks(_wide_worker, world, (n, pairs))}
     from oracle import oracle as O
     allk = np.concatenate([O.gen_uniform_u64(n, first=r * n) for r in range(world)])
     got = np.concatenate([res[r][0] for r in range(world)])
@@ -555,10 +468,8 @@ def _zipf64(n, rank):
     return z * z + (z >> np.uint64(3))
 
 
-def _sampled64_worker(rank, world, port, n, pairs, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _sampled64_worker(rank, world, port, q, n, pairs):
+    init_gloo(rank, world, port)
     from inplacemsdradixsort_amd.dist import sort_sharded_pairs_u64_sampled, sort_sharded_u64_sampled
     k = _zipf64(n, rank)
     keys = torch.from_numpy(k.view(np.int64).copy())
@@ -580,19 +491,7 @@ def test_sampled_sharded_u64_and_tuple_sort_over_gloo(world, pairs):
     splitters, one range pass, one exchange; global order, every rid with its key, and no rank above 1.6 n where the radix
     split would put most keys on rank 0."""
     n = 20000 if world < 8 else 8000
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_sampled64_worker, args=(r, world, port, n, pairs, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = {}
-    for _ in range(world):
-        r, k, v = q.get(timeout=120)
-        res[r] = (k, v)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = {r: (k, v) for r, k, v in run_ranks(_sampled64_worker, world, (n, pairs))}
     allk = np.concatenate([_zipf64(n, r) for r in range(world)])
     got = np.concatenate([res[r][0] for r in range(world)])
     assert (got == np.sort(allk)).all()

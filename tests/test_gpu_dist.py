@@ -1,67 +1,38 @@
 """Multi-rank sort with the REAL HIP engine: two (and four) processes share cuda:0 and run
-inplacemsdradixsort_amd.dist.sort_sharded_u32; the exchange goes through a gloo-via-CPU stand-in
-for torch.distributed (RCCL cannot run several ranks on one device; the driver's N-GPU bench uses
+inplacemsdradixsort_amd.dist.sort_sharded_u32; the exchange goes through dist.HostStagedDist
+(gloo, staged through host memory) in place of torch.distributed (RCCL cannot run several ranks on one device; the driver's N-GPU bench uses
 the same function with backend "nccl")."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from spawn_support import init_gloo, run_ranks  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-class GlooViaCpu:
-    """all_to_all_single / all_gather for CUDA tensors over the gloo backend (copies through host memory)."""
-
-    get_rank = staticmethod(dist.get_rank)
-
-    @staticmethod
-    def all_gather(outs, t, group=None):
-        tmp = [torch.empty(o.shape, dtype=o.dtype) for o in outs]
-        dist.all_gather(tmp, t.cpu(), group=group)
-        for o, x in zip(outs, tmp):
-            o.copy_(x)
-
-    @staticmethod
-    def all_to_all_single(output, input, output_split_sizes=None, input_split_sizes=None, group=None):
-        o = torch.empty(output.shape, dtype=output.dtype)
-        dist.all_to_all_single(o, input.cpu(), output_split_sizes=output_split_sizes,
-                               input_split_sizes=input_split_sizes, group=group)
-        output.copy_(o)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, n, kind, q, sampled=False):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker(rank, world, port, q, n, kind, sampled=False):
+    init_gloo(rank, world, port)
     from inplacemsdradixsort_amd import MsdContext
-    from inplacemsdradixsort_amd.dist import sort_sharded_u32, sort_sharded_u32_sampled
+    from inplacemsdradixsort_amd.dist import HostStagedDist, sort_sharded_u32, sort_sharded_u32_sampled
+    staged = HostStagedDist(dist)
     ctx = MsdContext(0)
     keys = torch.empty(n, dtype=torch.int32, device="cuda:0")
     (ctx.gen_uniform_u32 if kind == "uniform" else ctx.gen_zipf_u32)(keys, first=rank * n)
     v0, s0, x0 = ctx.check(keys)
     recv = torch.empty(n * world, dtype=torch.int32, device="cuda:0")
     if sampled == "work":   # runs gathered bucket-major into a second buffer, segmented local sort (round 2's N > 1 path)
-        out = sort_sharded_u32(ctx, keys, recv, GlooViaCpu, world, work=torch.empty(n * world, dtype=torch.int32, device="cuda:0"), scheme="coarse")
+        out = sort_sharded_u32(ctx, keys, recv, staged, world, work=torch.empty(n * world, dtype=torch.int32, device="cuda:0"), scheme="coarse")
     elif sampled == "fine":  # top 16 bits before the exchange, counting leaf over the arrived extents (bench.py's N > 1 path)
-        out = sort_sharded_u32(ctx, keys, recv, GlooViaCpu, world, work=torch.empty(n * world, dtype=torch.int32, device="cuda:0"), scheme="fine")
+        out = sort_sharded_u32(ctx, keys, recv, staged, world, work=torch.empty(n * world, dtype=torch.int32, device="cuda:0"), scheme="fine")
     else:
-        out = (sort_sharded_u32_sampled if sampled else sort_sharded_u32)(ctx, keys, recv, GlooViaCpu, world)
+        out = (sort_sharded_u32_sampled if sampled else sort_sharded_u32)(ctx, keys, recv, staged, world)
     v, s, x = ctx.check(out)
     lo = int(out[0].item()) & 0xFFFFFFFF if out.numel() else -1
     hi = int(out[-1].item()) & 0xFFFFFFFF if out.numel() else -1
@@ -71,12 +42,11 @@ def _worker(rank, world, port, n, kind, q, sampled=False):
     ctx.close()
 
 
-def _pipeline_worker(rank, world, port, n, shards, q, scheme=None):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _pipeline_worker(rank, world, port, q, n, shards, scheme=None):
+    init_gloo(rank, world, port)
     from inplacemsdradixsort_amd import MsdContext
-    from inplacemsdradixsort_amd.dist import ShardedSorter
+    from inplacemsdradixsort_amd.dist import HostStagedDist, ShardedSorter
+    staged = HostStagedDist(dist)
     ctx = MsdContext(0)
     ctx.set_option("direct_min", 1 << 16)   # the pre-exchange pass and the local sorts place directly at this size
     bufs, sums = [], []
@@ -87,7 +57,7 @@ def _pipeline_worker(rank, world, port, n, shards, q, scheme=None):
         sums.append(ctx.check(t)[1:])
     recv = [torch.empty(n * world, dtype=torch.int32, device="cuda:0") for _ in range(2)]
     work = [torch.empty(n * world, dtype=torch.int32, device="cuda:0") for _ in range(2)]
-    sorter = ShardedSorter(ctx, GlooViaCpu, world, recv, work_bufs=work, scheme=scheme)
+    sorter = ShardedSorter(ctx, staged, world, recv, work_bufs=work, scheme=scheme)
     res = []
 
     def take(out):
@@ -112,16 +82,7 @@ def test_pipelined_sharded_sorter_real_engine(scheme):
     """bench.py's N > 1 loop (ShardedSorter) with the HIP engine: 2 ranks on one device, 3 shards in a row; the
     concatenated outputs equal the sorted union of the regenerated inputs."""
     world, n, shards = 2, 1 << 22, 3
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    port = _free_port()
-    procs = [mpc.Process(target=_pipeline_worker, args=(r, world, port, n, shards, q, scheme)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = sorted(q.get(timeout=300) for _ in range(world))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = run_ranks(_pipeline_worker, world, (n, shards, scheme), get_timeout=300, join_timeout=120)
     for s in range(shards):
         per_rank = [got[r][1][s] for r in range(world)]
         assert sum(x[0] for x in per_rank) == n * world
@@ -144,16 +105,7 @@ def test_pipelined_sharded_sorter_real_engine(scheme):
                                                (2, "uniform", 1 << 22, True), (4, "zipf", 1 << 20, True),
                                                (2, "uniform", 1 << 22, "fine"), (4, "uniform", 1 << 21, "fine"), (4, "zipf", 1 << 20, "fine")])
 def test_sharded_sort_real_engine(world, kind, n, work):
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    port = _free_port()
-    procs = [mpc.Process(target=_worker, args=(r, world, port, n, kind, q, work if isinstance(work, str) else ("work" if work else False))) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=300) for _ in range(world))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, world, (n, kind, work if isinstance(work, str) else ("work" if work else False)), get_timeout=300, join_timeout=120)
     total = sum(r[1] for r in res)
     assert total == n * world
     assert all(r[2] == 0 for r in res)                                 # every rank's range is sorted
@@ -179,16 +131,7 @@ def test_sharded_sort_real_engine(world, kind, n, work):
 
 @pytest.mark.parametrize("world,kind,n", [(2, "zipf", 1 << 21), (4, "zipf", 1 << 20)])
 def test_sampled_splitter_sort_real_engine(world, kind, n):
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    port = _free_port()
-    procs = [mpc.Process(target=_worker, args=(r, world, port, n, kind, q, True)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=300) for _ in range(world))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, world, (n, kind, True), get_timeout=300, join_timeout=120)
     assert sum(r[1] for r in res) == n * world and all(r[2] == 0 for r in res)
     M = 1 << 64
     assert sum(r[3] for r in res) % M == sum(r[5] for r in res) % M
@@ -203,12 +146,11 @@ def test_sampled_splitter_sort_real_engine(world, kind, n):
     assert (np.concatenate([r[9] for r in res]) == np.sort(allk)).all()
 
 
-def _pairs_worker(rank, world, port, n, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _pairs_worker(rank, world, port, q, n):
+    init_gloo(rank, world, port)
     from inplacemsdradixsort_amd import MsdContext
-    from inplacemsdradixsort_amd.dist import sort_sharded_pairs_u64
+    from inplacemsdradixsort_amd.dist import HostStagedDist, sort_sharded_pairs_u64
+    staged = HostStagedDist(dist)
     ctx = MsdContext(0)
     keys = torch.empty(n, dtype=torch.int64, device="cuda:0")
     ctx.gen_uniform_u64(keys, first=rank * n)
@@ -216,7 +158,7 @@ def _pairs_worker(rank, world, port, n, q):
     v0, s0, x0 = ctx.check(keys)
     rk = torch.empty(2 * n, dtype=torch.int64, device="cuda:0")
     rr = torch.empty(2 * n, dtype=torch.int64, device="cuda:0")
-    out_k, out_r = sort_sharded_pairs_u64(ctx, keys, rids, rk, rr, GlooViaCpu, world)
+    out_k, out_r = sort_sharded_pairs_u64(ctx, keys, rids, rk, rr, staged, world)
     v, s, x = ctx.check(out_k, out_r)       # order + key == rid
     M = (1 << 64) - 1
     lo = int(out_k[0].item()) & M if out_k.numel() else -1
@@ -231,16 +173,7 @@ def _pairs_worker(rank, world, port, n, q):
 def test_sharded_tuple_sort_real_engine(world, n):
     """The reference's sort() across devices: (u64 key, u64 rid) tuples, one (keys, rids) pair per rank; sorted per
     rank, key == rid everywhere, key sum and xor preserved, rank r owns the keys whose top bits are r."""
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    port = _free_port()
-    procs = [mpc.Process(target=_pairs_worker, args=(r, world, port, n, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=300) for _ in range(world))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    res = run_ranks(_pairs_worker, world, (n,), get_timeout=300, join_timeout=120)
     assert sum(r[1] for r in res) == n * world and all(r[2] == 0 for r in res)
     M = 1 << 64
     assert sum(r[3] for r in res) % M == sum(r[5] for r in res) % M
