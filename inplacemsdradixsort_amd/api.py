@@ -19,6 +19,18 @@ from . import _args, _lib
 from ._args import MsdError, _torch, ptr   # (the argument rules, their error and the null-or-address of a tensor live in _args.py)
 
 
+# Every name msd_stat knows (the table of csrc/msd_options.hpp; the C ABI cannot enumerate them, so
+# tests/test_option_defaults.py holds the two equal).
+STAT_NAMES = ("rounds", "parents", "stripes", "children", "slots", "holes", "chain_steps",
+              "small_segments", "count_segments", "big_count_segments", "direct_rounds", "regpart_rounds", "skipped_bits", "bit_skip_restarts", "bit_skip_checked_by_histogram",
+              "leaves_behind_round", "rounds_planned_early", "front_count_sorts", "front_count_declined", "excess_blocks", "child_scan_split_rounds", "count16_rejected", "count_slow_segments",
+              "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes",
+              "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below",
+              "topk_rows_kernel_rows", "topk_rows_looped_rows",
+              "sort_rows_kernel_rows", "sort_rows_segment_rows", "sort_rows_lanes",
+              "sort_keys_split", "sort_keys_reversed")   # (these two wait for the stream: include/msd_sort_keys_hip.h)
+
+
 class MsdContext:
     """One sorting context (device + stream + auxiliary workspace)."""
 
@@ -1092,15 +1104,9 @@ class MsdContext:
         return [(self._L.msd_phase_name(self._h, i).decode(), float(self._L.msd_phase_us(self._h, i))) for i in range(n)]
 
     def stats(self) -> Dict[str, int]:
+        """The counters of the last call that msd_stat knows by now (:data:`STAT_NAMES`)."""
         out = {}
-        for name in ("rounds", "parents", "stripes", "children", "slots", "holes", "chain_steps",
-                     "small_segments", "count_segments", "big_count_segments", "direct_rounds", "regpart_rounds", "skipped_bits", "bit_skip_restarts", "bit_skip_checked_by_histogram",
-                     "leaves_behind_round", "rounds_planned_early", "front_count_sorts", "front_count_declined", "excess_blocks", "child_scan_split_rounds", "count16_rejected", "count_slow_segments",
-                     "merge_rejected", "leaf17_segments", "leaf17_rejected", "leaf17_slow_segments", "leaf17_launches", "workspace_bytes",
-                     "select_hist_passes", "select_skipped_bits", "select_candidates", "select_below",
-                     "topk_rows_kernel_rows", "topk_rows_looped_rows",
-                     "sort_rows_kernel_rows", "sort_rows_segment_rows", "sort_rows_lanes",
-                     "sort_keys_split", "sort_keys_reversed"):   # (these two wait for the stream: include/msd_sort_keys_hip.h)
+        for name in STAT_NAMES:
             v = C.c_uint64()
             if self._L.msd_stat(self._h, name.encode(), C.byref(v)) == 0:
                 out[name] = int(v.value)

@@ -142,8 +142,26 @@ struct Counters { // one per sort call, zeroed per round where noted
 	uint32_t err_sites;      // cumulative: which checks raised `errors` (bit = site, msd_note_error)
 	uint32_t nexcess;        // cumulative (stat): excess blocks cleanup_kernel put behind the leftovers
 };
+// The checks of internal invariants, named for what they found.  The values are the bit positions in Counters::err_sites
+// that an MSD_EINTERNAL message prints ("checks 0x%x"): they stay as they are.
+enum ErrSite : uint32_t {
+	kErrEvictPoolFull = 0,           // list_prepare_kernel: the evicted blocks do not fit the pool
+	kErrChainListExhausted = 1,      // chains_kernel: a list's cursor ran past its end
+	kErrChainSlotOutOfRange = 2,     // chains_kernel: a list entry or a hole names a slot outside the round
+	kErrListNotConsumed = 3,         // cleanup_kernel (chains_verify): a list's cursor is not at its length
+	kErrHotShardNotConsumed = 4,     // cleanup_kernel (chains_verify): a shard of a hot list's chain-continuing entries is not used up
+	kErrHotListEndsNotConsumed = 5,  // cleanup_kernel (chains_verify): a hot list's own cursor is not at its chain-ending entries
+	kErrSmallListFull = 6,           // collect_kernel: more leaf segments than the small / counting list holds
+	kErrBigListFull = 7,             // count_walk_kernel: a segment for the multi-workgroup counting sort, and its list is full or absent
+	kErrDirectNoSlot = 8,            // classify_direct2_kernel (flush_block): a full buffer found no slot of its round
+	kErrDirectJobSlotOutOfRange = 9, // classify_direct2_kernel: a flush job names a slot outside the round
+	kErrDirectFullBufferLeft = 10,   // classify_direct2_kernel (epilogue): the last round left a full buffer
+	kErrRegpartParentTooBig = 11,    // regpart_kernel: a parent beyond the register-resident capacity
+	kErrRegpartCountMismatch = 12,   // regpart_kernel: the digit counts do not add up to the parent
+	kErrBigcountCountMismatch = 13,  // bigcount_scan_kernel: the value counts do not add up to the segment
+};
 // an internal invariant does not hold: counted, and the place remembered for the error message
-__device__ __forceinline__ void msd_note_error(Counters *ctr, uint32_t site)
+__device__ __forceinline__ void msd_note_error(Counters *ctr, ErrSite site)
 {
 	atomicAdd(&ctr->errors, 1u);
 	atomicOr(&ctr->err_sites, 1u << site);
@@ -922,7 +940,7 @@ __global__ __launch_bounds__(256) void list_prepare_kernel(uint32_t nchildren, C
 	if (ev) {
 		first = atomicAdd(&ctr->nevict, ev);
 		if (first + ev > pool_cap) { // (cannot happen: the pool holds kMinChains + two blocks per child)
-			msd_note_error(ctr, 0u);
+			msd_note_error(ctr, kErrEvictPoolFull);
 			ev = 0;
 		}
 	}
@@ -1187,7 +1205,7 @@ __global__ __launch_bounds__(256) void chains_kernel(ChildArrays ca, const ListE
 			}
 			if (retry) {
 			} else if (idx >= len) { // cannot happen when the bookkeeping is right
-				msd_note_error(ctr, 1u);
+				msd_note_error(ctr, kErrChainListExhausted);
 				active = false;
 			} else {
 				tries = 0;
@@ -1201,7 +1219,7 @@ __global__ __launch_bounds__(256) void chains_kernel(ChildArrays ca, const ListE
 				src = e.slot;
 				src_owner = e.owner;
 				if (!slot_ok(src) || !slot_ok(hole)) {
-					msd_note_error(ctr, 2u);
+					msd_note_error(ctr, kErrChainSlotOutOfRange);
 					active = false;
 				} else if (!last) { // the next step's list: on its way while this step's blocks move
 					nom = ca.lmeta[src_owner];
@@ -1261,7 +1279,7 @@ __device__ __forceinline__ void chains_verify(const ChildArrays &ca, uint32_t ci
 {
 	const uint32_t len = (uint32_t)ca.list_len[ci], hot = flags >> 8;
 	if (!hot) {
-		if (ca.rpos[(size_t)ci * kRposStride] != len) msd_note_error(ctr, 3u);
+		if (ca.rpos[(size_t)ci * kRposStride] != len) msd_note_error(ctr, kErrListNotConsumed);
 		return;
 	}
 	// sharded cursors: every shard of the chain-continuing entries used up (lanes that found a shard empty have bumped
@@ -1269,9 +1287,9 @@ __device__ __forceinline__ void chains_verify(const ChildArrays &ca, uint32_t ci
 	const uint32_t nint = ca.n_int[ci];
 	for (uint32_t sh = 0; sh < kHotShards; ++sh) {
 		const uint32_t sb = (uint32_t)((uint64_t)nint * sh / kHotShards), se = (uint32_t)((uint64_t)nint * (sh + 1) / kHotShards);
-		if (ca.hot_cur[(size_t)((hot - 1) * kHotShards + sh) * kRposStride] < se - sb) msd_note_error(ctr, 4u);
+		if (ca.hot_cur[(size_t)((hot - 1) * kHotShards + sh) * kRposStride] < se - sb) msd_note_error(ctr, kErrHotShardNotConsumed);
 	}
-	if (ca.rpos[(size_t)ci * kRposStride] != len - nint) msd_note_error(ctr, 5u);
+	if (ca.rpos[(size_t)ci * kRposStride] != len - nint) msd_note_error(ctr, kErrHotListEndsNotConsumed);
 }
 
 // ------------------------------------------------------------- C: cleanup
@@ -1450,7 +1468,7 @@ __global__ __launch_bounds__(256) void collect_kernel(const Parent *__restrict__
 	else if (at < small_cap)
 		(which == 0 ? small : small_count)[at] = s;
 	else
-		msd_note_error(ctr, 6u);
+		msd_note_error(ctr, kErrSmallListFull);
 }
 
 } // namespace msd
@@ -1716,7 +1734,7 @@ __global__ __launch_bounds__(kCountTh, 8) void count_walk_kernel(K *__restrict__
 					fallback[fallback_base + at] = sg;
 				} else {            // ... to the multi-workgroup counting sort (32-bit counters)
 					const uint32_t at = big ? atomicAdd(&ctr->nbig, 1u) : 0xFFFFFFFFu;
-					if (at < big_cap) big[at] = sg; else msd_note_error(ctr, 7u);
+					if (at < big_cap) big[at] = sg; else msd_note_error(ctr, kErrBigListFull);
 				}
 			}
 		} else {

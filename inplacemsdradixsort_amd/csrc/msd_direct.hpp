@@ -268,7 +268,7 @@ __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) vo
 					*reinterpret_cast<uint4 *>(vals + dst) = *reinterpret_cast<const uint4 *>(vbuf + d * B + sub * VEC);
 			}
 		} else if (sub == 0)
-			msd_note_error(ctr, 8u);
+			msd_note_error(ctr, kErrDirectNoSlot);
 	};
 	// per bucket: a full buffer becomes a block; it takes the next consumed slot of the bucket's own piece
 	// or joins the steal list.  `consumed_now`: the bucket's slot of this tile is in registers by now.
@@ -339,7 +339,7 @@ __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) vo
 						st16<NTS>(keys + dst, q[u]);
 						if constexpr (HV) st16<NTS>(vals + dst, qv[u]);
 					} else if (ss[u] != NONE && sub == 0)
-						msd_note_error(ctr, 9u);
+						msd_note_error(ctr, kErrDirectJobSlotOutOfRange);
 				}
 			}
 		}
@@ -493,7 +493,7 @@ __global__ __launch_bounds__((Direct2Cfg<K, V>::TH), (Direct2Cfg<K, V>::WPE)) vo
 	uint32_t fill_r = 0, lc = 0;
 	if (tid < kP) {
 		fill_r = cnt[tid]; // < B: the last round left no full buffer
-		if (fill_r >= (uint32_t)B) msd_note_error(ctr, 10u);
+		if (fill_r >= (uint32_t)B) msd_note_error(ctr, kErrDirectFullBufferLeft);
 		lc = fill_r + hc[tid];
 	}
 	uint32_t ltot;

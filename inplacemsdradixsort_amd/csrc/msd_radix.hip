@@ -17,6 +17,7 @@
 #include "msd_setops.hpp"
 #include "msd_join.hpp"
 #include "msd_args.hpp" // the argument rules, each stated once (host only)
+#include "msd_options.hpp" // the options and the counters of the context, each stated once (host only)
 #include "../../include/msd_radix_hip.h"
 #include "../../include/msd_sort_keys_hip.h"
 #include "../../include/msd_sort_rows_hip.h"
@@ -66,39 +67,20 @@ struct msd_ctx {
 	std::vector<hipEvent_t> ev_pool;
 	size_t ev_used = 0;
 	std::vector<std::pair<std::string, double>> phase_us;
-	std::vector<std::pair<std::string, uint64_t>> stats;
+	uint64_t stat[kStatCount] = {}; // the counters of msd_stat (msd_options.hpp) ...
+	uint64_t stat_written = 0;      // ... and which of them the last call has written (bit = slot)
+	Options opt;                    // the knobs of msd_set_option (msd_options.hpp)
 	int sm_count = 256;
 	int chains_per_cu[3] = { 4, 4, 2 }; // resident chains_kernel workgroups per CU: u32 keys, u64 keys, tuples (measured at msd_create)
-	// direct block placement in the first round: 0 off, 1 when the sampled
-	// children are about equally big, 2 whenever the geometry allows (tests)
-	int direct_mode = 1;
-	uint64_t direct_min = 1ull << 22; // smallest round (elements) it is tried on (tools/size_sweep.py: from 2^22 on it is never slower by more than 7 %, and up to 47 % faster)
-	uint64_t direct_min_parent = 1ull << 17; // rounds after the first: smallest parent
-	int regpart = 1;       // u64 keys / tuples: rounds of small parents as one register-resident pass (0: A/B comparisons)
-	int count16 = 1;       // u32 keys: count_place16_kernel in front of count_place_kernel (0: A/B comparisons)
-	int leaf17 = 1;        // u64 keys and tuples: segments of <= 17408 elements are finished by leaf17_kernel (0: tuples: register partition + small leaves, keys: leaf_count_sort_kernel; A/B comparisons)
-	int mid_leaf = 1;      // u32 keys: merge_count_kernel (list mode) in front of count_walk_kernel (0: A/B comparisons)
-	int early_leaves = 1;  // keys only: the counting leaves go behind a last round without waiting for its end (0: A/B comparisons)
-	int early_plan = 1;    // a round that is not the last: the next round is planned and enqueued while its fix-up runs (0: A/B comparisons)
-	int front_count = 1;   // u32 keys, two direct 8-bit rounds: the top 16 bits are counted once up front and both rounds placed from that (msd_front16.hpp; 0: A/B comparisons)
-	uint64_t front_min = 1ull << 29; // smallest sort the front pass is tried on (tools/size_sweep.py: 0.7 % slower at 2^28 keys, 1 % faster at 2^29, 1.5 % at 2^30)
 	const uint32_t *order_keys = nullptr; // msd_order_low16_counts_u32 has run on these keys and its tables are still in the slab
 	uint64_t order_n = 0;
-	int merge_leaf = 0;    // msd_merge_buckets_u32: 0 = by bucket size, 1 = merge_place16_kernel, 2 = merge_count_kernel (tests)
 	char *sel = nullptr;   // msd_topk_* / msd_select_*: search state, per-pass bins, candidate buffer (lives across the internal sorts)
 	size_t sel_bytes = 0;
-	uint64_t select_cap = 1ull << 20; // candidate capacity (elements): the search stops once the pivot bucket fits
-	int topk_rows_mode = 0; // msd_topk_rows: 0 = the library chooses, 1 = always the loop over msd_topk_keys, 2 = always the row kernel
-	int topk_rows_lanes = 0; // the row kernel's lanes per row: 0 = by row length, 64 / 256 / 1024 = forced where the row fits (A/B comparisons)
 	char *rows_stage = nullptr; // msd_topk_rows, looped path: one row + k output elements for rows that are not 16-byte aligned
 	size_t rows_stage_bytes = 0;
-	int sort_rows_mode = 0; // msd_sort_rows: 0 = the library chooses, 1 = always the segment path, 2 = always the row kernel
-	int sort_rows_lanes = 0; // the row kernel's lanes per row: 0 = by row length, 64 / 256 / 1024 = forced where the row fits (A/B comparisons)
 	uint64_t *fix_plan = nullptr; // msd_sort_keys: the plan words of msd_reverse.hpp (kFixWords), allocated by msd_create
 	int fix_stats = 0;            // "sort_keys_split" / "sort_keys_reversed" of the last typed sort: 0 none yet, 1 fix_split and 0 (nothing was launched), 2 in the plan words
 	uint64_t fix_split = 0;
-	int search_mode = 0;               // msd_search_sorted with sorted needles: 0 = the library chooses, 1 = always direct, 2 = always merge
-	uint64_t search_merge_ratio = 32;  // R: the library chooses merge when m >= n / R (the measured crossover lies near n / 37 for 4-byte and n / 24 for 8-byte keys: DESIGN.md section 10.7)
 };
 
 static int fail(msd_ctx *c, int code, const char *fmt, ...)
@@ -138,23 +120,14 @@ static int launch_at(msd_ctx *c, const char *what, const char *file, int line, v
 		if (int rc_ = LAUNCH_RC(c, kernel, grid, block, lds, __VA_ARGS__)) return rc_;      \
 	} while (0)
 
-static void set_stat(msd_ctx *c, const char *name, uint64_t v)
+static void set_stat(msd_ctx *c, Stat slot, uint64_t v)
 {
-	for (auto &s : c->stats)
-		if (s.first == name) {
-			s.second = v;
-			return;
-		}
-	c->stats.emplace_back(name, v);
+	c->stat[slot] = v;
+	c->stat_written |= 1ull << slot;
 }
-static void add_stat(msd_ctx *c, const char *name, uint64_t v)
+static void add_stat(msd_ctx *c, Stat slot, uint64_t v)
 {
-	for (auto &s : c->stats)
-		if (s.first == name) {
-			s.second += v;
-			return;
-		}
-	c->stats.emplace_back(name, v);
+	set_stat(c, slot, (c->stat_written >> slot & 1 ? c->stat[slot] : 0) + v);
 }
 
 // ------------------------------------------------------------ workspace slab
@@ -244,6 +217,13 @@ template <typename F> static int slab_carve(msd_ctx *c, F &&carve, size_t min_by
 	return MSD_OK;
 }
 
+// The slab as it stands -- whoever reserved it knows that `carve` fits -- laid out once more
+template <typename F> static void slab_recarve(msd_ctx *c, F &&carve)
+{
+	Bump real(c->slab);
+	carve(real);
+}
+
 // ------------------------------------------------------------ host <-> device through the pinned staging buffer
 
 struct ToDevice { void *dst; const void *src; size_t bytes; };
@@ -262,7 +242,7 @@ static int upload(msd_ctx *c, std::initializer_list<ToDevice> pieces)
 	return MSD_OK;
 }
 
-struct ToHost { size_t at; const void *src; size_t bytes; }; // (at: offset in the staging buffer)
+struct ToHost { size_t at; const void *src; size_t bytes; void *out = nullptr; }; // (at: offset in the staging buffer; out: where the host wants a copy)
 // The counters, and with them the non-empty `extra` device ranges (to their places in the staging buffer): one synchronisation
 static int read_counters(msd_ctx *c, const Counters *ctr, Counters &hc, std::initializer_list<ToHost> extra = {})
 {
@@ -271,6 +251,17 @@ static int read_counters(msd_ctx *c, const Counters *ctr, Counters &hc, std::ini
 		if (p.bytes) HIPCHK(c, hipMemcpyAsync((char *)c->pinned + p.at, p.src, p.bytes, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	memcpy(&hc, c->pinned, sizeof hc);
+	for (const ToHost &p : extra)
+		if (p.out) memcpy(p.out, (const char *)c->pinned + p.at, p.bytes);
+	return MSD_OK;
+}
+
+// `count` values of a device array to `out` on the host (the caller has reserved the staging buffer; one copy, one synchronisation)
+template <typename T> static int read_back(msd_ctx *c, const T *src, T *out, size_t count = 1)
+{
+	HIPCHK(c, hipMemcpyAsync(c->pinned, src, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	memcpy(out, c->pinned, count * sizeof(T));
 	return MSD_OK;
 }
 
@@ -711,9 +702,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		const uint64_t cnt = (n + stride - 1) / stride;
 		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (cnt + 255) / 256);
 		LAUNCH(c, (vary_kernel<K>), grid, 256, 0, keys, n, stride, vres);
-		HIPCHK(c, hipMemcpyAsync(c->pinned, vres, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		const unsigned long long *h = (const unsigned long long *)c->pinned;
+		unsigned long long h[2];
+		if (int rc = read_back(c, vres, h, 2)) return rc;
 		*vary_out = h[0] ^ h[1];
 		return MSD_OK;
 	}
@@ -736,17 +726,17 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		vary &= low_mask;
 		const int top_sample = vary ? 64 - __builtin_clzll(vary) : 0;
 		if (top_sample + 8 <= end_bit) { // at least one whole leading digit looks constant
-			if (top_sample > 0 && c->direct_mode != 0 && n >= c->direct_min && n >= ((uint64_t)1 << 24)) {
+			if (top_sample > 0 && c->opt.direct_mode != 0 && n >= c->opt.direct_min && n >= ((uint64_t)1 << 24)) {
 				unverified = true;
 				claimed_const = low_mask & ~(((uint64_t)1 << top_sample) - 1ull);
 				cur[0].bits = (uint32_t)top_sample;
-				set_stat(c, "skipped_bits", (uint64_t)(end_bit - top_sample));
+				set_stat(c, kStatSkippedBits, (uint64_t)(end_bit - top_sample));
 			} else { // make sure at once
 				rc = run_vary(1, &vary);
 				if (rc) return rc;
 				vary &= low_mask;
 				const int top = vary ? 64 - __builtin_clzll(vary) : 0;
-				set_stat(c, "skipped_bits", (uint64_t)(end_bit - top));
+				set_stat(c, kStatSkippedBits, (uint64_t)(end_bit - top));
 				if (top == 0)
 					cur.clear(); // every key is the same on the bits in question: already sorted
 				else
@@ -777,14 +767,14 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	int front_count()
 	{
 		if constexpr (!HV && sizeof(K) == 4) {
-			if (!c->front_count || job.kind != SortJob<K>::kWhole || job.stop_bits || end_bit != 32 || cur.size() != 1 || c->direct_mode == 0 ||
-			    n < c->direct_min || n < c->front_min || n < ((uint64_t)1 << 20) || n >= ((uint64_t)1 << 32))
+			if (!c->opt.front_count || job.kind != SortJob<K>::kWhole || job.stop_bits || end_bit != 32 || cur.size() != 1 || c->opt.direct_mode == 0 ||
+			    n < c->opt.direct_min || n < c->opt.front_min || n < ((uint64_t)1 << 20) || n >= ((uint64_t)1 << 32))
 				return MSD_OK;
 			{ // would today's plan run two direct 8-bit rounds on evenly spread keys?  (Round 1's parents an eighth below and
 			  // above the mean must still get 8-bit digits: near the size where the planner changes its mind -- 2^27 -- half
 			  // of them do not, and the count would be paid for nothing.)
 				const uint64_t mean = n / kP;
-				if (pick_width(n, 32, small_max, count_bits) != 8 || mean - mean / 8 < c->direct_min_parent ||
+				if (pick_width(n, 32, small_max, count_bits) != 8 || mean - mean / 8 < c->opt.direct_min_parent ||
 				    pick_width(mean - mean / 8, 24, small_max, count_bits) != 8 || pick_width(mean + mean / 8, 24, small_max, count_bits) != 8)
 					return MSD_OK;
 			}
@@ -796,31 +786,30 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			static_assert(((size_t)kP * kP + 16) * sizeof(Segment) >= (size_t)kP * kP * 4 + sizeof(FrontSummary), "the counts and the summary fit a quarter of the lists");
 			const unsigned grid = (unsigned)std::min<uint64_t>({ (uint64_t)c->sm_count, std::max<uint64_t>(1, n >> 18), c->slab_bytes / (kF16Words * sizeof(uint32_t)) });
 			if (!grid) return MSD_OK;
-			uint32_t *partials = reinterpret_cast<uint32_t *>(c->slab);
+			uint32_t *partials = nullptr;
+			slab_recarve(c, [&](Bump &b) { partials = b.take<uint32_t>((size_t)grid * kF16Words); });
 			LAUNCH(c, (front_probe_kernel<K>), 1, 1024, 0, keys, n, 16u, front_sum()); // (clears the summary first)
 			LAUNCH(c, (front_count16_kernel<K>), grid, kF16Th, kF16Lds, keys, n, 16u, partials, front_sum());
 			LAUNCH(c, front_plan_kernel, kP, 256, 0, partials, grid, front_hist(), front_sum(), 16u, job.stop_bits, count_bits, small_max,
 			       std::max<uint64_t>(small_max, kCountMedMax));
 			LAUNCH(c, front_top_kernel, 1, 256, 0, front_sum());
-			HIPCHK(c, hipMemcpyAsync(c->pinned, front_sum(), sizeof(FrontSummary), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(c, hipStreamSynchronize(c->stream));
-			memcpy(&fsum, c->pinned, sizeof fsum);
+			if ((rc = read_back(c, front_sum(), &fsum))) return rc;
 			phase_mark(c, "front count");
 			const uint64_t vary = (fsum.v_or ^ fsum.v_and) & low_mask;
 			const int top = vary ? 64 - __builtin_clzll(vary) : 0;
 			if (fsum.hopeless) { // front_probe_kernel: skewed or in runs by a sample, nothing was counted
-				add_stat(c, "front_count_declined", 1);
+				add_stat(c, kStatFrontCountDeclined, 1);
 				return MSD_OK;
 			}
 			bool ok = !fsum.overflow && top + 8 > end_bit && !fsum.uneven[0] && !fsum.uneven[1] && fsum.nroute[kRouteCount + 1] == (uint32_t)kP * kP;
 			std::vector<Segment> next = front_parents();
 			uint64_t total = 0;
 			for (const Segment &sg : next) { // round 1 as the host will plan it: every parent big enough, with an 8-bit digit
-				ok = ok && sg.count >= c->direct_min_parent && pick_width(sg.count, sg.bits, small_max, count_bits) == 8;
+				ok = ok && sg.count >= c->opt.direct_min_parent && pick_width(sg.count, sg.bits, small_max, count_bits) == 8;
 				total += sg.count;
 			}
 			if (!fsum.overflow && total != n) return fail(c, MSD_EINTERNAL, "front count: the counts add up to %llu of %llu keys", (unsigned long long)total, (unsigned long long)n);
-			add_stat(c, ok ? "front_count_sorts" : "front_count_declined", 1);
+			add_stat(c, ok ? kStatFrontCountSorts : kStatFrontCountDeclined, 1);
 			front = ok;
 		}
 		return MSD_OK;
@@ -892,7 +881,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				// of a general round: the last partition round of the tuple sort (65536 parents of about 2^14 tuples at 2^30)
 				// (dev_np: the previous round left only parents that fit, and their list stayed on the device -- it is
 				// planned there too, regpart_plan_kernel; otherwise the host sorts the fitting parents out of its list)
-				if (!job.single_pass() && c->regpart) {
+				if (!job.single_pass() && c->opt.regpart) {
 					std::vector<Segment> fit, rest;
 					if (!dev_np)
 						for (auto &sg : cur) (register_parent(sg) ? fit : rest).push_back(sg);
@@ -902,7 +891,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 						dev_np = 0;
 						// (tuples: such a segment is finished by leaf17_kernel instead, while nothing stands against it)
 						if constexpr (HV)
-							rc = c->leaf17 && leaf17_ok && !unverified ? leaf17_pass(fit, rest, np) : regpart_round(fit, rest, np);
+							rc = c->opt.leaf17 && leaf17_ok && !unverified ? leaf17_pass(fit, rest, np) : regpart_round(fit, rest, np);
 						else
 							rc = regpart_round(fit, rest, np);
 						if (rc) return rc;
@@ -943,10 +932,13 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	int leaf17_pass(const std::vector<Segment> &fit, const std::vector<Segment> &rest, const uint32_t np)
 	{
 		const bool on_device = fit.empty();
-		int rc = slab_reserve(c, 2 * (size_t)np * sizeof(Segment) + 4096);
+		Segment *d_segs = nullptr, *d_rej = nullptr;
+		int rc = slab_carve(c, [&](Bump &b) {
+			d_segs = b.take<Segment>(np);
+			d_rej = b.take<Segment>(np);
+		});
 		if (!rc) rc = pinned_reserve(c, (size_t)np * sizeof(Segment) + 4096);
 		if (rc) return rc;
-		Segment *d_segs = reinterpret_cast<Segment *>(c->slab), *d_rej = d_segs + np;
 		if (on_device)
 			HIPCHK(c, hipMemcpyAsync(d_segs, dev_list, (size_t)np * sizeof(Segment), hipMemcpyDeviceToDevice, c->stream));
 		else if ((rc = upload(c, { { d_segs, fit.data(), (size_t)np * sizeof(Segment) } })))
@@ -959,13 +951,13 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		Counters hc;
 		if ((rc = read_counters(c, ctr, hc))) return rc;
 		if (hc.errors) return fail(c, MSD_EINTERNAL, "leaf17: %u internal invariant violations (checks 0x%x)", hc.errors, hc.err_sites);
-		add_stat(c, "leaf17_segments", np - hc.nslow2);
-		add_stat(c, "leaf17_slow_segments", hc.l17_slow);
+		add_stat(c, kStatLeaf17Segments, np - hc.nslow2);
+		add_stat(c, kStatLeaf17SlowSegments, hc.l17_slow);
 		cur = rest;
 		if (hc.nslow2) { // rejected segments: the register partition + the small leaves finish them
 			if ((rc = fetch_segments(c, d_rej, hc.nslow2, cur))) return rc;
 			leaf17_ok = false; // (for the rest of this call)
-			add_stat(c, "leaf17_rejected", hc.nslow2);
+			add_stat(c, kStatLeaf17Rejected, hc.nslow2);
 		}
 		phase_mark(c, "readback");
 		return MSD_OK;
@@ -1017,10 +1009,10 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if ((rc = read_counters(c, ctr, hc, { { offsetof(Staging, sum.segs), d_next, ahead * sizeof(Segment) } }))) return rc;
 		if (hc.errors) return fail(c, MSD_EINTERNAL, "register partition round: %u internal invariant violations (checks 0x%x)", hc.errors, hc.err_sites);
 		adopt(hc, false);
-		add_stat(c, "rounds", 1);
-		add_stat(c, "regpart_rounds", 1);
-		add_stat(c, "parents", np);
-		add_stat(c, "children", nc);
+		add_stat(c, kStatRounds, 1);
+		add_stat(c, kStatRegpartRounds, 1);
+		add_stat(c, kStatParents, np);
+		add_stat(c, kStatChildren, nc);
 		cur = rest;
 		if (hc.next_parents && (rc = fetch_segments(c, d_next, hc.next_parents, cur, staged(offsetof(Staging, sum.segs)), ahead))) return rc;
 		next_round();
@@ -1075,7 +1067,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	Deferred pending = { Deferred::kLeavesCounters }, parked = { Deferred::kParkSlot };
 	bool enqueue_ahead = false; // the round being enqueued now goes behind a running one: no synchronisation, no allocation
 	Counters *park() const { return ctr + 2; }
-	static constexpr uint32_t kCountWalkSites = 1u << 7; // msd_note_error sites in the leaves' counters that are no round's: count_walk_kernel's
+	static constexpr uint32_t kCountWalkSites = 1u << kErrBigListFull; // msd_note_error sites in the leaves' counters that are no round's: count_walk_kernel's
 	// (behind adopt, ahead of next_round)
 	void defer(Deferred &d, const Round &r) { d = { d.source, true, round, r.np, r.ns, r.nc, r.rp.nslots, prev_direct ? "used" : "not used" }; }
 	ToHost parked_piece() const { return { offsetof(Staging, parked), park(), parked.open ? sizeof(Counters) : 0 }; }
@@ -1117,7 +1109,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// (with room for the plan of a next round that goes behind this one: at most kReadAhead parents, and about as many
 			// stripes as a round of all n keys has, one more per parent)
 			const size_t next_stripes = (size_t)std::max<uint64_t>((uint64_t)c->sm_count * MSD_STRIPE_WANT, n >> MSD_STRIPE_CAP_LOG) + 2 * kReadAhead + 64;
-			const size_t want = !ahead && c->early_plan && !job.single_pass() ? stage2_bytes(kReadAhead, next_stripes) : 0;
+			const size_t want = !ahead && c->opt.early_plan && !job.single_pass() ? stage2_bytes(kReadAhead, next_stripes) : 0;
 			if ((rc = pinned_reserve(c, std::max({ sizeof(typename Staging::Summary), r.np * sizeof(Parent) + r.ns * sizeof(Stripe), want })))) return rc;
 			char *stage = staged(ahead ? offsetof(Staging, stage2) : 0);
 			if (!ahead) HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
@@ -1143,11 +1135,11 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	{
 		const RoundPlan &rp = r.rp;
 		const uint32_t np = r.np, ns = r.ns;
-		bool try_direct = c->direct_mode != 0 && rp.round_keys >= c->direct_min && !job.splitters;
-		for (size_t i = 0; i < np && try_direct; ++i) try_direct = rp.parents[i].width == 8 || c->direct_mode == 2;
+		bool try_direct = c->opt.direct_mode != 0 && rp.round_keys >= c->opt.direct_min && !job.splitters;
+		for (size_t i = 0; i < np && try_direct; ++i) try_direct = rp.parents[i].width == 8 || c->opt.direct_mode == 2;
 		if (try_direct && np > 1) {
 			try_direct = prev_direct && np <= kDirectMaxParents;
-			for (size_t i = 0; i < np && try_direct; ++i) try_direct = rp.parents[i].count >= c->direct_min_parent;
+			for (size_t i = 0; i < np && try_direct; ++i) try_direct = rp.parents[i].count >= c->opt.direct_min_parent;
 		}
 		// A workgroup of a direct round reads its pieces, not its stripe: up to one slot per bucket more than
 		// the stripe holds.  Its leftovers (< B per bucket + head/tail) must fit the stripe's leftover area,
@@ -1179,7 +1171,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			r.hist_checks = unverified && rp.round_keys == n;
 			if (r.hist_checks) {
 				if (int rc = vres_init()) return rc;
-				add_stat(c, "bit_skip_checked_by_histogram", 1);
+				add_stat(c, kStatBitSkipCheckedByHistogram, 1);
 			}
 			LAUNCH(c, (direct_hist_kernel<K>), ns, 1024, 0, keys, rb.stripes, rb.parents, rb.plans, r.hist_checks ? vres : nullptr);
 		}
@@ -1189,7 +1181,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		// runs) stays on the device: the direct kernel returns at once if it is non-zero, the streaming kernel
 		// launched behind it if it is zero.  The host learns it with the round's summary.
 		r.tried_direct = true;
-		const uint32_t force = c->direct_mode == 2 ? 1u : 0u;
+		const uint32_t force = c->opt.direct_mode == 2 ? 1u : 0u;
 		// (an array beyond the memory-side cache is streamed with the kernel's nontemporal policy: kStreamMinBytes)
 		const bool big = (uint64_t)n * (sizeof(K) + (HV ? sizeof(uint64_t) : 0)) >= kStreamMinBytes;
 		LAUNCH(c, (big ? classify_direct2_kernel<K, V, true> : classify_direct2_kernel<K, V, false>), ns, (Direct2Cfg<K, V>::TH), (Direct2Lds<K, V>::bytes), keys,
@@ -1203,7 +1195,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	int classify(Round &r)
 	{
 		if (int rc = classify_direct(r)) return rc;
-		if (!r.tried_direct || c->direct_mode != 2) {
+		if (!r.tried_direct || c->opt.direct_mode != 2) {
 			const RoundBufs &rb = r.rb;
 			const uint32_t *run_if = r.tried_direct ? &ctr->direct_uneven : nullptr;
 			if (job.splitters)
@@ -1223,11 +1215,11 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		const RoundBufs &rb = r.rb;
 		const uint32_t np = r.np, ns = r.ns, nc = r.nc;
 		const uint8_t *full_map = r.tried_direct ? slot_full : nullptr;
-		const uint32_t force_map = c->direct_mode == 2 ? 1u : 0u;
+		const uint32_t force_map = c->opt.direct_mode == 2 ? 1u : 0u;
 		if (const uint32_t groups = child_scan_groups(r.rp); groups > 1) {
 			LAUNCH(c, child_scan_part_kernel, dim3(np, groups), 256, 0, rb.parents, rb.fb, rb.lo_cnt, rb.scan_part);
 			LAUNCH(c, (child_scan_split_kernel<B>), dim3(np, groups), 256, 0, rb.parents, rb.lo_cnt, rb.scan_part, rb.lo_dst, rb.ca);
-			add_stat(c, "child_scan_split_rounds", 1);
+			add_stat(c, kStatChildScanSplitRounds, 1);
 		} else
 			LAUNCH(c, (child_scan_kernel<B>), np, 1024, 0, rb.parents, rb.fb, rb.lo_cnt, rb.lo_dst, rb.ca);
 		// every child's start and count are final: the children go to the next round or the leaf lists now, so that the
@@ -1263,7 +1255,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	{
 		uint64_t leaf_max = small_max;
 		if constexpr (sizeof(K) == 8)
-			if (c->regpart) leaf_max = std::max<uint64_t>(leaf_max, kRpCap - 1);
+			if (c->opt.regpart) leaf_max = std::max<uint64_t>(leaf_max, kRpCap - 1);
 		for (const Parent &p : r.rp.parents)
 			if ((p.count >> p.width) > leaf_max) return true;
 		return false;
@@ -1294,11 +1286,11 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		// A keys-only round in which no parent leaves more open bits than one counting pass takes has no next parents
 		// (route_child; a full big list or a child of 2^32 keys would make one: the early counters show it).  Not behind an
 		// unconfirmed leading-bit skip: no leaf may run before the check.
-		bool leaves_follow = !HV && !sp && !unverified && c->early_leaves;
+		bool leaves_follow = !HV && !sp && !unverified && c->opt.early_leaves;
 		for (size_t i = 0; i < r.np && leaves_follow; ++i) leaves_follow = r.rp.parents[i].shift <= count_bits;
 		if (leaves_follow)
 			r.end = Round::kLeavesFollow;
-		else if (c->early_plan && !sp && !r.hist_checks && !parked.open && c->pinned_bytes >= offsetof(Staging, stage2) && may_leave_parents(r)) {
+		else if (c->opt.early_plan && !sp && !r.hist_checks && !parked.open && c->pinned_bytes >= offsetof(Staging, stage2) && may_leave_parents(r)) {
 			// a round that may leave parents (one that carries the check behind a sampled bit skip decides about a restart
 			// first; one parked round at a time): the counters and the first next parents travel early, so that the host can
 			// plan the next round while this one's fix-up runs
@@ -1362,22 +1354,22 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	}
 	void round_stats(const Counters &hc, uint32_t np, uint32_t ns, uint32_t nc, uint64_t nslots)
 	{
-		add_stat(c, "rounds", 1);
-		add_stat(c, "parents", np);
-		add_stat(c, "stripes", ns);
-		add_stat(c, "children", nc);
-		add_stat(c, "slots", nslots);
-		add_stat(c, "holes", hc.nholes);
-		set_stat(c, "chain_steps", hc.chain_steps);
-		set_stat(c, "excess_blocks", hc.nexcess);
+		add_stat(c, kStatRounds, 1);
+		add_stat(c, kStatParents, np);
+		add_stat(c, kStatStripes, ns);
+		add_stat(c, kStatChildren, nc);
+		add_stat(c, kStatSlots, nslots);
+		add_stat(c, kStatHoles, hc.nholes);
+		set_stat(c, kStatChainSteps, hc.chain_steps);
+		set_stat(c, kStatExcessBlocks, hc.nexcess);
 	}
 
 	// ---- a round's counters have reached the host, early or with its summary: whether it placed directly, and the leaf lists'
 	// lengths (regpart_round: a round that tries no direct placement); next_round closes the round on the host
 	void adopt(const Counters &hc, bool tried_direct)
 	{
-		prev_direct = tried_direct && (hc.direct_uneven == 0 || c->direct_mode == 2);
-		if (prev_direct) add_stat(c, "direct_rounds", 1);
+		prev_direct = tried_direct && (hc.direct_uneven == 0 || c->opt.direct_mode == 2);
+		if (prev_direct) add_stat(c, kStatDirectRounds, 1);
 		nsmall_host = hc.nsmall, ncount_host = hc.ncount, nbig_host = hc.nbig;
 	}
 	void next_round() { phase_mark(c, "readback"), ++round; }
@@ -1395,7 +1387,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		sort_by_start(next);
 		// ... if its next parents take a register-resident pass or stay on the device (rounds(), round_summary),
 		if constexpr (sizeof(K) == 8)
-			if (c->regpart && register_pass((size_t)std::count_if(next.begin(), next.end(), register_parent), next.size())) return MSD_OK;
+			if (c->opt.regpart && register_pass((size_t)std::count_if(next.begin(), next.end(), register_parent), next.size())) return MSD_OK;
 		{ // ... or if a buffer of the next round would have to grow (that synchronises)
 			RoundPlan rp;
 			RoundBufs rb;
@@ -1409,7 +1401,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		adopt(hc, r.tried_direct);
 		defer(parked, r);
 		enqueue_ahead = true;
-		add_stat(c, "rounds_planned_early", 1);
+		add_stat(c, kStatRoundsPlannedEarly, 1);
 		cur = std::move(next);
 		next_round();
 		ended = true;
@@ -1426,7 +1418,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if (hc.next_parents || hc.ncount == 0 || hc.errors) return MSD_OK;
 		adopt(hc, r.tried_direct);
 		defer(pending, r);
-		add_stat(c, "leaves_behind_round", 1);
+		add_stat(c, kStatLeavesBehindRound, 1);
 		cur.clear();
 		next_round();
 		ended = true;
@@ -1462,7 +1454,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 		if constexpr (sizeof(K) == 8) {
 			// every next parent fits a workgroup's registers, and they are enough for a pass (rounds()): the list stays on the
 			// device and is planned there
-			if (c->regpart && hc.next_parents >= kRegPassMin && fits_registers(hc.next_max)) {
+			if (c->opt.regpart && hc.next_parents >= kRegPassMin && fits_registers(hc.next_max)) {
 				HIPCHK(c, hipMemcpyAsync(dev_list, r.rb.next_parents, (size_t)hc.next_parents * sizeof(Segment), hipMemcpyDeviceToDevice, c->stream));
 				dev_np = hc.next_parents;
 				stays_on_device = true;
@@ -1495,8 +1487,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 	{
 		const uint64_t vary = exact_vary & low_mask;
 		const int top = vary ? 64 - __builtin_clzll(vary) : 0;
-		set_stat(c, "skipped_bits", (uint64_t)(end_bit - top));
-		add_stat(c, "bit_skip_restarts", 1);
+		set_stat(c, kStatSkippedBits, (uint64_t)(end_bit - top));
+		add_stat(c, kStatBitSkipRestarts, 1);
 		cur.clear();
 		if (top > 0 && (uint32_t)top > job.stop_bits) cur.push_back({ 0, n, (uint32_t)top, 0 });
 		nsmall_host = ncount_host = nbig_host = dev_np = 0;
@@ -1514,15 +1506,19 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			if (!ncount_host || job.single_pass()) return MSD_OK;
 			// persistent workgroups (two per CU fit the LDS), segments handed out by ticket; what the fast
 			// kernel cannot place directly is queued (in the round slab, dead by now) for the walking kernel
-			int rc = slab_reserve(c, 3 * (size_t)ncount_host * sizeof(Segment) + 4096);
+			Segment *slow = nullptr, *rej16 = nullptr, *slow2 = nullptr;
+			int rc = slab_carve(c, [&](Bump &b) {
+				slow = b.take<Segment>(ncount_host);
+				rej16 = b.take<Segment>(ncount_host);
+				slow2 = b.take<Segment>(ncount_host);
+			});
 			if (rc) return rc;
-			Segment *slow = reinterpret_cast<Segment *>(c->slab), *rej16 = slow + ncount_host, *slow2 = rej16 + ncount_host;
 			const uint32_t count_grid = std::min<uint32_t>(ncount_host, (uint32_t)c->sm_count * 2);
 			// u32 keys with 16 open bits (what the planner aims for): the specialised kernel first, the general one
 			// takes what that leaves (other bit counts, long or crowded segments)
 			// (it pays for segments of about 2^14 keys -- 2^30-key inputs; on shorter ones the per-segment work on the
 			// 2^16 counters dominates and 1024-thread workgroups hide its latency better: 1.15 vs 1.44 ms at 2^28)
-			const bool c16 = sizeof(K) == 4 && (c->count16 == 2 || (c->count16 == 1 && n / ncount_host >= 12000));
+			const bool c16 = sizeof(K) == 4 && (c->opt.count16 == 2 || (c->opt.count16 == 1 && n / ncount_host >= 12000));
 			if constexpr (sizeof(K) == 4)
 				if (c16) LAUNCH(c, ((uint64_t)n * sizeof(K) >= kStreamMinBytes ? count_place16_kernel<true> : count_place16_kernel<false>), count_grid, kC16Th, kC16Lds, keys, small_count(), ncount_host, rej16, ctr, n);
 			LAUNCH(c, (count_place_kernel<K>), count_grid, kCountTh, kCountLds, keys, c16 ? rej16 : small_count(), c16 ? 0u : ncount_host,
@@ -1534,7 +1530,7 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 				// inputs), crowded ones -- takes the 16-bit-counter leaf (msd_merge16.hpp, list mode: one workgroup per
 				// segment, all of it counted before the first key is written back, so the sort is in place); only what that
 				// does not take either (a key with >= 2^16 copies, a 256-value group with >= 2^16 keys) walks its counters.
-				if (c->mid_leaf) {
+				if (c->opt.mid_leaf) {
 					LAUNCH(c, (merge_count_kernel<true>), std::min<uint32_t>(ncount_host, (uint32_t)c->sm_count), kMcTh, kMcLds, keys, keys, nullptr,
 					       nullptr, nullptr, 0, 0, 0, 0, slow, &ctr->nslow, slow2, &ctr->nslow2, &ctr->count_ticket4, nullptr);
 					walk_n = &ctr->nslow2;
@@ -1548,8 +1544,8 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// (the last round's summary travels with the leaves' counters: early_summary)
 			if ((rc = read_counters(c, ctr, hc, { parked_piece() })) || (rc = settle(parked, hc)) || (rc = settle(pending, hc))) return rc;
 			if (hc.errors) return fail(c, MSD_EINTERNAL, "counting leaf: %u segments could not be queued", hc.errors);
-			set_stat(c, "count16_rejected", hc.nslow16);     // segments count_place16_kernel left to count_place_kernel
-			set_stat(c, "count_slow_segments", hc.nslow);     // segments the register-resident kernels left to the 16-bit-counter leaf / the walk
+			set_stat(c, kStatCount16Rejected, hc.nslow16);     // segments count_place16_kernel left to count_place_kernel
+			set_stat(c, kStatCountSlowSegments, hc.nslow);     // segments the register-resident kernels left to the 16-bit-counter leaf / the walk
 			nbig_host = hc.nbig;
 			nfallback_known = hc.nfallback;
 		}
@@ -1621,16 +1617,16 @@ template <typename K, typename V> struct SortRun : KeepBufs {
 			// u64 keys, segments of about 2^14 (what two 8-bit rounds leave of 2^30 keys): leaf17_kernel -- counters for up to
 			// 16 bits where the staging buffer will be, one lane per group of equal counted bits -- finishes a segment in 0.6
 			// of this leaf's time; what it leaves (segments shorter than 4096 keys, a group of more than 48) goes on to it.
-			if (c->leaf17 && nsmall_host && n / nsmall_host >= 8192) {
-				if (int rc = slab_reserve(c, (size_t)nsmall_host * sizeof(Segment) + 4096)) return rc;
-				Segment *d_rej = reinterpret_cast<Segment *>(c->slab);
+			if (c->opt.leaf17 && nsmall_host && n / nsmall_host >= 8192) {
+				Segment *d_rej = nullptr;
+				if (int rc = slab_carve(c, [&](Bump &b) { d_rej = b.take<Segment>(nsmall_host); })) return rc;
 				HIPCHK(c, hipMemsetAsync(&ctr->nslow2, 0, sizeof(uint32_t), c->stream));
 				HIPCHK(c, hipMemsetAsync(&ctr->l17_slow, 0, sizeof(uint32_t), c->stream));
 				LAUNCH(c, (leaf17_kernel<NoVal>), std::min<uint32_t>(nsmall_host, (uint32_t)c->sm_count), kL17Th, kL17Lds, keys, nullptr, small(), nsmall_host,
 				       d_rej, &ctr->nslow2, ctr, 4096);
 				LAUNCH(c, (leaf_count_sort_kernel<K, V>), leaf_grid(nsmall_host), C::SORT_TH, leaf_lds, keys, vals, d_rej, nsmall_host, small() + nsmall_host,
 				       ctr, &ctr->leaf_ticket[0], &ctr->nslow2);
-				add_stat(c, "leaf17_launches", 1);
+				add_stat(c, kStatLeaf17Launches, 1);
 				small_done = true;
 			}
 		}
@@ -1664,7 +1660,7 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 	if (end_bit < 0 || end_bit > (int)sizeof(K) * 8) return fail(c, MSD_EINVAL, "end_bit out of range");
 	if (n >= ((uint64_t)1 << 36)) return fail(c, MSD_EINVAL, "n too large for 32-bit block slots");
 	HIPCHK(c, hipSetDevice(c->device));
-	c->stats.clear();
+	c->stat_written = 0;
 	phase_begin(c);
 	SortRun<K, V> s(c, keys, vals, n, end_bit, job);
 	int rc = s.initial_segments();
@@ -1683,11 +1679,11 @@ static int sort_impl(msd_ctx *c, K *keys, uint64_t *vals, uint64_t n, int end_bi
 	if (!rc) rc = s.count_leaves();
 	if (!rc) rc = s.big_count_sort();
 	if (rc) return rc;
-	set_stat(c, "big_count_segments", s.nbig_host);
+	set_stat(c, kStatBigCountSegments, s.nbig_host);
 	if ((rc = s.lds_leaves())) return rc;
-	set_stat(c, "count_segments", s.ncount_host);
-	set_stat(c, "small_segments", s.nsmall_host);
-	set_stat(c, "workspace_bytes", c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment));
+	set_stat(c, kStatCountSegments, s.ncount_host);
+	set_stat(c, kStatSmallSegments, s.nsmall_host);
+	set_stat(c, kStatWorkspaceBytes, c->slab_bytes + c->keep_bytes + 4 * c->lists_cap * sizeof(Segment));
 	phase_end(c);
 	return MSD_OK;
 }
@@ -1833,16 +1829,18 @@ static int gather_impl(msd_ctx *c, K *dst, const K *src, const uint64_t *src_off
 		while (r + 1 < nreal && runs[r + 1].first_chunk <= ch) ++r;
 		coarse[i] = (uint32_t)r;
 	}
+	// (one block, the runs in front of the coarse index, so that one copy takes both to the device)
 	const size_t runs_bytes = align_up(runs.size() * sizeof(GatherRun), 256), bytes = runs_bytes + ncoarse * sizeof(uint32_t);
+	std::vector<char> block(bytes);
+	memcpy(block.data(), runs.data(), runs.size() * sizeof(GatherRun));
+	memcpy(block.data() + runs_bytes, coarse.data(), ncoarse * sizeof(uint32_t));
+	char *d_block = nullptr;
 	int rc = pinned_reserve(c, bytes);
-	if (!rc) rc = slab_reserve(c, bytes + 4096); // (between sorts nothing in the slab is live)
+	if (!rc) rc = slab_carve(c, [&](Bump &b) { d_block = b.take<char>(bytes); }); // (between sorts nothing in the slab is live)
+	if (!rc) rc = upload(c, { { d_block, block.data(), bytes } });
 	if (rc) return rc;
-	HIPCHK(c, hipStreamSynchronize(c->stream)); // the staging buffer may still be in flight
-	memcpy(c->pinned, runs.data(), runs.size() * sizeof(GatherRun));
-	memcpy((char *)c->pinned + runs_bytes, coarse.data(), ncoarse * sizeof(uint32_t));
-	GatherRun *d_runs = reinterpret_cast<GatherRun *>(c->slab);
-	const uint32_t *d_coarse = reinterpret_cast<const uint32_t *>(c->slab + runs_bytes);
-	HIPCHK(c, hipMemcpyAsync(d_runs, c->pinned, bytes, hipMemcpyHostToDevice, c->stream));
+	const GatherRun *d_runs = reinterpret_cast<const GatherRun *>(d_block);
+	const uint32_t *d_coarse = reinterpret_cast<const uint32_t *>(d_block + runs_bytes);
 	// (one workgroup per 8 KiB chunk, no loop: 4.3-4.5 TB/s; persistent workgroups with larger chunks: 3.6)
 	const unsigned grid = (unsigned)nchunks;
 	LAUNCH(c, (gather_runs_kernel<K>), grid, 256, 0, dst, src, d_runs, runs.size() - 1, nchunks, d_coarse);
@@ -1873,13 +1871,12 @@ int msd_create(msd_ctx **out, int device, void *stream)
 	if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->sm_count = prop.multiProcessorCount;
 	// A/B switches for benchmarks: the same knobs as msd_set_option, through the same range checks (an out-of-range
 	// value is reported and ignored)
-	for (const char *name : { "direct_mode", "regpart", "count16" }) {
-		const char *env = !strcmp(name, "direct_mode") ? "MSD_DIRECT" : !strcmp(name, "regpart") ? "MSD_REGPART" : "MSD_COUNT16";
-		const char *v = getenv(env);
+	for (const OptionEntry &e : kOptions) {
+		const char *v = e.env ? getenv(e.env) : nullptr;
 		if (!v) continue;
 		char *end = nullptr;
 		const long x = strtol(v, &end, 10);
-		if (end == v || *end || msd_set_option(c, name, x) != MSD_OK) fprintf(stderr, "msd_create: ignoring %s=%s\n", env, v);
+		if (end == v || *end || msd_set_option(c, e.name, x) != MSD_OK) fprintf(stderr, "msd_create: ignoring %s=%s\n", e.env, v);
 	}
 	const auto attrs = [c](auto k, auto v) { return set_lds_attrs<decltype(k), decltype(v)>(c); };
 	int rc = with_layout(4, 0, attrs);
@@ -1985,16 +1982,18 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	// (the leaf reads extents while other workgroups write finished buckets)
 	if (ranges_overlap(src, src_cap * sizeof(IN), dst, dst_cap * 4)) return fail(c, MSD_EINVAL, "merge_buckets: source and destination overlap");
 	HIPCHK(c, hipSetDevice(c->device));
-	c->stats.clear();
+	c->stat_written = 0;
 	phase_begin(c);
 	if (n_expected == 0) return MSD_OK;
-	Counters *ctr = nullptr;
-	uint32_t *status = nullptr, *cnt32 = nullptr;
+	struct Zeroed { // (cleared by one memset before the plan kernel)
+		Counters ctr;
+		alignas(256) uint32_t status[64]; // [0]: the counts do not add up (merge_plan_kernel)
+	} *zeroed = nullptr;
+	uint32_t *cnt32 = nullptr;
 	uint64_t *soff = nullptr, *doff = nullptr;
 	Segment *rej = nullptr;
 	int rc = slab_carve(c, [&](Bump &b) {
-		ctr = b.take<Counters>(1);
-		status = b.take<uint32_t>(64);
+		zeroed = b.take<Zeroed>(1);
 		cnt32 = b.take<uint32_t>((size_t)nsrc * nb);
 		soff = b.take<uint64_t>((size_t)nsrc * nb);
 		doff = b.take<uint64_t>((size_t)nb + 1);
@@ -2002,7 +2001,9 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	});
 	if (!rc) rc = pinned_reserve(c, 4096);
 	if (rc) return rc;
-	HIPCHK(c, hipMemsetAsync(ctr, 0, (char *)(status + 64) - (char *)ctr, c->stream));
+	Counters *ctr = &zeroed->ctr;
+	uint32_t *status = zeroed->status;
+	HIPCHK(c, hipMemsetAsync(zeroed, 0, sizeof *zeroed, c->stream));
 	MergeBase mb = {};
 	for (uint32_t x = 0; x < nsrc; ++x) mb.b[x] = src_base[x];
 	LAUNCH(c, merge_plan_kernel, nsrc + 1, 1024, 0, d_counts, mb, nsrc, nb, n_expected, cnt32, soff, doff, status);
@@ -2010,7 +2011,7 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	// ones (2^30 keys per rank: nsrc x 2^14 keys per bucket) merge_count_kernel
 	// (low halves: merge_count_kernel at every bucket size -- shorter buckets cost it more per key, the exchange it follows
 	// cost half)
-	const bool in_regs = !IN16 && !HIST && (c->merge_leaf == 1 || (c->merge_leaf == 0 && n_expected / nb <= 12000 && open_bits >= (int)kC16MinBits));
+	const bool in_regs = !IN16 && !HIST && (c->opt.merge_leaf == 1 || (c->opt.merge_leaf == 0 && n_expected / nb <= 12000 && open_bits >= (int)kC16MinBits));
 	if (in_regs) {
 		if constexpr (!IN16 && !HIST) { // (whole keys only)
 			const unsigned grid = (unsigned)std::min<uint64_t>(nb, (uint64_t)c->sm_count * 2);
@@ -2025,8 +2026,9 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 	phase_mark(c, "merge leaf");
 	// what the leaf did not take (rare: long or crowded buckets) lies unsorted at its place in dst: the general leaves finish it
 	Counters hc;
-	if ((rc = read_counters(c, ctr, hc, { { 1024, status, sizeof(uint32_t) } }))) return rc;
-	if (*(const uint32_t *)((char *)c->pinned + 1024)) return fail(c, MSD_EINVAL, "merge_buckets: the counts do not add up to the expected %llu keys (or a count exceeds 32 bits)", (unsigned long long)n_expected);
+	uint32_t bad_counts = 0;
+	if ((rc = read_counters(c, ctr, hc, { { sizeof(Counters), status, sizeof bad_counts, &bad_counts } }))) return rc;
+	if (bad_counts) return fail(c, MSD_EINVAL, "merge_buckets: the counts do not add up to the expected %llu keys (or a count exceeds 32 bits)", (unsigned long long)n_expected);
 	const uint32_t nrej = hc.nslow16;
 	phase_end(c);
 	if (nrej) {
@@ -2034,7 +2036,7 @@ static int merge_impl(msd_ctx *c, const IN *src, uint64_t src_cap, const uint64_
 		if ((rc = fetch(c, rej, nrej, segs))) return rc;
 		if ((rc = sort_impl<uint32_t, NoVal>(c, dst, nullptr, n_expected, 32, SortJob<uint32_t>::list(segs)))) return rc;
 	}
-	set_stat(c, "merge_rejected", nrej);
+	set_stat(c, kStatMergeRejected, nrej);
 	return MSD_OK;
 }
 
@@ -2147,9 +2149,8 @@ int msd_order_low16_scatter_u32(msd_ctx *c, const uint32_t *d_keys, uint64_t n, 
 	if (!aligned16(d_out)) return fail(c, MSD_EINVAL, "order_low16: buffers must be 16-byte aligned");
 	if (ranges_overlap(d_keys, n * 4, d_out, n * 2)) return fail(c, MSD_EINVAL, "order_low16: source and destination overlap");
 	HIPCHK(c, hipSetDevice(c->device));
-	Bump real(c->slab); // (as msd_order_low16_counts_u32 left it)
 	Low16Tables t;
-	t.carve(real);
+	slab_recarve(c, [&](Bump &b) { t.carve(b); }); // (as msd_order_low16_counts_u32 left it)
 	if (n) LAUNCH(c, scatter_low16_kernel, 256 * kS16Chunks, kS16Th, kS16Lds, d_keys, n, t.pb, t.base, d_out);
 	return MSD_OK;
 }
@@ -2286,19 +2287,22 @@ int msd_exclusive_scan_u64(msd_ctx *c, const uint64_t *in, uint64_t *out, uint64
 	HIPCHK(c, hipSetDevice(c->device));
 	if (n == 0) return MSD_OK;
 	const size_t ntiles = (n + kScanTile - 1) / kScanTile;
-	int rc = slab_reserve(c, ntiles * 8 + 4096);
+	uint32_t *ctr = nullptr; // [0] tile counter, [2] error flag
+	unsigned long long *state = nullptr;
+	int rc = slab_carve(c, [&](Bump &b) {
+		ctr = b.take<uint32_t>(64);
+		state = b.take<unsigned long long>(ntiles);
+	});
 	if (rc) return rc;
-	unsigned long long *state = (unsigned long long *)(c->slab + 256);
-	uint32_t *ctr = (uint32_t *)c->slab; // [0] tile counter, [2] error flag
-	HIPCHK(c, hipMemsetAsync(c->slab, 0, 256, c->stream));
+	HIPCHK(c, hipMemsetAsync(ctr, 0, 64 * sizeof(uint32_t), c->stream));
 	HIPCHK(c, hipMemsetAsync(state, 0, ntiles * 8, c->stream));
 	LAUNCH(c, scan_lookback_kernel, (unsigned)ntiles, kScanTh, 0, in, out, n, state, ctr, ctr + 2);
 	// the look-back gives up after a bounded number of polls and sets a flag: report it (one small readback)
 	rc = pinned_reserve(c, 64);
 	if (rc) return rc;
-	HIPCHK(c, hipMemcpyAsync(c->pinned, ctr + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	if (*(const uint32_t *)c->pinned) return fail(c, MSD_EINTERNAL, "exclusive scan: a tile's look-back timed out");
+	uint32_t timed_out = 0;
+	if ((rc = read_back(c, ctr + 2, &timed_out))) return rc;
+	if (timed_out) return fail(c, MSD_EINTERNAL, "exclusive scan: a tile's look-back timed out");
 	return MSD_OK;
 }
 
@@ -2375,7 +2379,7 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 			return fail(c, MSD_EINVAL, "the output must not overlap the input");
 	}
 	HIPCHK(c, hipSetDevice(c->device));
-	const uint64_t cap = c->select_cap;
+	const uint64_t cap = c->opt.select_cap;
 	const K flip = which == MSD_LARGEST ? (K)~(K)0 : (K)0;
 	// what the kernels do with a key (msd_select.hpp): plain keys have instances of their own
 	typedef typename std::conditional<EMIT == kSelRaw, SelPlain<K>, SelCoded<K>>::type HOW;
@@ -2398,7 +2402,7 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	E *cand = r.take<E>(cap);
 	uint64_t *cand_rids = HV ? r.take<uint64_t>(cap) : nullptr;
 
-	c->stats.clear();
+	c->stat_written = 0;
 	phase_begin(c);
 	HIPCHK(c, hipMemsetAsync(c->sel, 0, zero_bytes, c->stream));
 	const uint64_t nvec = n / Vec16<K>::N;
@@ -2421,9 +2425,8 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 	LAUNCH(c, (select_filter_kernel<K, V, TOPK, EMIT, HOW>), filter_grid, kSelTh, (size_t)(stage_cand + stage_below) * elem, keys, rids, n, how, st, out,
 	       out_rids, cand, cand_rids, stage_cand, stage_below);
 	phase_mark(c, "select_filter");
-	HIPCHK(c, hipMemcpyAsync(c->pinned, st, sizeof(SelectState), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const SelectState h = *(const SelectState *)c->pinned;
+	SelectState h;
+	if ((rc = read_back(c, st, &h))) return rc;
 	phase_end(c);
 	std::vector<std::pair<std::string, double>> phases = c->phase_us;
 	const uint64_t needed = h.rank + 1; // candidates that belong to the answer (top-k)
@@ -2468,15 +2471,15 @@ static int select_impl(msd_ctx *c, const K *keys, const uint64_t *rids, uint64_t
 			if ((rc = sort_impl<E, V>(c, cand, nullptr, h.bucket, open, SortJob<E>::whole()))) return rc;
 			phases_append(c, phases);
 		}
-		HIPCHK(c, hipMemcpyAsync(c->pinned, cand + (smallest ? h.rank : h.bucket - 1 - h.rank), sizeof(K), hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(c, hipStreamSynchronize(c->stream));
-		*value = codec.dec(*(const K *)c->pinned);
+		K found;
+		if ((rc = read_back(c, reinterpret_cast<const K *>(cand + (smallest ? h.rank : h.bucket - 1 - h.rank)), &found))) return rc;
+		*value = codec.dec(found);
 	}
 	c->phase_us = phases;
-	set_stat(c, "select_hist_passes", h.passes);
-	set_stat(c, "select_skipped_bits", h.skipped);
-	set_stat(c, "select_candidates", h.bucket);
-	set_stat(c, "select_below", TOPK ? h.below : 0);
+	set_stat(c, kStatSelectHistPasses, h.passes);
+	set_stat(c, kStatSelectSkippedBits, h.skipped);
+	set_stat(c, kStatSelectCandidates, h.bucket);
+	set_stat(c, kStatSelectBelow, TOPK ? h.below : 0);
 	return MSD_OK;
 }
 
@@ -2658,8 +2661,8 @@ static int rows_lanes(const msd_ctx *c, uint64_t rows, uint64_t row_len, uint64_
 		by_shape = 64;
 	else if (row_len < kRowsMidMaxLen || (rows > 2 * (uint64_t)c->sm_count && row_len * key_bytes <= (1u << 20)))
 		by_shape = 256;
-	if (c->topk_rows_lanes == 0 || (c->topk_rows_lanes == 64 && row_len > kRowsWaveMaxLen)) return by_shape; // (a wave's buffer holds its whole row)
-	return c->topk_rows_lanes;
+	if (c->opt.topk_rows_lanes == 0 || (c->opt.topk_rows_lanes == 64 && row_len > kRowsWaveMaxLen)) return by_shape; // (a wave's buffer holds its whole row)
+	return c->opt.topk_rows_lanes;
 }
 
 template <typename K>
@@ -2742,13 +2745,13 @@ int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 		return fail(c, MSD_EINVAL, "indices of a 32-bit key type need row_len <= 2^32 (the position travels in 32 bits)");
 	if (outputs_overlap(buf, 1)) return fail(c, MSD_EINVAL, "the outputs must not overlap the input or each other");
 	const bool inside = rows_in_envelope(row_len, k);
-	if (c->topk_rows_mode == 2 && !inside)
+	if (c->opt.topk_rows_mode == 2 && !inside)
 		return fail(c, MSD_EINVAL, "topk_rows_mode 2: the row kernel takes row_len <= %llu and k <= %u", (unsigned long long)kRowsMaxLen, kRowsMaxK);
-	const bool kernel = inside && (c->topk_rows_mode == 2 || (c->topk_rows_mode == 0 && rows_kernel_wins(rows, row_len)));
+	const bool kernel = inside && (c->opt.topk_rows_mode == 2 || (c->opt.topk_rows_mode == 0 && rows_kernel_wins(rows, row_len)));
 	HIPCHK(c, hipSetDevice(c->device));
 	int rc;
 	if (kernel) {
-		c->stats.clear();
+		c->stat_written = 0;
 		rc = with_key_type(key_type, [&](auto k0, auto) { // (the 4-byte / 8-byte choice only: the row kernel decodes every type)
 			typedef decltype(k0) K;
 			return rows_kernel_path<K>(c, (const K *)d_keys, key_type, rows, row_len, row_stride, k, which, (K *)d_out_keys, d_out_idx);
@@ -2756,8 +2759,8 @@ int msd_topk_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 	} else
 		rc = rows_looped_path(c, (const char *)d_keys, key_type, rows, row_len, row_stride, k, which, (char *)d_out_keys, d_out_idx);
 	if (rc) return rc;
-	set_stat(c, "topk_rows_kernel_rows", kernel ? rows : 0);
-	set_stat(c, "topk_rows_looped_rows", kernel ? 0 : rows);
+	set_stat(c, kStatTopkRowsKernelRows, kernel ? rows : 0);
+	set_stat(c, kStatTopkRowsLoopedRows, kernel ? 0 : rows);
 	return MSD_OK;
 }
 
@@ -2789,7 +2792,7 @@ template <typename K, bool IDX> static int sort_rows_lanes(const msd_ctx *c, uin
 {
 	constexpr uint64_t cap64 = sort_rows_cap<K, IDX, 64>(), cap256 = sort_rows_cap<K, IDX, 256>();
 	const int by_shape = row_len <= cap64 ? 64 : row_len <= cap256 ? 256 : 1024;
-	const int forced = c->sort_rows_lanes;
+	const int forced = c->opt.sort_rows_lanes;
 	if (forced == 0 || (forced == 64 && row_len > cap64) || (forced == 256 && row_len > cap256)) return by_shape;
 	return forced;
 }
@@ -2800,7 +2803,7 @@ static int sort_rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64
 	const K flip = order == MSD_DESCENDING ? (K)~(K)0 : (K)0;
 	const KeyCodec<K> codec = key_codec<K>(key_type);
 	const int lanes = sort_rows_lanes<K, IDX>(c, row_len);
-	c->stats.clear();
+	c->stat_written = 0;
 	phase_begin(c);
 	const int rc = with_lanes(lanes, [&](auto l) {
 		constexpr int LANES = decltype(l)::value;
@@ -2814,7 +2817,7 @@ static int sort_rows_kernel_path(msd_ctx *c, const K *keys, int key_type, uint64
 	if (rc) return rc;
 	phase_mark(c, "sort_rows");
 	phase_end(c);
-	set_stat(c, "sort_rows_lanes", (uint64_t)lanes);
+	set_stat(c, kStatSortRowsLanes, (uint64_t)lanes);
 	return MSD_OK;
 }
 
@@ -2852,7 +2855,7 @@ static int sort_rows_segments(msd_ctx *c, const K *keys, int key_type, uint64_t 
 		return MSD_OK;
 	});
 	if (rc) return rc;
-	set_stat(c, "sort_rows_lanes", 0);
+	set_stat(c, kStatSortRowsLanes, 0);
 	return MSD_OK;
 }
 
@@ -2885,11 +2888,11 @@ int msd_sort_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 		return fail(c, MSD_EINVAL, "the outputs must not overlap the input (but d_out_keys == d_keys with row_stride == row_len) or each other");
 	const uint64_t max_len = sort_rows_max_len((int)es, d_out_idx != nullptr);
 	const bool inside = row_len <= max_len;
-	if (c->sort_rows_mode == 2 && !inside)
+	if (c->opt.sort_rows_mode == 2 && !inside)
 		return fail(c, MSD_EINVAL, "sort_rows_mode 2: the row kernel takes row_len <= %llu for this key type", (unsigned long long)max_len);
 	// the segment path's own rules for the outputs and the sizes (a null d_out_idx is aligned)
 	const bool seg_aligned = aligned16(d_out_keys) && aligned16(d_out_idx), seg_fits = rows < ((uint64_t)1 << 32) && ext.out_elems < kMaxElems;
-	const bool kernel = inside && (c->sort_rows_mode == 2 || (c->sort_rows_mode == 0 && sort_rows_kernel_wins(es, d_out_idx != nullptr, row_len, seg_aligned && seg_fits)));
+	const bool kernel = inside && (c->opt.sort_rows_mode == 2 || (c->opt.sort_rows_mode == 0 && sort_rows_kernel_wins(es, d_out_idx != nullptr, row_len, seg_aligned && seg_fits)));
 	if (!kernel && !seg_aligned)
 		return fail(c, MSD_EINVAL, "rows beyond the row kernel (row_len > %llu, or sort_rows_mode 1) go through the segment sort, whose rule this is: "
 					   "d_out_keys and d_out_idx must be 16-byte aligned",
@@ -2906,8 +2909,8 @@ int msd_sort_rows(msd_ctx *c, const void *d_keys, int key_type, uint64_t rows, u
 		});
 	});
 	if (rc) return rc;
-	set_stat(c, "sort_rows_kernel_rows", kernel ? rows : 0);
-	set_stat(c, "sort_rows_segment_rows", kernel ? 0 : rows);
+	set_stat(c, kStatSortRowsKernelRows, kernel ? rows : 0);
+	set_stat(c, kStatSortRowsSegmentRows, kernel ? 0 : rows);
 	return MSD_OK;
 }
 
@@ -3322,7 +3325,7 @@ int msd_search_sorted(msd_ctx *c, const void *d_sorted, int key_type, uint64_t n
 	if (n >= kMaxElems || m >= kMaxElems) return fail(c, MSD_EINVAL, "n or m too large: fewer than 2^36 elements each");
 	if (m && outputs_overlap(buf, 3)) return fail(c, MSD_EINVAL, "d_out must not overlap d_sorted, d_needles or d_positions");
 	if (m == 0) return MSD_OK; // nothing to write
-	const bool merge = needles_sorted && c->search_mode != 1 && (c->search_mode == 2 || n / c->search_merge_ratio <= m);
+	const bool merge = needles_sorted && c->opt.search_mode != 1 && (c->opt.search_mode == 2 || n / c->opt.search_merge_ratio <= m);
 	HIPCHK(c, hipSetDevice(c->device));
 	return with_width((int)es, [&](auto k0) {
 		return with_flag(d_positions != nullptr, [&](auto pos) {
@@ -3575,21 +3578,20 @@ static int check_impl(msd_ctx *c, const K *k, const uint64_t *r, uint64_t n, uin
 {
 	if (!c) return MSD_EINVAL;
 	HIPCHK(c, hipSetDevice(c->device));
-	int rc = slab_reserve(c, 4096);
+	CheckResult *res = nullptr;
+	int rc = slab_carve(c, [&](Bump &b) { res = b.take<CheckResult>(1); });
 	if (!rc) rc = pinned_reserve(c, 4096);
 	if (rc) return rc;
-	CheckResult *res = (CheckResult *)c->slab;
 	HIPCHK(c, hipMemsetAsync(res, 0, sizeof *res, c->stream));
 	if (n) {
 		const unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)c->sm_count * 8, (n + 255) / 256);
 		LAUNCH(c, (check_kernel<K>), grid, 256, 0, k, r, n, res);
 	}
-	HIPCHK(c, hipMemcpyAsync(c->pinned, res, sizeof *res, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	const CheckResult *h = (const CheckResult *)c->pinned;
-	if (viol) *viol = h->violations;
-	if (sum) *sum = h->sum;
-	if (xr) *xr = h->xr;
+	CheckResult h;
+	if ((rc = read_back(c, res, &h))) return rc;
+	if (viol) *viol = h.violations;
+	if (sum) *sum = h.sum;
+	if (xr) *xr = h.xr;
 	return MSD_OK;
 }
 extern "C" {
@@ -3694,60 +3696,9 @@ int msd_plan_first_round(uint64_t n, int key_bytes, int val_bytes, int end_bit, 
 int msd_set_option(msd_ctx *c, const char *name, int64_t value)
 {
 	if (!c || !name) return MSD_EINVAL;
-	if (!strcmp(name, "direct_mode")) {
-		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "direct_mode must be 0, 1 or 2");
-		c->direct_mode = (int)value;
-	} else if (!strcmp(name, "direct_min")) {
-		if (value < 1) return fail(c, MSD_EINVAL, "direct_min must be positive");
-		c->direct_min = (uint64_t)value;
-	} else if (!strcmp(name, "regpart")) {
-		c->regpart = value != 0;
-	} else if (!strcmp(name, "count16")) {
-		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "count16 must be 0, 1 or 2");
-		c->count16 = (int)value;
-	} else if (!strcmp(name, "leaf17")) {
-		c->leaf17 = value != 0;
-	} else if (!strcmp(name, "mid_leaf")) {
-		c->mid_leaf = value != 0;
-	} else if (!strcmp(name, "early_leaves")) {
-		c->early_leaves = value != 0;
-	} else if (!strcmp(name, "early_plan")) {
-		c->early_plan = value != 0;
-	} else if (!strcmp(name, "front_count")) {
-		c->front_count = value != 0;
-	} else if (!strcmp(name, "front_min")) {
-		if (value < 1) return fail(c, MSD_EINVAL, "front_min must be positive");
-		c->front_min = (uint64_t)value;
-	} else if (!strcmp(name, "merge_leaf")) {
-		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "merge_leaf must be 0, 1 or 2");
-		c->merge_leaf = (int)value;
-	} else if (!strcmp(name, "select_cap")) {
-		if (value < 1 || value > ((int64_t)1 << 28)) return fail(c, MSD_EINVAL, "select_cap must be 1 .. 2^28 elements");
-		c->select_cap = (uint64_t)value;
-	} else if (!strcmp(name, "topk_rows_mode")) {
-		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "topk_rows_mode must be 0, 1 or 2");
-		c->topk_rows_mode = (int)value;
-	} else if (!strcmp(name, "topk_rows_lanes")) {
-		if (value != 0 && value != 64 && value != 256 && value != 1024) return fail(c, MSD_EINVAL, "topk_rows_lanes must be 0, 64, 256 or 1024");
-		c->topk_rows_lanes = (int)value;
-	} else if (!strcmp(name, "sort_rows_mode")) {
-		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "sort_rows_mode must be 0, 1 or 2");
-		c->sort_rows_mode = (int)value;
-	} else if (!strcmp(name, "sort_rows_lanes")) {
-		if (value != 0 && value != 64 && value != 256 && value != 1024) return fail(c, MSD_EINVAL, "sort_rows_lanes must be 0, 64, 256 or 1024");
-		c->sort_rows_lanes = (int)value;
-	} else if (!strcmp(name, "search_mode")) {
-		if (value < 0 || value > 2) return fail(c, MSD_EINVAL, "search_mode must be 0, 1 or 2");
-		c->search_mode = (int)value;
-	} else if (!strcmp(name, "search_merge_ratio")) {
-		if (value < 1) return fail(c, MSD_EINVAL, "search_merge_ratio must be at least 1");
-		c->search_merge_ratio = (uint64_t)value;
-	} else if (!strcmp(name, "direct_min_parent")) {
-		if (value < 1) return fail(c, MSD_EINVAL, "direct_min_parent must be positive");
-		c->direct_min_parent = (uint64_t)value;
-	} else
-		return fail(c, MSD_EINVAL, "unknown option %s", name);
-	return MSD_OK;
+	const char *refusal = nullptr;
+	if (options_set(c->opt, name, value, &refusal)) return MSD_OK;
+	return refusal ? fail(c, MSD_EINVAL, "%s", refusal) : fail(c, MSD_EINVAL, "unknown option %s", name);
 }
 
 #ifdef MSD_STAMPS
@@ -3776,7 +3727,8 @@ int msd_stat(const msd_ctx *c, const char *name, uint64_t *v)
 {
 	if (!c || !name || !v) return MSD_EINVAL;
 	// the typed sort's two counters live in device words: these two names wait for the context's stream
-	const int fix_word = !strcmp(name, "sort_keys_split") ? kFixSplit : !strcmp(name, "sort_keys_reversed") ? kFixReversed : -1;
+	const int slot = stat_by_name(name);
+	const int fix_word = slot == kStatSortKeysSplit ? kFixSplit : slot == kStatSortKeysReversed ? kFixReversed : -1;
 	if (fix_word >= 0) {
 		if (c->fix_stats == 0) return MSD_EINVAL;
 		*v = fix_word == kFixSplit ? c->fix_split : 0;
@@ -3786,12 +3738,9 @@ int msd_stat(const msd_ctx *c, const char *name, uint64_t *v)
 			return MSD_EHIP;
 		return MSD_OK;
 	}
-	for (auto &s : c->stats)
-		if (s.first == name) {
-			*v = s.second;
-			return MSD_OK;
-		}
-	return MSD_EINVAL;
+	if (slot == kStatCount || !(c->stat_written >> slot & 1)) return MSD_EINVAL;
+	*v = c->stat[slot];
+	return MSD_OK;
 }
 
 } // extern "C"

@@ -10,8 +10,8 @@ import sort_rows_expect as E
 
 TAIL = 64                           # elements of every output buffer behind the ones that a call may write
 _INT = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
-# Every name msd_set_option takes, with the initialiser of the same-named member of struct msd_ctx (csrc/msd_radix.hip;
-# tests/test_option_defaults.py reads both from the source and compares).  Whoever changes an option on the session's
+# Every name msd_set_option takes, with its default: the table MSD_OPTIONS of csrc/msd_options.hpp restated
+# (tests/test_option_defaults.py has tests/options_main.cpp print that table and compares).  Whoever changes an option on the session's
 # context restores DEFAULTS[name], never a literal: the next file is to meet the library as it ships.
 DEFAULTS = {
     "direct_mode": 1, "direct_min": 1 << 22, "direct_min_parent": 1 << 17, "regpart": 1, "count16": 1, "leaf17": 1, "mid_leaf": 1,

@@ -1,6 +1,9 @@
 """Every kernel variant a tuning knob selects gives the oracle's result: the specialised 16-bit counting leaf
 (count16 = 0 / 1 / 2), the register-resident partition round (regpart = 0 / 1), direct placement on and off --
-so that A/B switches used for measurements cannot hide a wrong path."""
+so that A/B switches used for measurements cannot hide a wrong path.  And the context's tables (csrc/msd_options.hpp) against
+what the library did before it had them: what msd_set_option takes and says (tests/golden/option_outcomes.json) and the
+counters of ten calls (tests/golden/stats_by_call.json), both recorded with that earlier library."""
+import json
 import os
 import sys
 
@@ -10,7 +13,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle as O  # noqa: E402
-from gpu_support import dev_bits as dev, host_bits as host
+from gpu_support import DEFAULTS, dev_bits as dev, host_bits as host
+import stats_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -167,3 +171,38 @@ def test_last_error_of_the_reference_api_is_empty_after_a_good_sort():
     L = _lib.load()
     L.msb_64_last_error.restype = C.c_char_p
     assert L.msb_64_last_error() == b"" and (keys[0] == np.sort(k)).all() and size == [n]
+
+
+def _golden(name):
+    with open(os.path.join(ROOT, "tests", "golden", name)) as f:
+        return json.load(f)
+
+
+def test_options_refuse_and_accept_as_recorded():
+    """Every option with every probe value, and an unknown name: the return code and the text of msd_last_error are the
+    recorded ones.  (On a context of its own, closed afterwards: the session's context keeps its defaults.)"""
+    want = _golden("option_outcomes.json")
+    assert sorted({w[0] for w in want} - {stats_cases.UNKNOWN_OPTION}) == sorted(DEFAULTS)
+    assert len(want) == len(DEFAULTS) * len(stats_cases.PROBES) + 1
+    got = stats_cases.option_outcomes(sorted(DEFAULTS))
+    assert [g for g, w in zip(got, want) if g != w] == [] and len(got) == len(want)
+
+
+# the counters that are functions of the input and the plan: none of them may be excused as depending on the order of atomics
+_EXACT = {"rounds", "parents", "stripes", "children", "slots", "small_segments", "count_segments", "big_count_segments", "direct_rounds",
+          "regpart_rounds", "skipped_bits", "workspace_bytes"}
+
+
+@pytest.mark.parametrize("case", sorted(stats_cases.CASES))
+def test_stats_are_the_recorded_numbers_under_the_recorded_names(case):
+    """stats() after the call, on a fresh context: the same names as recorded, and the same values except for the names
+    that differed between two recordings with the earlier library (they depend on the order of atomics)."""
+    golden = _golden("stats_by_call.json")
+    loose = set(golden["order_dependent"])
+    assert loose <= {"holes", "chain_steps", "excess_blocks"}
+    assert not any(n in _EXACT or n.startswith(("select_", "sort_keys_")) or "_rows" in n for n in loose)
+    assert sorted(golden["cases"]) == sorted(stats_cases.CASES)
+    want, got = golden["cases"][case], stats_cases.stats_after(case)
+    print(case, got)
+    assert sorted(got) == sorted(want)
+    assert {n: (got[n], v) for n, v in want.items() if n not in loose and got[n] != v} == {}
