@@ -51,14 +51,15 @@ constexpr uint32_t kC16CwWords = kC16Words + (kC16Words >> 6) * 4; // with 4 wor
 static_assert(kC16CwWords == kC16Cap, "counters and output buffer share one LDS area");
 // [counters | output buffer][per-thread bases][junk words: 64 counters + 64 keys][wave totals, flags]
 constexpr size_t kC16Lds = (size_t)kC16Cap * 4 + kC16Th * 4 + 128 * 4 + 128;
-__device__ __forceinline__ uint32_t c16_at(uint32_t w) { return w + ((w >> 6) << 2); }
 
 template <bool BIG> // BIG: the array exceeds the memory-side cache, MSD_C16_NT applies (kStreamMinBytes, msd_device.hpp)
 __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place16_kernel(uint32_t *__restrict__ keys,
 	const Segment *__restrict__ segs, uint32_t nsegs, Segment *__restrict__ rejected, Counters *__restrict__ ctr,
 	uint64_t n_total)
 {
-	constexpr int TH = kC16Th, NV = kC16Vec, NT = kC16Tail, NK = NV * 4 + NT;
+	using Tile = RegTile<kC16Th, kC16Vec, kC16Tail>; // the segment on the array's 16-byte grid
+	constexpr int TH = kC16Th, NV = kC16Vec, NK = Tile::NK;
+	static_assert(Tile::CAP == kC16Cap, "the output buffer holds the tile");
 	constexpr int CH = TH >= 1024 ? 4 : 8; // fetch-adds / look-ups in flight per thread (register budget: 64 or 128 VGPRs)
 	constexpr bool NTL = BIG && kC16NtLoad, NTS = BIG && kC16NtStore;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -78,25 +79,9 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 	const uint32_t ntake = nsegs > 64u * gridDim.x ? 2u : 1u;
 	if (tid == 0) {
 		wtot[13] = 0;
-		if (kEarlyTicket) {
-			wtot[12] = atomicAdd(&ctr->count_ticket3, ntake) + gridDim.x;
-			wtot[13] = ntake;
-		}
+		if (kEarlyTicket) bc_tickets_in(wtot, atomicAdd(&ctr->count_ticket3, ntake) + gridDim.x, ntake);
 	}
-	// segment descriptors are the same in every lane: keep them in scalar registers (loaded through vector
-	// memory or LDS they would make every address a per-lane 64-bit computation)
-	auto uniform = [](Segment g) -> Segment {
-		Segment u;
-		// (the builtin returns a signed int: without the cast to uint32_t a low word >= 2^31 sign-extends into the high
-		// word -- element offsets that large exist only in arrays of more than 2^31 keys.  THIS was round 2's GPU fault
-		// at 2^32 keys: `keys + start` pointed 16 GiB below the array and the segment's first 16-byte load faulted.)
-		auto rfl = [](uint32_t x) -> uint64_t { return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(x); };
-		u.start = rfl((uint32_t)g.start) | (rfl((uint32_t)(g.start >> 32)) << 32);
-		u.count = rfl((uint32_t)g.count) | (rfl((uint32_t)(g.count >> 32)) << 32);
-		u.bits = (uint32_t)rfl(g.bits);
-		u.pad = 0;
-		return u;
-	};
+	// (segment descriptors are the same in every lane: kept in scalar registers)
 	Segment sg = uniform(segs[blockIdx.x]);
 
 	// TWO register sets of one register per key: the key (prefetched) -> value | rank << 16 -> value | place << 16 -> dead.
@@ -104,11 +89,9 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 	// receives the next segment's keys (requested as soon as the 32 counter registers are dead); the loop body exists
 	// twice with the sets' roles swapped, so no register is copied and no wait sits between the two segments.
 	uint32_t rka[NK], rkb[NK];
-	// the segment's elements on the 16-byte grid: vector v of thread t = grid elements (v * TH + t) * 4 .. + 3,
-	// tail element s of thread t = grid element NV * TH * 4 + s * TH + t.  Branch-free and unconditional (a register
-	// set written on only some paths becomes a loop-carried value and spills): lanes beyond the segment re-read its
-	// last vector / element; of a segment this kernel will not take, and when there is no next segment (!live), only
-	// the first vector is read.  Addresses come from an opaque copy of the thread index (not hoisted out of the loop).
+	// the segment's elements on the 16-byte grid (Tile::load).  Of a segment this kernel will not take, and when there
+	// is no next segment (!live), only the first vector is read.  Addresses come from an opaque copy of the thread index
+	// (not hoisted out of the loop).
 	auto prefetch = [&](uint32_t (&rk)[NK], const Segment &g, bool live) __attribute__((always_inline)) {
 		uint32_t tp = tid;
 		asm volatile("" : "+v"(tp));
@@ -119,30 +102,14 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		// the array's last segment may extend up to 12 bytes behind the allocation -- such a segment is not taken, n_total
 		// is the array's length)
 		const bool take = live && g.bits >= kC16MinBits && g.bits <= 16 && tot <= (uint64_t)kC16Cap && ((g.start - off + tot + 3) & ~3ull) <= n_total;
-		const uint32_t totc = take ? (uint32_t)tot : 1u;
-		const uint32_t lastv = (totc - 1u) >> 2;
-#pragma unroll
-		for (int v = 0; v < NV; ++v) {
-			const u32x4 q = ld16<NTL>(base + min((uint32_t)(v * TH) + tp, lastv) * 4u);
-			rk[v * 4 + 0] = q.x; rk[v * 4 + 1] = q.y; rk[v * 4 + 2] = q.z; rk[v * 4 + 3] = q.w;
-		}
-#pragma unroll
-		for (int s = 0; s < NT; ++s) {
-			const uint32_t *e = base + min((uint32_t)(NV * TH * 4 + s * TH) + tp, totc - 1u);
-			if constexpr (NTL) rk[NV * 4 + s] = __builtin_nontemporal_load(e);
-			else rk[NV * 4 + s] = *e;
-		}
+		Tile::load<NTL>(rk, base, take ? (uint32_t)tot : 1u, tp);
 	};
 	// the whole counter / output area to zero (16-byte stores): before the first segment and behind a rejected one;
 	// behind a sorted segment the store phase leaves the area cleared
 	auto clear_all = [&]() __attribute__((always_inline)) {
 		uint32_t zero = 0, tc = tid;
 		asm volatile("" : "+v"(zero), "+v"(tc));
-#pragma unroll
-		for (uint32_t j = 0; j < (kC16Cap / 4 + TH - 1) / TH; ++j) {
-			const uint32_t q = j * TH + tc;
-			if (q < kC16Cap / 4) reinterpret_cast<u32x4 *>(cw)[q] = u32x4{ zero, zero, zero, zero };
-		}
+		bc_clear<TH, kC16Cap>(cw, zero, tc);
 	};
 	prefetch(rka, sg, true);
 	clear_all();
@@ -165,13 +132,8 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		asm volatile("" : "+v"(zero), "+v"(tq));
 		// (the counters are clear: the store phase of the segment before, or clear_all, left them so)
 		if (tid == 0) {
-			if (!kEarlyTicket && wtot[13] == 0) {
-				wtot[12] = atomicAdd(&ctr->count_ticket3, ntake) + gridDim.x;
-				wtot[13] = ntake;
-			}
-			*nexti = wtot[12]; // (a ticket is in hand: drawn before the loop or during the segment before)
-			wtot[12] += 1;
-			wtot[13] -= 1;
+			if (!kEarlyTicket && wtot[13] == 0) bc_tickets_in(wtot, atomicAdd(&ctr->count_ticket3, ntake) + gridDim.x, ntake);
+			bc_ticket_next(wtot, nexti); // (a ticket is in hand: drawn before the loop or during the segment before)
 			*crowded = 0;
 			const uint32_t k0 = off == 0 ? rk[0] : off == 1 ? rk[1] : off == 2 ? rk[2] : rk[3]; // first key
 			*hi_l = k0 & ~((1u << sg.bits) - 1u); // common prefix of the whole segment
@@ -189,7 +151,7 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 				for (int i = 0; i < CH; ++i) {
 					const int u = u0 + i;
 					if (u < NK) {
-						const uint32_t el = u < NV * 4 ? (uint32_t)((u / 4) * TH * 4) + tid * 4 + (u % 4) : (uint32_t)(NV * TH * 4 + (u - NV * 4) * TH) + tid;
+						const uint32_t el = Tile::elem(u, tid);
 						const uint32_t val = (rk[u] << vsh) & 0xFFFFu; // (fewer than 16 open bits: spread over the counters, order kept)
 						const bool in = el >= off && el < tot;
 						const uint32_t a = in ? c16_at(val >> 2) : (uint32_t)(junkc - cw) + lane; // word index from cw
@@ -208,7 +170,7 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		MSD_STAMP(2); // fetch-adds (incl. the wait for the keys)
 		__syncthreads();
 		MSD_STAMP(3);
-		const uint32_t nxt = (uint32_t)__builtin_amdgcn_readfirstlane(*nexti), hi = (uint32_t)__builtin_amdgcn_readfirstlane(*hi_l);
+		const uint32_t nxt = uniform_u32(*nexti), hi = uniform_u32(*hi_l);
 		const bool more = nxt < nsegs;
 		// the next segment's descriptor travels during the counter phases (loaded where its keys are prefetched,
 		// its whole memory latency would sit in front of that prefetch)
@@ -224,42 +186,18 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		u32x4 *cq = reinterpret_cast<u32x4 *>(cw + c16_at(tid * (uint32_t)WPT)); // (16-byte aligned)
 		uint32_t cr[WPT];
 		uint32_t totk = 0;
-		if (fits) {
-#pragma unroll
-			for (int j = 0; j < WPT / 4; ++j) {
-				const u32x4 q = cq[j];
-				cr[4 * j + 0] = q.x; cr[4 * j + 1] = q.y; cr[4 * j + 2] = q.z; cr[4 * j + 3] = q.w;
-			}
-#pragma unroll
-			for (int j = 0; j < WPT; ++j) totk = __builtin_amdgcn_sad_u8(cr[j], 0u, totk);
-		}
+		if (fits) totk = bc_sums<WPT, 1>(cq, cr, totk);
 		if (totk > 255u) *crowded = 1; // (a byte prefix would not fit)
-		const uint32_t inc = wave_incl_scan(totk);
-		if ((tq & 63u) == 63u) wtot[tq >> 6] = inc;
+		const uint32_t inc = wg_scan_publish(totk, wtot, tq);
 		MSD_STAMP(4); // counters read + byte sums + wave scan
 		__syncthreads();
-		uint32_t pos = inc - totk, all = 0;
-#pragma unroll
-		for (uint32_t ww = 0; ww < TH / 64; ++ww) {
-			const uint32_t t = wtot[ww];
-			if (ww < w) pos += t;
-			all += t;
-		}
+		const WgScan sc = wg_scan_collect<TH>(wtot, w, inc - totk);
+		const uint32_t pos = sc.pos, all = sc.all;
 		// a byte that overflowed carried into its neighbour: the sum of all bytes then falls short of n
 		const bool ok = fits && all == n && *crowded == 0;
 		MSD_STAMP(5);
 		if (ok) {
-			uint32_t run = 0;
-#pragma unroll
-			for (int j = 0; j < WPT / 4; ++j) {
-#pragma unroll
-				for (int e = 0; e < 4; ++e) {
-					const uint32_t x = cr[4 * j + e], y = x * 0x01010101u; // bytes of y: inclusive sums inside the word
-					cr[4 * j + e] = (y - x) + run * 0x01010101u;
-					run += y >> 24;
-				}
-				cq[j] = u32x4{ cr[4 * j + 0], cr[4 * j + 1], cr[4 * j + 2], cr[4 * j + 3] };
-			}
+			bc_prefixes<WPT, 1>(cq, cr);
 			tbase[tid] = pos + off; // (output positions are on the array's 16-byte grid)
 		} else if (tid == 0)
 			rejected[atomicAdd(&ctr->nslow16, 1u)] = sg; // untouched
@@ -271,36 +209,12 @@ __global__ __launch_bounds__(kC16Th, (kC16Th >= 1024 ? 8 : 4)) void count_place1
 		const Segment nsg = uniform(nraw);
 		prefetch(rn, nsg, more);
 		__builtin_amdgcn_sched_barrier(0);
-		if (refill) {
-			wtot[12] = drawn + gridDim.x;
-			wtot[13] = ntake;
-		}
+		if (refill) bc_tickets_in(wtot, drawn + gridDim.x, ntake);
 		if (ok) {
 			MSD_STAMP(6); // byte prefixes, prefetch issue
 			__syncthreads();
 			// ---- place of every key: base[owner of its value] + prefix[value] + rank
-			// (the place, < 2^15, replaces the rank in bits 16..30)
-#pragma unroll
-			for (int u0 = 0; u0 < NK; u0 += CH) {
-				uint32_t tb[CH], cv[CH];
-#pragma unroll
-				for (int i = 0; i < CH; ++i) {
-					if (u0 + i < NK) {
-						const uint32_t wi = (rk[u0 + i] & 0xFFFFu) >> 2;
-						tb[i] = tbase[wi / (uint32_t)WPT];
-						cv[i] = cw[c16_at(wi)];
-					}
-				}
-#pragma unroll
-				for (int i = 0; i < CH; ++i) {
-					if (u0 + i < NK) {
-						const uint32_t r = rk[u0 + i];
-						const uint32_t pl = tb[i] + ((cv[i] >> ((r & 3u) * 8u)) & 0xFFu) + ((r >> 16) & 0xFFu);
-						rk[u0 + i] = (r & 0x8000FFFFu) | (pl << 16);
-					}
-				}
-				__builtin_amdgcn_sched_barrier(0);
-			}
+			bc_places<NK, CH, WPT>(rk, tbase, cw);
 			MSD_STAMP(7); // positions
 			__syncthreads(); // counters are dead: the area is the output buffer now
 #pragma unroll

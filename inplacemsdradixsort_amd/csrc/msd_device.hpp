@@ -248,6 +248,89 @@ __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v)
 	}
 	return v;
 }
+// inclusive max-scan inside a wave (DPP row shifts + row broadcasts, as wave_incl_scan)
+__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v)
+{
+	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false)); // row_shr:1
+	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false)); // row_shr:2
+	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false)); // row_shr:4
+	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false)); // row_shr:8
+	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false)); // row_bcast:15 into rows 1, 3
+	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false)); // row_bcast:31 into rows 2, 3
+	return v;
+}
+
+// The scan of one value per thread over a workgroup of TH threads, in two halves with the caller's barrier between
+// them (three kernels stamp in front of that barrier).  wtot: TH / 64 words of LDS.
+// publish: the inclusive scan inside the wave; the wave's last lane leaves the wave's total in wtot.  `t` is the thread
+// index -- or the caller's opaque copy of it.
+__device__ __forceinline__ uint32_t wg_scan_publish(uint32_t v, uint32_t *wtot, uint32_t t)
+{
+	const uint32_t inc = wave_incl_scan(v);
+	if ((t & 63u) == 63u) wtot[t >> 6] = inc;
+	return inc;
+}
+// collect: pos = the thread's exclusive sum inside its wave (inc - v) + the totals of the waves below wave w, all = the
+// sum over the workgroup.  UNROLL: of the loop over the TH / 64 totals.
+struct WgScan {
+	uint32_t pos, all;
+};
+template <int TH, int UNROLL = TH / 64> __device__ __forceinline__ WgScan wg_scan_collect(const uint32_t *wtot, uint32_t w, uint32_t excl)
+{
+	uint32_t pos = excl, all = 0;
+#pragma unroll UNROLL
+	for (uint32_t ww = 0; ww < TH / 64; ++ww) {
+		const uint32_t t = wtot[ww];
+		if (ww < w) pos += t;
+		all += t;
+	}
+	return WgScan{ pos, all };
+}
+
+// A value that is the same in every lane, in a scalar register (loaded through vector memory or LDS it would make
+// every address derived from it a per-lane 64-bit computation).
+// (the builtin returns a signed int: without the cast to uint32_t a low word >= 2^31 sign-extends into the high word of
+// a 64-bit value put together from two of them -- element offsets that large exist only in arrays of more than 2^31
+// keys.  THIS was round 2's GPU fault at 2^32 keys: `keys + start` pointed 16 GiB below the array and the segment's
+// first 16-byte load faulted.)
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t x)
+{
+	return (uint64_t)uniform_u32((uint32_t)x) | ((uint64_t)uniform_u32((uint32_t)(x >> 32)) << 32);
+}
+__device__ __forceinline__ Segment uniform(const Segment &g)
+{
+	Segment u;
+	u.start = uniform_u64(g.start);
+	u.count = uniform_u64(g.count);
+	u.bits = (uint32_t)uniform_u64(g.bits); // (through the 64-bit form, whose high word folds away: uniform_u32 here moves two instructions of count_place16_kernel)
+	u.pad = 0;
+	return u;
+}
+
+// Padded LDS counter layouts: word w of the counters lives at w + (w / GROUP) * PAD, PAD words of padding behind every
+// GROUP words.  Three layouts are in use, each for the access pattern of its scan:
+//  * cw_at, 1 per 32 (count_place_kernel, count_walk_kernel): a thread owns up to 16 consecutive words and walks them
+//    one 4-byte access at a time; unpadded, the stride-16 walk of neighbouring lanes is a 32-way bank conflict, one
+//    word per 32 moves every lane's run on by a bank.
+//  * c16_at, 4 per 64 (count_place16_kernel, merge_place16_kernel, merge_count_kernel): a thread owns 32 consecutive
+//    words and reads them as 16-byte vectors; four words keep the 16-byte alignment, and the b128 accesses of the lanes
+//    that are served together fall on different banks.
+//  * c32_at, 4 per 32 (hist2_pack_kernel, leaf17_kernel): as c16_at for threads that own runs of 4 .. 32 words -- with
+//    a chunk of 32 no run crosses the padding, whatever its length.
+template <uint32_t GROUP, uint32_t PAD> __device__ __forceinline__ uint32_t pad_at(uint32_t w) { return w + (w / GROUP) * PAD; }
+__device__ __forceinline__ uint32_t cw_at(uint32_t w) { return pad_at<32, 1>(w); }
+__device__ __forceinline__ uint32_t c16_at(uint32_t w) { return pad_at<64, 4>(w); }
+__device__ __forceinline__ uint32_t c32_at(uint32_t w) { return pad_at<32, 4>(w); }
+
+// Four byte counters in a word -> their exclusive prefix sums (each < 256) on top of `run`, the sum of the words before
+// it, in place; `run` moves on by the word's own sum.
+__device__ __forceinline__ void byte_prefix(uint32_t &word, uint32_t &run)
+{
+	const uint32_t x = word, y = x * 0x01010101u; // bytes of y: inclusive sums inside the word
+	word = (y - x) + run * 0x01010101u;
+	run += y >> 24;
+}
 
 // Exclusive scan over the first 256 threads' values; every thread of the block
 // must call it (it contains barriers).  tmp: >= 5 uint32 of LDS.  Returns the
@@ -1473,6 +1556,7 @@ __global__ __launch_bounds__(256) void collect_kernel(const Parent *__restrict__
 
 } // namespace msd
 #include "msd_front16.hpp"
+#include "msd_regtile.hpp"
 #include "msd_regpart.hpp"
 namespace msd {
 
@@ -1490,12 +1574,10 @@ constexpr int kCountMaxBits = 16;
 #define MSD_COUNT_MED_LOG 17
 #endif
 constexpr uint64_t kCountMedMax = 1ull << MSD_COUNT_MED_LOG; // largest segment one workgroup counts by itself
-// counter word i lives at i + i/32: a thread's 16 consecutive words and its neighbours' then
-// fall on different LDS banks (unpadded, the stride-16 walk is a 32-way bank conflict)
+// (counter word i lives at cw_at(i), one word of padding per 32)
 constexpr size_t kCountCwBytes = (((size_t)1 << kCountMaxBits) / 4 + ((size_t)1 << kCountMaxBits) / 128 + 4) * 4;
 constexpr int kCountStageBytes = 14080; // output window; with the counters: two workgroups per CU
 constexpr size_t kCountLds = kCountCwBytes + kCountStageBytes + 128; // 128: wave totals, flag, ticket, prefix
-__device__ __forceinline__ uint32_t cw_at(uint32_t i) { return i + (i >> 5); }
 
 // Persistent workgroups: each takes segments by ticket and loads the first keys of its NEXT segment
 // while it stores the current one.  Two kernels share the counting phase:
@@ -1525,7 +1607,7 @@ __global__ __launch_bounds__(kCountTh, 8) void count_place_kernel(K *__restrict_
 	K *hi_l = reinterpret_cast<K *>(wtot + 18); // 8 bytes
 	uint32_t *crowded = wtot + 21;
 	static_assert((size_t)PF * kCountTh * sizeof(K) <= kCountCwBytes + kCountStageBytes, "output buffer");
-	const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const uint32_t tid = threadIdx.x, w = tid >> 6;
 	if (blockIdx.x >= nsegs) return;
 	Segment sg = segs[blockIdx.x];
 	K pk[PF];
@@ -1591,17 +1673,12 @@ __global__ __launch_bounds__(kCountTh, 8) void count_place_kernel(K *__restrict_
 			for (uint32_t j = 0; j < wpt; ++j) tot = __builtin_amdgcn_sad_u8(cww[j], 0u, tot); // byte sum
 		}
 		if (tot > 255u) *crowded = 1;
-		const uint32_t inc = wave_incl_scan(tot);
-		if (lane == 63) wtot[w] = inc;
+		const uint32_t inc = wg_scan_publish(tot, wtot, tid);
 		MSD_STAMP(4); // byte sums + wave scan
 		__syncthreads();
-		uint32_t pos = inc - tot, all = 0;
-#pragma unroll 2
-		for (uint32_t ww = 0; ww < kCountTh / 64; ++ww) {
-			const uint32_t t = wtot[ww];
-			if (ww < w) pos += t;
-			all += t;
-		}
+		const WgScan sc = wg_scan_collect<kCountTh, 2>(wtot, w, inc - tot);
+		uint32_t pos = sc.pos;
+		const uint32_t all = sc.all;
 		// a byte that overflowed carried into its neighbour: the sum of all bytes then falls short of n
 		const bool ok = in_regs && all == n && *crowded == 0;
 		MSD_STAMP(5); // barrier + block scan
@@ -1609,11 +1686,7 @@ __global__ __launch_bounds__(kCountTh, 8) void count_place_kernel(K *__restrict_
 			uint32_t run = 0;
 			if (w0 < nwords) {
 #pragma unroll 4
-				for (uint32_t j = 0; j < wpt; ++j) {
-					const uint32_t x = cww[j], y = x * 0x01010101u; // bytes of y: inclusive sums inside the word
-					cww[j] = (y - x) + run * 0x01010101u;
-					run += y >> 24;
-				}
+				for (uint32_t j = 0; j < wpt; ++j) byte_prefix(cww[j], run);
 			}
 			tbase[tid] = pos;
 			MSD_STAMP(6); // prefix inside the thread's words
@@ -1667,7 +1740,7 @@ __global__ __launch_bounds__(kCountTh, 8) void count_walk_kernel(K *__restrict__
 	uint32_t *nexti = wtot + 17;
 	K *hi_l = reinterpret_cast<K *>(wtot + 18); // 8 bytes
 	uint32_t *tfree = wtot + 20;
-	const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const uint32_t tid = threadIdx.x, w = tid >> 6;
 	const uint32_t nsegs = *nsegs_dev;
 	if (blockIdx.x >= nsegs) return;
 	Segment sg = segs[blockIdx.x];
@@ -1717,16 +1790,11 @@ __global__ __launch_bounds__(kCountTh, 8) void count_walk_kernel(K *__restrict__
 				nz |= (uint64_t)((((hb >> 7) * 0x01020408u) >> 24) & 0xFu) << (4u * j);
 			}
 		}
-		const uint32_t inc = wave_incl_scan(tot);
-		if (lane == 63) wtot[w] = inc;
+		const uint32_t inc = wg_scan_publish(tot, wtot, tid);
 		__syncthreads();
-		uint32_t pos = inc - tot, all = 0;
-#pragma unroll 2
-		for (uint32_t ww = 0; ww < kCountTh / 64; ++ww) {
-			const uint32_t t = wtot[ww];
-			if (ww < w) pos += t;
-			all += t;
-		}
+		const WgScan sc = wg_scan_collect<kCountTh, 2>(wtot, w, inc - tot);
+		uint32_t pos = sc.pos;
+		const uint32_t all = sc.all;
 		if (all != n) { // some value occurs > 255 times: hand the untouched segment on
 			if (tid == 0) {
 				if (n <= lds_cap) { // ... to the general LDS sort

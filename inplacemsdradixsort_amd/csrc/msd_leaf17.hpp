@@ -39,7 +39,6 @@ constexpr size_t kL17Side = kL17Cap;                                 // a byte p
 // The 16-bit counters (two per word) lie where the staging buffer and the distances will be -- the keys wait in registers
 // while they are counted.  A thread scans a contiguous run of 4..32 words: 4 padding words behind every 32 keep the
 // 16-byte accesses of neighbouring lanes on different banks.
-__device__ __forceinline__ uint32_t l17_at(uint32_t w) { return w + ((w >> 5) << 2); }
 constexpr size_t kL17CwBytes = ((((size_t)1 << kL17BitsMax) / 2) / 32 * 36) * 4;
 constexpr uint32_t kL17ListCap = 3072;                               // groups of two or more the list holds (2^14 uniform keys: about 1750)
 constexpr size_t kL17Lds = (size_t)kL17Cap * 8 + kL17Side + 64 * 8 + 256 + kL17ListCap * 2; // staging | distances | junk | misc | group list
@@ -57,14 +56,15 @@ __global__ __launch_bounds__(kL17Th, 4) void leaf17_kernel(uint64_t *__restrict_
 	constexpr int TH = kL17Th, NV = kL17Vec, NK = NV * 2 + 1;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	uint64_t *stage = reinterpret_cast<uint64_t *>(smem);                        // kL17Cap elements
-	uint32_t *cw = reinterpret_cast<uint32_t *>(smem);                           // before that: 2 x 16-bit counters per word (l17_at)
+	uint32_t *cw = reinterpret_cast<uint32_t *>(smem);                           // before that: 2 x 16-bit counters per word (c32_at)
 	int8_t *dl = reinterpret_cast<int8_t *>(smem + (size_t)kL17Cap * 8);         // distance to the final place, per position
 	uint64_t *junk = reinterpret_cast<uint64_t *>(smem + (size_t)kL17Cap * 8 + kL17Side); // per-lane junk word
 	uint32_t *wtot = reinterpret_cast<uint32_t *>(junk + 64);                    // 16 wave totals, [16] [18] flags, [17] listed groups
 	uint64_t *s_or = reinterpret_cast<uint64_t *>(wtot + 32);                    // OR / AND of the keys
 	uint16_t *list = reinterpret_cast<uint16_t *>(smem + (size_t)kL17Cap * 8 + kL17Side + 64 * 8 + 256); // first positions of the groups
 	const uint32_t tid0 = threadIdx.x;
-	auto rfl = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane(x); };
+	// (the 64-bit descriptor words below are put together by hand from two uniform_u32: through uniform_u64 this kernel's
+	// address arithmetic comes out differently -- DESIGN.md 1.1)
 
 	// The keys of a workgroup's NEXT segment are requested as soon as the current ones have left their registers for the
 	// staging buffer.  Measured (2^30 u64 keys / tuples, -DMSD_L17_PREFETCH=0 against 1 on one box): no difference -- the
@@ -80,9 +80,9 @@ __global__ __launch_bounds__(kL17Th, 4) void leaf17_kernel(uint64_t *__restrict_
 		uint32_t tl = tid0;
 		asm volatile("" : "+v"(tl));
 		const Segment g2 = segs[min(sj, nsegs - 1u)];
-		const uint64_t start2 = (uint64_t)rfl((uint32_t)g2.start) | ((uint64_t)rfl((uint32_t)(g2.start >> 32)) << 32);
+		const uint64_t start2 = (uint64_t)uniform_u32((uint32_t)g2.start) | ((uint64_t)uniform_u32((uint32_t)(g2.start >> 32)) << 32);
 		const uint32_t off2 = (uint32_t)(start2 & 1u);
-		const uint32_t tot2 = max(rfl((uint32_t)g2.count) + off2, 1u);
+		const uint32_t tot2 = max(uniform_u32((uint32_t)g2.count) + off2, 1u);
 		const uint64_t *kb2 = keys + (start2 - off2);
 		const uint32_t lastv2 = (tot2 - 1u) >> 1;
 #pragma unroll
@@ -107,9 +107,9 @@ __global__ __launch_bounds__(kL17Th, 4) void leaf17_kernel(uint64_t *__restrict_
 		asm volatile("" : "+v"(tid));
 		const uint32_t lane = tid & 63u, w = tid >> 6;
 		const Segment g = segs[si];
-		const uint64_t start = (uint64_t)rfl((uint32_t)g.start) | ((uint64_t)rfl((uint32_t)(g.start >> 32)) << 32);
-		const uint64_t cnt64 = (uint64_t)rfl((uint32_t)g.count) | ((uint64_t)rfl((uint32_t)(g.count >> 32)) << 32);
-		const uint32_t bits = rfl(g.bits);
+		const uint64_t start = (uint64_t)uniform_u32((uint32_t)g.start) | ((uint64_t)uniform_u32((uint32_t)(g.start >> 32)) << 32);
+		const uint64_t cnt64 = (uint64_t)uniform_u32((uint32_t)g.count) | ((uint64_t)uniform_u32((uint32_t)(g.count >> 32)) << 32);
+		const uint32_t bits = uniform_u32(g.bits);
 		const uint32_t off = (uint32_t)(start & 1u);
 		if (cnt64 + off > kL17Cap || cnt64 < min_count || cnt64 < 2 || bits == 0 || bits > 64) {
 			// too long for the staging buffer (with its first element on an odd index), or shorter than this kernel is worth:
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kL17Th, 4) void leaf17_kernel(uint64_t *__restrict_
 		// from n alone, so that the counters can be cleared while the keys are still on their way)
 		const uint32_t lb = min((uint32_t)kL17BitsMax, max((uint32_t)kL17BitsMin, 34u - (uint32_t)__builtin_clz(n - 1u)));
 		{
-			const uint32_t pw = l17_at(((uint32_t)1 << lb) / 2); // padded words, a multiple of 4
+			const uint32_t pw = c32_at(((uint32_t)1 << lb) / 2); // padded words, a multiple of 4
 			const u32x4 zero = { 0u, 0u, 0u, 0u };
 			for (uint32_t j = tid * 4u; j < pw; j += TH * 4u) *reinterpret_cast<u32x4 *>(cw + j) = zero;
 		}
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(kL17Th, 4) void leaf17_kernel(uint64_t *__restrict_
 			const uint32_t el = elem(u);
 			const bool in = el >= off && el < tot;
 			const uint32_t v = (uint32_t)(k[u] >> shift) & mask, sh = 16u * (v & 1u);
-			uint32_t *a = in ? cw + l17_at(v >> 1) : reinterpret_cast<uint32_t *>(junk + lane);
+			uint32_t *a = in ? cw + c32_at(v >> 1) : reinterpret_cast<uint32_t *>(junk + lane);
 			pr[u] = ((atomicAdd(a, 1u << sh) >> sh) & 0xFFFFu) | (in ? 0u : 0x80000000u);
 			if (u % 6 == 5) __builtin_amdgcn_sched_barrier(0); // (six fetch-adds in flight: all seventeen with their addresses spill)
 		}
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(kL17Th, 4) void leaf17_kernel(uint64_t *__restrict_
 		// ---- counts -> exclusive positions, in place; thread t owns wpt = 4..32 consecutive words (inside one padding chunk)
 		{
 			const uint32_t wpt = max((((uint32_t)1 << (nbits - shift)) / 2) / (uint32_t)TH, 4u);
-			uint32_t *mine = cw + l17_at(tid * wpt);
+			uint32_t *mine = cw + c32_at(tid * wpt);
 			uint32_t acc = 0; // (both halves at once: no half ever exceeds the segment's 17408 elements)
 #pragma unroll 1
 			for (uint32_t j = 0; j < wpt; j += 4) {
@@ -218,13 +218,13 @@ __global__ __launch_bounds__(kL17Th, 4) void leaf17_kernel(uint64_t *__restrict_
 		// all seventeen in registers across the scan -- and spills)
 		const uint64_t lowmask = shift ? (1ull << shift) - 1ull : 0ull;
 		const bool groups = shift && (vopen & lowmask) != 0; // more bits vary than were counted
-		uint32_t shift2 = rfl(shift);
+		uint32_t shift2 = uniform_u32(shift);
 		asm volatile("" : "+s"(shift2));
 		uint32_t m1 = 0;
 #pragma unroll
 		for (int u = 0; u < NK; ++u) {
 			const uint32_t v = (uint32_t)(k[u] >> shift2) & mask;
-			const uint32_t p = ((cw[l17_at(v >> 1)] >> (16u * (v & 1u))) & 0xFFFFu) + (pr[u] & 0xFFFFu);
+			const uint32_t p = ((cw[c32_at(v >> 1)] >> (16u * (v & 1u))) & 0xFFFFu) + (pr[u] & 0xFFFFu);
 			m1 |= pr[u] == 1u ? 1u << u : 0u; // (rank 1, an element of the segment)
 			pr[u] = (pr[u] & 0x80000000u) | p;
 			if (u % 6 == 5) __builtin_amdgcn_sched_barrier(0);

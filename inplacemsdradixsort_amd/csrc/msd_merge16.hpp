@@ -41,7 +41,6 @@ __global__ __launch_bounds__(1024) void merge_plan_kernel(const uint64_t *__rest
 	uint64_t n_expected, uint32_t *__restrict__ cnt32, uint64_t *__restrict__ src_off, uint64_t *__restrict__ dst_off,
 	uint32_t *__restrict__ status)
 {
-	__shared__ uint64_t tmp[8];
 	__shared__ uint64_t wsum[16];
 	const uint32_t row = blockIdx.x, tid = threadIdx.x;
 	const uint32_t per = (nb + 1023u) / 1024u, j0 = tid * per, j1 = min(j0 + per, nb);
@@ -67,7 +66,6 @@ __global__ __launch_bounds__(1024) void merge_plan_kernel(const uint64_t *__rest
 		if (w < (tid >> 6)) pre += wsum[w];
 		total += wsum[w];
 	}
-	(void)tmp;
 	uint64_t at = pre + (row < nsrc ? base.b[row] : 0ull);
 	for (uint32_t j = j0; j < j1; ++j) {
 		const uint64_t v = val(j);
@@ -104,8 +102,6 @@ __global__ __launch_bounds__(kC16Th, 4) void merge_place16_kernel(const uint32_t
 	uint32_t *nexti = wtot + 9, *crowded = wtot + 11;
 	const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 	if (*status != 0 || blockIdx.x >= nb) return;
-	auto rfl = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane(x); };
-	auto rfl64 = [&](uint64_t x) -> uint64_t { return (uint64_t)rfl((uint32_t)x) | ((uint64_t)rfl((uint32_t)(x >> 32)) << 32); };
 
 	// a bucket's extents, uniform: packed o | (o + len) << 8 per extent (o: misalignment of the extent's first
 	// element on the 16-byte grid of `src`, o + len <= ECAP < 2^24 when the bucket is taken)
@@ -127,11 +123,11 @@ __global__ __launch_bounds__(kC16Th, 4) void merge_place16_kernel(const uint32_t
 #pragma unroll
 		for (int x = 0; x < G; ++x) {
 			const bool have = (uint32_t)x < nsrc;
-			sx[x] = have ? rfl64(src_off[(size_t)x * nb + j]) : 0ull;
-			lx[x] = have ? rfl(cnt32[(size_t)x * nb + j]) : 0u;
+			sx[x] = have ? uniform_u64(src_off[(size_t)x * nb + j]) : 0ull;
+			lx[x] = have ? uniform_u32(cnt32[(size_t)x * nb + j]) : 0u;
 			n64 += lx[x];
 		}
-		ds.d = rfl64(dst_off[j]);
+		ds.d = uniform_u64(dst_off[j]);
 #pragma unroll
 		for (int x = 0; x < G; ++x) {
 			const uint32_t o = (uint32_t)(sx[x] & 3u);
@@ -214,7 +210,7 @@ __global__ __launch_bounds__(kC16Th, 4) void merge_place16_kernel(const uint32_t
 			}
 		}
 		__syncthreads();
-		const uint32_t nxt = rfl(*nexti);
+		const uint32_t nxt = uniform_u32(*nexti);
 		const uint32_t hi = (prefix0 + cur) << bits;
 		// the thread's 32 counter words are read in two halves, twice (byte sums, then byte prefixes): all 32 in registers
 		// beside this kernel's 36-40 key registers spill
@@ -303,8 +299,8 @@ __global__ __launch_bounds__(kC16Th, 4) void merge_place16_kernel(const uint32_t
 			uint64_t at = sg.d;
 #pragma unroll 1
 			for (uint32_t x = 0; x < nsrc; ++x) {
-				const uint64_t s0 = rfl64(src_off[(size_t)x * nb + cur]);
-				const uint32_t len = rfl(cnt32[(size_t)x * nb + cur]);
+				const uint64_t s0 = uniform_u64(src_off[(size_t)x * nb + cur]);
+				const uint32_t len = uniform_u32(cnt32[(size_t)x * nb + cur]);
 				for (uint32_t i = tid; i < len; i += TH) dst[at + i] = src[s0 + i];
 				at += len;
 			}
@@ -371,17 +367,6 @@ __global__ __launch_bounds__(kC16Th, 4) void merge_place16_kernel(const uint32_t
 // LIST = false: buckets of the multi-GPU exchange (extents from merge_plan_kernel's tables, output to another buffer).
 // LIST = true: segments of a list, sorted in place (one extent; all of it is read before the first tile is written) --
 // the 17 Ki .. 512 Ki-key segments of skewed inputs that count_walk_kernel used to take.
-// inclusive max-scan inside a wave (DPP row shifts + row broadcasts, as wave_incl_scan)
-__device__ __forceinline__ uint32_t wave_incl_max(uint32_t v)
-{
-	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false)); // row_shr:1
-	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false)); // row_shr:2
-	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false)); // row_shr:4
-	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false)); // row_shr:8
-	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false)); // row_bcast:15 into rows 1, 3
-	v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false)); // row_bcast:31 into rows 2, 3
-	return v;
-}
 
 #ifndef MSD_MC_NB // (overridable for experiments)
 #define MSD_MC_NB 4
@@ -431,9 +416,7 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 	uint16_t *seg_va = reinterpret_cast<uint16_t *>(ext + 48); // the value whose run holds every segment's first key (+ one behind the last)
 	const uint32_t tid0 = threadIdx.x;
 	if (status && *status != 0) return;
-	auto rfl = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane(x); };
-	auto rfl64 = [&](uint64_t x) -> uint64_t { return (uint64_t)rfl((uint32_t)x) | ((uint64_t)rfl((uint32_t)(x >> 32)) << 32); };
-	const uint32_t nbk = LIST ? rfl(*nsegs_dev) : nb;
+	const uint32_t nbk = LIST ? uniform_u32(*nsegs_dev) : nb;
 	const uint32_t nx = LIST ? 1u : nsrc;
 	uint32_t cur = blockIdx.x;
 	MSD_STAMP_DECL(8);
@@ -451,21 +434,18 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 		uint64_t d, n64;
 		Segment lsg = {};
 		if constexpr (LIST) {
-			const Segment g = segs[cur];
-			lsg.start = rfl64(g.start);
-			lsg.count = rfl64(g.count);
-			lsg.bits = rfl(g.bits);
+			lsg = uniform(segs[cur]);
 			bits = lsg.bits;
 			d = lsg.start;
 			n64 = lsg.count;
 		} else {
-			d = rfl64(dst_off[cur]);
-			n64 = rfl64(dst_off[cur + 1]) - d;
+			d = uniform_u64(dst_off[cur]);
+			n64 = uniform_u64(dst_off[cur + 1]) - d;
 		}
 		const bool bits_ok = bits >= 1 && bits <= 16 && ((!IN16 && !HIST) || bits == 16);
 		const uint32_t mask = bits_ok ? (1u << bits) - 1u : 0u;
 		if constexpr (LIST)
-			hi = n64 ? rfl(src[d]) & ~mask : 0u; // (read before anything is written: the sort is in place)
+			hi = n64 ? uniform_u32(src[d]) & ~mask : 0u; // (read before anything is written: the sort is in place)
 		else
 			hi = (prefix0 + cur) << (bits_ok ? bits : 0u);
 		const uint32_t off = (uint32_t)(d & 3u);
@@ -479,8 +459,8 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 				s = d;
 				len = n;
 			} else {
-				s = (uint64_t)rfl(ext[3 * x]) | ((uint64_t)rfl(ext[3 * x + 1]) << 32);
-				len = rfl(ext[3 * x + 2]);
+				s = (uint64_t)uniform_u32(ext[3 * x]) | ((uint64_t)uniform_u32(ext[3 * x + 1]) << 32);
+				len = uniform_u32(ext[3 * x + 2]);
 			}
 		};
 		if constexpr (!LIST) {
@@ -502,7 +482,7 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 		MSD_STAMP(0); // clear + ticket
 		__syncthreads();
 		MSD_STAMP(1);
-		const uint32_t nxt = rfl(flags[0]);
+		const uint32_t nxt = uniform_u32(flags[0]);
 		if (n64 == 0) { // (empty bucket)
 			cur = nxt;
 			__syncthreads();
@@ -534,7 +514,7 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 			// ... and the values with three or more copies: the field says 3, the entry the rest
 			for (uint32_t x = 0; x < nx; ++x) {
 				const uint32_t *ex = reinterpret_cast<const uint32_t *>(record(x) + kH2Fields);
-				const uint32_t ne = min(rfl(ex[0]), kH2MaxExc);
+				const uint32_t ne = min(uniform_u32(ex[0]), kH2MaxExc);
 				if (tid < ne) {
 					const uint32_t e = ex[1u + tid], v = e >> 16, c = e & 0xFFFFu;
 					if (c > 3u) (void)__hip_atomic_fetch_add(&cw[c16_at(v >> 1)], (c - 3u) << ((v & 1u) << 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -640,9 +620,9 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 #pragma unroll
 			for (int j = 0; j < 32; ++j) tot += (cr[j] & 0xFFFFu) + (cr[j] >> 16);
 		}
-		const uint32_t inc = wave_incl_scan(tot);
-		if (lane == 63) wtot[w] = inc;
+		const uint32_t inc = wg_scan_publish(tot, wtot, tid);
 		__syncthreads();
+		// (the collect half written out: as the inlined function it commutes the operands of these sixteen additions)
 		uint32_t pos = inc - tot, all = 0;
 #pragma unroll
 		for (uint32_t ww = 0; ww < TH / 64; ++ww) {
@@ -698,8 +678,8 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 			uint32_t *segb = dst + (d - off);
 			uint32_t *wst = stage + (w << 8);
 			// (segments by ticket, not round robin: the waves of a workgroup finished 20 thousand cycles apart)
-			for (uint32_t sgi = w; sgi < nseg; sgi = rfl(lane == 0 ? atomicAdd(&flags[2], 1u) : 0u)) {
-				const uint32_t va = rfl(seg_va[sgi]), vb = min(rfl(seg_va[sgi + 1]), mask); // (no key has a value above the mask)
+			for (uint32_t sgi = w; sgi < nseg; sgi = uniform_u32(lane == 0 ? atomicAdd(&flags[2], 1u) : 0u)) {
+				const uint32_t va = uniform_u32(seg_va[sgi]), vb = min(uniform_u32(seg_va[sgi + 1]), mask); // (no key has a value above the mask)
 				const uint32_t q0 = sgi * kMcSeg;
 				const uint32_t plo = (q0 > off ? q0 : off) - off, phi = min(q0 + kMcSeg, n + off) - off; // the segment in bucket positions
 				reinterpret_cast<u32x4 *>(wst)[lane] = u32x4{ 0u, 0u, 0u, 0u };
@@ -772,7 +752,7 @@ __global__ __launch_bounds__(kMcTh) void merge_count_kernel(const IN *src, uint3
 					const u32x4 q = *reinterpret_cast<const u32x4 *>(record(x) + 16u * tid);
 					const uint32_t wq[4] = { q.x, q.y, q.z, q.w };
 					const uint32_t *ex = reinterpret_cast<const uint32_t *>(record(x) + kH2Fields);
-					const uint32_t ne = min(rfl(ex[0]), kH2MaxExc);
+					const uint32_t ne = min(uniform_u32(ex[0]), kH2MaxExc);
 					auto copies = [&](uint32_t f) -> uint32_t { // of value 64 tid + f
 						uint32_t c = (wq[f >> 4] >> (2u * (f & 15u))) & 3u;
 						if (c == 3u)
@@ -843,7 +823,6 @@ __global__ __launch_bounds__(256) void pack_low16_kernel(const uint32_t *__restr
 // (first version: 2^16 16-bit counters, one 1024-thread workgroup per CU: 2.2 ms per 2^30 keys; this one: see DESIGN.md)
 constexpr int kH2Th = 512;
 constexpr uint32_t kH2Words = 16384 + (16384 >> 5) * 4;   // byte counters, four per word, 4 words of padding per 32
-__device__ __forceinline__ uint32_t h2_at(uint32_t w) { return w + ((w >> 5) << 2); }
 constexpr size_t kH2Lds = ((size_t)kH2Words + (kH2MaxExc + 1) + 8) * 4;
 static_assert(2 * kH2Lds <= 160 * 1024, "two workgroups per CU");
 // IN = uint16_t: the buckets' LOW HALVES, as msd_order_low16_u32 leaves them (half the bytes to read).
@@ -854,11 +833,10 @@ __global__ __launch_bounds__(kH2Th, 2) void hist2_pack_kernel(const IN *__restri
 	constexpr int TH = kH2Th;
 	constexpr uint32_t VE = 16 / sizeof(IN); // values per 16-byte vector
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-	uint32_t *cw = reinterpret_cast<uint32_t *>(smem); // byte counters (h2_at)
+	uint32_t *cw = reinterpret_cast<uint32_t *>(smem); // byte counters (c32_at)
 	uint32_t *exc = cw + kH2Words;                     // [0] entries, then the entries
 	uint32_t *bad = exc + (kH2MaxExc + 1);             // a byte counter has overflowed
 	const uint32_t tid0 = threadIdx.x;
-	auto rfl = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane(x); };
 	constexpr int U = sizeof(IN) == 2 ? 4 : 8; // 16-byte vectors in flight per thread: all of a 2^14-key bucket at once
 	// a bucket on the array's 16-byte grid: single elements at both ends, whole vectors [vfirst, vend) between them
 	struct Where {
@@ -867,9 +845,7 @@ __global__ __launch_bounds__(kH2Th, 2) void hist2_pack_kernel(const IN *__restri
 		bool fits;
 	};
 	auto where = [&](uint32_t bb) -> Where {
-		const uint64_t s0 = bounds[bb], s1 = bounds[bb + 1];
-		const uint64_t s = (uint64_t)rfl((uint32_t)s0) | ((uint64_t)rfl((uint32_t)(s0 >> 32)) << 32);
-		const uint64_t e = (uint64_t)rfl((uint32_t)s1) | ((uint64_t)rfl((uint32_t)(s1 >> 32)) << 32);
+		const uint64_t s = uniform_u64(bounds[bb]), e = uniform_u64(bounds[bb + 1]);
 		Where wq;
 		wq.fits = e - s <= 65535u;
 		wq.n = wq.fits ? (uint32_t)(e - s) : 0u;
@@ -917,7 +893,7 @@ __global__ __launch_bounds__(kH2Th, 2) void hist2_pack_kernel(const IN *__restri
 		// (fetch-adds without return value; a counter that has spilled into its neighbour shows in the sum of all bytes below)
 		auto count = [&](uint32_t key) {
 			const uint32_t v = key & 0xFFFFu;
-			(void)__hip_atomic_fetch_add(&cw[h2_at(v >> 2)], 1u << ((v & 3u) << 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			(void)__hip_atomic_fetch_add(&cw[c32_at(v >> 2)], 1u << ((v & 3u) << 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 		};
 		auto eat = [&](const u32x4 (&qq)[U], uint32_t v0) {
 #pragma unroll
@@ -956,7 +932,7 @@ __global__ __launch_bounds__(kH2Th, 2) void hist2_pack_kernel(const IN *__restri
 		__syncthreads();
 		MSD_STAMP(5); // barrier
 		// ---- thread t packs values [128 t, 128 t + 128) = 32 counter words into 32 bytes of fields
-		const u32x4 *cq = reinterpret_cast<const u32x4 *>(cw + h2_at(tid * 32u));
+		const u32x4 *cq = reinterpret_cast<const u32x4 *>(cw + c32_at(tid * 32u));
 		uint32_t out[8], bsum = 0, many = 0; // many: bit = a word of mine that holds a value with three or more copies
 #pragma unroll
 		for (int j = 0; j < 8; ++j) {
@@ -985,7 +961,7 @@ __global__ __launch_bounds__(kH2Th, 2) void hist2_pack_kernel(const IN *__restri
 		while (many) {
 			const uint32_t wi = (uint32_t)__builtin_ctz(many);
 			many &= many - 1u;
-			const uint32_t w = cw[h2_at(tid * 32u + wi)];
+			const uint32_t w = cw[c32_at(tid * 32u + wi)];
 			for (uint32_t k2 = 0; k2 < 4; ++k2) {
 				const uint32_t c = (w >> (8 * k2)) & 0xFFu;
 				if (c >= 3u) {

@@ -61,13 +61,12 @@ __global__ __launch_bounds__(kRpTh, 4) void regpart_kernel(uint64_t *__restrict_
 	uint64_t *junk = reinterpret_cast<uint64_t *>(bstart + kP);      // per-lane junk word
 	uint32_t *misc = reinterpret_cast<uint32_t *>(junk + 64);
 	const uint32_t tid = threadIdx.x, lane = tid & 63;
-	auto rfl = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane(x); };
 
 	for (uint32_t pi = blockIdx.x; pi < nparents; pi += gridDim.x) {
 		const Parent pa = parents[pi];
 		// (uniform values in scalar registers: addresses below are base + 32-bit lane offset)
-		const uint64_t start = (uint64_t)rfl((uint32_t)pa.start) | ((uint64_t)rfl((uint32_t)(pa.start >> 32)) << 32);
-		const uint32_t n = rfl((uint32_t)pa.count), shift = rfl(pa.shift), width = rfl(pa.width), cbase = rfl(pa.child_base);
+		const uint64_t start = uniform_u64(pa.start);
+		const uint32_t n = uniform_u32((uint32_t)pa.count), shift = uniform_u32(pa.shift), width = uniform_u32(pa.width), cbase = uniform_u32(pa.child_base);
 		const uint32_t mask = (1u << width) - 1u, nb = 1u << width;
 		const uint32_t off = (uint32_t)(start & 1u), tot = n + off; // the parent on the 16-byte grid: elements [off, tot)
 		uint64_t *kb = keys + (start - off), *vb = HV ? vals + (start - off) : nullptr;

@@ -38,10 +38,7 @@ static_assert(2 * kS16Lds <= 160 * 1024, "two workgroups per CU");
 // chunk j of parent p (the keys whose top byte is p lie in [pb[p], pb[p + 1])): whole 16-byte vectors of the parent's range
 __device__ __forceinline__ void s16_chunk(const uint64_t *__restrict__ pb, uint32_t p, uint32_t j, uint64_t &a, uint64_t &b)
 {
-	auto rfl64 = [](uint64_t x) -> uint64_t {
-		return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)x) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32);
-	};
-	const uint64_t ps = rfl64(pb[p]), pe = rfl64(pb[p + 1]);
+	const uint64_t ps = uniform_u64(pb[p]), pe = uniform_u64(pb[p + 1]);
 	const uint64_t per = ((pe - ps + kS16Chunks - 1) / kS16Chunks + 3) & ~3ull;
 	a = ps + (uint64_t)j * per < pe ? ps + (uint64_t)j * per : pe;
 	b = a + per < pe ? a + per : pe;

@@ -20,6 +20,11 @@ dominate; 50 calls), sorted int32 keys with about 16 elements per run, N = the s
   run_encode_N, reduce_runs_sum_f32_N, reduce_runs_min_i32_N (and _keys64_N: int64 keys), scan_runs_sum_f32_N, compact_range_N (the middle half of the key range, with values)
   searchsorted_merge_N (N ascending needles in N keys), merge_sorted_N, set_union_N, join_groups_N (N / 2 keys a side),
   join_pairs_N (all pairs of those groups)
+and the leaves of the multi-GPU exchange at about 2^26 keys (50 calls):
+  merge_buckets_{2,4,8}src_2^26 (msd_merge_buckets_u32: merge_place16_kernel) and merge_buckets_low16_2^26 (4 sources of low
+  halves: merge_count_kernel): 4096 buckets of about 2^14 keys with 16 open bits, the sources' extents back to back behind
+  gaps of 0 .. 6 elements (the bucket shapes of tests/test_gpu_merge.py);
+  hist2_pack_2^26 (msd_hist2_pack_u32): 2^26 sorted uniform keys, 65536 buckets of about 1024 keys
 and prints one JSON line per case; the driver appends them to profiles/host_layer_ab.jsonl and prints the comparison:
 per case the parent's min-max over its runs against the median of this build's runs.  The small cases are the ones where
 host time dominates (a sort of 2^16 keys is a dozen launches and two synchronisations)."""
@@ -116,6 +121,37 @@ def child():
         groups = ctx.join_groups(au, bu)
         case(f"join_pairs_{tag}", lambda: ctx.join_pairs(groups, N // 2, N // 2, N), calls=calls)
         del keys, fv, other, a, b, au, bu, groups
+    exchange = [f"merge_buckets_{x}src_2^26" for x in (2, 4, 8)] + ["merge_buckets_low16_2^26", "hist2_pack_2^26"]
+    if not only or any(c.startswith(p) for p in only for c in exchange):
+        nb, first, gg = 4096, 5 * 4096, torch.Generator("cuda").manual_seed(26)
+
+        def arrivals(nsrc):  # per source: its buckets first .. first + nb - 1 in order, unsorted inside a bucket
+            counts = torch.poisson(torch.full((nsrc, nb), 16384.0 / nsrc, device="cuda"), generator=gg).to(torch.int64)
+            parts, base, at = [], [], 0
+            for x in range(nsrc):
+                pre = torch.repeat_interleave(torch.arange(first, first + nb, device="cuda"), counts[x])
+                low = torch.randint(0, 1 << 16, (pre.numel(),), device="cuda", generator=gg)
+                parts += [torch.full((x % 7,), -1, dtype=torch.int32, device="cuda"), ((pre << 16) | low).to(torch.int32)]
+                base.append(at + x % 7)
+                at += x % 7 + pre.numel()
+            parts.append(torch.full((8,), -1, dtype=torch.int32, device="cuda"))
+            return torch.cat(parts), counts, base, int(counts.sum())
+
+        for nsrc in (2, 4, 8):
+            src, counts, base, n = arrivals(nsrc)
+            dst = torch.empty(n + 5, dtype=torch.int32, device="cuda")
+            case(f"merge_buckets_{nsrc}src_2^26", lambda: ctx.merge_buckets(src, counts, base, 16, first, dst, n), calls=50)
+            if nsrc == 4:
+                low = src.to(torch.int16)
+                case("merge_buckets_low16_2^26", lambda: ctx.merge_buckets(low, counts, base, 16, first, dst, n), calls=50)
+                del low
+            del src, counts, dst
+        keys = torch.randint(-(1 << 31), 1 << 31, (1 << 26,), dtype=torch.int64, device="cuda", generator=gg).to(torch.int32)
+        ctx.sort_u32(keys)
+        bounds = ctx.bucket_bounds(keys, 16, 65536)
+        rec = torch.empty(65536 * ctx.HIST2_RECORD_BYTES, dtype=torch.uint8, device="cuda")
+        case("hist2_pack_2^26", lambda: ctx.hist2_pack(keys, bounds, rec), calls=50)
+        del keys, bounds, rec
     ctx.close()
     if not only or any("bench_2^30_u32".startswith(p) for p in only):
         buf = io.StringIO()
